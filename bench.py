@@ -18,7 +18,12 @@ N > 1 the finalize stays with the first launch and ONE all-reduce of the flat [s
 (captured inside the step's graph by default, `--two-graphs` for an eager collective between two graphs).
 --torch-optimizer runs the O(I) part as PyTorch autograd + torch.optim.Adam instead.
 
-Adds to the contract line:
+A plain run sets up, warms up, times exactly --steps steps (one block) and prints the contract line: metric, value, unit,
+higher_is_better, dtype, ms_per_step (the wall time of one timed step) and the configuration.  --dump-outputs DIR then writes
+what the last timed step computed -- its loss and the parameters it left in the model -- as DIR/<name>.npy (float32).
+Everything below takes runs, timers or comparisons of its own and comes with --full only (which also makes --blocks 5).
+
+With --full, adds to the contract line:
   roofline      the fused kernel's achieved HBM GB/s = algorithmic bytes (5 + 12A/I per term) x terms per launch
                 / its mean duration INSIDE the replayed step: events cannot be recorded inside a replayed graph, so right after
                 the timed region the same step is replayed as two hipGraphs (fused ELBO call | epilogue) with a HIP event on the
@@ -60,6 +65,7 @@ for p in (ROOT, PKG_DIR):
     if p not in sys.path:
         sys.path.insert(0, p)
 
+import numpy as np
 import torch
 
 
@@ -68,7 +74,9 @@ def parse():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=20)
     ap.add_argument('--warmup', type=int, default=3)
-    ap.add_argument('--blocks', type=int, default=5, help='the timed region is run this many times back to back, each exactly --steps steps between barrier + synchronize pairs; value / ms_per_step = the MEDIAN block, all of them listed (ms_per_step_blocks)')
+    ap.add_argument('--full', action='store_true', help='also the legs beyond the headline: roofline and kernel timings, the ELBO check against the CPU oracle, ability_dim 1, BASELINE configs[1], Format P, other shapes, the CPU baseline (see the docstring)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write the last step\'s loss and the parameters it left as DIR/<name>.npy')
+    ap.add_argument('--blocks', type=int, default=None, help='the timed region is run this many times back to back (default 1; 5 with --full), each exactly --steps steps between barrier + synchronize pairs; value / ms_per_step = the MEDIAN block, all of them listed (ms_per_step_blocks)')
     ap.add_argument('--persons', type=int, default=1_000_000, help='persons of the whole matrix (--scaling strong) / per GPU (--scaling weak)')
     ap.add_argument('--items', type=int, default=1000)
     ap.add_argument('--ability-dim', type=int, default=8)
@@ -92,7 +100,10 @@ def parse():
     ap.add_argument('--one-graph', action='store_true', help='(default for N > 1; kept for compatibility) the RCCL all-reduce captured inside the step\'s hipGraph: one graph per step, no host round trip')
     ap.add_argument('--two-graphs', action='store_true', help='multi-GPU: two hipGraphs around an EAGER all-reduce instead of the captured collective (both forms are pinned bitwise on a 1-rank nccl group, tests/test_gpu_rccl.py; a failed capture falls back to this form by itself)')
     ap.add_argument('--force-dist', action='store_true', help='create the process group even for one rank (tests the RCCL path)')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.blocks is None:
+        args.blocks = 5 if args.full else 1
+    return args
 
 
 def synth_responses(irt, P, I, A, missing, device, seed):
@@ -216,6 +227,17 @@ def parse_traffic(kernel_tag):
         f'parsed from profiles/{PROFILE_FILE}: 2*FETCH_SIZE + WRITE_SIZE of {kernel_tag} (KiB counters, separate --pmc passes)'
 
 
+def write_outputs(out_dir, arrays, limit=32 << 20):
+    """--dump-outputs: one .npy per array (float32 / float64).  Should they exceed `limit` bytes in all (items in the millions),
+    every array is cut to the same fixed stride sample of its flattened elements, so that two builds still compare entry for entry."""
+    os.makedirs(out_dir, exist_ok=True)
+    stride = sum(a.nbytes for a in arrays.values()) // limit + 1
+    for name, a in arrays.items():
+        if stride > 1:
+            a = np.ascontiguousarray(a.reshape(-1)[::stride])
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def main():
     args = parse()
     if args.ability_merge == 'mean':
@@ -254,8 +276,9 @@ def main():
         return args.persons if scaling == 'weak' else (args.persons * (rank + 1)) // world - (args.persons * rank) // world
     persons_rank = shard(args.scaling)
 
-    def measure(A, codes=False, extra=False, persons=None):
-        """-> dict(dt, kern_ms, final_loss, graph) for ability_dim A on this rank's shard."""
+    def measure(A, codes=False, extra=False, persons=None, outputs=False):
+        """-> dict(dt, kern_ms, final_loss, graph) for ability_dim A on this rank's shard (kern_ms and the rest of the per-kernel
+        figures with --full only; outputs=True: + the last timed step's loss and parameters as numpy arrays)."""
         P, I = (persons_rank if persons is None else persons), args.items
         resp, mask = synth_responses(irt, P, I, A, args.missing, dev, args.seed + 1000 * rank)
         if codes:           # Format P: the same matrix as one byte per cell (VIBO_MASK_CODES)
@@ -275,7 +298,7 @@ def main():
         # in-situ timer: the matrix kernel stamps its own entry / exit (100 MHz chip-wide clock) inside whatever it runs in --
         # the replayed graphs of the timed region included (ops.InsituTimer, vibo_set_insitu_timer); armed before the captures
         # so that the captured launches carry the block's address
-        insitu_tm = ops.InsituTimer(dev) if trainer is not None else None
+        insitu_tm = ops.InsituTimer(dev) if trainer is not None and args.full else None
         if insitu_tm is not None:
             insitu_tm.arm()
         # HIP events around the native call, on the stream it is launched on
@@ -296,7 +319,8 @@ def main():
             events.append((e0, e1))
             return out
 
-        ops._BACKEND['elbo'] = timed_native
+        if args.full:
+            ops._BACKEND['elbo'] = timed_native
 
         graph = None
         launch_mode = 'eager'
@@ -407,6 +431,11 @@ def main():
             if dist is not None:
                 dist.broadcast(pick, 0)
             step, launch_mode = forms['one' if int(pick) == 0 else 'two']
+        if not args.full:
+            # a plain run times a single block, and the first ~20 steps after the probe's short bursts ran 1-6 % slow on the
+            # MI355X (the first of --full's blocks shows it; its median leaves it out): settle a fixed 20 steps back to back first
+            for _ in range(20):
+                loss = step()
         # The timed region, `--blocks` times back to back: each block is exactly --steps steps between barrier + synchronize
         # pairs (max over ranks); the line's value / ms_per_step are the MEDIAN block, every block is listed.  (One block of
         # 20 steps is an 18 ms sample: round 5's three clocks disagreed by more than the margin they were quoted with.)
@@ -455,6 +484,16 @@ def main():
         blocks_info = {'blocks': len(block_dt), 'ms_per_step': [b / args.steps * 1e3 for b in block_dt],
                        'median': dt / args.steps * 1e3, 'min': min(block_dt) / args.steps * 1e3, 'max': max(block_dt) / args.steps * 1e3}
         final_loss = float(loss.detach())
+        out_arrays = None
+        if outputs:
+            # what a caller of the step receives: the loss, and the parameters the step updated in place
+            out_arrays = {'loss': loss.detach().float().cpu().numpy()}
+            out_arrays.update((k, v.detach().float().cpu().numpy()) for k, v in model.state_dict().items())
+        if not args.full:
+            del resp, mask, model, opt, trainer
+            torch.cuda.empty_cache()
+            return dict(dt=dt, final_loss=final_loss, launch=launch_mode if graph is not None else 'eager', form_probe=form_probe,
+                        blocks=blocks_info, outputs=out_arrays)
 
         bare_ms, instep, phase_ms = None, None, None
         if graph is not None and trainer is not None:
@@ -550,7 +589,7 @@ def main():
         torch.cuda.empty_cache()
         return dict(dt=dt, kern_ms=kern_ms, final_loss=final_loss, graph=graph is not None, rel=rel, sweep=sweep,
                     launch=launch_mode if graph is not None else 'eager', phase_ms=phase_ms, bare_ms=bare_ms, instep=instep, form_probe=form_probe,
-                    insitu=insitu, events_ms=events_ms, blocks=blocks_info)
+                    insitu=insitu, events_ms=events_ms, blocks=blocks_info, outputs=out_arrays)
 
     def elbo_rel_err(model, resp, mask, A, n=4096):
         """ELBO of the same parameters, rows and noise: HIP step vs the CPU restatement of the reference (fp32 and fp64).
@@ -809,19 +848,19 @@ def main():
         return out
 
     P, I, A = persons_rank, args.items, args.ability_dim
-    m = measure(A, extra=not args.no_extra)
-    dt, kern_ms, final_loss = m['dt'], m['kern_ms'], m['final_loss']
-    bytes_per_term = 5.0 + 12.0 * A / I
-    achieved = bytes_per_term * P * I / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+    m = measure(A, extra=not args.no_extra, outputs=args.dump_outputs is not None and rank == 0)
+    if m['outputs'] is not None:
+        write_outputs(args.dump_outputs, m['outputs'])
+    dt, final_loss = m['dt'], m['final_loss']
     total_persons = float(args.persons) * (world if args.scaling == 'weak' else 1)
     also_weak = None
-    if world > 1 and args.scaling == 'strong' and not args.no_also_weak:
+    if args.full and world > 1 and args.scaling == 'strong' and not args.no_also_weak:
         # the same step with --persons rows on EVERY rank (weak scaling), in the same run
         mw = measure(A, persons=args.persons)
         also_weak = {'scaling': 'weak', 'persons_per_rank': args.persons, 'value': float(args.persons) * world * I * args.steps / mw['dt'],
                      'unit': 'terms/s', 'ms_per_step': mw['dt'] / args.steps * 1e3, 'kernel_ms': mw['kern_ms'], 'launch': mw['launch']}
     also = None
-    if args.also_ability_dim and args.also_ability_dim != A:
+    if args.full and args.also_ability_dim and args.also_ability_dim != A:
         A2 = args.also_ability_dim
         m2 = measure(A2)
         b2 = 5.0 + 12.0 * A2 / I
@@ -836,7 +875,7 @@ def main():
                 'elbo_rel_err_kernel': m2['rel']['kernel'] if m2.get('rel') else None}
 
     also_config2 = None
-    if world == 1 and not args.no_also_config2 and not args.eval_only:
+    if args.full and world == 1 and not args.no_also_config2 and not args.eval_only:
         # BASELINE configs[1] literally (100k x 1k, ability_dim 1): a short launch, reported with its own fractions
         Pc2 = 100_000
         save = args.no_extra
@@ -857,7 +896,7 @@ def main():
                         'note': '3 125 batches of 32 rows over 256 workgroups = 12.2 per workgroup (13 rounds) + the kernel\'s one-shot prologue / end code: a short-launch regime, not the streaming one of the headline'}
 
     format_p = None
-    if not args.no_format_p:
+    if args.full and not args.no_format_p:
         m3 = measure(A, codes=True)
         b3 = 1.0 + 12.0 * A / I
         format_p = {'workload': 'same matrix and step as the headline, rows stored as 1-byte cell codes (Format P, VIBO_MASK_CODES): '
@@ -875,24 +914,10 @@ def main():
     default_wl = (args.persons, I, irt, abs(args.missing - 0.1) < 1e-9, world) == (1_000_000, 1000, 2, True, 1)
     # (mangled template arguments <IRT, GRAD, RM = 0 fp32 rows, FLOWS = 0, ...> of vibo::msplit_kernel: the summary keeps the names' tails)
     kernel_tag = f'ILi{irt}ELb{0 if args.eval_only else 1}ELi0ELb0E'
-    traffic, traffic_note = (parse_traffic(kernel_tag) if default_wl and A == 8 else (None, 'not measured for this workload'))
     if format_p is not None and default_wl and A == 8:
         format_p['traffic'], _ = parse_traffic(f'ILi{irt}ELb{0 if args.eval_only else 1}ELi2ELb0E')
     if rank == 0:
         terms = total_persons * I * args.steps
-        frac_note = ''
-        if m.get('insitu'):
-            frac_note += ('frac = algorithmic bytes / kernel_ms_insitu: the fused kernel\'s mean duration over every launch of the timed region\'s '
-                          'blocks, stamped by the kernel itself (earliest workgroup entry -> latest workgroup exit on the chip-wide 100 MHz clock; '
-                          'kernel_timing_insitu).  kernel_ms_events = the estimate of rounds 4-5, kept beside it: ')
-        if m.get('instep'):
-            frac_note += ('the fused call\'s mean duration in the step captured as its two halves and replayed back to back right after the timed '
-                          'region, HIP events on the launch stream around the first (an upper bound: the event packets cost a few us; kernel_timing '
-                          'has mean / min / max' + (', mean = max over ranks' if world > 1 else '') + '); ')
-        elif not m.get('insitu'):
-            frac_note += 'frac = algorithmic bytes / mean duration of the fused call by HIP events on its stream (eager pass after the timed region); '
-        frac_note += ('bare_launch_ms = the same call in a loop of bare eager launches (a note, not the claim); frac_step = the same bytes / ms_per_step '
-                      f'(median block); the rocprofv3 kernel-trace average of the same command is in profiles/{PROFILE_FILE}')
         line = {
             'metric': 'person x item ELBO terms/sec (train step: fwd + bwd + all-reduce + Adam)'
                       if not args.eval_only else 'person x item ELBO terms/sec (forward ELBO only)',
@@ -909,19 +934,37 @@ def main():
                        'noise': 'torch.randn' if (args.torch_optimizer or args.eval_only or args.rng == 'torch') else 'Philox4x32-10 drawn in the prologue kernel (vibo_train_prologue_noise = the vibo_fill_normal streams)',
                        'final_loss_per_term': final_loss / (total_persons * I),
                        'persons_per_rank': P, 'phases_ms': m.get('phase_ms'), 'launch_probe_ms': m.get('form_probe')},
-            'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': 8000.0, 'unit': 'GB/s',
-                         'frac': achieved / 8000.0, 'frac_of_measured_copy_peak': achieved / 6290.0,
-                         # the same bytes over the whole timed step (kernel with its prologue, [finalize, all-reduce], epilogue + Adam + noise)
-                         'frac_step': bytes_per_term * P * I / (dt / args.steps) / 1e9 / 8000.0,
-                         'kernel_ms_insitu': m['insitu']['mean_ms'] if m.get('insitu') else None,
-                         'kernel_ms_events': m.get('events_ms'),
-                         'kernel_timing_insitu': m.get('insitu'),
-                         'frac_note': frac_note,
-                         'traffic': traffic, 'traffic_note': traffic_note,
-                         'kernel': 'vibo::msplit_kernel (its own prologue forms the item sample and the encoder table)' + (' + the finalize helper' if world > 1 else ''),
-                         'kernel_ms': kern_ms, 'kernel_timing': m.get('instep'), 'bare_launch_ms': m.get('bare_ms'),
-                         'bytes_per_term': bytes_per_term},
         }
+        if args.full:
+            kern_ms = m['kern_ms']
+            bytes_per_term = 5.0 + 12.0 * A / I
+            achieved = bytes_per_term * P * I / (kern_ms * 1e-3) / 1e9 if kern_ms > 0 else 0.0
+            traffic, traffic_note = (parse_traffic(kernel_tag) if default_wl and A == 8 else (None, 'not measured for this workload'))
+            frac_note = ''
+            if m.get('insitu'):
+                frac_note += ('frac = algorithmic bytes / kernel_ms_insitu: the fused kernel\'s mean duration over every launch of the timed region\'s '
+                              'blocks, stamped by the kernel itself (earliest workgroup entry -> latest workgroup exit on the chip-wide 100 MHz clock; '
+                              'kernel_timing_insitu).  kernel_ms_events = the estimate of rounds 4-5, kept beside it: ')
+            if m.get('instep'):
+                frac_note += ('the fused call\'s mean duration in the step captured as its two halves and replayed back to back right after the timed '
+                              'region, HIP events on the launch stream around the first (an upper bound: the event packets cost a few us; kernel_timing '
+                              'has mean / min / max' + (', mean = max over ranks' if world > 1 else '') + '); ')
+            elif not m.get('insitu'):
+                frac_note += 'frac = algorithmic bytes / mean duration of the fused call by HIP events on its stream (eager pass after the timed region); '
+            frac_note += ('bare_launch_ms = the same call in a loop of bare eager launches (a note, not the claim); frac_step = the same bytes / ms_per_step '
+                          f'(median block); the rocprofv3 kernel-trace average of the same command is in profiles/{PROFILE_FILE}')
+            line['roofline'] = {'bound': 'hbm', 'achieved': achieved, 'peak': 8000.0, 'unit': 'GB/s',
+                                'frac': achieved / 8000.0, 'frac_of_measured_copy_peak': achieved / 6290.0,
+                                # the same bytes over the whole timed step (kernel with its prologue, [finalize, all-reduce], epilogue + Adam + noise)
+                                'frac_step': bytes_per_term * P * I / (dt / args.steps) / 1e9 / 8000.0,
+                                'kernel_ms_insitu': m['insitu']['mean_ms'] if m.get('insitu') else None,
+                                'kernel_ms_events': m.get('events_ms'),
+                                'kernel_timing_insitu': m.get('insitu'),
+                                'frac_note': frac_note,
+                                'traffic': traffic, 'traffic_note': traffic_note,
+                                'kernel': 'vibo::msplit_kernel (its own prologue forms the item sample and the encoder table)' + (' + the finalize helper' if world > 1 else ''),
+                                'kernel_ms': kern_ms, 'kernel_timing': m.get('instep'), 'bare_launch_ms': m.get('bare_ms'),
+                                'bytes_per_term': bytes_per_term}
         if also_weak is not None:
             line['also_weak'] = also_weak
         if m.get('rel') is not None:
@@ -935,7 +978,7 @@ def main():
             line['also_config2'] = also_config2
         if format_p is not None:
             line['format_p'] = format_p
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line['cpu_baseline'] = cpu_baseline(args, irt)
         print(json.dumps(line))
     if dist is not None:

@@ -109,7 +109,7 @@ def test_bench_two_ranks_share_one_device_over_gloo(scaling):
     env = dict(os.environ, VIBO_BENCH_ONE_DEVICE='1', PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, 'variational-item-response-theory-public_amd')]))
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '2', '--master-addr', '127.0.0.1',
            '--master-port', '29571', os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '4', '--warmup', '1', '--scaling', scaling,
-           '--persons', '100000']          # (otherwise the flags the driver passes: extras, `also` and Format P legs must not deadlock)
+           '--persons', '100000', '--full']          # (--full: the extras, `also` and Format P legs must not deadlock either)
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Run on the GPU box: rocprofv3 evidence for `python bench.py --steps 5 --warmup 2 --no-cpu-baseline`.
+# Run on an MI355X: rocprofv3 evidence for `python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline`.
 # Writes a text summary to gpurun_out/profile_summary.txt (the rocpd databases are deleted: too large to copy back).
 # Counter passes follow MI355X_MICROARCH.md: FETCH_SIZE and WRITE_SIZE in separate --pmc passes, no tracing flags
 # other than the implicit kernel dispatch table.
@@ -10,7 +10,7 @@ W=/tmp/vibo_prof; rm -rf $W; mkdir -p $W
 cd /tmp && export TMPDIR=/tmp
 # (--also-ability-dim 0 --no-also-config2: those legs run the same kernel instantiation and would blur the per-kernel averages;
 #  config 2 -- 100k x 1k, ability_dim 1 -- gets its own kernel trace at the end)
-B="python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra --also-ability-dim 0 --no-also-config2 $BENCH_ARGS"
+B="python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra --also-ability-dim 0 --no-also-config2 $BENCH_ARGS"
 S=$OUT/profile_summary.txt
 {
 echo "# command: rocprofv3 --kernel-trace --stats -- $B"
@@ -28,7 +28,7 @@ for pass in "FETCH_SIZE" "WRITE_SIZE" "SQ_WAVES SQ_WAVE_CYCLES SQ_INSTS_VALU SQ_
   python $R/tools/rocpd_summary.py $W/$n/p_results.db vibo | grep -E "ElboParams|msplit_kernel|split_kernel|finalize|epilogue|prologue"
 done
 echo; echo "# BASELINE configs[1] (100k x 1k, ability_dim 1) as the main workload of the same command:"
-C2="python $R/bench.py --steps 20 --warmup 3 --persons 100000 --ability-dim 1 --no-cpu-baseline --no-extra --also-ability-dim 0 --no-also-config2 --no-format-p"
+C2="python $R/bench.py --full --steps 20 --warmup 3 --persons 100000 --ability-dim 1 --no-cpu-baseline --no-extra --also-ability-dim 0 --no-also-config2 --no-format-p"
 echo "# command: rocprofv3 --kernel-trace --stats -- $C2"
 rocprofv3 --kernel-trace --stats -d $W/k2 -o kt -- $C2 > $W/k2.log 2>&1
 grep "^{" $W/k2.log | cut -c1-400

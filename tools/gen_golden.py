@@ -336,7 +336,10 @@ def saturation_3pl_case(ref_models, ref_utils, out_dir):
             rec[f'll_g{gi}_x{int(x)}'] = ll.detach().reshape(-1).numpy()
             rec[f'dll_db_g{gi}_x{int(x)}'] = g[:, 1].numpy()
             rec[f'dll_dguess_g{gi}_x{int(x)}'] = g[:, 2].numpy()
-    np.savez_compressed(os.path.join(out_dir, 'saturation_3pl.npz'), **rec)
+    # under MKL_CBWR=COMPATIBLE (MKL's code path that every x86-64 host reproduces; the default one depends on the CPU):
+    # the twin fixture the host-independent bitwise test reads
+    name = 'saturation_3pl_mkl_compatible' if os.environ.get('MKL_CBWR') == 'COMPATIBLE' else 'saturation_3pl'
+    np.savez_compressed(os.path.join(out_dir, f'{name}.npz'), **rec)
 
 
 def seeded_init_case(ref_models, out_dir):
@@ -472,6 +475,8 @@ def main():
         if args.only and args.only not in case[0]:
             continue
         print(f'{case[0]:34s} loss={run_mle_case(ref_models, case, out_dir):.6f}')
+    if args.only == 'saturation_3pl':         # MKL_CBWR=COMPATIBLE python tools/gen_golden.py --only saturation_3pl
+        saturation_3pl_case(ref_models, ref_utils, out_dir)
     if not args.only:
         saturation_case(ref_utils, out_dir)
         saturation_3pl_case(ref_models, ref_utils, out_dir)
