@@ -345,12 +345,21 @@ int vibo_train_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, c
  *     for vibo_train_epilogue_fused.  vibo_train_step_supported(d): bit 0 = this descriptor can take the folded step
  *     (single-launch row-split path: 4..1024 items, chunkable rows, no int64 mask, KL regulariser, gradients; otherwise the
  *     call returns -8), bit 1 = skip_finalize too.
+ * vibo_elbo_fwd_bwd_step_noise = vibo_elbo_fwd_bwd_step that may draw the ability noise itself.  Where
+ *     vibo_train_step_draws_noise(d) is 1 (the folded step runs the matrix row-split kernel):
+ *       eps == NULL: the kernel draws eps[b][a] = entry b * A + a of vibo_fill_normal's stream ability_stream_id of `seed`
+ *                    at counter step_count[1] -- the values vibo_fill_normal(eps, B * A, seed, step_count + 1,
+ *                    ability_stream_id) would leave in memory, bit for bit (row b = minibatch position, row_index or not);
+ *       ability_mu == ability_logvar == NULL: the posterior's mean / log-variance are not written (`ability` still is).
+ *     The same NULLs are accepted by vibo_elbo_fwd_bwd_step (ability_mu / ability_logvar) there; elsewhere they return -5.
+ *     A step that draws its own noise needs no eps_ability fill from the epilogue before it: pass eps_ability = NULL,
+ *     n_eps_ability = 0 to vibo_train_epilogue_fused (no noise blocks) and skip the fill in front of vibo_train_prime.
  * vibo_train_epilogue_fused = [finalize] + vibo_train_epilogue for THIS step + vibo_train_prologue_noise for the NEXT one.
  *     workspace != NULL: the workspace a vibo_elbo_fwd_bwd_step(skip_finalize) call with the same descriptor just filled;
  *         the fixed-order sums over its partial records happen here (same order as the stand-alone finalize: bit-identical)
  *         and are also written to `flat` ([8 scalars | grad_table[2][2][2A] | grad_item[I][D]]).
  *     workspace == NULL: `flat` already holds the sums (person-sharded: finalize ran before the all-reduce).
- *     Then, from the updated parameters: eps_item (in place) and eps_ability[0 .. n_eps_ability) are redrawn with the
+ *     Then, from the updated parameters: eps_item (in place) and eps_ability[0 .. n_eps_ability) (none: NULL, 0) are redrawn with the
  *     vibo_fill_normal streams 0 / ability_stream_id at counter step_count[0] (= what the next step's
  *     vibo_train_prologue_noise would draw), item_feat / the next half of kl_parts / table / saved_h are recomputed --
  *     the same statements in the same order as vibo_train_prologue: the two forms of the step agree bit for bit.
@@ -364,6 +373,11 @@ int vibo_elbo_fwd_bwd_step(const vibo_desc* d, int32_t* step_count, int skip_fin
                            const int64_t* row_index, const float* table, const float* item, const float* eps, float* out_scalars,
                            float* ability_mu, float* ability_logvar, float* ability, float* grad_table, float* grad_item,
                            void* workspace, size_t workspace_bytes, void* stream);
+int vibo_train_step_draws_noise(const vibo_desc* d);
+int vibo_elbo_fwd_bwd_step_noise(const vibo_desc* d, int32_t* step_count, int skip_finalize, const float* response, const void* mask,
+                                 const int64_t* row_index, const float* table, const float* item, const float* eps, uint64_t seed,
+                                 uint32_t ability_stream_id, float* out_scalars, float* ability_mu, float* ability_logvar, float* ability,
+                                 float* grad_table, float* grad_item, void* workspace, size_t workspace_bytes, void* stream);
 int vibo_train_epilogue_fused(const vibo_desc* d, int hidden_dim, const void* workspace, float* flat, float* saved_h,
                               float* kl_parts, float* eps_item, const float* beta, const float* lr, int32_t* step_count,
                               float* mlp_params, float* mlp_m, float* mlp_v, float* item_mu, float* item_logvar, float* item_m,

@@ -1004,6 +1004,8 @@ static bool step_plan_ok(const vibo_desc* d, const Plan& pl) {
     return d->posterior == VIBO_POSTERIOR_UNCONDITIONAL && d->n_flows == 0 && d->reg_mode == VIBO_REG_KL && d->want_grad &&
            !pl.general && pl.panels == 0 && pl.split_ok;
 }
+// ... and where that step runs the matrix kernel, it may draw its own ability noise and skip the posterior's mean / log-variance
+static bool step_draws_noise(const vibo_desc* d, const Plan& pl) { return step_plan_ok(d, pl) && pl.msplit; }
 
 // counts of the call's rows from the caller's per-source-row counts (vibo_elbo_fwd_bwd_counts with a row_index)
 __global__ __launch_bounds__(256) void gather_counts_kernel(const int32_t* __restrict__ all, const int64_t* __restrict__ row_index,
@@ -1016,12 +1018,17 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, int32_t* step_count, int skip_f
                              const int64_t* row_index, const float* table, const float* item, const float* eps, const float* flow,
                              float* out_scalars, float* ability_mu, float* ability_logvar, float* ability,
                              float* ability_k, float* ability_ladj, float* grad_table, float* grad_item,
-                             float* grad_flow, void* workspace, size_t workspace_bytes, void* stream, const int32_t* row_counts = nullptr) {
+                             float* grad_flow, void* workspace, size_t workspace_bytes, void* stream, const int32_t* row_counts = nullptr,
+                             uint64_t noise_seed = 0, uint32_t noise_stream = 0) {
     const int num_cu = device_cus();
     int rc = check_desc(d);
     if (rc) return rc;
-    if ((!response && d->mask_dtype != VIBO_MASK_CODES) || !table || !item || !eps || !out_scalars || !ability_mu || !ability_logvar || !ability)
+    if ((!response && d->mask_dtype != VIBO_MASK_CODES) || !table || !item || !out_scalars || !ability)
         return fail(-5, "null required pointer");
+    // (null eps / ability_mu / ability_logvar: the folded step on the matrix kernel only, checked once the plan is known)
+    const bool own_post = eps && ability_mu && ability_logvar;
+    if (!own_post && !step_count) return fail(-5, "null required pointer");
+    if ((ability_mu == nullptr) != (ability_logvar == nullptr)) return fail(-5, "ability_mu / ability_logvar: both or neither");
     if ((d->mask_dtype == VIBO_MASK_NONE) != (mask == nullptr)) return fail(-5, "mask pointer / mask_dtype mismatch");
     if (d->want_grad && (!grad_table || !grad_item)) return fail(-5, "want_grad needs grad_table and grad_item");
     if (d->n_flows > 0 && (!flow || !ability_k || !ability_ladj)) return fail(-5, "flows need flow, ability_k, ability_ladj");
@@ -1044,6 +1051,9 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, int32_t* step_count, int skip_f
     if ((step_count || skip_finalize) && !(step_plan_ok(d, pl) && vec))
         return fail(-8, "vibo_elbo_fwd_bwd_step: single-launch row-split calls of the plain model only (unconditional posterior, no "
                         "flows, KL regulariser, gradients, 4..1024 items, aligned rows): use vibo_train_prologue + vibo_elbo_fwd_bwd");
+    if (!own_post && !step_draws_noise(d, pl))
+        return fail(-5, "null eps / ability_mu / ability_logvar: only where the folded step runs the matrix kernel "
+                        "(vibo_train_step_draws_noise)");
     if (pl.general || (d->n_flows > 0 && !(pl.split_ok && vec) && pl.panels == 0) || (pl.panels > 0 && !vec)) {
         const size_t n_table = (size_t)(d->posterior == VIBO_POSTERIOR_CONDITIONAL ? 2 * I * 2 * A : 2 * 2 * A);
         const size_t n_flow = (size_t)d->n_flows * (2 * A + 1);
@@ -1097,6 +1107,7 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, int32_t* step_count, int skip_f
     p.row_cnt = nullptr; p.item0 = 0; p.I_total = I; p.primary = 1;
     p.step_tick = step_count;
     p.insitu = g_insitu;
+    p.noise_seed_lo = (uint32_t)noise_seed; p.noise_seed_hi = (uint32_t)(noise_seed >> 32); p.noise_stream = noise_stream;
 
     const bool grad = d->want_grad != 0;
     int nblk_used = pl.nblk;
@@ -1352,6 +1363,23 @@ int vibo_elbo_fwd_bwd_step(const vibo_desc* d, int32_t* step_count, int skip_fin
                              ability_logvar, ability, nullptr, nullptr, grad_table, grad_item, nullptr, workspace, workspace_bytes, stream);
 }
 
+int vibo_train_step_draws_noise(const vibo_desc* d) {
+    if (check_desc(d) != 0) return 0;
+    Plan pl;
+    if (make_plan(d, &pl) < 0) return 0;
+    return step_draws_noise(d, pl) ? 1 : 0;
+}
+
+int vibo_elbo_fwd_bwd_step_noise(const vibo_desc* d, int32_t* step_count, int skip_finalize, const float* response, const void* mask,
+                                 const int64_t* row_index, const float* table, const float* item, const float* eps, uint64_t seed,
+                                 uint32_t ability_stream_id, float* out_scalars, float* ability_mu, float* ability_logvar, float* ability,
+                                 float* grad_table, float* grad_item, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!step_count) return fail(-5, "null step_count");
+    return elbo_fwd_bwd_impl(d, step_count, skip_finalize, response, mask, row_index, table, item, eps, nullptr, out_scalars, ability_mu,
+                             ability_logvar, ability, nullptr, nullptr, grad_table, grad_item, nullptr, workspace, workspace_bytes, stream,
+                             nullptr, seed, ability_stream_id);
+}
+
 int vibo_train_epilogue_fused(const vibo_desc* d, int hidden_dim, const void* workspace, float* flat, float* saved_h,
                               float* kl_parts, float* eps_item, const float* beta, const float* lr, int32_t* step_count,
                               float* mlp_params, float* mlp_m, float* mlp_v, float* item_mu, float* item_logvar, float* item_m,
@@ -1363,7 +1391,7 @@ int vibo_train_epilogue_fused(const vibo_desc* d, int hidden_dim, const void* wo
     if (d->posterior != VIBO_POSTERIOR_UNCONDITIONAL || d->n_flows != 0 || d->reg_mode != VIBO_REG_KL)
         return fail(-6, "vibo_train_epilogue_fused: plain model only (unconditional posterior, no flows, KL regulariser)");
     if (!flat || !saved_h || !kl_parts || !eps_item || !beta || !lr || !step_count || !mlp_params || !mlp_m || !mlp_v || !item_mu ||
-        !item_logvar || !item_m || !item_v || !loss_out || !item_feat || !table || !eps_ability || n_eps_ability < 0)
+        !item_logvar || !item_m || !item_v || !loss_out || !item_feat || !table || (!eps_ability && n_eps_ability != 0) || n_eps_ability < 0)
         return fail(-5, "null required pointer");
     EpiParams e;
     memset(&e, 0, sizeof(e));

@@ -32,6 +32,7 @@
 #include "../../include/vibo_hip.h"
 #include "vibo_device.hpp"
 #include "vibo_params.hpp"
+#include "vibo_philox.hpp"
 
 #ifdef VIBO_MS_TIMING
 // development build (make TIMING=1): shader-clock time per phase of the batch loop, summed per wave
@@ -92,6 +93,8 @@ constexpr int kMsGuessFloats = 2 * 4 * 16;
 // XM == 3 only (behind the guess block): per wave the experts of its 128 items -- [u-step][tile t][chunk i16] x (tau | mu tau of a
 // wrong answer, tau | mu tau of a right one) -- and its share of the batch's per-person sums [lam | s][row]
 constexpr int kMsFuseFloats = 2 * 4 * 16 * 4 + 2 * kMsRows;
+// the folded train step's own ability noise (p.eps null): one batch's 32 rows x A entries, behind everything else
+constexpr int kMsNoiseBytes = kMsRows * 8 * (int)sizeof(float);
 inline size_t msplit_lds_bytes(int nw, bool flows = false, bool guess = false, bool fuse = false) {
     return sizeof(MsCommonLds) + (size_t)nw * sizeof(MsWaveLds) + (flows ? sizeof(MsFlowLds) : 0) +
            (guess ? (size_t)nw * kMsGuessFloats * sizeof(float) : 0) + (fuse ? (size_t)nw * kMsFuseFloats * sizeof(float) : 0);
@@ -322,6 +325,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             s0 = q; s1 = 4; step = nw;
         }
     };
+    constexpr bool kDraw = XM == 0 && !FLOWS && GRAD;
+    const bool draw = kDraw && p.eps == nullptr;      // (wave-uniform) the kernel draws the noise: see draw_eps
     float epn = 0.f;                                  // eps of this wave's slot of the next batch (4 or more waves), loaded a batch ahead
     auto fetch_eps = [&](const int bt, const int par) __attribute__((always_inline)) {
         if ((!NW8 && nw < 4) || bt >= n_batches) return;
@@ -334,7 +339,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             //  values, reloaded from scratch right here in every batch)
             int ed = lane & 7;
             asm volatile("" : "+v"(ed));
-            epn = (ed < A && row < p.B) ? p.eps[(long long)row * A + ed] : 0.f;
+            if (!draw) epn = (ed < A && row < p.B) ? p.eps[(long long)row * A + ed] : 0.f;
             if constexpr (XGIVEN && kPrs) {            // caller-supplied posterior (given_pre_kernel's statements)
                 const bool lv = ed < A && row < p.B;
                 const float* po = p.given_post + (size_t)(lv ? row : 0) * 2 * A;
@@ -354,6 +359,37 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 }
             }
         }
+    };
+    // The folded train step's ability noise drawn here (p.eps null; XM 0 without flows, with gradients: the host checks): per batch
+    // ONE wave draws the batch's 32 rows x A stream entries -- 8 A Philox blocks, one per lane (entry (32 bt + r) A + ed: a batch
+    // starts on a block boundary) -- a batch ahead, where fetch_eps sits, into 1 KB of LDS; the slot lanes read it behind the next
+    // batch barrier.  The same values vibo_fill_normal(eps, B A, seed, step_count + 1, stream) leaves in memory, bit for bit.  The
+    // drawing wave rotates with the batch (its ~100 VALU instructions land on each SIMD in turn).  One buffer is enough: it is
+    // written after barrier B of the batch before, whose slot lanes read theirs between its barriers A and B.
+    float* const nz = reinterpret_cast<float*>(ms_smem + sizeof(MsCommonLds) + (size_t)nw * sizeof(MsWaveLds) +
+                                               (IRT == 3 ? (size_t)nw * kMsGuessFloats * sizeof(float) : 0));
+    const uint32_t nz_step = draw ? (uint32_t)__builtin_amdgcn_readfirstlane(p.step_tick[1]) : 0u;     // completed steps
+    int nz_wave = 0;
+    auto draw_eps = [&](const int bt) __attribute__((always_inline)) {
+        if constexpr (kDraw) {
+            if (draw) {
+                if (q == nz_wave && bt < n_batches && lane < 8 * A)
+                    reinterpret_cast<float4*>(nz)[lane] =
+                        philox_normal4((long long)bt * (8 * A) + lane, nz_step, p.noise_stream, p.noise_seed_lo, p.noise_seed_hi);
+                nz_wave = nz_wave + 1 == nw ? 0 : nz_wave + 1;
+            }
+        }
+    };
+    // eps of slot s of batch bt: drawn (LDS) or loaded (e0)
+    auto slot_eps = [&](const int bt, const int s, const float e0) __attribute__((always_inline)) {
+        if constexpr (kDraw) {
+            if (draw) {
+                const int r = (64 * s + lane) >> 3;
+                const float v = nz[r * A + ed];
+                return (ed < A && bt * R + r < p.B) ? v : 0.f;
+            }
+        }
+        return e0;
     };
     // ---- One-shot requests.
     // What the start of a launch costs (tools/ms_timing.py, prologue marks; 100 000 x 1 000): every workgroup needs its whole first
@@ -376,6 +412,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) load_quarter(bt, src_first, 1, j, x2, m2);
             fetch_eps(bt, 0);
+            draw_eps(bt);
             fetch_idx(bt + G, ridx_n);
         }
     };
@@ -903,8 +940,10 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             const float alv = -kLn2 * fast_log2(lam);
             // (non-temporal: 96 MB of per-person outputs per 1M x 8 launch that nothing on the device reads back soon -- kept out
             //  of the L2 the row loads share their segment-edge lines through: -0.9 % on the headline call)
-            __builtin_nontemporal_store(amu, p.ability_mu + o);
-            __builtin_nontemporal_store(alv, p.ability_logvar + o);
+            if (!kDraw || p.ability_mu) {           // (the folded train step passes none: nothing reads them)
+                __builtin_nontemporal_store(amu, p.ability_mu + o);
+                __builtin_nontemporal_store(alv, p.ability_logvar + o);
+            }
             __builtin_nontemporal_store(th0, p.ability + o);
             if constexpr (FLOWS) {
                 p.ability_k[o] = thv;
@@ -1074,16 +1113,16 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
 #pragma unroll 1
                 for (int s = s0; s < s1; s += step) {
                     float eps_c = epn;
-                    if (nw < 4) {
+                    if (nw < 4 && !draw) {
                         const int row = bt * R + ((64 * s + lane) >> 3);
                         eps_c = (ed < A && row < p.B) ? p.eps[(long long)row * A + ed] : 0.f;
                     }
-                    forward_slot(std::integral_constant<bool, EXTRA>{}, bt, par, s, eps_c);
+                    forward_slot(std::integral_constant<bool, EXTRA>{}, bt, par, s, slot_eps(bt, s, eps_c));
                 }
                 return;
             }
         }
-        if (s0 < s1) forward_slot(std::false_type{}, bt, par, s0, epn);
+        if (s0 < s1) forward_slot(std::false_type{}, bt, par, s0, slot_eps(bt, s0, epn));
     };
     auto person_backward = [&](const int bt, const int par) {
         int s0, s1, step;
@@ -1481,6 +1520,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         auto pack_a_burst_b = [&]() {
             pack_half(nxt, 0, cwB0, cwB1, pk, x, m, sn);
             fetch_eps(nxt, par ^ 1);                  // (complete by the second pack: free to carry across the back edge)
+            draw_eps(nxt);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int j = 0; j < 4; ++j) load_quarter(nxt, sn, 1, j, x, m);
@@ -1540,6 +1580,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             tile(IC0{}, IC3{}, db0, db1, da0, da1, cwA0, bopA, bopB);
             MS_T(0)
             fetch_eps(nxt, par ^ 1);                  // (complete by the second pack: free to carry across the back edge)
+            draw_eps(nxt);
             MS_T(1)
         } else {
             tile(IC0{}, IC0{}, da0, da1, db0, db1, cwA0, bopB, bopA);
@@ -1722,11 +1763,14 @@ static hipError_t launch_msplit_inst(const ElboParams& p, int nw, int grid, hipS
     static bool lds_opt_in = false;
     if (!lds_opt_in) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)msplit_lds_bytes(8, FLOWS, IRT == 3));
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)msplit_lds_bytes(8, FLOWS, IRT == 3) + kMsNoiseBytes);
         if (e != hipSuccess) return e;
         lds_opt_in = true;
     }
-    hipLaunchKernelGGL((msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>), dim3(grid), dim3(64 * nw), msplit_lds_bytes(nw, FLOWS, IRT == 3), s, p);
+    // (p.eps null: the kernel draws the noise -- XM 0 without flows, with gradients only; 1 KB more LDS)
+    if (!p.eps && !(XM == 0 && !FLOWS && GRAD && p.step_tick)) return hipErrorInvalidValue;
+    const size_t lds = msplit_lds_bytes(nw, FLOWS, IRT == 3) + (p.eps ? 0 : kMsNoiseBytes);
+    hipLaunchKernelGGL((msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>), dim3(grid), dim3(64 * nw), lds, s, p);
     return hipGetLastError();
 }
 // XM == 3 (p.cond_table): its own translation units (vibo_msplit_xa / xg.hip)

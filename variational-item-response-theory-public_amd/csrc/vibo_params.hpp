@@ -87,6 +87,10 @@ struct ElboParams {
     PartialLayout lay;
     int32_t* step_tick;       // non-null: workgroup 0 increments it (the train step's Adam counter, vibo_elbo_fwd_bwd_step)
     unsigned long long* insitu;   // non-null: the in-situ launch timer's eight words (vibo_set_insitu_timer; matrix row-split kernel)
+    // eps null (the folded train step on the matrix row-split kernel): the kernel draws the ability noise itself, Philox stream
+    // noise_stream of seed noise_seed_hi:lo at counter step_tick[1] -- what vibo_fill_normal(eps, B A, seed, step_tick + 1,
+    // noise_stream) would have left in eps
+    uint32_t noise_seed_lo, noise_seed_hi, noise_stream;
 };
 
 // the conditional posterior's table-gradient finalize riding in the ELBO finalize launch (vibo_cond_finalize.hpp)

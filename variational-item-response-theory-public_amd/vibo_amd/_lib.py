@@ -72,7 +72,8 @@ EXPORTED_SYMBOLS = ('vibo_version', 'vibo_last_error_string', 'vibo_workspace_by
                     'vibo_code_table_scratch_bytes', 'vibo_code_table_sum_forward', 'vibo_code_table_sum_backward',
                     'vibo_train_step_supported', 'vibo_elbo_fwd_bwd_step', 'vibo_train_epilogue_fused', 'vibo_train_prime',
                     'vibo_mtrain_param_floats', 'vibo_mtrain_prologue', 'vibo_mean_encoder_backward_sets', 'vibo_mtrain_epilogue',
-                    'vibo_set_insitu_timer', 'vibo_insitu_timer_reset', 'vibo_selftest_lane_swaps', 'vibo_elbo_fwd_bwd_counts')
+                    'vibo_set_insitu_timer', 'vibo_insitu_timer_reset', 'vibo_selftest_lane_swaps', 'vibo_elbo_fwd_bwd_counts',
+                    'vibo_train_step_draws_noise', 'vibo_elbo_fwd_bwd_step_noise')
 
 _lib = None
 
@@ -170,6 +171,13 @@ def load():
     lib.vibo_elbo_fwd_bwd_step.argtypes = [dp, vp, ctypes.c_int, fp, vp, i64p, fp, fp, fp,              # step counter, skip, inputs
                                            fp, fp, fp, fp, fp, fp,                                   # scalars, posterior, grads
                                            vp, ctypes.c_size_t, vp]                                  # workspace, stream
+    lib.vibo_train_step_draws_noise.restype = ctypes.c_int
+    lib.vibo_train_step_draws_noise.argtypes = [dp]
+    lib.vibo_elbo_fwd_bwd_step_noise.restype = ctypes.c_int
+    lib.vibo_elbo_fwd_bwd_step_noise.argtypes = [dp, vp, ctypes.c_int, fp, vp, i64p, fp, fp, fp,        # step counter, skip, inputs
+                                                 ctypes.c_uint64, ctypes.c_uint32,                      # noise seed, stream
+                                                 fp, fp, fp, fp, fp, fp,                                # scalars, posterior, grads
+                                                 vp, ctypes.c_size_t, vp]                               # workspace, stream
     lib.vibo_train_epilogue_fused.restype = ctypes.c_int
     lib.vibo_train_epilogue_fused.argtypes = ([dp, ctypes.c_int, vp] + [fp] * 6 + [vp] + [fp] * 8 +
                                               [ctypes.c_uint64, fp, fp, fp, ctypes.c_int64, ctypes.c_uint32, vp])

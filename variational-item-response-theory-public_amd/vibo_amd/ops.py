@@ -60,8 +60,8 @@ class RawElbo:
     n_item: int
     n_flow: int
     table_shape: tuple
-    ability_mu: torch.Tensor
-    ability_logvar: torch.Tensor
+    ability_mu: Optional[torch.Tensor]      # (None: the folded train step that draws its own noise)
+    ability_logvar: Optional[torch.Tensor]
     ability: torch.Tensor
     ability_k: Optional[torch.Tensor]
     ability_ladj: Optional[torch.Tensor]
@@ -370,9 +370,11 @@ def _resident_row_counts(spec, response, mask, mask_code):
 def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, eps, flow, reg_mode,
                      want_grad, num_person, train_step=None):
     """Single call into vibo_elbo_fwd_bwd on the current stream.
-    train_step = (step_count tensor, skip_finalize): vibo_elbo_fwd_bwd_step instead -- the same call that also ticks Adam's
-    step counter (the folded train step, trainer.FusedTrainer); with skip_finalize the partial records stay in
-    RawElbo.workspace for vibo_train_epilogue_fused and `flat` is filled by that call."""
+    train_step = (step_count tensor, skip_finalize[, (seed, stream) | None]): vibo_elbo_fwd_bwd_step instead -- the same call that
+    also ticks Adam's step counter (the folded train step, trainer.FusedTrainer); with skip_finalize the partial records stay in
+    RawElbo.workspace for vibo_train_epilogue_fused and `flat` is filled by that call.  With (seed, stream) (where
+    vibo_train_step_draws_noise says so; eps None) the kernel draws the ability noise of Philox stream `stream` at counter
+    step_count[1] itself and writes no posterior mean / log-variance: RawElbo.ability_mu / ability_logvar are None."""
     lib = _lib.load()
     _require_device(response, mask, table, item, eps)
     dev = response.device
@@ -386,7 +388,8 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     n_flow = spec.n_flows * (2 * A + 1)
     n_item = I * D
     flat = torch.empty(_lib.NUM_SCALARS + 2 * n_table + n_item + 2 * n_flow, dtype=torch.float32, device=dev)
-    post = torch.empty(3, B, A, dtype=torch.float32, device=dev)
+    own_noise = train_step is not None and len(train_step) > 2 and train_step[2] is not None
+    post = torch.empty(1 if own_noise else 3, B, A, dtype=torch.float32, device=dev)
     ability_k = torch.empty(B, A, dtype=torch.float32, device=dev) if spec.n_flows else None
     ladj = torch.empty(B, dtype=torch.float32, device=dev) if spec.n_flows else None
     d = _make_desc(spec, B, I, mask_code, reg_mode, want_grad, response.stride(0),
@@ -400,7 +403,15 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     o_item = o_tab + 2 * n_table
     o_flow = o_item + n_item
     stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    if train_step is not None:
+    if own_noise:
+        rc = lib.vibo_elbo_fwd_bwd_step_noise(
+            ctypes.byref(d), _ptr(train_step[0]), 1 if train_step[1] else 0, _ptr(response), _ptr(mask), _ptr(row_index),
+            _ptr(table), _ptr(item), None, ctypes.c_uint64(train_step[2][0]), ctypes.c_uint32(train_step[2][1]),
+            ctypes.c_void_p(fbase), None, None, _ptr(post[0]),
+            ctypes.c_void_p(fbase + esz * o_tab), ctypes.c_void_p(fbase + esz * o_item),
+            _ptr(ws), ctypes.c_size_t(ws_bytes), stream)
+        _lib.check(rc, 'vibo_elbo_fwd_bwd_step_noise')
+    elif train_step is not None:
         rc = lib.vibo_elbo_fwd_bwd_step(
             ctypes.byref(d), _ptr(train_step[0]), 1 if train_step[1] else 0, _ptr(response), _ptr(mask), _ptr(row_index),
             _ptr(table), _ptr(item), _ptr(eps),
@@ -427,7 +438,7 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
             _ptr(ws), ctypes.c_size_t(ws_bytes), stream)
         _lib.check(rc, 'vibo_elbo_fwd_bwd')
     raw = RawElbo(flat=flat, n_table=n_table, n_item=n_item, n_flow=n_flow, table_shape=table_shape,
-                  ability_mu=post[0], ability_logvar=post[1], ability=post[2],
+                  ability_mu=None if own_noise else post[0], ability_logvar=None if own_noise else post[1], ability=post[-1],
                   ability_k=ability_k, ability_ladj=ladj)
     if train_step is not None and train_step[1]:
         raw.workspace = ws          # (kept alive until the epilogue has summed the partial records)

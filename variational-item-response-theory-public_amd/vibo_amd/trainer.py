@@ -5,7 +5,10 @@ reference loop (vibo.py:243-268) as TWO kernel launches instead of ~80.
     loss = trainer.step(response, mask, beta=1.0, row_index=rows)      # device scalar, parameters updated in place
 
 What runs (the folded step, `fold=True` with rng='native', the default of the CLI and the benchmark):
-    vibo_elbo_fwd_bwd_step     the fused ELBO forward + backward over the rows (ticks Adam's step counter)
+    vibo_elbo_fwd_bwd_step     the fused ELBO forward + backward over the rows (ticks Adam's step counter); on the matrix
+                               row-split kernel it draws the ability noise itself (vibo_elbo_fwd_bwd_step_noise) and leaves
+                               the posterior's mean / log-variance unwritten: `trainer.last.ability_mu` / `.ability_logvar`
+                               are None there, `trainer.last.ability` (the sample) and `.flat` are what they always were
     [person-sharded: finalize inside that call, then ONE all-reduce of the flat buffer]
     vibo_train_epilogue_fused  finalize (one GPU), loss, encoder-MLP / item backward, Adam -- and the NEXT step's head: Philox
                                noise, item sample, item KL, the 2-row encoder table from the parameters just updated
@@ -18,7 +21,9 @@ re-primes), or build the trainer with fold=False, whose four-launch step recompu
 A folded forward_backward() has to be followed by update() before the next one (it raises otherwise: the second call would
 tick Adam's counter and flip the double-buffered item-KL half under the pending update).  The ability-noise buffer never
 moves once a hipGraph may have captured it: size it up front with `max_batch`, a larger minibatch arriving later bumps
-`trainer.generation` (GraphedTrainStep re-captures when it changes).
+`trainer.generation` (GraphedTrainStep re-captures when it changes).  From the first step that draws its own noise on, no
+epilogue fills that buffer any more (32 MB written and read back per 1M x 8 step saved); a later step on another kernel (a
+short minibatch on the VALU kernel) fills it itself in front of its ELBO launch, and `generation` is bumped once at the switch.
 `fold=False`, rng='torch' (noise from torch's generators: not known a step ahead) and shapes the folded step does not cover
 (more than 1024 items, int64 masks, unaligned rows) take the four-launch form (vibo_train_prologue[_noise] ->
 vibo_elbo_fwd_bwd = kernel + finalize -> vibo_train_epilogue); the two forms agree bit for bit (tests/test_gpu_trainer.py).
@@ -78,6 +83,7 @@ class FusedTrainer:
         self._max_batch = int(max_batch) if max_batch else 0      # persons of the largest minibatch to expect (sizes _eps_cap once)
         self.generation = 0                   # bumped when a buffer a captured hipGraph points at was replaced (re-capture then)
         self._folded_open = False             # a folded forward_backward() whose update() has not run yet
+        self._draw_mode = False               # a folded step drew its own ability noise: epilogues no longer fill _eps_cap
         mlp = model.ability_encoder.mlp
         self.hidden = mlp[0].weight.shape[0]
         if self.hidden > 256:
@@ -249,19 +255,29 @@ class FusedTrainer:
                 self.generation += 1
             self._eps_cap = torch.empty(max(need, self._max_batch * A), device=dev)
             self._primed_for = None
+        # On the matrix kernel the step draws its ability noise in the kernel (the same Philox values the fill would leave):
+        # from then on the epilogues skip the fill, and a step on another kernel fills the buffer itself.  A graph captured
+        # before the switch expects the epilogue's fill: re-capture (`generation`).
+        draws = bool(lib.vibo_train_step_draws_noise(ctypes.byref(d)))
+        if draws and not self._draw_mode:
+            self._draw_mode = True
+            self.generation += 1
         state = (self._eps_cap.numel(),) + self._param_versions()
+        noise_step = ctypes.c_void_p(self._steps.data_ptr() + 4)              # completed steps (step_count[1])
         if self._primed_for != state:
-            noise_step = ctypes.c_void_p(self._steps.data_ptr() + 4)          # completed steps (step_count[1])
             _lib.check(lib.vibo_fill_normal(p(self._eps_item), self._eps_item.numel(), self.seed, noise_step, 0, stream), 'vibo_fill_normal')
-            _lib.check(lib.vibo_fill_normal(p(self._eps_cap), self._eps_cap.numel(), self.seed, noise_step, ab_stream, stream), 'vibo_fill_normal')
+            if not self._draw_mode:
+                _lib.check(lib.vibo_fill_normal(p(self._eps_cap), self._eps_cap.numel(), self.seed, noise_step, ab_stream, stream), 'vibo_fill_normal')
             rc = lib.vibo_train_prime(ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv), p(self._eps_item),
                                       p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts), p(self._steps), stream)
             _lib.check(rc, 'vibo_train_prime')
             self._primed_for = state
         eps_item, eps_ab = self._eps_item, self._eps_cap[:need].view(B, A)
+        if self._draw_mode and not draws:
+            _lib.check(lib.vibo_fill_normal(p(eps_ab), need, self.seed, noise_step, ab_stream, stream), 'vibo_fill_normal')
         fused_finalize = bool(step_bits & 2) and model._reducer is None
-        raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, eps_ab, None, _lib.REG_KL, True, B,
-                                   train_step=(self._steps, fused_finalize))
+        raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, None if draws else eps_ab, None,
+                                   _lib.REG_KL, True, B, train_step=(self._steps, fused_finalize, (self.seed, ab_stream) if draws else None))
         self._pending = (d, eps_item, raw, ab_stream)
         self._folded_open = True
         self.last = raw
@@ -286,7 +302,8 @@ class FusedTrainer:
                                                p(self.kl_parts), p(eps_item), p(self.beta), p(self.lr), p(self._steps),
                                                p(self.mlp_flat), p(self.mlp_m), p(self.mlp_v), p(self.item_mu), p(self.item_lv),
                                                p(self.item_m), p(self.item_v), p(self.loss), self.seed, p(self.item_feat),
-                                               p(self.table), p(self._eps_cap), self._eps_cap.numel(), folded_stream, stream)
+                                               p(self.table), None if self._draw_mode else p(self._eps_cap),
+                                               0 if self._draw_mode else self._eps_cap.numel(), folded_stream, stream)
             _lib.check(rc, 'vibo_train_epilogue_fused')
             return self.loss
         rc = lib.vibo_train_epilogue(ctypes.byref(d), self.hidden, p(raw.flat), p(self.saved_h), p(self.kl_parts),
