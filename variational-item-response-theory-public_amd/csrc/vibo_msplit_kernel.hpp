@@ -509,7 +509,11 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     //
     // Range of the f16 pieces.  A two-piece f16 value carries an ABSOLUTE error of ~2^-24 once its lo piece is subnormal
     // (|x| < 2^-3), and saturates above 65 504.  Two per-launch powers of two keep the operands where the split is good
-    // for any item parameters -- at no cost in the hot path (the cells' codes stay +-1, the logits come out unscaled):
+    // for item parameters of ONE magnitude, whatever it is -- at no cost in the hot path (the cells' codes stay +-1, the
+    // logits come out unscaled).  Both follow the LARGEST |a| and |b| of the workgroup's items (a panel of at most 1024): beside one
+    // outlier item the ordinary items' pieces fall onto the absolute 2^-24 grid (measured, tests/test_gpu_split_worst_case.py,
+    // one |a| = 2^20 item -> 7e-4 on ordinary logits, ~40 x the fp32 bound; one |b| = 2^29 -> 1.4e-3, ~140 x; up to
+    // |a| = 2^10 / |b| = 2^20 within ~4 x):
     //   * theta <-> a balance 2^jsh: the image holds a 2^jsh, the (person, dim) lanes hand over theta 2^-jsh; jsh =
     //     -floor(exponent(max |a|) / 2), i.e. both sides near sqrt(|a theta|) (discriminations of 1e-4 or 1e6 alike).
     //     d LL/d theta = sum g a comes out times 2^jsh, d LL/d a = sum g theta times 2^-jsh: undone for free in the
