@@ -142,7 +142,7 @@ def test_decoder_desc_struct_matches_header():
 
 
 def test_planner_thresholds_agree_with_the_committed_calibration_tables():
-    """want_msplit's thresholds (csrc/vibo_capi.hip) are hand-written from tools/calibrate_planner.py's tables; tools/check_planner_table.py
+    """want_msplit's thresholds (csrc/vibo_planner.hip) are hand-written from tools/calibrate_planner.py's tables; tools/check_planner_table.py
     replays the committed tables (two MI355X boxes, profiles/*planner_calibration*.txt) against vibo_plan_kernel: no calibrated
     shape may go to the kernel that was measured more than 15 % slower on every box (the one island the rules do not follow --
     16 384 x 256 at ability_dim 8, 11-12 % -- stays under that; the tool's default 8 % lists it)."""

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Check the planner's kernel choice (want_msplit in csrc/vibo_capi.hip: matrix row-split kernel vs VALU row-split kernel)
+"""Check the planner's kernel choice (want_msplit in csrc/vibo_planner.hip: matrix row-split kernel vs VALU row-split kernel)
 against this box: time both kernels (vibo_desc.flags pins them) over a grid of persons x items x ability_dim, print the
 measured crossover and every shape where the planner's default is the slower one by more than 5 %.
    python tools/calibrate_planner.py [--grad 1] [--codes] > profiles/rNN_planner_calibration.txt"""

@@ -1,4 +1,4 @@
-"""The planner's kernel choice (csrc/vibo_capi.hip: want_msplit / want_narrow, hand-written thresholds) against the committed
+"""The planner's kernel choice (csrc/vibo_planner.hip: want_msplit / want_narrow, hand-written thresholds) against the committed
 calibration tables (profiles/*planner_calibration*.txt, written by tools/calibrate_planner.py on two MI355X boxes: hipGraph
 replays of both row-split kernels over persons x items x ability_dim).  No GPU needed: vibo_plan_kernel reads the descriptor.
 

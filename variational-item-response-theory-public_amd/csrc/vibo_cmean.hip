@@ -13,7 +13,7 @@
 //     X = [tau | mu tau] with tau = 1/(exp(logvar) + eps) (N = 2 A <= 16: the precision and the precision-weighted mean of a
 //     person's experts, plus the observed count), G = the ELBO kernel's per-person coefficients [head][P1 | P2][dim]
 //     (N = 4 A <= 32), from which d/d mu = S1 tau, d/d logvar = -(S1 mu + S2) tau^2 exp(logvar)  (launch_cond_pre_mfma /
-//     launch_cond_post_mfma, called by vibo_capi.hip around the row-split kernel; round 2 ran these as VALU kernels with one
+//     launch_cond_post_mfma, called by vibo_capi.hip (first_pass / gradient_tail) around the row-split kernel; round 2 ran these as VALU kernels with one
 //     register accumulator per (item, code, coefficient): two launches each at ability_dim 5..8, 4.8 ms at 1M x 1k A = 8).
 //
 // Both run on v_mfma_f32_16x16x32_bf16 straight from the 1-byte cell codes (0 wrong / 1 right / 2 missing).  The one-hot

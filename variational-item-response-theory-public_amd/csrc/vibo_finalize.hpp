@@ -1,5 +1,5 @@
 // vibo_finalize.hpp -- the fixed-order sum over the per-workgroup partial records, shared by finalize_kernel
-// (vibo_capi.hip) and by the train epilogue that folds the finalize into its own launch (vibo_trainer.hip).
+// (vibo_helpers.hip) and by the train epilogue that folds the finalize into its own launch (vibo_trainer.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vibo_params.hpp"

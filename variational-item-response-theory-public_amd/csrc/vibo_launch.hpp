@@ -1,6 +1,6 @@
 // vibo_launch.hpp -- per-ability-width launchers of the fused ELBO kernel.
 // One translation unit per template ability width keeps hipcc compile times
-// parallel (see Makefile); vibo_capi.hip dispatches to these.
+// parallel (see Makefile); vibo_capi.hip dispatches to these (launch_split / run_single).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vibo_params.hpp"
@@ -51,7 +51,7 @@ hipError_t launch_elbo_msplit_xg(const ElboParams& p, int irt, bool grad, int nw
 
 // narrow-row kernel: waves per SIMD each instantiation is compiled for (registers: items x (parameters + gradient accumulators) + one
 // unit of rows; 3PL with gradients at 8 items per lane: 128 registers were 4-12 short -- spilled, and a spill reload waits behind the
-// row loads).  ONE definition for the kernel's launch bounds (vibo_narrow.hip) and the planner's grid (vibo_capi.hip: workgroups per
+// row loads).  ONE definition for the kernel's launch bounds (vibo_narrow.hip) and the planner's grid (vibo_planner.hip: workgroups per
 // CU = waves per SIMD): the grid has to match the occupancy the kernel was compiled for.
 constexpr int narrow_waves_per_simd(int at, int il, bool g3 = false) {
     return at == 1 ? ((g3 && il == 8) ? 3 : 4) : at == 2 ? (il == 4 ? 4 : 3) : (il == 4 ? 3 : 2);
