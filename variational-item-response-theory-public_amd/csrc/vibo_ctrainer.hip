@@ -16,6 +16,7 @@
 #include "../../include/vibo_hip.h"
 #include "vibo_device.hpp"
 #include "vibo_philox.hpp"
+#include "vibo_train_hook.hpp"
 
 namespace vibo {
 
@@ -39,7 +40,7 @@ struct CtLayout {
 };
 __host__ __device__ inline CtLayout ct_layout(int I, int A, int irt, int cond, int F, int H) {
     CtLayout L;
-    L.H = H; L.A = A; L.O = 2 * A; L.D = irt == 1 ? 1 : irt == 2 ? A + 1 : A + 2; L.F = F; L.I = I; L.cond = cond;
+    L.H = H; L.A = A; L.O = 2 * A; L.D = item_feat_dim(irt, A); L.F = F; L.I = I; L.cond = cond;
     L.xin = 1 + (cond ? L.D : 0);
     L.rows = 2 * (cond ? I : 1);
     L.w0 = 0; L.b0 = L.w0 + H * L.xin; L.w1 = L.b0 + H; L.b1 = L.w1 + H * H; L.w2 = L.b1 + H; L.b2 = L.w2 + L.O * H;
@@ -60,7 +61,6 @@ __host__ __device__ inline CtLayout ct_layout(int I, int A, int irt, int cond, i
     return L;
 }
 
-__device__ __forceinline__ float ct_elu(float x) { return x > 0.f ? x : expm1f(x); }
 __device__ __forceinline__ float ct_softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }      // F.softplus (threshold 20)
 __device__ __forceinline__ float ct_tanh(float a) {
     return 1.0f - 2.0f / (1.0f + expf(2.0f * fminf(fmaxf(a, -15.f), 15.f)));      // (the flow kernels' form: vibo_flow.hip)
@@ -99,11 +99,14 @@ __device__ inline void ct_unpack_flow_grad(const float* __restrict__ p, int dim,
     out[2 * dim] = g[2 * dim];
 }
 
-__device__ __forceinline__ void ct_adam(float& p, float& m, float& v, const float g, const float lr, const float bc1, const float bc2_sqrt) {
+// NOT adam_update (vibo_train_hook.hpp): these unpinned expressions compile to other roundings -- v = fma(g, 0.001 g, 0.999 v) and
+// m = two multiplies and an unfused add, against fma(0.999, v, (0.001 g) g) and fma(0.9, m, 0.1 g) there -- so swapping one for the
+// other moves this trainer's parameter trajectories in the last bit.  Kept as it is: merging the two is a change of arithmetic.
+__device__ __forceinline__ void ct_adam(float& p, float& m, float& v, const float g, const float lr, const AdamBias bc) {
     m = 0.9f * m + 0.1f * g;                       // torch: exp_avg.lerp_(grad, 1 - beta1)
     v = 0.999f * v + 0.001f * g * g;
-    const float denom = sqrtf(v) / bc2_sqrt + 1e-8f;
-    p -= (lr / bc1) * (m / denom);
+    const float denom = sqrtf(v) / bc.bc2_sqrt + 1e-8f;
+    p -= (lr / bc.bc1) * (m / denom);
 }
 
 // parameters of the prologue launch (ct_prologue_kernel, after the table tiles below)
@@ -196,14 +199,14 @@ __device__ __forceinline__ void ct_tile_forward(const CtLayout& L, const Feat& f
             float a = R.b0j;
 #pragma unroll
             for (int d = 0; d < kCtMaxDim + 1; ++d) a = fmaf(R.w0r[d], S.X[r][d], a);
-            S.H0[r][j] = j < L.H ? ct_elu(a) : 0.f;
+            S.H0[r][j] = j < L.H ? elu(a) : 0.f;
         }
     }
     __syncthreads();
     const ct_f32x4 c = ct_contract64(S.H0, R.b1v, i16, kk);
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
-        const float h = unit < L.H ? ct_elu(c[rr] + R.b1u) : 0.f;
+        const float h = unit < L.H ? elu(c[rr] + R.b1u) : 0.f;
         h1c[rr] = h;
         S.H1[4 * kk + rr][unit] = h;
     }
@@ -268,9 +271,8 @@ __global__ __launch_bounds__(kCtItems) void ct_prologue_kernel(const CtProParams
         ct_table_body(L, q.params, feat, q.table, q.tpb, (int)blockIdx.x - 1 - L.n_ib - q.ab_blocks, S);
         return;
     }
-    if ((int)blockIdx.x > L.n_ib) {                  // ability noise (stream ab_stream), 4 normals per thread
-        const long long g = (long long)(blockIdx.x - 1 - L.n_ib) * kCtItems + tid;
-        if (4 * g < q.n_ab) store_normal4(q.eps_ab, q.n_ab, g, philox_normal4(g, (uint32_t)q.step_count[1], q.ab_stream, q.seed_lo, q.seed_hi));
+    if ((int)blockIdx.x > L.n_ib) {                  // ability noise (stream ab_stream)
+        ability_noise_block(blockIdx.x - 1 - L.n_ib, kCtItems, tid, q.eps_ab, q.n_ab, (uint32_t)q.step_count[1], q.ab_stream, q.seed_lo, q.seed_hi);
         return;
     }
     if (tid < F) {
@@ -525,8 +527,7 @@ __device__ __forceinline__ void ct_item_update_body(const CtItemParams& q, const
     const int n = L.I * D;
     const size_t o_item = VIBO_NUM_SCALARS + 2 * (size_t)L.rows * L.O;
     const float beta = *q.beta_p, lr = *q.lr_p;
-    const float t_ = (float)q.step_count[0];
-    const float bc1 = 1.0f - powf(0.9f, t_), bc2_sqrt = sqrtf(1.0f - powf(0.999f, t_));
+    const AdamBias bc = adam_bias(q.step_count[0]);
     const bool kl_mode = F == 0;
 #pragma unroll
     for (int d = 0; d < kCtMaxDim; ++d)
@@ -540,8 +541,8 @@ __device__ __forceinline__ void ct_item_update_body(const CtItemParams& q, const
             const float g_lv = gf * 0.5f * expf(0.5f * l) * q.eps[idx] + (kl_mode ? -0.5f * beta * (1.0f - expf(l)) : -0.5f);
             float nm = m, nl = l;
             float m0 = q.im[idx], v0 = q.iv[idx], m1 = q.im[n + idx], v1 = q.iv[n + idx];
-            ct_adam(nm, m0, v0, g_mu, lr, bc1, bc2_sqrt);
-            ct_adam(nl, m1, v1, g_lv, lr, bc1, bc2_sqrt);
+            ct_adam(nm, m0, v0, g_mu, lr, bc);
+            ct_adam(nl, m1, v1, g_lv, lr, bc);
             q.mu[idx] = nm;
             q.lv[idx] = nl;
             q.im[idx] = m0; q.iv[idx] = v0;
@@ -563,8 +564,7 @@ __device__ __forceinline__ void ct_mlp_adam_body(const CtFinParams& q, const int
     __shared__ float part[4][64];
     const int tid = threadIdx.x;
     const float lr = *q.lr_p;
-    const float t_ = (float)q.step_count[0];
-    const float bc1 = 1.0f - powf(0.9f, t_), bc2_sqrt = sqrtf(1.0f - powf(0.999f, t_));
+    const AdamBias bc = adam_bias(q.step_count[0]);
     const int e = tid & 63, sl = tid >> 6;
     const int k = block * 64 + e;
     // (fixed order; four records in flight per thread: the loop is latency-bound)
@@ -585,7 +585,7 @@ __device__ __forceinline__ void ct_mlp_adam_body(const CtFinParams& q, const int
     __syncthreads();
     if (sl == 0 && k < L.n_mlp) {
         const float g = (part[0][e] + part[1][e]) + (part[2][e] + part[3][e]);
-        ct_adam(p, m, v, g, lr, bc1, bc2_sqrt);
+        ct_adam(p, m, v, g, lr, bc);
         q.P[k] = p; q.M[k] = m; q.V[k] = v;
     }
 }
@@ -596,8 +596,7 @@ __device__ __forceinline__ void ct_finish_last_body(const CtFinParams& q) {
     __shared__ float fg[VIBO_MAX_FLOWS][2 * kCtMaxDim + 1];
     const int tid = threadIdx.x;
     const float lr = *q.lr_p;
-    const float t_ = (float)q.step_count[0];
-    const float bc1 = 1.0f - powf(0.9f, t_), bc2_sqrt = sqrtf(1.0f - powf(0.999f, t_));
+    const AdamBias bc = adam_bias(q.step_count[0]);
     const int A = L.A, D = L.D, F = L.F;
     if (tid < 64) {                          // item-side scalars: the prologue's partial sums, fixed order
         float kl = 0.f, lq = 0.f, lp = 0.f;
@@ -629,7 +628,7 @@ __device__ __forceinline__ void ct_finish_last_body(const CtFinParams& q) {
     for (int e = tid; e < nfa; e += 256) {
         const int k = L.fa + e;
         float p = q.P[k], m = q.M[k], v = q.V[k];
-        ct_adam(p, m, v, fg[e / (2 * A + 1)][e % (2 * A + 1)], lr, bc1, bc2_sqrt);
+        ct_adam(p, m, v, fg[e / (2 * A + 1)][e % (2 * A + 1)], lr, bc);
         q.P[k] = p; q.M[k] = m; q.V[k] = v;
     }
     __syncthreads();
@@ -651,7 +650,7 @@ __device__ __forceinline__ void ct_finish_last_body(const CtFinParams& q) {
     for (int e = tid; e < nfi; e += 256) {
         const int k = L.fi + e;
         float p = q.P[k], m = q.M[k], v = q.V[k];
-        ct_adam(p, m, v, fg[e / (2 * D + 1)][e % (2 * D + 1)], lr, bc1, bc2_sqrt);
+        ct_adam(p, m, v, fg[e / (2 * D + 1)][e % (2 * D + 1)], lr, bc);
         q.P[k] = p; q.M[k] = m; q.V[k] = v;
     }
 }

@@ -7,10 +7,10 @@
 // mlp2 is affine in w_p = n_correct / n_observed:  z_p = u + w_p v,  u = W20 h0 + b20,  v = W20 (h1 - h0)  (vibo_mean.hip does the
 // per-person rest).  Here:
 //   mt_prologue_kernel   block 0: the 2-row mlp1 forward, u, v (+ the activations kept for the backward);
-//                        other blocks: item sample / item KL / optional Philox noise, as train_prologue_kernel
+//                        other blocks: item sample / item KL / optional Philox noise: train_prologue_kernel's (vibo_train_hook.hpp)
 //   mt_reduce_kernel     fixed-order sums of vibo_mean_encoder_backward's per-wave records -> d/du | d/dv | d/dW22 | d/db22
 //   mt_epilogue_kernel   block 0: loss, the backward through u, v, mlp2[0] and the 2-row mlp1 by hand, Adam on all of it;
-//                        other blocks: item backward + Adam, as train_epilogue_kernel
+//                        other blocks: item backward + Adam: train_epilogue_kernel's (epi_item_update)
 // Parameter layout (one flat buffer, the nn.Parameters are views of it):
 //   W10 [H] | b10 [H] | W12 [H][H] | b12 [H] | W20 [H][H] | b20 [H] | W22 [2A][H] | b22 [2A]
 #include <hip/hip_runtime.h>
@@ -77,30 +77,11 @@ __global__ __launch_bounds__(256) void mt_prologue_kernel(int H, int A2, int I, 
         }
         return;
     }
-    if ((int)blockIdx.x > n_item_blocks) {          // ability noise (stream ab_stream), 4 normals per thread
-        const long long g = (long long)(blockIdx.x - 1 - n_item_blocks) * 256 + tid;
-        if (4 * g < n_ab) store_normal4(eps_ab, n_ab, g, philox_normal4(g, (uint32_t)step_count[1], ab_stream, seed_lo, seed_hi));
+    if ((int)blockIdx.x > n_item_blocks) {          // ability noise (stream ab_stream)
+        ability_noise_block(blockIdx.x - 1 - n_item_blocks, 256, tid, eps_ab, n_ab, (uint32_t)step_count[1], ab_stream, seed_lo, seed_hi);
         return;
     }
-    // item side: as train_prologue_kernel (dimension-major entries, one KL part per wave)
-    const int n_item_entries = I * D;
-    const int k = (blockIdx.x - 1) * 256 + tid;
-    float kl = 0.f;
-    if (k < n_item_entries) {
-        const int idx = item_entry_index(k, I, D);
-        const float m = mu[idx], l = lv[idx];
-        float e;
-        if (gen) {
-            e = philox_normal1(idx, (uint32_t)step_count[1], 0u, seed_lo, seed_hi);
-            eps_w[idx] = e;
-        } else {
-            e = eps[idx];
-        }
-        item_feat[idx] = item_sample(m, l, e);
-        kl = item_kl_term(m, l);
-    }
-    kl = wave_total(kl);
-    if ((tid & 63) == 0 && 256 * ((int)blockIdx.x - 1) + (tid & ~63) < n_item_entries) kl_parts[4 * (blockIdx.x - 1) + (tid >> 6)] = kl;
+    item_prologue_block(blockIdx.x - 1, tid, I, D, mu, lv, eps, eps_w, gen, step_count + 1, seed_lo, seed_hi, item_feat, kl_parts);
 }
 
 // out[e] = sum over the records of part[r][e], fixed order (16 slices, fp64): 64 outputs per workgroup
@@ -118,13 +99,6 @@ __global__ __launch_bounds__(1024) void mt_reduce_kernel(const float* __restrict
     }
 }
 
-__device__ __forceinline__ void mt_adam(float& p, float& m, float& v, const float g, const float lr, const float bc1, const float bc2_sqrt) {
-    m = fmaf(0.9f, m, 0.1f * g);
-    v = fmaf(0.999f, v, (0.001f * g) * g);
-    const float denom = sqrtf(v) / bc2_sqrt + 1e-8f;
-    p -= (lr / bc1) * (m / denom);
-}
-
 constexpr int kMtThreads = 1024;
 __global__ __launch_bounds__(kMtThreads) void mt_epilogue_kernel(int H, int A2, int n_item_entries, const float* __restrict__ flat,
                                                                  const float* __restrict__ gsum, const float* __restrict__ saved,
@@ -136,8 +110,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_epilogue_kernel(int H, int A2, 
     __shared__ float df[2][kMtMaxHidden], dpre[2][kMtMaxHidden];
     const int tid = threadIdx.x;
     const float beta = *beta_p, lr = *lr_p;
-    const float t = (float)step_count[0];
-    const float bc1 = 1.0f - powf(0.9f, t), bc2_sqrt = sqrtf(1.0f - powf(0.999f, t));
+    const AdamBias bc = adam_bias(step_count[0]);
     constexpr int BS = kMtThreads;
     if (blockIdx.x == 0) {
         if (tid == 0) step_count[1] += 1;
@@ -150,13 +123,7 @@ __global__ __launch_bounds__(kMtThreads) void mt_epilogue_kernel(int H, int A2, 
             du[k] = gsum[k];
             dv[k] = gsum[H + k];
         }
-        if (tid < 64) {                  // item KL: the prologue's partial sums, fixed order
-            float kl = 0.f;
-            const int n_parts = kl_part_count(n_item_entries);
-            for (int k = tid; k < n_parts; k += 64) kl += kl_parts[k];
-            kl = wave_total(kl);
-            if (tid == 0) *loss_out = fmaf(beta, flat[VIBO_S_REG] + kl, -flat[VIBO_S_LL]);
-        }
+        item_kl_loss(tid, kl_parts, kl_part_count(n_item_entries), flat, beta, loss_out);
         __syncthreads();
         // d hf[c][k] = sum_j W20[j][k] (du[j] - dv[j] | dv[j]), through the ELU of the features
         for (int e = tid; e < 2 * H; e += BS) {
@@ -200,28 +167,18 @@ __global__ __launch_bounds__(kMtThreads) void mt_epilogue_kernel(int H, int A2, 
                 g = gsum[2 * H + (k - o.w22)];
             }
             float pv = P[k], mv = M[k], vv = V[k];
-            mt_adam(pv, mv, vv, g, lr, bc1, bc2_sqrt);
+            adam_update(pv, mv, vv, g, lr, bc);
             P[k] = pv; M[k] = mv; V[k] = vv;
         }
         return;
     }
     const int idx = (blockIdx.x - 1) * BS + tid;
-    if (idx < n_item_entries) {
-        const float gf = -flat[VIBO_NUM_SCALARS + 2 * n_table + idx];          // d loss / d item_feat = -dLL/ditem
-        const float m = mu[idx], l = lv[idx];
-        const float g_mu = fmaf(beta, m, gf);
-        const float half_sd = 0.5f * expf(0.5f * l);
-        const float klg = (0.5f * beta) * (1.0f - expf(l));
-        const float g_lv = fmaf(gf * half_sd, eps[idx], -klg);
-        float pm = m, pl = l;
-        mt_adam(pm, im[idx], iv[idx], g_mu, lr, bc1, bc2_sqrt);
-        mt_adam(pl, im[n_item_entries + idx], iv[n_item_entries + idx], g_lv, lr, bc1, bc2_sqrt);
-        mu[idx] = pm;
-        lv[idx] = pl;
+    if (idx < n_item_entries) {        // d loss / d item_feat = -dLL/ditem
+        float pm, pl;
+        epi_item_update(idx, n_item_entries, -flat[VIBO_NUM_SCALARS + 2 * n_table + idx], eps[idx], beta, lr, bc, mu, lv, im, iv, pm, pl);
     }
 }
 
-static int mt_item_dim(const vibo_desc* d) { return d->irt_model == 1 ? 1 : (d->irt_model == 2 ? d->ability_dim + 1 : d->ability_dim + 2); }
 static int mt_check(const vibo_desc* d, int H) {
     if (!d || d->abi_version != VIBO_ABI_VERSION) return -2;
     if (d->ability_dim < 1 || d->ability_dim > VIBO_MAX_ABILITY_DIM || d->num_item < 1 || d->num_person < 1) return -3;
@@ -247,7 +204,7 @@ extern "C" int vibo_mtrain_prologue(const vibo_desc* d, int hidden_dim, const fl
     if (rc) return rc;
     if (!params || !item_mu || !item_logvar || !eps_item || !item_feat || !uv || !saved || !kl_parts || !step_count) return -5;
     if (draw_noise && !eps_ability) return -5;
-    const int D = mt_item_dim(d), n = d->num_item * D;
+    const int D = item_feat_dim(d->irt_model, d->ability_dim), n = d->num_item * D;
     const int item_blocks = (n + 255) / 256;
     const long long n_ab = draw_noise ? (long long)d->num_person * d->ability_dim : 0;
     const long long ab_blocks = ((n_ab + 3) / 4 + 255) / 256;
@@ -274,7 +231,7 @@ extern "C" int vibo_mtrain_epilogue(const vibo_desc* d, int hidden_dim, const fl
     hipLaunchKernelGGL(mt_reduce_kernel, dim3((n_out + 63) / 64), dim3(1024), 0, s, partials, grad_sums, n_partials, n_out);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
-    const int n = d->num_item * mt_item_dim(d);
+    const int n = d->num_item * item_feat_dim(d->irt_model, d->ability_dim);
     const long long n_table = (long long)d->num_person * A2;       // floats per table-gradient set of the VIBO_POSTERIOR_GIVEN call
     hipLaunchKernelGGL(mt_epilogue_kernel, dim3(1 + (n + kMtThreads - 1) / kMtThreads), dim3(kMtThreads), 0, s, H, A2, n, flat, grad_sums,
                        saved, kl_parts, eps_item, beta, lr, step_count, n_table, params, adam_m, adam_v, item_mu, item_logvar, item_m, item_v,

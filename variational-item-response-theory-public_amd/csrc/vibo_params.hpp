@@ -14,6 +14,9 @@ constexpr int code_tile_stride(int waves) { return waves >= 16 ? 1040 : waves ==
 // template ability width for a runtime ability_dim (1,2,4,8)
 inline int padded_ability_dim(int a) { return a <= 1 ? 1 : a <= 2 ? 2 : a <= 4 ? 4 : 8; }
 
+// entries of an item's feature row: 1PL b | 2PL a[A], b | 3PL a[A], b, guess
+__host__ __device__ inline int item_feat_dim(int irt, int A) { return irt == 1 ? 1 : (irt == 2 ? A + 1 : A + 2); }
+
 // floats per prepped item row (see item_prep_kernel):
 //   1PL: [+1'.. (A times), b', 0..]  2PL: [-a'_0..-a'_{AT-1}, b', 0..]
 //   3PL: [-a'_0..-a'_{AT-1}, b', guess, 1-guess, 0..]      (x' = x * log2(e): logits in log2 units)

@@ -19,7 +19,6 @@ int codes_unsupported();
 // the pointer checks the entry points that read person rows share (after check_desc)
 int require_rows(const vibo_desc* d, const float* response, const void* mask);
 
-inline int item_feat_dim(int irt, int A) { return irt == 1 ? 1 : (irt == 2 ? A + 1 : A + 2); }
 // min(num_cu * per_cu, ceil(persons / rows_per_wg)): a grid that fills the chip but gives every workgroup at least one batch of rows
 inline int clamp_grid(int num_cu, int per_cu, int persons, int rows_per_wg) {
     const int n = num_cu * per_cu, cap = (persons + rows_per_wg - 1) / rows_per_wg;

@@ -3,6 +3,8 @@
 // train_epilogue_fused_kernel, which leaves the NEXT step's head behind (vibo_trainer.hip).  Both execute the same statements
 // in the same order, so the two forms of the step agree bit for bit
 // (tests/test_gpu_trainer.py::test_folded_step_equals_the_unfolded_step).
+// Below the MLP: what the plain, mean-merge and conditional / flow trainers (vibo_trainer.hip, vibo_mtrainer.hip,
+// vibo_ctrainer.hip) have in common -- the item side of a prologue, the ability-noise block, Adam, the item update and the loss.
 //
 // Reference statements (models.py:356-361, 575-582, 713-726, 506-510; utils.py:85-88):
 //     item_feat = item_mu + exp(0.5 item_logvar) * eps_item
@@ -11,8 +13,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "../../include/vibo_hip.h"
 #include "vibo_device.hpp"
 #include "vibo_params.hpp"
+#include "vibo_philox.hpp"
 
 namespace vibo {
 
@@ -86,5 +90,87 @@ __device__ __forceinline__ float item_kl_term(const float m, const float l) { re
 __device__ __forceinline__ int item_entry_index(const int k, const int I, const int D) { return (k % I) * D + k / I; }
 constexpr int kKlGroup = 64;
 __host__ __device__ inline int kl_part_count(const int n_entries) { return (n_entries + kKlGroup - 1) / kKlGroup; }
+
+// One item block (256 threads) of a prologue launch: entries 256 block + tid in that order, noise drawn (gen: Philox stream 0 at
+// `counter`, kept in eps_w; its group of 4 is recomputed by 4 threads: O(I) work) or read from eps, item sample, KL term, and one
+// KL part per wave into parts[4 block + wave] (the caller picks `parts`: the plain trainer double-buffers it by step parity).
+__device__ __forceinline__ void item_prologue_block(const unsigned block, const int tid, const int I, const int D, const float* __restrict__ mu,
+                                                    const float* __restrict__ lv, const float* __restrict__ eps, float* __restrict__ eps_w,
+                                                    const int gen, const int32_t* counter, const uint32_t seed_lo, const uint32_t seed_hi,
+                                                    float* __restrict__ item_feat, float* parts) {
+    const int n_item_entries = I * D;
+    const int k = block * 256 + tid;
+    float kl = 0.f;
+    if (k < n_item_entries) {
+        const int idx = item_entry_index(k, I, D);
+        const float m = mu[idx], l = lv[idx];
+        float e;
+        if (gen) {
+            e = philox_normal1(idx, (uint32_t)*counter, 0u, seed_lo, seed_hi);
+            eps_w[idx] = e;
+        } else {
+            e = eps[idx];
+        }
+        item_feat[idx] = item_sample(m, l, e);
+        kl = item_kl_term(m, l);
+    }
+    kl = wave_total(kl);
+    if ((tid & 63) == 0 && 256 * (int)block + (tid & ~63) < n_item_entries) parts[4 * block + (tid >> 6)] = kl;
+}
+
+// One ability-noise block (BS threads, 4 normals per thread) behind the item blocks: what vibo_fill_normal leaves in eps_ab [n_ab]
+// for stream ab_stream at `counter`
+__device__ __forceinline__ void ability_noise_block(const unsigned block, const int BS, const int tid, float* __restrict__ eps_ab,
+                                                    const long long n_ab, const uint32_t counter, const uint32_t ab_stream,
+                                                    const uint32_t seed_lo, const uint32_t seed_hi) {
+    const long long g = (long long)block * BS + tid;
+    if (4 * g < n_ab) store_normal4(eps_ab, n_ab, g, philox_normal4(g, counter, ab_stream, seed_lo, seed_hi));
+}
+
+// Adam's bias corrections at step t: 1 - 0.9^t and sqrt(1 - 0.999^t)
+struct AdamBias {
+    float bc1, bc2_sqrt;
+};
+__device__ __forceinline__ AdamBias adam_bias(const int step) {
+    const float t = (float)step;
+    return {1.0f - powf(0.9f, t), sqrtf(1.0f - powf(0.999f, t))};
+}
+// torch.optim.Adam's update (betas 0.9 / 0.999, eps 1e-8).  Every product-sum is pinned to one fma: the epilogue kernels of
+// vibo_trainer.hip must agree bit for bit, and the contraction hipcc picks for a sum of two products depends on the
+// surrounding code.
+__device__ __forceinline__ void adam_update(float& p, float& m, float& v, const float g, const float lr, const AdamBias bc) {
+    m = fmaf(0.9f, m, 0.1f * g);                   // torch: exp_avg.lerp_(grad, 1 - beta1)
+    v = fmaf(0.999f, v, (0.001f * g) * g);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
+    const float denom = sqrtf(v) / bc.bc2_sqrt + 1e-8f;
+    p -= (lr / bc.bc1) * (m / denom);
+}
+
+// item entry idx: d loss / d item_feat = gf -> (item_mu, item_logvar) through the sample and the item KL, Adam in place
+__device__ __forceinline__ void epi_item_update(const int idx, const int n_item_entries, const float gf, const float e, const float beta,
+                                                const float lr, const AdamBias bc, float* mu, float* lv, float* im, float* iv, float& pm,
+                                                float& pl) {
+    const float m = mu[idx], l = lv[idx];
+    const float g_mu = fmaf(beta, m, gf);
+    const float half_sd = 0.5f * expf(0.5f * l);
+    const float klg = (0.5f * beta) * (1.0f - expf(l));
+    const float g_lv = fmaf(gf * half_sd, e, -klg);
+    pm = m; pl = l;
+    adam_update(pm, im[idx], iv[idx], g_mu, lr, bc);
+    adam_update(pl, im[n_item_entries + idx], iv[n_item_entries + idx], g_lv, lr, bc);
+    mu[idx] = pm;
+    lv[idx] = pl;
+}
+
+// Wave 0 of an epilogue's block 0: item KL = the prologue's partial sums in a fixed order (lane-strided, then the wave sum), and
+// loss = -LL + beta (REG + KL_item) from the ELBO scalars sc (VIBO_S_*)
+__device__ __forceinline__ void item_kl_loss(const int tid, const float* __restrict__ kl_parts, const int n_kl_parts, const float* sc,
+                                             const float beta, float* loss_out) {
+    if (tid < 64) {
+        float kl = 0.f;
+        for (int k = tid; k < n_kl_parts; k += 64) kl += kl_parts[k];
+        kl = wave_total(kl);
+        if (tid == 0) *loss_out = fmaf(beta, sc[VIBO_S_REG] + kl, -sc[VIBO_S_LL]);
+    }
+}
 
 }  // namespace vibo

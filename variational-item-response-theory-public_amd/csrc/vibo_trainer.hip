@@ -38,59 +38,13 @@ __global__ __launch_bounds__(256) void train_prologue_kernel(int H, int O, int I
         mlp2_layer2(P, o, H, O, h1, h2, tid, 256, table, saved_h);
         return;
     }
-    if ((int)blockIdx.x > n_item_blocks) {          // ability noise (stream ab_stream), 4 normals per thread
-        const long long g = (long long)(blockIdx.x - 1 - n_item_blocks) * 256 + tid;
-        if (4 * g < n_ab) store_normal4(eps_ab, n_ab, g, philox_normal4(g, (uint32_t)step_count[1], ab_stream, seed_lo, seed_hi));
+    if ((int)blockIdx.x > n_item_blocks) {          // ability noise (stream ab_stream)
+        ability_noise_block(blockIdx.x - 1 - n_item_blocks, 256, tid, eps_ab, n_ab, (uint32_t)step_count[1], ab_stream, seed_lo, seed_hi);
         return;
     }
-    // item side: 256 entries per workgroup, dimension-major (item_entry_index); one KL part per wave
-    const int n_item_entries = I * D;
-    const int k = (blockIdx.x - 1) * 256 + tid;
-    float kl = 0.f;
-    if (k < n_item_entries) {
-        const int idx = item_entry_index(k, I, D);
-        const float m = mu[idx], l = lv[idx];
-        float e;
-        if (gen) {                                   // entry idx of stream 0 (its group of 4 is recomputed by 4 threads: O(I) work)
-            e = philox_normal1(idx, (uint32_t)step_count[1], 0u, seed_lo, seed_hi);
-            eps_w[idx] = e;
-        } else {
-            e = eps[idx];
-        }
-        item_feat[idx] = item_sample(m, l, e);
-        kl = item_kl_term(m, l);
-    }
-    kl = wave_total(kl);
     // (tick == 0: the part buffer of the step that is about to run, step_count[0] + 1)
-    float* parts = kl_parts + (tick ? 0 : (((*step_count + 1) & 1) ? kl_part_count(n_item_entries) : 0));
-    if ((tid & 63) == 0 && 256 * ((int)blockIdx.x - 1) + (tid & ~63) < n_item_entries) parts[4 * (blockIdx.x - 1) + (tid >> 6)] = kl;
-}
-
-// torch.optim.Adam's update (betas 0.9 / 0.999, eps 1e-8).  Every product-sum is pinned to one fma: the two epilogue
-// kernels below must agree bit for bit, and the contraction hipcc picks for a sum of two products depends on the
-// surrounding code.
-__device__ __forceinline__ void adam_update(float& p, float& m, float& v, const float g, const float lr, const float bc1,
-                                            const float bc2_sqrt) {
-    m = fmaf(0.9f, m, 0.1f * g);                   // torch: exp_avg.lerp_(grad, 1 - beta1)
-    v = fmaf(0.999f, v, (0.001f * g) * g);         // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
-    const float denom = sqrtf(v) / bc2_sqrt + 1e-8f;
-    p -= (lr / bc1) * (m / denom);
-}
-
-// item entry idx: d loss / d item_feat = gf -> (item_mu, item_logvar) through the sample and the item KL, Adam in place
-__device__ __forceinline__ void epi_item_update(const int idx, const int n_item_entries, const float gf, const float e, const float beta,
-                                                const float lr, const float bc1, const float bc2_sqrt, float* mu, float* lv, float* im,
-                                                float* iv, float& pm, float& pl) {
-    const float m = mu[idx], l = lv[idx];
-    const float g_mu = fmaf(beta, m, gf);
-    const float half_sd = 0.5f * expf(0.5f * l);
-    const float klg = (0.5f * beta) * (1.0f - expf(l));
-    const float g_lv = fmaf(gf * half_sd, e, -klg);
-    pm = m; pl = l;
-    adam_update(pm, im[idx], iv[idx], g_mu, lr, bc1, bc2_sqrt);
-    adam_update(pl, im[n_item_entries + idx], iv[n_item_entries + idx], g_lv, lr, bc1, bc2_sqrt);
-    mu[idx] = pm;
-    lv[idx] = pl;
+    float* parts = kl_parts + (tick ? 0 : (((*step_count + 1) & 1) ? kl_part_count(I * D) : 0));
+    item_prologue_block(blockIdx.x - 1, tid, I, D, mu, lv, eps, eps_w, gen, step_count + 1, seed_lo, seed_hi, item_feat, parts);
 }
 
 constexpr int kEpiThreads = 1024;      // block 0's chain of small dependent stages is latency-bound: more lanes per stage, fewer passes
@@ -109,7 +63,7 @@ constexpr int kEpiU = 8;
 template <int HC>
 __device__ __forceinline__ void epi_mlp_block(EpiLds& L, const int H_, const int O, const int n_kl_parts, const float* sc, const float* gtab,
                                               const float* __restrict__ saved_h, const float* __restrict__ kl_parts, const float beta,
-                                              const float lr, const float bc1, const float bc2_sqrt, const float* W, const MlpOffsets ow,
+                                              const float lr, const AdamBias bc, const float* W, const MlpOffsets ow,
                                               float* Wout, float* P, float* M, float* V, float (&pv)[kEpiU], float (&mv)[kEpiU],
                                               float (&vv)[kEpiU], float* loss_out, const int tid) {
     constexpr int BS = kEpiThreads;
@@ -122,12 +76,7 @@ __device__ __forceinline__ void epi_mlp_block(EpiLds& L, const int H_, const int
     }
     // d loss / d table = -dLL + beta dREG
     for (int k = tid; k < n_table; k += BS) L.gout[k / O][k % O] = fmaf(beta, gtab[n_table + k], -gtab[k]);
-    if (tid < 64) {                  // item KL: the prologue's partial sums, fixed order (lane-strided, then the wave sum)
-        float kl = 0.f;
-        for (int k = tid; k < n_kl_parts; k += 64) kl += kl_parts[k];
-        kl = wave_total(kl);
-        if (tid == 0) *loss_out = fmaf(beta, sc[VIBO_S_REG] + kl, -sc[VIBO_S_LL]);
-    }
+    item_kl_loss(tid, kl_parts, n_kl_parts, sc, beta, loss_out);
     __syncthreads();
     // g_h2 = W2^T g_out * elu'(pre2),  elu'(x) = x > 0 ? 1 : elu(x) + 1
     for (int k = tid; k < 2 * H; k += BS) {
@@ -197,7 +146,7 @@ __device__ __forceinline__ void epi_mlp_block(EpiLds& L, const int H_, const int
                 const int q = k - o.b2;
                 g = L.gout[0][q] + L.gout[1][q];
             }
-            adam_update(pv[u], mv[u], vv[u], g, lr, bc1, bc2_sqrt);
+            adam_update(pv[u], mv[u], vv[u], g, lr, bc);
             P[k] = pv[u];
             M[k] = mv[u];
             V[k] = vv[u];
@@ -227,8 +176,7 @@ __global__ __launch_bounds__(kEpiThreads) void train_epilogue_kernel(int H, int 
     __shared__ EpiLds L;
     const int tid = threadIdx.x;
     const float beta = *beta_p, lr = *lr_p;
-    const float t = (float)(*step_count);
-    const float bc1 = 1.0f - powf(0.9f, t), bc2_sqrt = sqrtf(1.0f - powf(0.999f, t));
+    const AdamBias bc = adam_bias(*step_count);
     const int n_table = 2 * O;
     constexpr int BS = kEpiThreads;
     if (blockIdx.x == 0) {
@@ -237,16 +185,16 @@ __global__ __launch_bounds__(kEpiThreads) void train_epilogue_kernel(int H, int 
         float pv[kEpiU], mv[kEpiU], vv[kEpiU];
         const MlpOffsets o = mlp_offsets(H, O);
         epi_mlp_prefetch(o.total, P, M, V, pv, mv, vv, tid);
-        if (H == 64) epi_mlp_block<64>(L, H, O, n_kl_parts, flat, flat + VIBO_NUM_SCALARS, saved_h, kl_parts, beta, lr, bc1, bc2_sqrt, P, o, nullptr,
+        if (H == 64) epi_mlp_block<64>(L, H, O, n_kl_parts, flat, flat + VIBO_NUM_SCALARS, saved_h, kl_parts, beta, lr, bc, P, o, nullptr,
                                        P, M, V, pv, mv, vv, loss_out, tid);
-        else epi_mlp_block<0>(L, H, O, n_kl_parts, flat, flat + VIBO_NUM_SCALARS, saved_h, kl_parts, beta, lr, bc1, bc2_sqrt, P, o, nullptr, P, M, V,
+        else epi_mlp_block<0>(L, H, O, n_kl_parts, flat, flat + VIBO_NUM_SCALARS, saved_h, kl_parts, beta, lr, bc, P, o, nullptr, P, M, V,
                               pv, mv, vv, loss_out, tid);
         return;
     }
     const int idx = (blockIdx.x - 1) * BS + tid;
     if (idx < n_item_entries) {        // d loss / d item_feat = -dLL/ditem
         float pm, pl;
-        epi_item_update(idx, n_item_entries, -flat[VIBO_NUM_SCALARS + 2 * n_table + idx], eps[idx], beta, lr, bc1, bc2_sqrt, mu, lv, im, iv, pm, pl);
+        epi_item_update(idx, n_item_entries, -flat[VIBO_NUM_SCALARS + 2 * n_table + idx], eps[idx], beta, lr, bc, mu, lv, im, iv, pm, pl);
     }
 }
 
@@ -279,14 +227,12 @@ __global__ __launch_bounds__(kEpiThreads) void train_epilogue_fused_kernel(const
     const int lane = tid % kEpiOut, slice = tid / kEpiOut;
     const int n_table = 2 * e.O;                 // floats per table-gradient set
     const int step = e.step_count[0];            // Adam's t of this step (ticked by the ELBO launch; nothing in this launch writes it)
-    if ((int)blockIdx.x > e.n_item_blocks) {     // the next step's ability noise, 4 normals per thread
-        const long long g = (long long)(blockIdx.x - 1 - e.n_item_blocks) * kEpiThreads + tid;
-        if (4 * g < e.n_ab) store_normal4(e.eps_ab, e.n_ab, g, philox_normal4(g, (uint32_t)step, e.ab_stream, e.seed_lo, e.seed_hi));
+    if ((int)blockIdx.x > e.n_item_blocks) {     // the next step's ability noise
+        ability_noise_block(blockIdx.x - 1 - e.n_item_blocks, kEpiThreads, tid, e.eps_ab, e.n_ab, (uint32_t)step, e.ab_stream, e.seed_lo, e.seed_hi);
         return;
     }
     const float beta = *e.beta, lr = *e.lr;
-    const float t = (float)step;
-    const float bc1 = 1.0f - powf(0.9f, t), bc2_sqrt = sqrtf(1.0f - powf(0.999f, t));
+    const AdamBias bc = adam_bias(step);
     const int n_parts = kl_part_count(e.n_item_entries);
     const float* kl_now = e.kl_parts + ((step & 1) ? n_parts : 0);
     float* kl_next = e.kl_parts + ((step & 1) ? 0 : n_parts);
@@ -361,7 +307,7 @@ __global__ __launch_bounds__(kEpiThreads) void train_epilogue_fused_kernel(const
             __syncthreads();
         }
         const float* W = staged ? Pl : e.P;
-        epi_mlp_block<HC>(L, H, e.O, n_parts, scp, gtp, e.saved_h, kl_now, beta, lr, bc1, bc2_sqrt, W, ow, staged ? Pl : nullptr, e.P, e.M, e.V,
+        epi_mlp_block<HC>(L, H, e.O, n_parts, scp, gtp, e.saved_h, kl_now, beta, lr, bc, W, ow, staged ? Pl : nullptr, e.P, e.M, e.V,
                       pv, mv, vv, e.loss_out, tid);
         // the next step's expert table from the parameters just written (this workgroup's own stores: visible after the barrier)
         __syncthreads();
@@ -398,7 +344,7 @@ __global__ __launch_bounds__(kEpiThreads) void train_epilogue_fused_kernel(const
         float kl = 0.f;
         if (live) {
             float pm, pl;
-            epi_item_update(idx, e.n_item_entries, -g, e.eps_item[idx], beta, lr, bc1, bc2_sqrt, e.mu, e.lv, e.im, e.iv, pm, pl);
+            epi_item_update(idx, e.n_item_entries, -g, e.eps_item[idx], beta, lr, bc, e.mu, e.lv, e.im, e.iv, pm, pl);
             const float en = philox_normal1(idx, (uint32_t)step, 0u, e.seed_lo, e.seed_hi);
             e.eps_item[idx] = en;
             e.item_feat[idx] = item_sample(pm, pl, en);
@@ -437,48 +383,49 @@ extern "C" int vibo_fill_normal(float* out, int64_t n, uint64_t seed, const int3
     return (int)hipGetLastError();
 }
 
-static int item_dim_of(const vibo_desc* d) { return d->irt_model == 1 ? 1 : (d->irt_model == 2 ? d->ability_dim + 1 : d->ability_dim + 2); }
+// what the train-step entry points of this file take (they return -6 otherwise): the plain model, encoder width <= kMaxHidden
+static bool plain_ok(const vibo_desc* d, int hidden_dim) {
+    return d && hidden_dim >= 1 && hidden_dim <= kMaxHidden && d->posterior == VIBO_POSTERIOR_UNCONDITIONAL && d->n_flows == 0;
+}
+// train_prologue_kernel: block 0, the item blocks and (gen) the ability-noise blocks behind them
+static int launch_prologue(const vibo_desc* d, int hidden_dim, const float* mlp_params, const float* item_mu, const float* item_logvar,
+                           const float* eps_item, float* item_feat, float* table, float* saved_h, float* kl_parts, int32_t* step_count,
+                           int tick, int gen, uint64_t seed, float* eps_w, float* eps_ability, uint32_t ab_stream, void* stream) {
+    const int D = item_feat_dim(d->irt_model, d->ability_dim);
+    const int item_blocks = (d->num_item * D + 255) / 256;
+    const long long n_ab = gen ? (long long)d->num_person * d->ability_dim : 0;
+    const long long ab_blocks = ((n_ab + 3) / 4 + 255) / 256;
+    hipLaunchKernelGGL(train_prologue_kernel, dim3((unsigned)(1 + item_blocks + ab_blocks)), dim3(256), 0, (hipStream_t)stream, hidden_dim,
+                       2 * d->ability_dim, d->num_item, D, mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts,
+                       step_count, tick, gen, (uint32_t)seed, (uint32_t)(seed >> 32), eps_w, eps_ability, n_ab, ab_stream, item_blocks);
+    return (int)hipGetLastError();
+}
 
 extern "C" int vibo_train_prologue(const vibo_desc* d, int hidden_dim, const float* mlp_params, const float* item_mu,
                                    const float* item_logvar, const float* eps_item, float* item_feat, float* table,
                                    float* saved_h, float* kl_parts, int32_t* step_count, void* stream) {
-    if (!d || hidden_dim < 1 || hidden_dim > kMaxHidden || d->posterior != VIBO_POSTERIOR_UNCONDITIONAL || d->n_flows != 0) return -6;
-    const int n = d->num_item * item_dim_of(d);
-    const int blocks = 1 + (n + 255) / 256;
-    hipLaunchKernelGGL(train_prologue_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, hidden_dim, 2 * d->ability_dim, d->num_item,
-                       item_dim_of(d), mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts, step_count, 1, 0, 0u, 0u,
-                       (float*)nullptr, (float*)nullptr, 0LL, 0u, (n + 255) / 256);
-    return (int)hipGetLastError();
+    if (!plain_ok(d, hidden_dim)) return -6;
+    return launch_prologue(d, hidden_dim, mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts, step_count, 1, 0, 0,
+                           nullptr, nullptr, 0u, stream);
 }
 
 extern "C" int vibo_train_prime(const vibo_desc* d, int hidden_dim, const float* mlp_params, const float* item_mu,
                                 const float* item_logvar, const float* eps_item, float* item_feat, float* table,
                                 float* saved_h, float* kl_parts, int32_t* step_count, void* stream) {
-    if (!d || hidden_dim < 1 || hidden_dim > kMaxHidden || d->posterior != VIBO_POSTERIOR_UNCONDITIONAL || d->n_flows != 0) return -6;
+    if (!plain_ok(d, hidden_dim)) return -6;
     if (!mlp_params || !item_mu || !item_logvar || !eps_item || !item_feat || !table || !saved_h || !kl_parts || !step_count) return -5;
-    const int n = d->num_item * item_dim_of(d);
-    const int blocks = 1 + (n + 255) / 256;
-    hipLaunchKernelGGL(train_prologue_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, hidden_dim, 2 * d->ability_dim, d->num_item,
-                       item_dim_of(d), mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts, step_count, 0, 0, 0u, 0u,
-                       (float*)nullptr, (float*)nullptr, 0LL, 0u, (n + 255) / 256);
-    return (int)hipGetLastError();
+    return launch_prologue(d, hidden_dim, mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts, step_count, 0, 0, 0,
+                           nullptr, nullptr, 0u, stream);
 }
 
 extern "C" int vibo_train_prologue_noise(const vibo_desc* d, int hidden_dim, const float* mlp_params, const float* item_mu,
                                          const float* item_logvar, float* eps_item, float* item_feat, float* table,
                                          float* saved_h, float* kl_parts, int32_t* step_count, uint64_t seed, float* eps_ability,
                                          uint32_t ability_stream_id, void* stream) {
-    if (!d || hidden_dim < 1 || hidden_dim > kMaxHidden || d->posterior != VIBO_POSTERIOR_UNCONDITIONAL || d->n_flows != 0) return -6;
+    if (!plain_ok(d, hidden_dim)) return -6;
     if (!eps_item || !eps_ability || !step_count) return -5;
-    const int n = d->num_item * item_dim_of(d);
-    const int item_blocks = (n + 255) / 256;
-    const long long n_ab = (long long)d->num_person * d->ability_dim;
-    const long long ab_blocks = ((n_ab + 3) / 4 + 255) / 256;
-    hipLaunchKernelGGL(train_prologue_kernel, dim3((unsigned)(1 + item_blocks + ab_blocks)), dim3(256), 0, (hipStream_t)stream,
-                       hidden_dim, 2 * d->ability_dim, d->num_item, item_dim_of(d), mlp_params, item_mu, item_logvar, (const float*)eps_item,
-                       item_feat, table, saved_h, kl_parts, step_count, 1, 1, (uint32_t)seed, (uint32_t)(seed >> 32), eps_item, eps_ability,
-                       n_ab, ability_stream_id, item_blocks);
-    return (int)hipGetLastError();
+    return launch_prologue(d, hidden_dim, mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts, step_count, 1, 1, seed,
+                           eps_item, eps_ability, ability_stream_id, stream);
 }
 
 extern "C" int vibo_train_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, const float* saved_h,
@@ -486,8 +433,8 @@ extern "C" int vibo_train_epilogue(const vibo_desc* d, int hidden_dim, const flo
                                    const int32_t* step_count, float* mlp_params, float* mlp_m, float* mlp_v,
                                    float* item_mu, float* item_logvar, float* item_m, float* item_v, float* loss_out,
                                    void* stream) {
-    if (!d || hidden_dim < 1 || hidden_dim > kMaxHidden || d->posterior != VIBO_POSTERIOR_UNCONDITIONAL || d->n_flows != 0) return -6;
-    const int n = d->num_item * item_dim_of(d);
+    if (!plain_ok(d, hidden_dim)) return -6;
+    const int n = d->num_item * item_feat_dim(d->irt_model, d->ability_dim);
     const int parts = kl_part_count(n);                      // the prologue's item-KL partial sums (one per 64 entries)
     hipLaunchKernelGGL(train_epilogue_kernel, dim3(1 + (n + kEpiThreads - 1) / kEpiThreads), dim3(kEpiThreads), 0, (hipStream_t)stream,
                        hidden_dim, 2 * d->ability_dim, n, parts, flat, saved_h, kl_parts, eps_item, beta, lr, step_count, mlp_params, mlp_m, mlp_v, item_mu,

@@ -89,44 +89,88 @@ class FusedTrainer:
         if self.hidden > 256:
             raise NotImplementedError('hidden_dim > 256')
         plist = [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, mlp[4].weight, mlp[4].bias]
-        dev = plist[0].device
-        # one flat buffer  W0 | b0 | W1 | b1 | W2 | b2 ; the nn.Parameters become views of it (state_dict unchanged)
-        self.mlp_flat = torch.cat([p.detach().reshape(-1) for p in plist]).contiguous()
+        self.mlp_flat, self.mlp_m, self.mlp_v = self._flatten(plist)      # W0 | b0 | W1 | b1 | W2 | b2
+        dev, n_item = self._init_state(model, lr)
+        self._watched = plist + [self.mlp_flat, self.item_mu, self.item_lv]
+        self.table = torch.empty(2, 2 * model.ability_dim, device=dev)
+        self.saved_h = torch.empty(4 * self.hidden, device=dev)
+        self.kl_parts = torch.empty(2 * ((n_item + 63) // 64), device=dev)      # (two halves: the folded step double-buffers them)
+        self._init_rng(rng, seed, keep_item_noise=rng == 'native')
+        self.fused_noise = bool(fused_noise)      # rng='native': draw the noise inside the prologue launch (2 launches fewer)
+
+    @staticmethod
+    def _flatten(plist):
+        """One flat buffer of the parameters in plist's order -- the nn.Parameters become views of it (state_dict unchanged) --
+        and Adam's two moments in the same layout."""
+        flat = torch.cat([p.detach().reshape(-1) for p in plist]).contiguous()
         off = 0
         for p in plist:
             n = p.numel()
-            p.data = self.mlp_flat[off:off + n].view_as(p)
+            p.data = flat[off:off + n].view_as(p)
             off += n
-        self.mlp_m = torch.zeros_like(self.mlp_flat)
-        self.mlp_v = torch.zeros_like(self.mlp_flat)
+        return flat, torch.zeros_like(flat), torch.zeros_like(flat)
+
+    def _init_state(self, model, lr):
+        """What every fused trainer keeps: the item tensors and their moments, Adam's counters and scalars, the item sample, the
+        loss and the step's bookkeeping.  Returns (device, item entries)."""
         self.item_mu = model.item_encoder.mu_lookup.weight
         self.item_lv = model.item_encoder.logvar_lookup.weight
         assert self.item_mu.is_contiguous() and self.item_lv.is_contiguous()
-        self._watched = plist + [self.mlp_flat, self.item_mu, self.item_lv]
-        n_item = self.item_mu.numel()
+        dev, n_item = self.item_mu.device, self.item_mu.numel()
         self.item_m = torch.zeros(2 * n_item, device=dev)
         self.item_v = torch.zeros(2 * n_item, device=dev)
         self._steps = torch.zeros(2, dtype=torch.int32, device=dev)      # [Adam step t, completed steps (noise counter)]
         self.lr = torch.tensor(float(lr), device=dev)
         self.beta = torch.tensor(1.0, device=dev)
         self._beta_host = 1.0
-        A = model.ability_dim
         self.item_feat = torch.empty_like(self.item_mu)
-        self.table = torch.empty(2, 2 * A, device=dev)
-        self.saved_h = torch.empty(4 * self.hidden, device=dev)
-        self.kl_parts = torch.empty(2 * ((n_item + 63) // 64), device=dev)      # (two halves: the folded step double-buffers them)
         self.loss = torch.zeros((), device=dev)
         self.last = None                      # RawElbo of the last step (posterior outputs, scalars)
         self._pending = None
-        # (person-sharded: item noise is the same on every rank, ability noise uses stream 1 + rank)
-        # reparameterisation noise: 'torch' = torch.randn on the model's generators (the reference's stream for a
-        # given seed), 'native' = vibo_fill_normal (Philox4x32-10 keyed by `seed`, ~5x faster on [1M, 8])
+        return dev, n_item
+
+    def _init_rng(self, rng, seed, keep_item_noise=True):
+        """Reparameterisation noise: 'torch' = torch.randn on the model's generators (the reference's stream for a given seed),
+        'native' = Philox4x32-10 keyed by `seed` (vibo_fill_normal's streams, ~5x faster on [1M, 8]).
+        (person-sharded: item noise is the same on every rank, ability noise uses stream 1 + rank)"""
         if rng not in ('torch', 'native'):
             raise ValueError("rng must be 'torch' or 'native'")
         self.rng, self.seed = rng, int(seed)
-        self.fused_noise = bool(fused_noise)      # rng='native': draw the noise inside the prologue launch (2 launches fewer)
-        self._eps_item = torch.empty_like(self.item_mu) if rng == 'native' else None
+        self._eps_item = torch.empty_like(self.item_mu) if keep_item_noise else None
         self._eps_ab = {}
+
+    def _begin(self, response, mask, beta, row_index, reg_mode):
+        """What every forward_backward() starts with: the KL weight, the rows as the kernels read them, the descriptor of this
+        call.  Returns (response, mask, code, B, I, stream, descriptor, ab_stream)."""
+        if beta is not None:
+            self.set_beta(beta)
+        response, mask, code = ops.prepare_rows(response, mask)
+        B = int(row_index.numel()) if row_index is not None else response.shape[0]
+        I = response.shape[1]
+        stream = ctypes.c_void_p(torch.cuda.current_stream(response.device).cuda_stream)
+        d = ops._make_desc(self.model.spec, B, I, code, reg_mode, True, response.stride(0), mask.stride(0) if mask is not None else 0)
+        ab_stream = 1 + getattr(self.model, '_shard_rank', 0)      # item noise: the same on every rank; ability noise: per rank
+        return response, mask, code, B, I, stream, d, ab_stream
+
+    def _ab_buffer(self, B, dev):
+        # one buffer per batch size, never freed or replaced: a captured hipGraph keeps the pointer it was recorded
+        # with, and the epoch's last, shorter minibatch runs eagerly in between the replays
+        eps_ab = self._eps_ab.get(B)
+        if eps_ab is None:
+            eps_ab = self._eps_ab[B] = torch.empty(B, self.model.ability_dim, device=dev)
+        return eps_ab
+
+    def _choose_noise(self, B, dev, eps_item, eps_ability):
+        """The noise of a step of the two sibling trainers -> (eps_item, eps_ab, native): the caller's (given), this trainer's
+        buffers for the prologue launch to fill (native), or torch's generators in the reference's draw order, item eps then
+        ability eps (models.py:361,368) -- the item draw happens here, eps_ab is None and the caller draws it after the prologue."""
+        if eps_item is not None:
+            if eps_ability is None:
+                raise ValueError('pass both eps_item and eps_ability, or neither')
+            return eps_item.contiguous().float(), eps_ability.contiguous().float(), False
+        if self.rng == 'native':
+            return self._eps_item, self._ab_buffer(B, dev), True
+        return self.model._randn(self.item_mu.shape, self.item_mu, self.model._item_gen), None, False
 
     def set_beta(self, beta):
         """KL weight (vibo.py:223-230).  A device scalar: update it between graph replays when annealing."""
@@ -162,17 +206,8 @@ class FusedTrainer:
         """Noise, prologue and the fused ELBO forward+backward of this rank's persons.  Returns the RawElbo whose
         `.flat` buffer [scalars | grads] a person-sharded caller all-reduces before `update()`.  (Split from
         `update()` so that a multi-GPU loop can replay the two halves as hipGraphs around an eager collective.)"""
-        if beta is not None:
-            self.set_beta(beta)
-        model, spec, lib = self.model, self.model.spec, _lib.load()
-        response, mask, code = ops.prepare_rows(response, mask)
-        B = int(row_index.numel()) if row_index is not None else response.shape[0]
-        I = response.shape[1]
-        dev = response.device
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        d = ops._make_desc(spec, B, I, code, _lib.REG_KL, True, response.stride(0), mask.stride(0) if mask is not None else 0)
-        p = ops._ptr
-        ab_stream = 1 + getattr(model, '_shard_rank', 0)      # item noise: the same on every rank; ability noise: per rank
+        model, spec, lib, p = self.model, self.model.spec, _lib.load(), ops._ptr
+        response, mask, code, B, I, stream, d, ab_stream = self._begin(response, mask, beta, row_index, _lib.REG_KL)
         given = eps_item is not None or eps_ability is not None
         if given and (eps_item is None or eps_ability is None):
             raise ValueError('pass both eps_item and eps_ability, or neither')
@@ -195,12 +230,7 @@ class FusedTrainer:
             return raw
         # reference draw order: item eps, then ability eps (models.py:361,368)
         if self.rng == 'native':
-            eps_item = self._eps_item
-            # one buffer per batch size, never freed or replaced: a captured hipGraph keeps the pointer it was recorded
-            # with, and the epoch's last, shorter minibatch runs eagerly in between the replays
-            eps_ab = self._eps_ab.get(B)
-            if eps_ab is None:
-                eps_ab = self._eps_ab[B] = torch.empty(B, model.ability_dim, device=dev)
+            eps_item, eps_ab = self._eps_item, self._ab_buffer(B, response.device)
             self._primed_for = None           # (these draws move on without refilling the folded step's buffers)
         else:
             eps_item = model._randn(self.item_mu.shape, self.item_mu, model._item_gen)
@@ -340,29 +370,9 @@ class FusedCondFlowTrainer(FusedTrainer):
             for st in (model.ability_norm_flows, model.item_norm_flows):
                 for fl in st.flows:
                     plist += [fl.u, fl.w, fl.b]
-        dev = plist[0].device
-        # one flat buffer (the layout of include/vibo_hip.h: vibo_ctrain_*); the nn.Parameters become views of it
-        self.par_flat = torch.cat([p.detach().reshape(-1) for p in plist]).contiguous()
-        off = 0
-        for p in plist:
-            n = p.numel()
-            p.data = self.par_flat[off:off + n].view_as(p)
-            off += n
-        self.par_m = torch.zeros_like(self.par_flat)
-        self.par_v = torch.zeros_like(self.par_flat)
-        self.item_mu = model.item_encoder.mu_lookup.weight
-        self.item_lv = model.item_encoder.logvar_lookup.weight
-        assert self.item_mu.is_contiguous() and self.item_lv.is_contiguous()
-        I, D = self.item_mu.shape
-        A = model.ability_dim
-        n_item = I * D
-        self.item_m = torch.zeros(2 * n_item, device=dev)
-        self.item_v = torch.zeros(2 * n_item, device=dev)
-        self._steps = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.lr = torch.tensor(float(lr), device=dev)
-        self.beta = torch.tensor(1.0, device=dev)
-        self._beta_host = 1.0
-        self.item_feat = torch.empty_like(self.item_mu)
+        self.par_flat, self.par_m, self.par_v = self._flatten(plist)      # (the layout of include/vibo_hip.h: vibo_ctrain_*)
+        dev, _ = self._init_state(model, lr)
+        I, A = self.item_mu.shape[0], model.ability_dim
         self.item_k = torch.empty_like(self.item_mu) if F > 0 else self.item_feat
         self.table = torch.empty((2, I, 2 * A) if model.conditional_posterior else (2, 2 * A), device=dev)
         self.flow_packed = torch.empty(F, 2 * A + 1, device=dev) if F > 0 else None
@@ -371,57 +381,24 @@ class FusedCondFlowTrainer(FusedTrainer):
         if lib.vibo_ctrain_param_floats(ctypes.byref(self._desc0), self.hidden) != self.par_flat.numel():
             raise RuntimeError('FusedCondFlowTrainer: parameter layout mismatch')
         self.scratch = torch.empty(int(lib.vibo_ctrain_scratch_floats(ctypes.byref(self._desc0), self.hidden)), device=dev)
-        self.loss = torch.zeros((), device=dev)
-        self.last = None
-        self._pending = None
-        if rng not in ('torch', 'native'):
-            raise ValueError("rng must be 'torch' or 'native'")
-        self.rng, self.seed = rng, int(seed)
+        self._init_rng(rng, seed)
         if not fused_noise:
             raise NotImplementedError('FusedCondFlowTrainer draws the native noise inside vibo_ctrain_prologue (there is no '
                                       'separate vibo_fill_normal form of this step): fused_noise=False is not available')
         self.fused_noise = True
-        self._eps_item = torch.empty_like(self.item_mu)
-        self._eps_ab = {}
 
     @torch.no_grad()
     def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
-        if beta is not None:
-            self.set_beta(beta)
-        model, spec, lib = self.model, self.model.spec, _lib.load()
-        response, mask, code = ops.prepare_rows(response, mask)
-        B = int(row_index.numel()) if row_index is not None else response.shape[0]
-        I = response.shape[1]
-        dev = response.device
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        F = model.n_norm_flows
-        reg_mode = _lib.REG_SAMPLED if F > 0 else _lib.REG_KL
-        d = ops._make_desc(spec, B, I, code, reg_mode, True, response.stride(0), mask.stride(0) if mask is not None else 0)
-        p = ops._ptr
-        ab_stream = 1 + getattr(model, '_shard_rank', 0)
-        native = self.rng == 'native' and eps_item is None
-        given_ab = None
-        if eps_item is not None:
-            if eps_ability is None:
-                raise ValueError('pass both eps_item and eps_ability, or neither')
-            eps_item, given_ab = eps_item.contiguous().float(), eps_ability.contiguous().float()
-            eps_ab = None
-        elif native:
-            eps_item = self._eps_item
-            eps_ab = self._eps_ab.get(B)
-            if eps_ab is None:
-                eps_ab = self._eps_ab[B] = torch.empty(B, model.ability_dim, device=dev)
-        else:
-            # reference draw order: item eps, then ability eps (models.py:361,368)
-            eps_item = model._randn(self.item_mu.shape, self.item_mu, model._item_gen)
-            eps_ab = None
+        model, spec, lib, p = self.model, self.model.spec, _lib.load(), ops._ptr
+        reg_mode = _lib.REG_SAMPLED if model.n_norm_flows > 0 else _lib.REG_KL
+        response, mask, code, B, I, stream, d, ab_stream = self._begin(response, mask, beta, row_index, reg_mode)
+        eps_item, eps_ab, native = self._choose_noise(B, response.device, eps_item, eps_ability)
         rc = lib.vibo_ctrain_prologue(ctypes.byref(d), self.hidden, p(self.par_flat), p(self.item_mu), p(self.item_lv),
-                                      p(eps_item), self.seed, 1 if native else 0, p(eps_ab), ab_stream, p(self.item_feat),
-                                      p(self.item_k), p(self.table), p(self.flow_packed), p(self.scratch), p(self._steps), stream)
+                                      p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, ab_stream,
+                                      p(self.item_feat), p(self.item_k), p(self.table), p(self.flow_packed), p(self.scratch),
+                                      p(self._steps), stream)
         _lib.check(rc, 'vibo_ctrain_prologue')
-        if given_ab is not None:
-            eps_ab = given_ab
-        elif not native:
+        if eps_ab is None:
             eps_ab = model._randn((B, model.ability_dim), self.item_mu, model._ability_gen)
         raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_k, eps_ab, self.flow_packed,
                                    reg_mode, True, B)
@@ -463,33 +440,13 @@ class FusedMeanTrainer(FusedTrainer):
         self.hidden = enc.mlp1[0].weight.shape[0]
         plist = [enc.mlp1[0].weight, enc.mlp1[0].bias, enc.mlp1[2].weight, enc.mlp1[2].bias,
                  enc.mlp2[0].weight, enc.mlp2[0].bias, enc.mlp2[2].weight, enc.mlp2[2].bias]
-        dev = plist[0].device
-        # one flat buffer (the layout of include/vibo_hip.h: vibo_mtrain_*); the nn.Parameters become views of it
-        self.par_flat = torch.cat([p.detach().reshape(-1) for p in plist]).contiguous()
-        off = 0
-        for p in plist:
-            n = p.numel()
-            p.data = self.par_flat[off:off + n].view_as(p)
-            off += n
-        self.par_m = torch.zeros_like(self.par_flat)
-        self.par_v = torch.zeros_like(self.par_flat)
-        self.item_mu = model.item_encoder.mu_lookup.weight
-        self.item_lv = model.item_encoder.logvar_lookup.weight
-        assert self.item_mu.is_contiguous() and self.item_lv.is_contiguous()
-        I, D = self.item_mu.shape
-        A, H = model.ability_dim, self.hidden
-        n_item = I * D
+        self.par_flat, self.par_m, self.par_v = self._flatten(plist)      # (the layout of include/vibo_hip.h: vibo_mtrain_*)
+        dev, n_item = self._init_state(model, lr)
+        I, A, H = self.item_mu.shape[0], model.ability_dim, self.hidden
         self._desc0 = ops._make_desc(model.spec, 1, I, _lib.MASK_NONE, _lib.REG_KL, True, I, 0)
         lib = _lib.load()
         if lib.vibo_mtrain_param_floats(ctypes.byref(self._desc0), H) != self.par_flat.numel():
             raise RuntimeError('FusedMeanTrainer: parameter layout mismatch')
-        self.item_m = torch.zeros(2 * n_item, device=dev)
-        self.item_v = torch.zeros(2 * n_item, device=dev)
-        self._steps = torch.zeros(2, dtype=torch.int32, device=dev)
-        self.lr = torch.tensor(float(lr), device=dev)
-        self.beta = torch.tensor(1.0, device=dev)
-        self._beta_host = 1.0
-        self.item_feat = torch.empty_like(self.item_mu)
         self.uv = torch.empty(2 * H, device=dev)
         self.saved = torch.empty(4 * H, device=dev)
         self.grad_sums = torch.empty(2 * H + 2 * A * H + 2 * A, device=dev)
@@ -497,50 +454,22 @@ class FusedMeanTrainer(FusedTrainer):
         o = 2 * H + H * H + H + H * H + H
         self._w22 = self.par_flat[o:o + 2 * A * H]
         self._b22 = self.par_flat[o + 2 * A * H:o + 2 * A * H + 2 * A]
-        self.loss = torch.zeros((), device=dev)
-        self.last = None
-        self._pending = None
-        if rng not in ('torch', 'native'):
-            raise ValueError("rng must be 'torch' or 'native'")
-        self.rng, self.seed = rng, int(seed)
+        self._init_rng(rng, seed)
         self.fused_noise = True
-        self._eps_item = torch.empty_like(self.item_mu)
-        self._eps_ab = {}
         self._parts = {}
 
     @torch.no_grad()
     def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
-        if beta is not None:
-            self.set_beta(beta)
         model, spec, lib, p = self.model, self.model.spec, _lib.load(), ops._ptr
         counts = ops.row_counts(response, mask)             # packed (n_correct << 16 | n_observed) of every resident row, cached
         if row_index is not None:
             counts = counts[row_index]
-        response, mask, code = ops.prepare_rows(response, mask)
-        B = int(row_index.numel()) if row_index is not None else response.shape[0]
-        I = response.shape[1]
+        response, mask, code, B, I, stream, d, ab_stream = self._begin(response, mask, beta, row_index, _lib.REG_KL)
         dev = response.device
         A, H = model.ability_dim, self.hidden
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        d = ops._make_desc(spec, B, I, code, _lib.REG_KL, True, response.stride(0), mask.stride(0) if mask is not None else 0)
-        given = eps_item is not None
-        native = self.rng == 'native' and not given
-        if given:
-            if eps_ability is None:
-                raise ValueError('pass both eps_item and eps_ability, or neither')
-            eps_item, eps_ab = eps_item.contiguous().float(), eps_ability.contiguous().float()
-        elif native:
-            eps_item = self._eps_item
-            eps_ab = self._eps_ab.get(B)
-            if eps_ab is None:
-                eps_ab = self._eps_ab[B] = torch.empty(B, A, device=dev)
-        else:
-            # reference draw order: item eps, then ability eps (models.py:361,368)
-            eps_item = model._randn(self.item_mu.shape, self.item_mu, model._item_gen)
-            eps_ab = None
-        ab_stream = 1 + getattr(model, '_shard_rank', 0)      # (person-sharded: item noise identical on every rank, ability noise per rank)
+        eps_item, eps_ab, native = self._choose_noise(B, dev, eps_item, eps_ability)
         rc = lib.vibo_mtrain_prologue(ctypes.byref(d), H, p(self.par_flat), p(self.item_mu), p(self.item_lv), p(eps_item), self.seed,
-                                      1 if native else 0, p(eps_ab) if native else ctypes.c_void_p(0), ab_stream, p(self.item_feat), p(self.uv),
+                                      1 if native else 0, p(eps_ab) if native else None, ab_stream, p(self.item_feat), p(self.uv),
                                       p(self.saved), p(self.kl_parts), p(self._steps), stream)
         _lib.check(rc, 'vibo_mtrain_prologue')
         if eps_ab is None:
