@@ -545,6 +545,56 @@ int vibo_decoder_fwd_bwd(const vibo_decoder_desc* d, const float* response, cons
                          float* ll_part, float* dU_part, float* dV_part, float* dL, float* dguess_part,
                          float* dW2_part, float* dvec_part, float* prob_out, void* stream);
 
+/*
+ * The whole train step of an MLP-decoder model (--generative-model link | deep | residual; product-of-experts encoder with the
+ * unconditional posterior, no flows, analytic KL; vibo.py:243-268 with models.py:337-443, 596-629, 769-919) around
+ * vibo_decoder_fwd_bwd -- what vibo_train_prologue / vibo_train_epilogue are for the IRT decoder.  A step is
+ *     vibo_dtrain_prologue          step_count[0] += 1; item sample, item KL parts, 3PL guess (+ the Philox noise with draw_noise, as
+ *                                   vibo_train_prologue_noise: streams 0 / ability_stream_id at counter step_count[1]); the 2-row
+ *                                   encoder table; deep / residual: mlp_item_feat over the item rows and
+ *                                   U = . mlp_concat[0].weight[:, :H]^T
+ *     vibo_dtrain_forward_backward  per chunk of at most person_chunk persons: the product of experts from the packed row counts
+ *                                   (vibo_row_counts of the minibatch's rows; models._posterior_from_counts), ability = mu +
+ *                                   exp(.5 logvar) eps, mlp_ability and V (link: V = link[0].bias), link / residual: the IRT logit;
+ *                                   vibo_decoder_fwd_bwd on the minibatch's dense rows (response fp32, mask u8 or NULL, strides in d);
+ *                                   then the backward of all of that into per-workgroup records
+ *     vibo_dtrain_epilogue          fixed-order sums of every record, loss = -LL + beta (KL_ability + KL_item), the backward through
+ *                                   mlp_item_feat, the guess and the 2-row encoder, item backward, Adam on every parameter IN PLACE
+ *                                   (torch.optim.Adam's update); step_count[1] += 1
+ *  decoder: VIBO_DECODER_*.  hidden_dim H <= 64 (the decoder kernel's width; narrower networks run zero-padded).  d: posterior
+ *  UNCONDITIONAL, n_flows 0, reg_mode KL, mask_dtype U8 or NONE, num_item <= 65535, ability_dim 1..16; anything else returns a
+ *  negative code before any launch (-6 for the width / posterior / flows, -8 for the mask type, -3 for the sizes).
+ *  params / adam_m / adam_v: one flat fp32 buffer each, in state_dict order (vibo_dtrain_param_floats(d, decoder, H) floats; the
+ *  two item embeddings stay their own tensors, as for the other trainers):
+ *      encoder W0 [H] | b0 [H] | W1 [H][H] | b1 [H] | W2 [2A][H] | b2 [2A], then
+ *      link:            link.0.weight [H] | .bias [H] | link.2.weight [H][H] | .bias [H] | link.4.weight [H] | .bias [1]
+ *      deep / residual: mlp_item_feat.0.weight [H][D] | .bias [H] | .2.weight [H][H] | .bias [H] | .4.weight [H][H] | .bias [H] |
+ *                       mlp_ability.0.weight [H][A] | .bias [H] | .2.weight [H][H] | .bias [H] | .4.weight [H][H] | .bias [H] |
+ *                       mlp_concat.0.weight [H][2H] | .bias [H] | .2.weight [H][H] | .bias [H] | .4.weight [H] | .bias [1]
+ *  scratch: vibo_dtrain_scratch_floats(d, decoder, H, person_chunk) floats (d->num_person = the minibatch), 16-byte aligned, handed
+ *  to the three calls of a step unchanged in between; vibo_dtrain_scratch_offset tells where the step leaves [LL, KL_ability, ...]
+ *  (VIBO_DTRAIN_SCALARS, 8 floats), the posterior (mu | logvar) [B][2A] (VIBO_DTRAIN_POSTERIOR) and the sample [B][A]
+ *  (VIBO_DTRAIN_ABILITY) in it.  person_chunk: persons per decoder launch (< 1 or > B: all at once).
+ *  step_count, beta, lr, item_m / item_v: as for vibo_train_prologue / vibo_train_epilogue.
+ * Every reduction is a fixed-order sum of records: bitwise reproducible; no host synchronisation, no allocation: hipGraph-capturable.
+ */
+enum { VIBO_DECODER_LINK = 1, VIBO_DECODER_DEEP = 2, VIBO_DECODER_RESIDUAL = 3 };
+enum { VIBO_DTRAIN_SCALARS = 0, VIBO_DTRAIN_POSTERIOR = 1, VIBO_DTRAIN_ABILITY = 2 };
+int64_t vibo_dtrain_param_floats(const vibo_desc* d, int decoder, int hidden_dim);
+int64_t vibo_dtrain_scratch_floats(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk);
+int64_t vibo_dtrain_scratch_offset(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, int which);
+int vibo_dtrain_prologue(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                         const float* item_mu, const float* item_logvar, float* eps_item, uint64_t seed, int draw_noise,
+                         float* eps_ability, uint32_t ability_stream_id, float* item_feat, float* scratch,
+                         int32_t* step_count, void* stream);
+int vibo_dtrain_forward_backward(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                                 const float* response, const uint8_t* mask, const int32_t* counts,
+                                 const float* eps_ability, const float* item_feat, float* scratch, void* stream);
+int vibo_dtrain_epilogue(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, float* scratch,
+                         const float* eps_item, const float* item_feat, const float* beta, const float* lr,
+                         int32_t* step_count, float* params, float* adam_m, float* adam_v, float* item_mu,
+                         float* item_logvar, float* item_m, float* item_v, float* loss_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

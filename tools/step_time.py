@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Train-step time of the module path (elbo_step + backward + Adam) eager vs replayed from a hipGraph
 (vibo_amd.torch_core.vibo.GraphedModuleStep), for the configurations FusedTrainer does not cover.
-   python tools/step_time.py [--irt 3] [--items 1000] [--ability-dim 1] [--batch 16] [--cond] [--flows 4] [--merge product]"""
+   python tools/step_time.py [--irt 3] [--items 1000] [--ability-dim 1] [--batch 16] [--cond] [--flows 4] [--merge product]
+With --generative-model link | deep | residual: the module step (eager) against FusedDecoderTrainer's native step, eager and
+replayed from a hipGraph, A/B interleaved on one box in --blocks blocks of --steps steps; medians and ranges per leg:
+   python tools/step_time.py --generative-model deep --irt 2 --items 100 --batch 16 --persons 20000 --blocks 5"""
 import argparse
 import os
 import sys
@@ -23,6 +26,10 @@ ap.add_argument('--batch', type=int, default=16)
 ap.add_argument('--cond', action='store_true')
 ap.add_argument('--flows', type=int, default=0)
 ap.add_argument('--merge', default='product')
+ap.add_argument('--generative-model', default='irt', choices=['irt', 'link', 'deep', 'residual'])
+ap.add_argument('--hidden-dim', type=int, default=64)
+ap.add_argument('--blocks', type=int, default=5, help='MLP decoders: interleaved timing blocks per leg')
+ap.add_argument('--steps', type=int, default=200, help='MLP decoders: steps per block')
 a = ap.parse_args()
 d = torch.device('cuda:0')
 g = torch.Generator(device=d).manual_seed(0)
@@ -38,6 +45,66 @@ data.response = (torch.rand(P, I, device=d, generator=g) < 0.5).float()
 data.mask = torch.rand(P, I, device=d, generator=g) >= 0.1
 data.device = d
 cls = {1: M.VIBO_1PL, 2: M.VIBO_2PL, 3: M.VIBO_3PL}[a.irt]
+
+
+def decoder_legs():
+    """Module step (eager; its captured form is not replayed here: DESIGN.md 4) vs the native step, eager and replayed."""
+    import statistics
+    from vibo_amd.trainer import FusedTrainer, fused_decoder_trainer_covers
+    kw = dict(hidden_dim=a.hidden_dim, ability_merge=a.merge, conditional_posterior=a.cond, n_norm_flows=a.flows,
+              generative_model=a.generative_model)
+    rows = [torch.randperm(P, device=d)[:B].contiguous() for _ in range(8)]
+    rbuf = torch.zeros(B, dtype=torch.int64, device=d)
+    torch.manual_seed(0)
+    m_mod = cls(A, I, **kw).to(d)
+    opt = torch.optim.Adam(m_mod.parameters(), lr=5e-3, fused=True)      # (as the CLI builds it)
+
+    def module_step(k):                   # train_epoch's own eager loop, on the current stream
+        opt.zero_grad(set_to_none=True)
+        loss = m_mod.elbo_step(data.response, data.mask, annealing_factor=1.0, row_index=rows[k % 8])
+        loss.backward()
+        opt.step()
+        return loss.detach()
+    legs = {'module eager': module_step}
+    if fused_decoder_trainer_covers(m_mod):
+        torch.manual_seed(0)
+        tr_e = FusedTrainer(cls(A, I, **kw).to(d), lr=5e-3, rng='native', seed=3)
+        legs['native eager'] = lambda k: tr_e.step(data.response, data.mask, row_index=rows[k % 8])
+        torch.manual_seed(0)
+        tr_g = FusedTrainer(cls(A, I, **kw).to(d), lr=5e-3, rng='native', seed=3)
+        for k in range(4):
+            rbuf.copy_(rows[k]); tr_g.step(data.response, data.mask, row_index=rbuf)
+        torch.cuda.synchronize()
+        gr = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(gr):
+            loss_g = tr_g.step(data.response, data.mask, row_index=rbuf)
+
+        def replay(k):
+            rbuf.copy_(rows[k % 8]); gr.replay()
+            return loss_g
+        legs['native graph'] = replay
+    for fn in legs.values():
+        for k in range(4):
+            fn(k)
+    torch.cuda.synchronize()
+    times = {name: [] for name in legs}
+    for blk in range(a.blocks):
+        for name, fn in legs.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for k in range(a.steps):
+                loss = fn(k)
+            torch.cuda.synchronize()
+            times[name].append((time.perf_counter() - t0) / a.steps * 1e6)
+            print(f'  block {blk} {name:13s}: {times[name][-1]:10.1f} us/step  loss {float(loss):.1f}')
+    for name, t in times.items():
+        print(f'{a.generative_model} irt={a.irt} I={I} A={A} B={B} H={a.hidden_dim} {name:13s}: median {statistics.median(t):10.1f} us/step  '
+              f'range {min(t):.1f} .. {max(t):.1f}  ({a.blocks} blocks x {a.steps} steps)')
+
+
+if a.generative_model != 'irt':
+    decoder_legs()
+    sys.exit(0)
 for mode in ('eager', 'graph'):
     torch.manual_seed(0)
     model = cls(A, I, ability_merge=a.merge, conditional_posterior=a.cond, n_norm_flows=a.flows).to(d)

@@ -4,7 +4,9 @@
 // in the same order, so the two forms of the step agree bit for bit
 // (tests/test_gpu_trainer.py::test_folded_step_equals_the_unfolded_step).
 // Below the MLP: what the plain, mean-merge and conditional / flow trainers (vibo_trainer.hip, vibo_mtrainer.hip,
-// vibo_ctrainer.hip) have in common -- the item side of a prologue, the ability-noise block, Adam, the item update and the loss.
+// vibo_ctrainer.hip) and the MLP-decoder trainer (vibo_dtrainer.hip) have in common -- the item side of a prologue, the
+// ability-noise block, Adam, the item update and the loss; at the end: the 2-row encoder backward + Adam of an epilogue's block 0
+// (epi_mlp_block: vibo_trainer.hip's three epilogues and vibo_dtrainer.hip's).
 //
 // Reference statements (models.py:356-361, 575-582, 713-726, 506-510; utils.py:85-88):
 //     item_feat = item_mu + exp(0.5 item_logvar) * eps_item
@@ -170,6 +172,126 @@ __device__ __forceinline__ void item_kl_loss(const int tid, const float* __restr
         for (int k = tid; k < n_kl_parts; k += 64) kl += kl_parts[k];
         kl = wave_total(kl);
         if (tid == 0) *loss_out = fmaf(beta, sc[VIBO_S_REG] + kl, -sc[VIBO_S_LL]);
+    }
+}
+
+constexpr int kEpiThreads = 1024;      // block 0's chain of small dependent stages is latency-bound: more lanes per stage, fewer passes
+struct EpiLds {
+    float h1[2][kMaxHidden], h2[2][kMaxHidden], gh2[2][kMaxHidden], gh1[2][kMaxHidden], gout[2][2 * VIBO_MAX_ABILITY_DIM_WIDE];
+};
+
+// Block 0 of the epilogue: loss, the 2-row MLP backward by hand, Adam on the MLP parameters.
+//   sc: the 8 ELBO scalars (VIBO_S_*); gtab: d LL / d table [2][O] then d REG / d table [2][O]
+//   W / ow: where the backward reads the weights and their layout -- the caller's flat buffer P (ld = H), or the fused
+//   epilogue's padded LDS copy, which then also receives the updated values (Wout) for the next step's forward
+//   pv / mv / vv: parameter, first and second moment of elements tid + 1024 u, loaded by the caller (as early as it can)
+//   HC: the hidden width as a compile-time constant (64: the reference default), or 0 for a runtime width -- the Adam loop
+//   decodes six flat indices per thread with / H and % H, ~40 instructions each when H is not a constant (5 us of the chain)
+constexpr int kEpiU = 8;
+template <int HC>
+__device__ __forceinline__ void epi_mlp_block(EpiLds& L, const int H_, const int O, const int n_kl_parts, const float* sc, const float* gtab,
+                                              const float* __restrict__ saved_h, const float* __restrict__ kl_parts, const float beta,
+                                              const float lr, const AdamBias bc, const float* W, const MlpOffsets ow,
+                                              float* Wout, float* P, float* M, float* V, float (&pv)[kEpiU], float (&mv)[kEpiU],
+                                              float (&vv)[kEpiU], float* loss_out, const int tid) {
+    constexpr int BS = kEpiThreads;
+    const int H = HC > 0 ? HC : H_;
+    const int n_table = 2 * O;
+    const MlpOffsets o = mlp_offsets(H, O);
+    for (int k = tid; k < 2 * H; k += BS) {
+        L.h1[k / H][k % H] = saved_h[k];
+        L.h2[k / H][k % H] = saved_h[2 * H + k];
+    }
+    // d loss / d table = -dLL + beta dREG
+    for (int k = tid; k < n_table; k += BS) L.gout[k / O][k % O] = fmaf(beta, gtab[n_table + k], -gtab[k]);
+    item_kl_loss(tid, kl_parts, n_kl_parts, sc, beta, loss_out);
+    __syncthreads();
+    // g_h2 = W2^T g_out * elu'(pre2),  elu'(x) = x > 0 ? 1 : elu(x) + 1
+    for (int k = tid; k < 2 * H; k += BS) {
+        const int r = k / H, j = k % H;
+        float a = 0.f;
+#pragma unroll 16
+        for (int q = 0; q < O; ++q) a = fmaf(W[ow.w2 + q * ow.ld + j], L.gout[r][q], a);      // 16 loads in flight
+        const float h = L.h2[r][j];
+        L.gh2[r][j] = a * (h > 0.f ? 1.0f : h + 1.0f);
+    }
+    __syncthreads();
+    // g_h1 = W1^T g_h2 * elu'(pre1): each of the 2 H dot products over H is cut into 8 pieces (8 neighbouring lanes)
+    {
+        const int len = (H + 7) / 8;
+        for (int k0 = 0; k0 < 2 * H * 8; k0 += BS) {
+            const int k = k0 + tid;
+            const int out = k >> 3, part = k & 7;
+            const int r = out / H, j = out % H;
+            float a = 0.f;
+            if (out < 2 * H) {
+                const int q1 = min(H, (part + 1) * len);
+                for (int q = part * len; q < q1; ++q) a = fmaf(W[ow.w1 + q * ow.ld + j], L.gh2[r][q], a);
+            }
+            a += __shfl_xor(a, 1);
+            a += __shfl_xor(a, 2);
+            a += __shfl_xor(a, 4);
+            if (out < 2 * H && part == 0) {
+                const float h = L.h1[r][j];
+                L.gh1[r][j] = a * (h > 0.f ? 1.0f : h + 1.0f);
+            }
+        }
+    }
+    __syncthreads();      // all reads of the OLD weights are done: parameters may now be updated in place
+    // Adam over the MLP parameters: 8 independent elements per thread and pass (the first pass's loads were issued by the caller)
+    constexpr int U = kEpiU;
+    for (int k0 = tid; k0 < o.total; k0 += BS * U) {
+        if (k0 != tid) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const int k = k0 + BS * u;
+                const bool ok = k < o.total;
+                pv[u] = ok ? P[k] : 0.f;
+                mv[u] = ok ? M[k] : 0.f;
+                vv[u] = ok ? V[k] : 0.f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int k = k0 + BS * u;
+            if (k >= o.total) continue;
+            float g;
+            if (k < o.b0) {                         // W0[j]: input of row r is r
+                g = L.gh1[1][k - o.w0];
+            } else if (k < o.w1) {
+                const int j = k - o.b0;
+                g = L.gh1[0][j] + L.gh1[1][j];
+            } else if (k < o.b1) {
+                const int j = (k - o.w1) / H, q = (k - o.w1) % H;
+                g = fmaf(L.gh2[0][j], L.h1[0][q], L.gh2[1][j] * L.h1[1][q]);
+            } else if (k < o.w2) {
+                const int j = k - o.b1;
+                g = L.gh2[0][j] + L.gh2[1][j];
+            } else if (k < o.b2) {
+                const int q = (k - o.w2) / H, j = (k - o.w2) % H;
+                g = fmaf(L.gout[0][q], L.h2[0][j], L.gout[1][q] * L.h2[1][j]);
+            } else {
+                const int q = k - o.b2;
+                g = L.gout[0][q] + L.gout[1][q];
+            }
+            adam_update(pv[u], mv[u], vv[u], g, lr, bc);
+            P[k] = pv[u];
+            M[k] = mv[u];
+            V[k] = vv[u];
+            if (Wout) Wout[mlp_reindex(k, H, O, ow)] = pv[u];      // (ow.ld = H + 1)
+        }
+    }
+}
+// the first pass's parameter / moment loads of epi_mlp_block
+__device__ __forceinline__ void epi_mlp_prefetch(const int total, const float* P, const float* M, const float* V, float (&pv)[kEpiU],
+                                                 float (&mv)[kEpiU], float (&vv)[kEpiU], const int tid) {
+#pragma unroll
+    for (int u = 0; u < kEpiU; ++u) {
+        const int k = tid + kEpiThreads * u;
+        const bool ok = k < total;
+        pv[u] = ok ? P[k] : 0.f;
+        mv[u] = ok ? M[k] : 0.f;
+        vv[u] = ok ? V[k] : 0.f;
     }
 }
 

@@ -21,6 +21,8 @@ KERNEL_NAMES = {1: 'matrix row-split (msplit_kernel)', 2: 'VALU row-split (split
 MAX_ABILITY_DIM = 16          # vibo_elbo_fwd_bwd / vibo_encode / vibo_decode (9..16: the wave-per-person kernel)
 MAX_ABILITY_DIM_FAST = 8      # row-split / matrix-pipe kernels, trainers' native conditional / flow step, mean merge
 MAX_FLOWS = 8
+DECODER_KINDS = {'link': 1, 'deep': 2, 'residual': 3}      # VIBO_DECODER_*
+DTRAIN_SCALARS, DTRAIN_POSTERIOR, DTRAIN_ABILITY = 0, 1, 2
 
 LIB_NAME = 'libvibo_hip.so'
 # VIBO_HIP_LIB points at another build of the same ABI (A/B timing of kernel variants); default: the in-tree build
@@ -73,7 +75,9 @@ EXPORTED_SYMBOLS = ('vibo_version', 'vibo_last_error_string', 'vibo_workspace_by
                     'vibo_train_step_supported', 'vibo_elbo_fwd_bwd_step', 'vibo_train_epilogue_fused', 'vibo_train_prime',
                     'vibo_mtrain_param_floats', 'vibo_mtrain_prologue', 'vibo_mean_encoder_backward_sets', 'vibo_mtrain_epilogue',
                     'vibo_set_insitu_timer', 'vibo_insitu_timer_reset', 'vibo_selftest_lane_swaps', 'vibo_elbo_fwd_bwd_counts',
-                    'vibo_train_step_draws_noise', 'vibo_elbo_fwd_bwd_step_noise')
+                    'vibo_train_step_draws_noise', 'vibo_elbo_fwd_bwd_step_noise',
+                    'vibo_dtrain_param_floats', 'vibo_dtrain_scratch_floats', 'vibo_dtrain_scratch_offset', 'vibo_dtrain_prologue',
+                    'vibo_dtrain_forward_backward', 'vibo_dtrain_epilogue')
 
 _lib = None
 
@@ -192,6 +196,19 @@ def load():
     lib.vibo_mean_encoder_backward_sets.argtypes = [dp, ctypes.c_int, vp, fp, fp, fp, fp, fp, fp, ctypes.c_int, vp]
     lib.vibo_mtrain_epilogue.restype = ctypes.c_int
     lib.vibo_mtrain_epilogue.argtypes = [dp, ctypes.c_int, fp, fp, ctypes.c_int, fp, fp, fp, fp, fp, fp, vp] + [fp] * 8 + [vp]
+    ci = ctypes.c_int
+    lib.vibo_dtrain_param_floats.restype = ctypes.c_int64
+    lib.vibo_dtrain_param_floats.argtypes = [dp, ci, ci]
+    lib.vibo_dtrain_scratch_floats.restype = ctypes.c_int64
+    lib.vibo_dtrain_scratch_floats.argtypes = [dp, ci, ci, ci]
+    lib.vibo_dtrain_scratch_offset.restype = ctypes.c_int64
+    lib.vibo_dtrain_scratch_offset.argtypes = [dp, ci, ci, ci, ci]
+    lib.vibo_dtrain_prologue.restype = ctypes.c_int
+    lib.vibo_dtrain_prologue.argtypes = [dp, ci, ci, ci, fp, fp, fp, fp, ctypes.c_uint64, ci, fp, ctypes.c_uint32, fp, fp, vp, vp]
+    lib.vibo_dtrain_forward_backward.restype = ctypes.c_int
+    lib.vibo_dtrain_forward_backward.argtypes = [dp, ci, ci, ci, fp, fp, vp, vp, fp, fp, fp, vp]
+    lib.vibo_dtrain_epilogue.restype = ctypes.c_int
+    lib.vibo_dtrain_epilogue.argtypes = [dp, ci, ci, ci] + [fp] * 5 + [vp] + [fp] * 8 + [vp]
     lib.vibo_selftest_lane_swaps.restype = ctypes.c_int
     lib.vibo_selftest_lane_swaps.argtypes = [fp, fp, vp]
     lib.vibo_set_insitu_timer.restype = ctypes.c_int

@@ -83,6 +83,11 @@ def build_parser():
                         'posterior, flows, mean merge, MLP decoders) from a hipGraph too; verified for small problems only: on this '
                         'PyTorch-ROCm stack a replayed autograd backward returns wrong bias gradients once a dense layer has a few '
                         'thousand rows (pure-PyTorch repro: tools/repro_graph_replay_bias_grad.py; DESIGN.md 4)')
+    p.add_argument('--native-decoder-step', action='store_true', default=False,
+                   help='run the whole train step of --generative-model link | deep | residual natively (FusedDecoderTrainer: no '
+                        'autograd, no torch.optim; replayed from a hipGraph unless --no-graph): needs --cuda, the product encoder with '
+                        'the unconditional posterior, no flows, one GPU; without the flag these models train through the module + '
+                        'torch.optim.Adam as before')
     p.add_argument('--no-graph', action='store_true', default=False,
                    help='launch every fused train step eagerly instead of replaying a hipGraph (single-GPU runs)')
     p.add_argument('--store-predictive-samples', action='store_true', default=False,
@@ -125,8 +130,29 @@ def check_supported(args):
         problems.append("--ability-merge mean with --ability-dim above 8 (its caller-supplied posterior needs the row-split kernels)")
     if args.response_dist != 'bernoulli':
         problems.append("--response-dist gaussian (the reference's loader has no *_continuous datasets either)")
+    if getattr(args, 'native_decoder_step', False):
+        why = native_decoder_step_problem(args)
+        if why:
+            problems.append(f"--native-decoder-step with {why} (that configuration trains through the module + torch.optim.Adam: drop the flag)")
     if problems:
         raise SystemExit('not supported by the MI355X engine: ' + '; '.join(problems))
+
+
+def native_decoder_step_problem(args):
+    """Why --native-decoder-step cannot serve these flags (None: it can): FusedDecoderTrainer's coverage, from the flags alone."""
+    if not args.cuda:
+        return 'no --cuda (the native step is GPU code)'
+    if args.torch_optimizer:
+        return '--torch-optimizer (the native step has its own Adam)'
+    if args.generative_model == 'irt':
+        return '--generative-model irt (the IRT decoder has its fused trainers already)'
+    if args.ability_merge != 'product':
+        return f'--ability-merge {args.ability_merge}'
+    if args.conditional_posterior:
+        return '--conditional-posterior'
+    if args.n_norm_flows > 0:
+        return '--n-norm-flows'
+    return None
 
 
 def out_dir_name(args):
@@ -487,6 +513,13 @@ def main(argv=None):
         # (--ability-merge mean, unconditional posterior) FusedMeanTrainer's -- same Adam arithmetic, 2-12 launches
         # per step, no PyTorch autograd inside the replayed graph
         from ..trainer import FusedTrainer
+        trainer = FusedTrainer(model, lr=args.lr, rng=args.rng, seed=args.seed, max_batch=local_bs)
+    if args.native_decoder_step:
+        # opt-in: the MLP decoders' whole step natively (FusedDecoderTrainer), replayed from a hipGraph below like the other trainers
+        from ..trainer import FusedTrainer, fused_decoder_trainer_covers
+        if world > 1 or not fused_decoder_trainer_covers(model, args.hidden_dim):
+            raise SystemExit('--native-decoder-step: ' + ('person sharding' if world > 1 else 'this model') + ' is not covered by '
+                             'FusedDecoderTrainer (it trains through the module + torch.optim.Adam: drop the flag)')
         trainer = FusedTrainer(model, lr=args.lr, rng=args.rng, seed=args.seed, max_batch=local_bs)
     graphed = None
     # The captured module step is opt-in (--graph-module-step): it is 3-4 x faster at small minibatches and follows the eager

@@ -32,8 +32,10 @@ populated.
 FusedTrainer covers the unconditional posterior without flows; `FusedTrainer(model)` returns its sibling
 FusedCondFlowTrainer (same interface, vibo_ctrain_* kernels) for --conditional-posterior / --n-norm-flows models.
 FusedMeanTrainer (vibo_mtrain_* kernels) is the same for --ability-merge mean with the unconditional posterior (person-sharded too).
-The MLP decoders and mean x conditional train through the module + torch.optim path
-(fused_trainer_covers() tells which).
+FusedDecoderTrainer (vibo_dtrain_* kernels around vibo_decoder_fwd_bwd) is the same for --generative-model link | deep | residual
+with the product encoder's unconditional posterior (`FusedTrainer(model)` returns it; fused_decoder_trainer_covers() tells which).
+Mean x conditional, and the MLP decoders with the conditional posterior / flows / mean merge, train through the module +
+torch.optim path (fused_trainer_covers() tells which of the IRT-decoder models are covered).
 """
 import ctypes
 
@@ -61,10 +63,23 @@ def fused_trainer_covers(model, hidden_dim=None):
     return True
 
 
+def fused_decoder_trainer_covers(model, hidden_dim=None):
+    """True when FusedDecoderTrainer runs the model's whole train step natively: --generative-model link | deep | residual on the
+    product-of-experts encoder with the unconditional posterior, no flows, not person-sharded, hidden width <= 64, at most 65 535
+    items (the packed row counts).  Everything else with an MLP decoder trains through the module + torch.optim.Adam."""
+    if getattr(model, 'generative_model', 'irt') not in _lib.DECODER_KINDS:
+        return False
+    H = hidden_dim if hidden_dim is not None else model.ability_encoder.mlp[0].weight.shape[0] if model.ability_merge == 'product' else 0
+    return (model.ability_merge == 'product' and not model.conditional_posterior and model.n_norm_flows == 0
+            and model._reducer is None and H <= 64 and model.num_item <= 65535 and model.ability_dim <= _lib.MAX_ABILITY_DIM)
+
+
 class FusedTrainer:
     def __new__(cls, model=None, *args, **kwargs):
         # one entry point: the conditional posterior / planar flows are served by the sibling class below
         # (model=None: copy / pickle re-create the object through cls.__new__(cls) and fill __dict__ themselves)
+        if cls is FusedTrainer and model is not None and getattr(model, 'generative_model', 'irt') != 'irt':
+            return super().__new__(FusedDecoderTrainer)
         if cls is FusedTrainer and model is not None and model.ability_merge == 'mean':
             return super().__new__(FusedMeanTrainer)
         if cls is FusedTrainer and model is not None and (model.conditional_posterior or model.n_norm_flows > 0):
@@ -529,4 +544,155 @@ class FusedMeanTrainer(FusedTrainer):
                                       p(self.par_m), p(self.par_v), p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v),
                                       p(self.loss), stream)
         _lib.check(rc, 'vibo_mtrain_epilogue')
+        return self.loss
+
+
+class _DecoderStep:
+    """What a FusedDecoderTrainer step leaves behind (`trainer.last`): flat = [LL, KL_ability, ...] (8 floats), the posterior and
+    the ability sample -- views of the step's scratch buffer."""
+    __slots__ = ('flat', 'ability_mu', 'ability_logvar', 'ability')
+
+    def __init__(self, flat, ability_mu, ability_logvar, ability):
+        self.flat, self.ability_mu, self.ability_logvar, self.ability = flat, ability_mu, ability_logvar, ability
+
+    scalars = property(lambda self: self.flat)
+
+
+class FusedDecoderTrainer(FusedTrainer):
+    """The fused train step for --generative-model link | deep | residual (vibo.py:243-268 with models.py:337-443, 596-629,
+    769-919): vibo_dtrain_prologue (item sample, item KL, 2-row encoder table, mlp_item_feat and U; optionally the Philox noise) ->
+    vibo_dtrain_forward_backward (per chunk of decoder.PERSON_CHUNK persons: product of experts from the packed row counts, ability
+    sample, mlp_ability and V, IRT logit; vibo_decoder_fwd_bwd; the backward of all that into fixed-order records) ->
+    vibo_dtrain_epilogue (record sums, loss, mlp_item_feat / guess / encoder / item backward, Adam on everything).  No PyTorch
+    autograd node and no torch.optim: the step replays from a hipGraph like FusedTrainer's, bitwise reproducible.  Same interface
+    (`FusedTrainer(model, ...)` returns this class for such models).  The decoder kernel walks dense fp32 rows: a `row_index`
+    minibatch is gathered into a persistent buffer (torch.index_select(out=)), cell codes are unpacked per step.
+    Covers the product encoder's unconditional posterior without flows, analytic KL, hidden width <= 64, one GPU."""
+
+    def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None):
+        kind = getattr(model, 'generative_model', 'irt')
+        why = None
+        if kind not in _lib.DECODER_KINDS:
+            why = 'an IRT-decoder model (FusedTrainer covers those)'
+        elif model.ability_merge != 'product':
+            why = '--ability-merge mean'
+        elif model.conditional_posterior:
+            why = 'the conditional posterior'
+        elif model.n_norm_flows > 0:
+            why = 'normalizing flows'
+        elif model._reducer is not None:
+            why = 'person sharding'
+        elif model.num_item > 65535:
+            why = 'more than 65 535 items (the packed row counts)'
+        if why is not None:
+            raise NotImplementedError(f'FusedDecoderTrainer does not cover {why}; use model.elbo_step + torch.optim.Adam')
+        self.model = model
+        self.kind = _lib.DECODER_KINDS[kind]
+        self.generation = 0                   # (no buffer of this step ever moves: see FusedTrainer.generation)
+        self._primed_for, self._folded_open = None, False      # (FusedTrainer.invalidate's fields: every step starts from the parameters)
+        mlp, dec = model.ability_encoder.mlp, model.decoder
+        self.hidden = mlp[0].weight.shape[0]
+        if self.hidden > 64 or dec.hidden_dim != self.hidden:
+            raise NotImplementedError('FusedDecoderTrainer: hidden_dim <= 64 (the per-term decoder kernel\'s width); '
+                                      'use model.elbo_step + torch.optim.Adam otherwise')
+        stacks = [dec.link] if kind == 'link' else [dec.mlp_item_feat, dec.mlp_ability, dec.mlp_concat]
+        plist = [t for st in [mlp] + stacks for k in (0, 2, 4) for t in (st[k].weight, st[k].bias)]
+        self.par_flat, self.par_m, self.par_v = self._flatten(plist)      # (the layout of include/vibo_hip.h: vibo_dtrain_*)
+        dev, _ = self._init_state(model, lr)
+        I = self.item_mu.shape[0]
+        self._desc0 = ops._make_desc(model.spec, 1, I, _lib.MASK_NONE, _lib.REG_KL, True, I, 0)
+        lib = _lib.load()
+        if lib.vibo_dtrain_param_floats(ctypes.byref(self._desc0), self.kind, self.hidden) != self.par_flat.numel():
+            raise RuntimeError('FusedDecoderTrainer: parameter layout mismatch')
+        self._init_rng(rng, seed)
+        self.fused_noise = True
+        self._scratch = {}                    # (persons, chunk) -> scratch buffer: never freed or replaced (captured graphs point at it)
+        self._rows = {}                       # (persons, mask given) -> the gathered minibatch's dense rows: never replaced
+
+    def _dense_rows(self, response, mask, row_index):
+        """The minibatch as the decoder kernel reads it: fp32 rows + u8 mask (or None), no autograd node."""
+        if isinstance(response, ops.CellCodes):
+            if mask is not None:
+                raise ValueError('CellCodes rows carry their own missingness: pass mask=None')
+            r, m = (response.rows(row_index) if row_index is not None else response).unpack()
+            return r, m.view(torch.uint8)
+        response = ops.prepare_response(response)
+        if mask is not None and mask.dtype == torch.int64:
+            raise NotImplementedError('FusedDecoderTrainer reads bool / uint8 masks; use model.elbo_step + torch.optim.Adam for int64 masks')
+        mask = ops.prepare_mask(mask)[0]
+        if row_index is None:
+            return response, mask
+        B = int(row_index.numel())
+        key = (B, mask is not None)           # one entry per kind of call: a captured graph keeps pointing at its own
+        bufs = self._rows.get(key)
+        if bufs is None:
+            I = response.shape[1]
+            bufs = self._rows[key] = (torch.empty(B, I, device=response.device),
+                                      None if mask is None else torch.empty(B, I, dtype=torch.uint8, device=response.device))
+        torch.index_select(response, 0, row_index, out=bufs[0])
+        if mask is not None:
+            torch.index_select(mask, 0, row_index, out=bufs[1])
+        return bufs
+
+    @torch.no_grad()
+    def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
+        from . import decoder
+        model, lib, p = self.model, _lib.load(), ops._ptr
+        if beta is not None:
+            self.set_beta(beta)
+        if mask is not None and mask.dtype == torch.int64:
+            raise NotImplementedError('FusedDecoderTrainer reads bool / uint8 masks; use model.elbo_step + torch.optim.Adam for int64 masks')
+        counts = ops.row_counts(response, mask)             # packed (n_correct << 16 | n_observed) of every resident row, cached
+        if row_index is not None:
+            counts = counts[row_index]
+        r, m = self._dense_rows(response, mask, row_index)
+        B, I = r.shape
+        dev = r.device
+        A, H = model.ability_dim, self.hidden
+        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        d = ops._make_desc(model.spec, B, I, _lib.MASK_NONE if m is None else _lib.MASK_U8, _lib.REG_KL, True, r.stride(0),
+                           m.stride(0) if m is not None else 0)
+        chunk = min(int(decoder.PERSON_CHUNK), B)
+        scratch = self._scratch.get((B, chunk))
+        if scratch is None:
+            n = int(lib.vibo_dtrain_scratch_floats(ctypes.byref(d), self.kind, H, chunk))
+            if n <= 0:
+                _lib.check(-6, 'vibo_dtrain_scratch_floats')
+            scratch = self._scratch[(B, chunk)] = torch.empty(n, device=dev)
+            scratch[:_lib.NUM_SCALARS].zero_()
+        eps_item, eps_ab, native = self._choose_noise(B, dev, eps_item, eps_ability)
+        rc = lib.vibo_dtrain_prologue(ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(self.item_mu), p(self.item_lv),
+                                      p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, 1, p(self.item_feat),
+                                      p(scratch), p(self._steps), stream)
+        _lib.check(rc, 'vibo_dtrain_prologue')
+        if eps_ab is None:
+            eps_ab = model._randn((B, A), self.item_mu, model._ability_gen)
+        rc = lib.vibo_dtrain_forward_backward(ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts), p(eps_ab),
+                                              p(self.item_feat), p(scratch), stream)
+        _lib.check(rc, 'vibo_dtrain_forward_backward')
+        off = [int(lib.vibo_dtrain_scratch_offset(ctypes.byref(d), self.kind, H, chunk, w))
+               for w in (_lib.DTRAIN_SCALARS, _lib.DTRAIN_POSTERIOR, _lib.DTRAIN_ABILITY)]
+        post = scratch[off[1]:off[1] + B * 2 * A].view(B, 2 * A)
+        self.last = _DecoderStep(scratch[off[0]:off[0] + _lib.NUM_SCALARS], post[:, :A], post[:, A:],
+                                 scratch[off[2]:off[2] + B * A].view(B, A))
+        self._pending = (d, eps_item, scratch, chunk)
+        return self.last
+
+    @torch.no_grad()
+    def step(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
+        self.forward_backward(response, mask, beta=beta, row_index=row_index, eps_item=eps_item, eps_ability=eps_ability)
+        return self.update()
+
+    @torch.no_grad()
+    def update(self):
+        if self._pending is None:
+            raise RuntimeError('FusedDecoderTrainer.update(): no forward_backward() is pending')
+        d, eps_item, scratch, chunk = self._pending
+        self._pending = None
+        lib, p = _lib.load(), ops._ptr
+        stream = ctypes.c_void_p(torch.cuda.current_stream(scratch.device).cuda_stream)
+        rc = lib.vibo_dtrain_epilogue(ctypes.byref(d), self.kind, self.hidden, chunk, p(scratch), p(eps_item), p(self.item_feat),
+                                      p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
+                                      p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.loss), stream)
+        _lib.check(rc, 'vibo_dtrain_epilogue')
         return self.loss
