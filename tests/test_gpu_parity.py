@@ -790,12 +790,16 @@ def test_conditional_posterior_one_dim_at_full_size(irt, P, I, monkeypatch):
         assert (t[:n].cpu() - ref[k].float()).abs().max() < 2e-5 * max(1.0, float(ref[k].abs().max())), k
 
 
-@pytest.mark.parametrize('codes', [False, True], ids=['fp32-rows', 'cell-codes'])
-def test_resident_row_counts_change_nothing(codes, monkeypatch):
+@pytest.mark.parametrize('codes,P,I,n_rows,second_stream',
+                         [(False, 3000, 2500, 700, False), (True, 3000, 2500, 700, False), (False, 64, 1028, 16, True), (True, 64, 1028, 16, True)],
+                         ids=['fp32-rows', 'cell-codes', 'fp32-rows-64x1028-second-stream', 'cell-codes-64x1028-second-stream'])
+def test_resident_row_counts_change_nothing(codes, P, I, n_rows, second_stream, monkeypatch):
     """Rows of more than 1024 items under the unconditional posterior: a matrix the process calls with a second time is counted once
     (ops._resident_row_counts -> vibo_elbo_fwd_bwd_counts) and the count pass in front of the panels goes away -- the whole matrix and
-    minibatches gathered from it give the bits of the counting call."""
-    irt, A, P, I = 2, 2, 3000, 2500
+    minibatches gathered from it give the bits of the counting call.  second_stream: the matrix is counted on the current stream
+    and consumed on another -- the same bits; that the consumer waits on the record's event (finding 3) is pinned by
+    test_host_logic.py::test_counts_are_ordered_behind_their_stream, a missing wait here would be a race, not a certain failure."""
+    irt, A = 2, 2
     d = dev()
     spec = ElboSpec(irt_model=irt, ability_dim=A)
     resp, mask, table, item, eps = _device_problem(irt, A, P, I, 0.2, seed=77, cond=False)
@@ -805,10 +809,11 @@ def test_resident_row_counts_change_nothing(codes, monkeypatch):
     else:
         rp, mp = ops.pad_rows(resp, mask)
         r2, m2, code = ops.prepare_rows(rp, mp)
-    rows = torch.randperm(P, device=d, generator=torch.Generator(device=d).manual_seed(3))[:700].contiguous()
+    rows = torch.randperm(P, device=d, generator=torch.Generator(device=d).manual_seed(3))[:n_rows].contiguous()
+    eps_rows = eps[rows].contiguous()
 
     def run(row_index=None):
-        e = eps if row_index is None else eps[row_index].contiguous()
+        e = eps if row_index is None else eps_rows
         B = P if row_index is None else int(row_index.numel())
         out = ops._hip_launch_elbo(spec, r2, m2, code, row_index, table, item, e, None, _lib.REG_KL, True, B)
         torch.cuda.synchronize()
@@ -818,11 +823,69 @@ def test_resident_row_counts_change_nothing(codes, monkeypatch):
     full0, mb0 = run(), run(rows)
     monkeypatch.setattr(ops, 'ROW_COUNT_CACHE', True)
     run()                                        # first sighting: still the counting call
-    assert r2._vibo_row_counts[3] is None
-    full1, mb1 = run(), run(rows)                # second: counted once, handed over from here on
-    assert r2._vibo_row_counts[3] is not None
+    assert r2._vibo_row_counts.counts is None
+    if second_stream:
+        full1 = ops._hip_launch_elbo(spec, r2, m2, code, None, table, item, eps, None, _lib.REG_KL, True, P)      # counted here, no sync
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            mb1 = ops._hip_launch_elbo(spec, r2, m2, code, rows, table, item, eps_rows, None, _lib.REG_KL, True, n_rows)
+        torch.cuda.synchronize()
+        assert r2._vibo_row_counts.stream == torch.cuda.current_stream(d) and r2._vibo_row_counts.stream != side
+    else:
+        full1, mb1 = run(), run(rows)            # second: counted once, handed over from here on
+    assert r2._vibo_row_counts.counts is not None
     for a, b in ((full0, full1), (mb0, mb1)):
         assert torch.equal(a.flat, b.flat) and torch.equal(a.ability_mu, b.ability_mu) and torch.equal(a.ability, b.ability)
+
+
+@pytest.mark.parametrize('gathered', [False, True], ids=['whole-matrix', 'row-index'])
+def test_captured_whole_matrix_call_counts_inside_the_graph(gathered, monkeypatch):
+    """ADVICE round 6, finding 1.  whole-matrix: a call with row_index=None captured into a hipGraph after the eager calls that left
+    counts behind records its own count pass (vibo_elbo_fwd_bwd) -- the usual static-input pattern `response.copy_(new);
+    mask.copy_(new_mask); replay()` gives the new data's posterior, ELBO and gradients, bit for bit those of an eager counting call
+    (the cached counts baked into the graph gave the old data's).  row-index: 16 rows gathered from a resident matrix that does not
+    change keep its cached counts under capture, with the bits of the eager counting call."""
+    irt, A, P, I = 2, 2, 64, 1028
+    d = dev()
+    spec = ElboSpec(irt_model=irt, ability_dim=A)
+    resp, mask, table, item, eps = _device_problem(irt, A, P, I, 0.2, seed=81, cond=False)
+    other, other_mask = _device_problem(irt, A, P, I, 0.2, seed=82, cond=False)[:2]
+    rp, mp = ops.pad_rows(resp, mask)
+    r2, m2, code = ops.prepare_rows(rp, mp)
+    rows = torch.randperm(P, device=d, generator=torch.Generator(device=d).manual_seed(4))[:16].contiguous() if gathered else None
+    e = eps[rows].contiguous() if gathered else eps
+    B = 16 if gathered else P
+
+    def call(row_index=rows, e=e, B=B):
+        return ops._hip_launch_elbo(spec, r2, m2, code, row_index, table, item, e, None, _lib.REG_KL, True, B)
+
+    def counting_call():
+        monkeypatch.setattr(ops, 'ROW_COUNT_CACHE', False)
+        out = call()
+        monkeypatch.setattr(ops, 'ROW_COUNT_CACHE', True)
+        torch.cuda.synchronize()
+        return [t.clone() for t in (out.flat, out.ability_mu, out.ability)]
+
+    call(None, eps, P), call(None, eps, P)                  # two eager calls: the resident matrix has its counts
+    assert r2._vibo_row_counts.counts is not None
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        out = call()
+
+    def replay():
+        graph.replay()
+        torch.cuda.synchronize()
+        return [t.clone() for t in (out.flat, out.ability_mu, out.ability)]
+
+    first, ref = replay(), counting_call()
+    assert all(torch.equal(a, b) for a, b in zip(first, ref))
+    if not gathered:
+        rp.copy_(other)
+        mp.copy_(other_mask)
+        second, ref2 = replay(), counting_call()
+        assert not torch.equal(ref2[0], ref[0])
+        assert all(torch.equal(a, b) for a, b in zip(second, ref2))
 
 
 def test_resident_row_counts_through_the_module(monkeypatch):
@@ -853,7 +916,7 @@ def test_resident_row_counts_through_the_module(monkeypatch):
     ref = steps()
     monkeypatch.setattr(ops, 'ROW_COUNT_CACHE', True)
     got = steps()
-    assert getattr(resp, '_vibo_row_counts', None) is not None and resp._vibo_row_counts[3] is not None, 'the resident matrix was not recognised'
+    assert getattr(resp, '_vibo_row_counts', None) is not None and resp._vibo_row_counts.counts is not None, 'the resident matrix was not recognised'
     for (l0, g0), (l1, g1) in zip(ref, got):
         assert torch.equal(l0, l1)
         for a, b in zip(g0, g1):

@@ -277,3 +277,216 @@ def test_elbo_accepts_a_materialised_response_mu_and_reruns_with_the_row_index(c
         assert abs(float(loss_c) - float(loss_d)) <= 1e-4 * abs(float(loss_d))
     finally:
         restore()
+
+
+# ---------------------------------------------------------------------------
+# the resident-matrix record of ops.py (ops.ResidentMatrix, ops._lookup_counts) on CPU tensors: every count goes through
+# ops._BACKEND['counts'], so the launches are counted by wrapping that entry around the CPU oracle's
+# ---------------------------------------------------------------------------
+@pytest.fixture()
+def count_calls(cpu_ops):
+    calls = []
+    inner = ops._BACKEND['counts']
+    ops._BACKEND['counts'] = lambda *a: (calls.append(a[3]), inner(*a))[1]
+    yield calls
+    ops._BACKEND['counts'] = inner
+
+
+def _matrix(P=12, I=9, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.rand(P, I, generator=g) < 0.5).float(), torch.rand(P, I, generator=g) > 0.2
+
+
+class _FakeStream:
+    def __init__(self, log, name):
+        self.log, self.name = log, name
+
+    def record_event(self):
+        self.log.append(('record', self.name))
+        return 'event of ' + self.name
+
+    def wait_event(self, event):
+        self.log.append(('wait', self.name, event))
+
+
+def _elbo_lookup(resp, mask, row_index=None, B=None, capturing=False, stream=_FakeStream([], 'a stream')):
+    """ops._lookup_counts as the ELBO launch calls it (ops._resident_row_counts behind its early-outs)."""
+    r, m, code = ops.prepare_rows(resp, mask)
+    B = (r.shape[0] if row_index is None else int(row_index.numel())) if B is None else B
+    return ops._lookup_counts(r, None if isinstance(resp, ops.CellCodes) else m, (r, m, code), row_index, B,
+                              for_elbo=True, capturing=lambda: capturing, stream=stream)
+
+
+def _expected_counts(resp, mask):
+    return (((resp == 1) & mask).sum(1).to(torch.int32) << 16) | mask.sum(1).to(torch.int32)
+
+
+def test_resident_record_never_confuses_a_dead_mask_with_no_mask(count_calls):
+    """ADVICE round 6, finding 2: a record made with a mask whose tensor has since been freed must not match mask=None (the
+    masked counts would serve an unmasked call), nor a record made without a mask a call with one."""
+    import gc
+    resp, mask = _matrix()
+    ops.row_counts(resp, mask)
+    rec = resp._vibo_row_counts
+    assert rec.has_mask and rec.counts is not None and rec.is_(resp, mask)
+    del mask
+    gc.collect()
+    assert rec.mask.ref() is None and not rec.is_(resp, None)
+    assert torch.equal(ops.row_counts(resp, None), _expected_counts(resp, torch.ones_like(resp, dtype=torch.bool)))
+    assert len(count_calls) == 2
+    rec = resp._vibo_row_counts
+    assert not rec.has_mask and rec.is_(resp, None) and not rec.is_(resp, _matrix(seed=1)[1])
+    assert _elbo_lookup(resp, _matrix(seed=1)[1]) is None and len(count_calls) == 2      # recorded without a mask, looked up with one: a first sighting
+
+
+@pytest.mark.parametrize('edit', ['response', 'mask'])
+def test_resident_record_misses_after_an_in_place_edit(count_calls, edit):
+    resp, mask = _matrix()
+    assert _elbo_lookup(resp, mask) is None and _elbo_lookup(resp, mask) is not None and len(count_calls) == 1
+    if edit == 'response':
+        resp[3, :] = 1.0
+    else:
+        mask[3, :] = False
+    assert not resp._vibo_row_counts.is_(resp, mask)
+    assert _elbo_lookup(resp, mask) is None and len(count_calls) == 1          # a first sighting again: the kernel counts
+    got = _elbo_lookup(resp, mask)                                               # the next one counts the matrix as it is now
+    assert len(count_calls) == 2 and torch.equal(got, _expected_counts(resp, mask))
+
+
+def test_elbo_lookup_policy_eager_and_capturing(count_calls):
+    """First sighting: recorded only.  Second: one whole-matrix count.  From then on: served.  While capturing (ADVICE round 6,
+    finding 1): never with row_index=None -- the captured input is the matrix, a replay has to count what is there then --, with a
+    row_index yes, and nothing is counted."""
+    resp, mask = _matrix()
+    rows = torch.tensor([5, 1, 7])
+    assert _elbo_lookup(resp, mask, capturing=True) is None and count_calls == []
+    assert _elbo_lookup(resp, mask, rows, capturing=True) is None and count_calls == []      # capturing, no counts yet: nothing is counted
+    cnt = _elbo_lookup(resp, mask)
+    assert count_calls == [None] and torch.equal(cnt, _expected_counts(resp, mask))
+    assert _elbo_lookup(resp, mask) is cnt and _elbo_lookup(resp, mask, rows) is cnt and count_calls == [None]
+    assert _elbo_lookup(resp, mask, capturing=True) is None
+    assert _elbo_lookup(resp, mask, rows, capturing=True) is cnt and count_calls == [None]
+
+
+def test_elbo_lookup_counts_nothing_it_would_throw_away(count_calls):
+    """ADVICE round 6, finding 3: row_index=None on fewer persons than the matrix has rows uses no whole-matrix counts."""
+    resp, mask = _matrix()
+    for _ in range(3):
+        assert _elbo_lookup(resp, mask, B=5) is None
+    assert count_calls == [] and not hasattr(resp, '_vibo_row_counts')
+
+
+def test_counts_are_ordered_behind_their_stream(count_calls):
+    """ADVICE round 6, finding 3: the counts remember their stream and an event; a consumer on another stream waits on it, the same
+    stream gets no extra call, a capturing stream (which cannot wait on an eager event) none either."""
+    resp, mask = _matrix()
+    log = []
+    main, side = _FakeStream(log, 'main'), _FakeStream(log, 'side')
+    _elbo_lookup(resp, mask, stream=main)
+    assert log == []
+    _elbo_lookup(resp, mask, stream=main)
+    assert log == [('record', 'main')]
+    _elbo_lookup(resp, mask, stream=main)
+    assert log == [('record', 'main')]
+    _elbo_lookup(resp, mask, stream=side)
+    assert log == [('record', 'main'), ('wait', 'side', 'event of main')]
+    _elbo_lookup(resp, mask, torch.tensor([1, 2]), stream=side, capturing=True)
+    assert len(log) == 2 and len(count_calls) == 1
+
+
+def test_row_counts_launches_per_resident_matrix(count_calls):
+    """The sequence of test_gpu_mean_merge.py::test_row_counts_are_cached_per_resident_matrix: the same launch counts."""
+    g = torch.Generator().manual_seed(1)
+    resp, mask = O.simulate_responses(2, 300, 100, 1, generator=g, missing_frac=0.2)
+    mask = mask.bool()
+    rows = torch.tensor([5, 7, 299])
+    a = ops.row_counts(resp, mask, rows)               # first gathered minibatch of this matrix: those rows only
+    a2 = ops.row_counts(resp, mask, rows)              # the matrix came back: counted as a whole, once
+    b = ops.row_counts(resp, mask)
+    c = ops.row_counts(resp, mask, rows)
+    assert len(count_calls) == 2 and torch.equal(a, b[rows]) and torch.equal(a, c) and torch.equal(a, a2)
+    mask[5, :] = False                                 # in-place change: counted again
+    d_ = ops.row_counts(resp, mask, rows)
+    assert len(count_calls) == 3 and int(d_[0]) == 0 and torch.equal(d_[1:], a[1:])
+    codes = ops.CellCodes(torch.where(mask, resp.to(torch.uint8), torch.full((), 2, dtype=torch.uint8)))
+    e = ops.row_counts(codes, None)
+    f = ops.row_counts(codes, None, rows)
+    assert len(count_calls) == 4 and torch.equal(e[rows], f) and torch.equal(e, ops.row_counts(resp, mask))
+    assert len(count_calls) == 4 and _elbo_lookup(codes, None) is e
+
+
+@pytest.mark.parametrize('mask_dtype', [torch.bool, torch.int64])
+def test_row_counts_and_the_elbo_lookup_recognise_the_same_matrix(count_calls, mask_dtype):
+    """row_counts() is called with the caller's tensors, the ELBO launch with prepare_rows()'s: one record serves both."""
+    resp, mask = _matrix()
+    mask = mask.to(mask_dtype)
+    cnt = ops.row_counts(resp, mask)
+    assert _elbo_lookup(resp, mask) is cnt and len(count_calls) == 1
+    resp2, mask2 = _matrix(seed=2)
+    mask2 = mask2.to(mask_dtype)
+    _elbo_lookup(resp2, mask2)
+    cnt2 = _elbo_lookup(resp2, mask2)
+    assert ops.row_counts(resp2, mask2) is cnt2 and torch.equal(ops.row_counts(resp2, mask2, torch.tensor([3])), cnt2[[3]])
+    assert len(count_calls) == 2
+
+
+def test_prepare_mask_narrows_once_per_live_mask():
+    import weakref
+    for dtype in (torch.bool, torch.int64):
+        mask = _matrix()[1].to(dtype)
+        a, code = ops.prepare_mask(mask)
+        assert code == ops._lib.MASK_U8 and a.dtype == torch.uint8 and ops.prepare_mask(mask)[0] is a
+        assert torch.equal(a != 0, mask != 0) and a.stride() == mask.stride()
+        mask[0, 0] = 1 - mask[0, 0] if dtype == torch.int64 else ~mask[0, 0]
+        b = ops.prepare_mask(mask)[0]
+        assert torch.equal(b != 0, mask != 0) and ops.prepare_mask(mask)[0] is b
+        if dtype == torch.int64:
+            assert b is not a and b.data_ptr() != a.data_ptr()          # a fresh copy after the in-place edit
+        else:
+            assert b.data_ptr() == mask.data_ptr()                      # read in place
+        narrowed, caller = weakref.ref(b), weakref.ref(mask)
+        del a, b, mask
+        assert narrowed() is None and caller() is None                  # freed with the mask, without the garbage collector
+    padded = ops.pad_rows(*_matrix(I=7))[1]                             # strided rows are aliased as they are
+    p8 = ops.prepare_mask(padded)[0]
+    assert p8.stride() == (8, 1) and p8.data_ptr() == padded.data_ptr() and torch.equal(p8 != 0, padded)
+
+
+@pytest.mark.parametrize('mask_dtype', [torch.bool, torch.int64])
+def test_an_edit_through_the_narrowed_mask_is_a_miss(count_calls, mask_dtype):
+    """prepare_rows() hands out the narrowed mask, and that is the tensor a caller of the ELBO launch holds: an in-place edit made
+    through it must miss like one made through the caller's own tensor (a bool mask's narrowed form shares its version counter; the
+    copy of an int64 mask stops standing for that mask once it has been edited itself)."""
+    resp, mask = _matrix()
+    mask = mask.to(mask_dtype)
+    r, m8, code = ops.prepare_rows(resp, mask)
+    look = lambda: ops._lookup_counts(r, m8, (r, m8, code), None, r.shape[0], for_elbo=True, capturing=lambda: False, stream=None)
+    assert look() is None and look() is not None and len(count_calls) == 1
+    m8[0, :] = 0
+    assert not r._vibo_row_counts.is_(r, m8)
+    assert look() is None and len(count_calls) == 1
+    got = look()
+    assert len(count_calls) == 2 and int(got[0]) == 0 and torch.equal(got, _expected_counts(resp, m8 != 0))
+    if mask_dtype == torch.int64:
+        assert ops.prepare_mask(mask)[0] is not m8          # the edited copy no longer stands for the caller's mask
+
+
+def test_counts_recorded_into_a_graph_are_not_served_to_the_elbo_launch(count_calls):
+    resp, mask = _matrix()
+    side = _FakeStream([], 'capturing')
+    cnt = ops._lookup_counts(resp, mask, lambda: ops.prepare_rows(resp, mask, keep_int64=True), None, resp.shape[0], for_elbo=False,
+                             capturing=lambda: True, stream=side)
+    assert cnt is not None and resp._vibo_row_counts.in_graph and side.log == []
+    assert _elbo_lookup(resp, mask) is None and _elbo_lookup(resp, mask, torch.tensor([1])) is None and len(count_calls) == 1
+    assert ops.row_counts(resp, mask) is cnt
+
+
+def test_bookkeeping_on_callers_tensors_is_not_saved_with_them(count_calls, tmp_path):
+    import copy
+    resp, mask = _matrix()
+    ops.row_counts(resp, mask)
+    ops.prepare_rows(resp, mask.long())
+    for k, t in enumerate((resp, mask, ops.prepare_mask(mask)[0])):
+        torch.save(t, tmp_path / f'{k}.pt')
+        back = torch.load(tmp_path / f'{k}.pt', weights_only=False)
+        assert torch.equal(back, t) and not any(vars(back).values()) and not any(vars(copy.deepcopy(t)).values())

@@ -45,11 +45,9 @@ def _launch(response, mask, U, V, L, guess, w1, W2, b2, w3, b3, resid, want_grad
     if want_prob:
         out['prob'] = torch.empty(B, I, **f32)
     p = ops._ptr
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    rc = lib.vibo_decoder_fwd_bwd(ctypes.byref(d), p(response), p(mask), p(U), p(V), p(L), p(guess), p(w1), p(W2), p(b2), p(w3),
-                                  p(b3), p(out['ll_part']), p(out.get('dU')), p(out.get('dV')), p(out.get('dL')),
-                                  p(out.get('dguess')), p(out.get('dW2')), p(out.get('dvec')), p(out.get('prob')), stream)
-    _lib.check(rc, 'vibo_decoder_fwd_bwd')
+    ops._call('vibo_decoder_fwd_bwd', ctypes.byref(d), p(response), p(mask), p(U), p(V), p(L), p(guess), p(w1), p(W2), p(b2), p(w3),
+              p(b3), p(out['ll_part']), p(out.get('dU')), p(out.get('dV')), p(out.get('dL')),
+              p(out.get('dguess')), p(out.get('dW2')), p(out.get('dvec')), p(out.get('prob')), ops._stream(dev))
     return out
 
 

@@ -10,6 +10,7 @@ optimizer.  Everything O(B x I) is inside the HIP kernel.
 """
 import contextlib
 import ctypes
+import math
 import weakref
 from dataclasses import dataclass
 from typing import Optional
@@ -88,8 +89,59 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
 
 
-_U8_VIEW_CACHE = []        # [(weakref to a bool mask, its uint8 view)], newest last, at most 4; an entry dies with its mask
-_I64_MASK_CACHE = []       # [(weakref to the int64 tensor, its _version, uint8 copy)], newest last, at most 4
+def _call(name, *args):
+    """One call into the library by its export's name; a non-zero return code raises (_lib.check)."""
+    _lib.check(getattr(_lib.load(), name)(*args), name)
+
+
+def _not_saved(self):
+    """__reduce__ of the bookkeeping this module hangs on callers' tensors: torch.save / pickle / deepcopy of the tensor see None."""
+    return type(None), ()
+
+
+class _Seen:
+    """A tensor as it was when last looked at: identity (held weakly) and version counter.  THE test of "the same tensor,
+    unmodified" in this module: the resident-matrix record and the narrowed masks both go through is_()."""
+    __slots__ = ('ref', 'version')
+    __reduce__ = _not_saved
+
+    def __init__(self, t):
+        self.ref, self.version = weakref.ref(t), t._version
+
+    def is_(self, t):
+        return t is not None and self.ref() is t and self.version == t._version
+
+
+class _Note(tuple):
+    __slots__ = ()
+    __reduce__ = _not_saved
+
+
+def _narrowed(mask):
+    """The uint8 form of a caller's bool / int64 mask: ONE object while that mask is alive and neither has been edited.  It hangs on
+    the mask (`_vibo_u8`) and points back weakly (`_vibo_mask`, see _caller_mask), so it is freed with the mask and never pins it.
+    A bool mask's shares its bytes AND its version counter (an edit through either shows in both); an int64 mask's is a copy."""
+    kept = getattr(mask, '_vibo_u8', None)
+    if kept is None or not (kept[0] is None or (kept[0].is_(mask) and _caller_mask(kept[1]) is mask)):
+        if mask.dtype == torch.bool:
+            # through detach(): whatever a view keeps of its base (`_base`) is then not the mask itself -- hung on the mask, that
+            # would be a cycle only the garbage collector frees, with the mask's GPU memory in it
+            m8, kept = mask.detach().view(torch.uint8), None
+        else:
+            m8, kept = (mask != 0).contiguous().view(torch.uint8), _Seen(mask)
+        m8._vibo_mask = _Note((weakref.ref(mask), None if kept is None else _Seen(m8)))
+        kept = mask._vibo_u8 = _Note((kept, m8))
+    return kept[1]
+
+
+def _caller_mask(mask):
+    """The caller's own tensor behind a mask _narrowed() made -- while that tensor lives and the narrowed copy of an int64 mask has
+    not been edited itself --, any other mask as it is."""
+    link = getattr(mask, '_vibo_mask', None)
+    if link is None or (link[1] is not None and not link[1].is_(mask)):
+        return mask
+    src = link[0]()
+    return mask if src is None else src
 
 
 def prepare_mask(mask, keep_int64=False):
@@ -97,7 +149,7 @@ def prepare_mask(mask, keep_int64=False):
 
     bool / uint8 masks (datasets.py:938 yields bool) are read in place, strided rows included.  int64 masks (the
     reference loop converts with `.long()`, vibo.py:240) cost 8 B per cell and are only understood by the fallback
-    kernels, so they are narrowed to uint8 once per tensor (identity-cached: a resident mask is converted a single
+    kernels, so they are narrowed to uint8 once per tensor (_narrowed: a resident mask is converted a single
     time); `keep_int64=True` hands them to the library unchanged (VIBO_MASK_I64)."""
     if mask is None:
         return None, _lib.MASK_NONE
@@ -107,28 +159,11 @@ def prepare_mask(mask, keep_int64=False):
         # rows may be strided (e.g. padded to 16 bytes, see pad_rows); only the cells must be unit-stride
         if mask.stride(-1) != 1:
             mask = mask.contiguous()
-        if mask.dtype == torch.uint8:
-            return mask, _lib.MASK_U8
-        # the uint8 view of a bool mask is ONE object per caller tensor while that tensor lives (a view is a new tensor object per
-        # call otherwise, and what is kept per resident matrix -- _resident_row_counts -- goes by the objects' identity)
-        for ref, view in _U8_VIEW_CACHE:
-            if ref() is mask:
-                return view, _lib.MASK_U8
-        view = mask.view(torch.uint8)
-        key = weakref.ref(mask, lambda r: _U8_VIEW_CACHE.__setitem__(slice(None), [e for e in _U8_VIEW_CACHE if e[0] is not r]))
-        _U8_VIEW_CACHE[:] = _U8_VIEW_CACHE[-3:]
-        _U8_VIEW_CACHE.append((key, view))
-        return view, _lib.MASK_U8
+        return (mask if mask.dtype == torch.uint8 else _narrowed(mask)), _lib.MASK_U8
     if mask.dtype == torch.int64 and keep_int64:
         return mask.contiguous(), _lib.MASK_I64
     if mask.dtype == torch.int64:
-        for ref, version, m8 in _I64_MASK_CACHE:
-            if ref() is mask and version == mask._version:
-                return m8, _lib.MASK_U8
-        m8 = (mask != 0).contiguous().view(torch.uint8)
-        _I64_MASK_CACHE[:] = [e for e in _I64_MASK_CACHE if e[0]() is not None and e[0]() is not mask][-3:]
-        _I64_MASK_CACHE.append((weakref.ref(mask), mask._version, m8))
-        return m8, _lib.MASK_U8
+        return _narrowed(mask), _lib.MASK_U8
     return (mask != 0).contiguous().view(torch.uint8), _lib.MASK_U8
 
 
@@ -171,7 +206,6 @@ class CellCodes:
 
 def pack_cell_codes(response, mask):
     """Repack device-resident [P, I(,1)] responses (+ mask or None) into CellCodes with vibo_pack_codes (one pass)."""
-    lib = _lib.load()
     response = prepare_response(response)
     mask, code = prepare_mask(mask, keep_int64=True)
     _require_device(response, mask)
@@ -181,10 +215,8 @@ def pack_cell_codes(response, mask):
     I4 = (I + 63) // 64 * 64 if I >= 256 else (I + 15) // 16 * 16
     codes = torch.full((P, I4), 2, dtype=torch.uint8, device=response.device)       # padding cells read as missing
     spec = ElboSpec(irt_model=1, ability_dim=1)
-    d = _make_desc(spec, P, I, code, _lib.REG_KL, False, response.stride(0), mask.stride(0) if mask is not None else 0)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(response.device).cuda_stream)
-    rc = lib.vibo_pack_codes(ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(codes), ctypes.c_int64(I4), stream)
-    _lib.check(rc, 'vibo_pack_codes')
+    d = _rows_desc(spec, P, response, mask, code, _lib.REG_KL, False)
+    _call('vibo_pack_codes', ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(codes), ctypes.c_int64(I4), _stream(response.device))
     return CellCodes(codes[:, :I])
 
 
@@ -259,15 +291,14 @@ class InsituTimer:
         self.reset()
 
     def reset(self):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(self.block.device).cuda_stream)
-        _lib.check(_lib.load().vibo_insitu_timer_reset(_ptr(self.block), stream), 'vibo_insitu_timer_reset')
+        _call('vibo_insitu_timer_reset', _ptr(self.block), _stream(self.block.device))
 
     def arm(self):
-        _lib.check(_lib.load().vibo_set_insitu_timer(_ptr(self.block)), 'vibo_set_insitu_timer')
+        _call('vibo_set_insitu_timer', _ptr(self.block))
 
     @staticmethod
     def disarm():
-        _lib.check(_lib.load().vibo_set_insitu_timer(ctypes.c_void_p(0)), 'vibo_set_insitu_timer')
+        _call('vibo_set_insitu_timer', ctypes.c_void_p(0))
 
     def __enter__(self):
         self.arm()
@@ -325,6 +356,17 @@ def _make_desc(spec, B, I, mask_code, reg_mode, want_grad, resp_stride, mask_str
     return d
 
 
+def _rows_desc(spec, B, response, mask, mask_code, reg_mode, want_grad):
+    """The descriptor of a call on B rows of (response, mask) as the library reads them (prepare_rows)."""
+    return _make_desc(spec, B, response.shape[1], mask_code, reg_mode, want_grad, response.stride(0),
+                      mask.stride(0) if mask is not None else 0)
+
+
+def _stream(device):
+    """torch's current stream on `device` as the hipStream_t argument of the library's calls."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def _require_device(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
@@ -335,36 +377,74 @@ def _require_device(*tensors):
 ROW_COUNT_CACHE = True     # (tests / A-B runs switch it off)
 
 
-def _resident_row_counts(spec, response, mask, mask_code):
-    """Whole-row counts (vibo_row_counts) of a matrix this process keeps calling with -- or None.
-
-    Rows of more than 1024 items under the unconditional posterior are counted in a pass of their own in front of the panels
-    (half of the call: 5 B/cell).  The counts depend on the data alone, so a matrix seen a second time (same tensors, unchanged
-    since: the resident training / evaluation split) is counted once, over all of its rows, and every later call -- the whole
-    matrix or minibatches gathered from it through row_index -- hands them to vibo_elbo_fwd_bwd_counts.
+class ResidentMatrix:
+    """One (response, mask) pair this process keeps calling with, as last seen, and what is known about it: the packed whole-row
+    counts (vibo_row_counts; None until the matrix has come back), the stream they were produced on and an event behind them.
+    ONE record per response tensor: a response that alternates between two masks is counted again at every switch.
     The record lives ON the response tensor (`_vibo_row_counts`): the counts are freed with the data they describe and never
     before -- a captured hipGraph that holds the data's address holds the counts' too."""
+    __slots__ = ('response', 'has_mask', 'mask', 'counts', 'stream', 'event', 'in_graph')
+    __reduce__ = _not_saved
+
+    def __init__(self, response, mask):
+        self.response, self.has_mask = _Seen(response), mask is not None
+        self.mask = _Seen(_caller_mask(mask)) if self.has_mask else None
+        self.counts = self.stream = self.event = None
+        self.in_graph = False                 # the count was recorded into a hipGraph: run when that graph replays
+
+    def is_(self, response, mask):
+        """THE predicate: the same response, unmodified; a mask given then and now, or neither time (whatever became of the
+        tensors); the same mask -- the caller's own or its narrowed form (prepare_mask) --, unmodified."""
+        if self.has_mask != (mask is not None) or not self.response.is_(response):
+            return False
+        return not self.has_mask or self.mask.is_(_caller_mask(mask))
+
+
+def _lookup_counts(response, mask, rows, row_index, num_person, *, for_elbo, capturing, stream):
+    """The one decision about a resident matrix -> its whole-row counts, or None: the caller counts its own rows.
+    response / mask: the tensors it is known by (CellCodes rows: the codes and None); rows: (response, mask, code) as
+    _BACKEND['counts'] reads them, or a callable that prepares them; capturing(): is the stream capturing -- asked only where the
+    answer matters; stream: the consumer's torch stream (None off the GPU).  Touches neither the GPU nor torch.cuda itself: the
+    count goes through _BACKEND['counts'], the ordering through `stream`'s own methods.
+    The ELBO launch (for_elbo): the first sighting records only (the kernel counts in its own pass), the second counts the whole
+    matrix once, from then on the whole matrix and minibatches gathered through row_index are served.  While the stream is
+    capturing it counts nothing and serves gathered minibatches only: with row_index=None the captured input IS the matrix, and a
+    replay after `response.copy_(new)` has to count what is there then.
+    row_counts(): a whole-matrix request counts and keeps at once; the first gathered minibatch of a tensor never seen gets
+    None, the matrix coming back is counted whole.  Capture changes nothing here (the trainers' contract: counted once), but
+    counts recorded into a graph are not handed to the ELBO launch: they exist once that graph has replayed."""
+    whole = row_index is None
+    if for_elbo and whole and num_person != response.shape[0]:
+        return None
+    rec = known = getattr(response, '_vibo_row_counts', None)
+    if rec is None or not rec.is_(response, mask):
+        rec = response._vibo_row_counts = ResidentMatrix(response, mask)
+        if for_elbo or (known is None and not whole):
+            return None
+    if rec.counts is None:
+        in_graph = stream is not None and capturing()
+        if for_elbo and in_graph:
+            return None              # (a count recorded into a hipGraph would not have run when the next eager call reads it)
+        rec.counts, rec.in_graph = _BACKEND['counts'](*(rows() if callable(rows) else rows), None), in_graph
+        if stream is not None and not in_graph:
+            rec.stream, rec.event = stream, stream.record_event()
+    elif for_elbo and (rec.in_graph or (whole and capturing())):
+        return None
+    elif rec.stream is not None and stream is not None and stream != rec.stream and not capturing():
+        stream.wait_event(rec.event)     # (a capturing stream cannot wait on an eager event: its capture began behind the count)
+    return rec.counts
+
+
+def _resident_row_counts(spec, response, mask, mask_code, row_index, num_person, stream):
+    """Whole-row counts for vibo_elbo_fwd_bwd_counts, or None.  Rows of more than 1024 items under the unconditional posterior are
+    counted in a pass of their own in front of the panels (half of the call: 5 B/cell); the counts depend on the data alone, so
+    a matrix that comes back (the resident training / evaluation split) is counted once: _lookup_counts."""
     I = response.shape[1]
     if (not ROW_COUNT_CACHE or spec.conditional or getattr(spec, 'given', False) or I <= 1024 or I > 32767
             or mask_code not in (_lib.MASK_NONE, _lib.MASK_U8, _lib.MASK_CODES)):
         return None
-    mv = mask._version if mask is not None else 0
-    rec = getattr(response, '_vibo_row_counts', None)      # [response version, weakref(mask) | None, mask version, counts | None]
-    if rec is not None and rec[0] == response._version and (rec[1]() if rec[1] is not None else None) is mask and rec[2] == mv:
-        if rec[3] is None:               # second sighting: count now
-            if torch.cuda.is_current_stream_capturing():
-                return None              # (a count recorded into a hipGraph would not have run when the next eager call reads it)
-            lib = _lib.load()
-            P = response.shape[0]
-            d = _make_desc(spec, P, I, mask_code, _lib.REG_SAMPLED if spec.n_flows else _lib.REG_KL, False, response.stride(0),
-                           mask.stride(0) if mask is not None else 0)
-            counts = torch.empty(P, dtype=torch.int32, device=response.device)
-            stream = ctypes.c_void_p(torch.cuda.current_stream(response.device).cuda_stream)
-            _lib.check(lib.vibo_row_counts(ctypes.byref(d), _ptr(response), _ptr(mask), ctypes.c_void_p(0), _ptr(counts), stream), 'vibo_row_counts')
-            rec[3] = counts
-        return rec[3]
-    response._vibo_row_counts = [response._version, weakref.ref(mask) if mask is not None else None, mv, None]
-    return None
+    return _lookup_counts(response, None if mask_code == _lib.MASK_CODES else mask, (response, mask, mask_code), row_index,
+                          num_person, for_elbo=True, capturing=torch.cuda.is_current_stream_capturing, stream=stream)
 
 
 def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, eps, flow, reg_mode,
@@ -382,61 +462,38 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     B = int(num_person)
     A, D = spec.ability_dim, spec.item_dim
     table_shape = tuple(table.shape) if table is not None else tuple(spec.table_shape(I))
-    n_table = 1
-    for n in table_shape:
-        n_table *= n
-    n_flow = spec.n_flows * (2 * A + 1)
-    n_item = I * D
+    n_table, n_item, n_flow = math.prod(table_shape), I * D, spec.n_flows * (2 * A + 1)
     flat = torch.empty(_lib.NUM_SCALARS + 2 * n_table + n_item + 2 * n_flow, dtype=torch.float32, device=dev)
     own_noise = train_step is not None and len(train_step) > 2 and train_step[2] is not None
     post = torch.empty(1 if own_noise else 3, B, A, dtype=torch.float32, device=dev)
     ability_k = torch.empty(B, A, dtype=torch.float32, device=dev) if spec.n_flows else None
     ladj = torch.empty(B, dtype=torch.float32, device=dev) if spec.n_flows else None
-    d = _make_desc(spec, B, I, mask_code, reg_mode, want_grad, response.stride(0),
-                   mask.stride(0) if mask is not None else 0)
+    d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, want_grad)
     ws_bytes = lib.vibo_workspace_bytes(ctypes.byref(d))
     if ws_bytes == 0:
         _lib.check(-1, 'vibo_workspace_bytes')
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-    fbase, esz = flat.data_ptr(), 4
-    o_tab = _lib.NUM_SCALARS
-    o_item = o_tab + 2 * n_table
-    o_flow = o_item + n_item
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    vp, fbase, o_item = ctypes.c_void_p, flat.data_ptr(), _lib.NUM_SCALARS + 2 * n_table
+    # the argument runs the four exports share (include/vibo_hip.h): the rows, the gradients, workspace and stream
+    stream = torch.cuda.current_stream(dev)
+    rows = (_ptr(response), _ptr(mask), _ptr(row_index))
+    grads = (vp(fbase + 4 * _lib.NUM_SCALARS), vp(fbase + 4 * o_item))
+    tail = (_ptr(ws), ctypes.c_size_t(ws_bytes), vp(stream.cuda_stream))
     if own_noise:
-        rc = lib.vibo_elbo_fwd_bwd_step_noise(
-            ctypes.byref(d), _ptr(train_step[0]), 1 if train_step[1] else 0, _ptr(response), _ptr(mask), _ptr(row_index),
-            _ptr(table), _ptr(item), None, ctypes.c_uint64(train_step[2][0]), ctypes.c_uint32(train_step[2][1]),
-            ctypes.c_void_p(fbase), None, None, _ptr(post[0]),
-            ctypes.c_void_p(fbase + esz * o_tab), ctypes.c_void_p(fbase + esz * o_item),
-            _ptr(ws), ctypes.c_size_t(ws_bytes), stream)
-        _lib.check(rc, 'vibo_elbo_fwd_bwd_step_noise')
+        name = 'vibo_elbo_fwd_bwd_step_noise'
+        args = (_ptr(train_step[0]), 1 if train_step[1] else 0, *rows, _ptr(table), _ptr(item), None, ctypes.c_uint64(train_step[2][0]),
+                ctypes.c_uint32(train_step[2][1]), vp(fbase), None, None, _ptr(post[0]), *grads, *tail)
     elif train_step is not None:
-        rc = lib.vibo_elbo_fwd_bwd_step(
-            ctypes.byref(d), _ptr(train_step[0]), 1 if train_step[1] else 0, _ptr(response), _ptr(mask), _ptr(row_index),
-            _ptr(table), _ptr(item), _ptr(eps),
-            ctypes.c_void_p(fbase), _ptr(post[0]), _ptr(post[1]), _ptr(post[2]),
-            ctypes.c_void_p(fbase + esz * o_tab), ctypes.c_void_p(fbase + esz * o_item),
-            _ptr(ws), ctypes.c_size_t(ws_bytes), stream)
-        _lib.check(rc, 'vibo_elbo_fwd_bwd_step')
-    elif (counts := _resident_row_counts(spec, response, mask, mask_code)) is not None and (row_index is not None or B == response.shape[0]):
-        rc = lib.vibo_elbo_fwd_bwd_counts(
-            ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(row_index), _ptr(counts), _ptr(table), _ptr(item), _ptr(eps),
-            _ptr(flow),
-            ctypes.c_void_p(fbase), _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), _ptr(ability_k), _ptr(ladj),
-            ctypes.c_void_p(fbase + esz * o_tab), ctypes.c_void_p(fbase + esz * o_item),
-            ctypes.c_void_p(fbase + esz * o_flow) if n_flow else ctypes.c_void_p(0),
-            _ptr(ws), ctypes.c_size_t(ws_bytes), stream)
-        _lib.check(rc, 'vibo_elbo_fwd_bwd_counts')
+        name = 'vibo_elbo_fwd_bwd_step'
+        args = (_ptr(train_step[0]), 1 if train_step[1] else 0, *rows, _ptr(table), _ptr(item), _ptr(eps), vp(fbase), _ptr(post[0]),
+                _ptr(post[1]), _ptr(post[2]), *grads, *tail)
     else:
-        rc = lib.vibo_elbo_fwd_bwd(
-            ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table), _ptr(item), _ptr(eps),
-            _ptr(flow),
-            ctypes.c_void_p(fbase), _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), _ptr(ability_k), _ptr(ladj),
-            ctypes.c_void_p(fbase + esz * o_tab), ctypes.c_void_p(fbase + esz * o_item),
-            ctypes.c_void_p(fbase + esz * o_flow) if n_flow else ctypes.c_void_p(0),
-            _ptr(ws), ctypes.c_size_t(ws_bytes), stream)
-        _lib.check(rc, 'vibo_elbo_fwd_bwd')
+        counts = _resident_row_counts(spec, response, mask, mask_code, row_index, B, stream)
+        name = 'vibo_elbo_fwd_bwd' if counts is None else 'vibo_elbo_fwd_bwd_counts'
+        args = (*rows, *(() if counts is None else (_ptr(counts),)), _ptr(table), _ptr(item), _ptr(eps), _ptr(flow), vp(fbase),
+                _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), _ptr(ability_k), _ptr(ladj), *grads,
+                vp(fbase + 4 * (o_item + n_item)) if n_flow else vp(0), *tail)
+    _call(name, ctypes.byref(d), *args)
     raw = RawElbo(flat=flat, n_table=n_table, n_item=n_item, n_flow=n_flow, table_shape=table_shape,
                   ability_mu=None if own_noise else post[0], ability_logvar=None if own_noise else post[1], ability=post[-1],
                   ability_k=ability_k, ability_ladj=ladj)
@@ -451,17 +508,16 @@ def _hip_multi_forward(spec, response, mask, mask_code, row_index, table, items,
     lib = _lib.load()
     _require_device(response, mask, table, items, eps)
     S, B, I = int(items.shape[0]), int(num_person), response.shape[1]
-    d = _make_desc(spec, B, I, mask_code, reg_mode, False, response.stride(0), mask.stride(0) if mask is not None else 0)
+    d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, False)
     ws_bytes = lib.vibo_multi_workspace_bytes(ctypes.byref(d), S)
     if ws_bytes == 0:
         return None
     dev = response.device
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(S, _lib.NUM_SCALARS, dtype=torch.float32, device=dev)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     rc = lib.vibo_elbo_multi_forward(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table),
                                      _ptr(items), _ptr(eps), _ptr(flow), _ptr(out), _ptr(ws), ctypes.c_size_t(ws_bytes),
-                                     stream)
+                                     _stream(dev))
     if rc == -8:
         return None
     _lib.check(rc, 'vibo_elbo_multi_forward')
@@ -472,76 +528,50 @@ def _hip_encode(spec, response, mask, mask_code, row_index, table, num_person):
     lib = _lib.load()
     _require_device(response, mask, table)
     dev = response.device
-    B, I, A = int(num_person), response.shape[1], spec.ability_dim
+    B, A = int(num_person), spec.ability_dim
     out = torch.empty(2, B, A, dtype=torch.float32, device=dev)
     # (the posterior does not depend on the flows; the descriptor only has to be self-consistent)
-    d = _make_desc(spec, B, I, mask_code, _lib.REG_SAMPLED if spec.n_flows else _lib.REG_KL, False, response.stride(0),
-                   mask.stride(0) if mask is not None else 0)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    d = _rows_desc(spec, B, response, mask, mask_code, _lib.REG_SAMPLED if spec.n_flows else _lib.REG_KL, False)
     ws_bytes = lib.vibo_workspace_bytes(ctypes.byref(d))          # scratch for the row statistics of the fast path
     ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
-    rc = lib.vibo_encode(ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table),
-                         _ptr(out[0]), _ptr(out[1]), _ptr(ws), ctypes.c_size_t(ws_bytes), stream)
-    _lib.check(rc, 'vibo_encode')
+    _call('vibo_encode', ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table),
+          _ptr(out[0]), _ptr(out[1]), _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(dev))
     return out[0], out[1]
 
 
 def _hip_decode(spec, ability, item):
-    lib = _lib.load()
     _require_device(ability, item)
     B, I = ability.shape[0], item.shape[0]
     out = torch.empty(B, I, dtype=torch.float32, device=ability.device)
     d = _make_desc(spec, B, I, _lib.MASK_NONE, _lib.REG_SAMPLED if spec.n_flows else _lib.REG_KL, False, I, 0)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(ability.device).cuda_stream)
-    rc = lib.vibo_decode(ctypes.byref(d), _ptr(ability), _ptr(item), _ptr(out), stream)
-    _lib.check(rc, 'vibo_decode')
+    _call('vibo_decode', ctypes.byref(d), _ptr(ability), _ptr(item), _ptr(out), _stream(ability.device))
     return out
 
 
 def _hip_row_counts(response, mask, mask_code, row_index):
     """vibo_row_counts: int32 [B], n_correct << 16 | n_observed per person row."""
-    lib = _lib.load()
     _require_device(response, mask)
     B = int(row_index.numel()) if row_index is not None else response.shape[0]
-    I = response.shape[1]
     out = torch.empty(B, dtype=torch.int32, device=response.device)
-    d = _make_desc(ElboSpec(irt_model=1, ability_dim=1), B, I, mask_code, _lib.REG_KL, False, response.stride(0),
-                   mask.stride(0) if mask is not None else 0)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(response.device).cuda_stream)
-    rc = lib.vibo_row_counts(ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(row_index), _ptr(out), stream)
-    _lib.check(rc, 'vibo_row_counts')
+    d = _rows_desc(ElboSpec(irt_model=1, ability_dim=1), B, response, mask, mask_code, _lib.REG_KL, False)
+    _call('vibo_row_counts', ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(row_index), _ptr(out), _stream(response.device))
     return out
-
-
-_COUNTS_CACHE = []         # [(weakref response, version, weakref mask | None, version, counts)], newest last, at most 4
-_COUNTS_SEEN = []          # [weakref to the last response tensor a gathered minibatch came from]
 
 
 def row_counts(response, mask, row_index=None):
     """int32 [B]: n_correct << 16 | n_observed per person -- the sufficient statistics of a Bernoulli response row for
     the unconditional encoders (here: the masked mean of --ability-merge mean, models.py:631-650).  The counts of a whole
     matrix are kept while the same (unmodified) tensors come back -- a resident dataset is counted once, not per step;
-    minibatches gathered through `row_index` index into them."""
-    key_r = response.codes if isinstance(response, CellCodes) else response       # the caller's own tensor objects
-    key_m = mask
-    for rr, rv, mr, mv, cnt in _COUNTS_CACHE:
-        if rr() is key_r and rv == key_r._version and (
-                (mr is None and key_m is None) or (mr is not None and mr() is key_m and mv == key_m._version)):
-            return cnt if row_index is None else cnt[row_index]
-    response, mask, code = prepare_rows(response, mask, keep_int64=True)
-    if row_index is not None and not (_COUNTS_SEEN and _COUNTS_SEEN[0]() is key_r):
+    minibatches gathered through `row_index` index into them.  Under hipGraph capture too: the mean-merge and decoder trainers'
+    captured steps read their resident matrix's counts, computed once (unlike the ELBO launch, _lookup_counts)."""
+    key = response.codes if isinstance(response, CellCodes) else response       # the caller's own tensor objects
+    cnt = _lookup_counts(key, mask, lambda: prepare_rows(response, mask, keep_int64=True), row_index, key.shape[0], for_elbo=False,
+                         capturing=torch.cuda.is_current_stream_capturing,
+                         stream=torch.cuda.current_stream(key.device) if key.is_cuda else None)
+    if cnt is None:
         # a gathered minibatch of a matrix seen for the first time: count those rows only; the whole matrix is counted
         # (once) when the same tensor comes back
-        _COUNTS_SEEN[:] = [weakref.ref(key_r)]
-        return _BACKEND['counts'](response, mask, code, row_index)
-    cnt = _BACKEND['counts'](response, mask, code, None)
-    try:
-        key_r._vibo_counts_keepalive = cnt      # (alive as long as the data: a captured hipGraph that reads the data reads these too)
-    except AttributeError:
-        pass
-    _COUNTS_CACHE[:] = [e for e in _COUNTS_CACHE if e[0]() is not None and (e[2] is None or e[2]() is not None)][-3:]
-    _COUNTS_CACHE.append((weakref.ref(key_r), key_r._version, weakref.ref(key_m) if key_m is not None else None,
-                          key_m._version if key_m is not None else 0, cnt))
+        return _BACKEND['counts'](*prepare_rows(response, mask, keep_int64=True), row_index)
     return cnt if row_index is None else cnt[row_index]
 
 
@@ -550,14 +580,12 @@ def _mean_desc(counts, A):
 
 
 def _hip_mean_encoder_fwd(counts, u, v, w2, b2):
-    lib = _lib.load()
     _require_device(counts, u, v, w2, b2)
     A2, H = w2.shape
     post = torch.empty(counts.numel(), A2, dtype=torch.float32, device=counts.device)
     d = _mean_desc(counts, A2 // 2)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(counts.device).cuda_stream)
-    rc = lib.vibo_mean_encoder_forward(ctypes.byref(d), H, _ptr(counts), _ptr(u), _ptr(v), _ptr(w2), _ptr(b2), _ptr(post), stream)
-    _lib.check(rc, 'vibo_mean_encoder_forward')
+    _call('vibo_mean_encoder_forward', ctypes.byref(d), H, _ptr(counts), _ptr(u), _ptr(v), _ptr(w2), _ptr(b2), _ptr(post),
+          _stream(counts.device))
     return post
 
 
@@ -569,10 +597,8 @@ def _hip_mean_encoder_bwd(counts, u, v, w2, gpost):
     d = _mean_desc(counts, A2 // 2)
     n_part = lib.vibo_mean_encoder_partials(ctypes.byref(d))
     part = torch.empty(n_part, 2 * H + A2 * H + A2, dtype=torch.float32, device=counts.device)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(counts.device).cuda_stream)
-    rc = lib.vibo_mean_encoder_backward(ctypes.byref(d), H, _ptr(counts), _ptr(u), _ptr(v), _ptr(w2), _ptr(gpost), _ptr(part),
-                                        n_part, stream)
-    _lib.check(rc, 'vibo_mean_encoder_backward')
+    _call('vibo_mean_encoder_backward', ctypes.byref(d), H, _ptr(counts), _ptr(u), _ptr(v), _ptr(w2), _ptr(gpost), _ptr(part),
+          n_part, _stream(counts.device))
     tot = part.sum(0)
     return tot[:H], tot[H:2 * H], tot[2 * H:2 * H + A2 * H].view(A2, H), tot[2 * H + A2 * H:]
 
@@ -600,21 +626,17 @@ class FlowStackFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, packed):
-        lib = _lib.load()
         z, packed = z.detach().contiguous().float(), packed.detach().contiguous().float()
         _require_device(z, packed)
         N, D = z.shape
         K = packed.shape[0]
         z_out, ladj, th = torch.empty_like(z), torch.empty(N, dtype=torch.float32, device=z.device), torch.empty(N, K, dtype=torch.float32, device=z.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-        _lib.check(lib.vibo_flow_stack_forward(N, D, K, _ptr(z), _ptr(packed), _ptr(z_out), _ptr(ladj), _ptr(th), stream),
-                   'vibo_flow_stack_forward')
+        _call('vibo_flow_stack_forward', N, D, K, _ptr(z), _ptr(packed), _ptr(z_out), _ptr(ladj), _ptr(th), _stream(z.device))
         ctx.save_for_backward(z_out, packed, th)
         return z_out, ladj
 
     @staticmethod
     def backward(ctx, g_z, g_l):
-        lib = _lib.load()
         z_out, packed, th = ctx.saved_tensors
         N, D = z_out.shape
         K = packed.shape[0]
@@ -622,9 +644,8 @@ class FlowStackFn(torch.autograd.Function):
         g_l = torch.zeros(N, dtype=torch.float32, device=z_out.device) if g_l is None else g_l.contiguous().float()
         g_in = torch.empty_like(z_out)
         parts = torch.empty((N + 255) // 256, K, 2 * D + 1, dtype=torch.float32, device=z_out.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(z_out.device).cuda_stream)
-        _lib.check(lib.vibo_flow_stack_backward(N, D, K, _ptr(z_out), _ptr(packed), _ptr(th), _ptr(g_z), _ptr(g_l), _ptr(g_in),
-                                                _ptr(parts), stream), 'vibo_flow_stack_backward')
+        _call('vibo_flow_stack_backward', N, D, K, _ptr(z_out), _ptr(packed), _ptr(th), _ptr(g_z), _ptr(g_l), _ptr(g_in),
+              _ptr(parts), _stream(z_out.device))
         return g_in, parts.sum(0)
 
 
@@ -634,14 +655,11 @@ def _hip_flow_stack(z, packed):
 
 def _hip_decode_mean(spec, abilities, items):
     """vibo_decode_mean: abilities [S,B,A], items [S,I,D] -> mean over S of P(response = 1) [B,I]."""
-    lib = _lib.load()
     _require_device(abilities, items)
     S, B, I = int(abilities.shape[0]), int(abilities.shape[1]), int(items.shape[1])
     out = torch.empty(B, I, dtype=torch.float32, device=abilities.device)
     d = _make_desc(spec, B, I, _lib.MASK_NONE, _lib.REG_SAMPLED if spec.n_flows else _lib.REG_KL, False, I, 0)
-    stream = ctypes.c_void_p(torch.cuda.current_stream(abilities.device).cuda_stream)
-    rc = lib.vibo_decode_mean(ctypes.byref(d), S, _ptr(abilities), _ptr(items), _ptr(out), stream)
-    _lib.check(rc, 'vibo_decode_mean')
+    _call('vibo_decode_mean', ctypes.byref(d), S, _ptr(abilities), _ptr(items), _ptr(out), _stream(abilities.device))
     return out
 
 
@@ -663,9 +681,8 @@ class CodeTableSumFn(torch.autograd.Function):
         if nbytes == 0:
             raise _lib.ViboLibraryError('vibo_code_table_sum: hidden_dim must be 64')
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=codes.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(codes.device).cuda_stream)
-        rc = lib.vibo_code_table_sum_forward(B, I, H, _ptr(codes), codes.stride(0), _ptr(feat), _ptr(out), _ptr(scratch), nbytes, stream)
-        _lib.check(rc, 'vibo_code_table_sum_forward')
+        _call('vibo_code_table_sum_forward', B, I, H, _ptr(codes), codes.stride(0), _ptr(feat), _ptr(out), _ptr(scratch), nbytes,
+              _stream(codes.device))
         ctx.cell_codes, ctx.shape = cell_codes, (I, H)
         return out
 
@@ -679,9 +696,8 @@ class CodeTableSumFn(torch.autograd.Function):
         dfeat = torch.empty(2, I, H, dtype=torch.float32, device=codes.device)
         nbytes = lib.vibo_code_table_scratch_bytes(B, I, H)
         scratch = torch.empty(nbytes, dtype=torch.uint8, device=codes.device)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(codes.device).cuda_stream)
-        rc = lib.vibo_code_table_sum_backward(B, I, H, _ptr(codes), codes.stride(0), _ptr(g), _ptr(dfeat), _ptr(scratch), nbytes, stream)
-        _lib.check(rc, 'vibo_code_table_sum_backward')
+        _call('vibo_code_table_sum_backward', B, I, H, _ptr(codes), codes.stride(0), _ptr(g), _ptr(dfeat), _ptr(scratch), nbytes,
+              _stream(codes.device))
         return dfeat, None
 
 

@@ -162,8 +162,8 @@ class FusedTrainer:
         response, mask, code = ops.prepare_rows(response, mask)
         B = int(row_index.numel()) if row_index is not None else response.shape[0]
         I = response.shape[1]
-        stream = ctypes.c_void_p(torch.cuda.current_stream(response.device).cuda_stream)
-        d = ops._make_desc(self.model.spec, B, I, code, reg_mode, True, response.stride(0), mask.stride(0) if mask is not None else 0)
+        stream = ops._stream(response.device)
+        d = ops._rows_desc(self.model.spec, B, response, mask, code, reg_mode, True)
         ab_stream = 1 + getattr(self.model, '_shard_rank', 0)      # item noise: the same on every rank; ability noise: per rank
         return response, mask, code, B, I, stream, d, ab_stream
 
@@ -233,10 +233,9 @@ class FusedTrainer:
         if given:
             eps_item, eps_ab = eps_item.contiguous().float(), eps_ability.contiguous().float()
             self._primed_for = None
-            rc = lib.vibo_train_prologue(ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
-                                         p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
-                                         p(self._steps), stream)
-            _lib.check(rc, 'vibo_train_prologue')
+            ops._call('vibo_train_prologue', ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
+                      p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
+                      p(self._steps), stream)
             raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, eps_ab, None,
                                        _lib.REG_KL, True, B)
             self._pending = (d, eps_item, raw, None)
@@ -250,19 +249,17 @@ class FusedTrainer:
         else:
             eps_item = model._randn(self.item_mu.shape, self.item_mu, model._item_gen)
         if self.rng == 'native' and self.fused_noise:       # noise drawn inside the prologue launch
-            rc = lib.vibo_train_prologue_noise(ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
-                                               p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
-                                               p(self._steps), self.seed, p(eps_ab), ab_stream, stream)
-            _lib.check(rc, 'vibo_train_prologue_noise')
+            ops._call('vibo_train_prologue_noise', ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
+                      p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
+                      p(self._steps), self.seed, p(eps_ab), ab_stream, stream)
         else:
             noise_step = ctypes.c_void_p(self._steps.data_ptr() + 4)          # completed steps (step_count[1])
             if self.rng == 'native':
-                _lib.check(lib.vibo_fill_normal(p(eps_item), eps_item.numel(), self.seed, noise_step, 0, stream), 'vibo_fill_normal')
-                _lib.check(lib.vibo_fill_normal(p(eps_ab), eps_ab.numel(), self.seed, noise_step, ab_stream, stream), 'vibo_fill_normal')
-            rc = lib.vibo_train_prologue(ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
-                                         p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
-                                         p(self._steps), stream)
-            _lib.check(rc, 'vibo_train_prologue')
+                ops._call('vibo_fill_normal', p(eps_item), eps_item.numel(), self.seed, noise_step, 0, stream)
+                ops._call('vibo_fill_normal', p(eps_ab), eps_ab.numel(), self.seed, noise_step, ab_stream, stream)
+            ops._call('vibo_train_prologue', ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
+                      p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
+                      p(self._steps), stream)
             if self.rng != 'native':
                 eps_ab = model._randn((B, model.ability_dim), self.item_mu, model._ability_gen)
         raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, eps_ab, None,
@@ -310,16 +307,15 @@ class FusedTrainer:
         state = (self._eps_cap.numel(),) + self._param_versions()
         noise_step = ctypes.c_void_p(self._steps.data_ptr() + 4)              # completed steps (step_count[1])
         if self._primed_for != state:
-            _lib.check(lib.vibo_fill_normal(p(self._eps_item), self._eps_item.numel(), self.seed, noise_step, 0, stream), 'vibo_fill_normal')
+            ops._call('vibo_fill_normal', p(self._eps_item), self._eps_item.numel(), self.seed, noise_step, 0, stream)
             if not self._draw_mode:
-                _lib.check(lib.vibo_fill_normal(p(self._eps_cap), self._eps_cap.numel(), self.seed, noise_step, ab_stream, stream), 'vibo_fill_normal')
-            rc = lib.vibo_train_prime(ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv), p(self._eps_item),
-                                      p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts), p(self._steps), stream)
-            _lib.check(rc, 'vibo_train_prime')
+                ops._call('vibo_fill_normal', p(self._eps_cap), self._eps_cap.numel(), self.seed, noise_step, ab_stream, stream)
+            ops._call('vibo_train_prime', ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv), p(self._eps_item),
+                      p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts), p(self._steps), stream)
             self._primed_for = state
         eps_item, eps_ab = self._eps_item, self._eps_cap[:need].view(B, A)
         if self._draw_mode and not draws:
-            _lib.check(lib.vibo_fill_normal(p(eps_ab), need, self.seed, noise_step, ab_stream, stream), 'vibo_fill_normal')
+            ops._call('vibo_fill_normal', p(eps_ab), need, self.seed, noise_step, ab_stream, stream)
         fused_finalize = bool(step_bits & 2) and model._reducer is None
         raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, None if draws else eps_ab, None,
                                    _lib.REG_KL, True, B, train_step=(self._steps, fused_finalize, (self.seed, ab_stream) if draws else None))
@@ -339,23 +335,21 @@ class FusedTrainer:
         if self._pending is None:
             raise RuntimeError('FusedTrainer.update(): no forward_backward() is pending')
         d, eps_item, raw, folded_stream = self._pending
-        lib, p = _lib.load(), ops._ptr
-        stream = ctypes.c_void_p(torch.cuda.current_stream(raw.flat.device).cuda_stream)
+        p = ops._ptr
+        stream = ops._stream(raw.flat.device)
         if folded_stream is not None:
             self._folded_open = False
-            rc = lib.vibo_train_epilogue_fused(ctypes.byref(d), self.hidden, p(raw.workspace), p(raw.flat), p(self.saved_h),
-                                               p(self.kl_parts), p(eps_item), p(self.beta), p(self.lr), p(self._steps),
-                                               p(self.mlp_flat), p(self.mlp_m), p(self.mlp_v), p(self.item_mu), p(self.item_lv),
-                                               p(self.item_m), p(self.item_v), p(self.loss), self.seed, p(self.item_feat),
-                                               p(self.table), None if self._draw_mode else p(self._eps_cap),
-                                               0 if self._draw_mode else self._eps_cap.numel(), folded_stream, stream)
-            _lib.check(rc, 'vibo_train_epilogue_fused')
+            ops._call('vibo_train_epilogue_fused', ctypes.byref(d), self.hidden, p(raw.workspace), p(raw.flat), p(self.saved_h),
+                      p(self.kl_parts), p(eps_item), p(self.beta), p(self.lr), p(self._steps),
+                      p(self.mlp_flat), p(self.mlp_m), p(self.mlp_v), p(self.item_mu), p(self.item_lv),
+                      p(self.item_m), p(self.item_v), p(self.loss), self.seed, p(self.item_feat),
+                      p(self.table), None if self._draw_mode else p(self._eps_cap),
+                      0 if self._draw_mode else self._eps_cap.numel(), folded_stream, stream)
             return self.loss
-        rc = lib.vibo_train_epilogue(ctypes.byref(d), self.hidden, p(raw.flat), p(self.saved_h), p(self.kl_parts),
-                                     p(eps_item), p(self.beta), p(self.lr), p(self._steps), p(self.mlp_flat),
-                                     p(self.mlp_m), p(self.mlp_v), p(self.item_mu), p(self.item_lv), p(self.item_m),
-                                     p(self.item_v), p(self.loss), stream)
-        _lib.check(rc, 'vibo_train_epilogue')
+        ops._call('vibo_train_epilogue', ctypes.byref(d), self.hidden, p(raw.flat), p(self.saved_h), p(self.kl_parts),
+                  p(eps_item), p(self.beta), p(self.lr), p(self._steps), p(self.mlp_flat),
+                  p(self.mlp_m), p(self.mlp_v), p(self.item_mu), p(self.item_lv), p(self.item_m),
+                  p(self.item_v), p(self.loss), stream)
         return self.loss
 
 
@@ -404,15 +398,14 @@ class FusedCondFlowTrainer(FusedTrainer):
 
     @torch.no_grad()
     def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
-        model, spec, lib, p = self.model, self.model.spec, _lib.load(), ops._ptr
+        model, spec, p = self.model, self.model.spec, ops._ptr
         reg_mode = _lib.REG_SAMPLED if model.n_norm_flows > 0 else _lib.REG_KL
         response, mask, code, B, I, stream, d, ab_stream = self._begin(response, mask, beta, row_index, reg_mode)
         eps_item, eps_ab, native = self._choose_noise(B, response.device, eps_item, eps_ability)
-        rc = lib.vibo_ctrain_prologue(ctypes.byref(d), self.hidden, p(self.par_flat), p(self.item_mu), p(self.item_lv),
-                                      p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, ab_stream,
-                                      p(self.item_feat), p(self.item_k), p(self.table), p(self.flow_packed), p(self.scratch),
-                                      p(self._steps), stream)
-        _lib.check(rc, 'vibo_ctrain_prologue')
+        ops._call('vibo_ctrain_prologue', ctypes.byref(d), self.hidden, p(self.par_flat), p(self.item_mu), p(self.item_lv),
+                  p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, ab_stream,
+                  p(self.item_feat), p(self.item_k), p(self.table), p(self.flow_packed), p(self.scratch),
+                  p(self._steps), stream)
         if eps_ab is None:
             eps_ab = model._randn((B, model.ability_dim), self.item_mu, model._ability_gen)
         raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_k, eps_ab, self.flow_packed,
@@ -424,13 +417,11 @@ class FusedCondFlowTrainer(FusedTrainer):
     @torch.no_grad()
     def update(self):
         d, eps_item, raw = self._pending
-        lib, p = _lib.load(), ops._ptr
-        stream = ctypes.c_void_p(torch.cuda.current_stream(raw.flat.device).cuda_stream)
-        rc = lib.vibo_ctrain_epilogue(ctypes.byref(d), self.hidden, p(raw.flat), p(eps_item), p(self.item_feat), p(self.item_k),
-                                      p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
-                                      p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.scratch),
-                                      p(self.loss), stream)
-        _lib.check(rc, 'vibo_ctrain_epilogue')
+        p = ops._ptr
+        ops._call('vibo_ctrain_epilogue', ctypes.byref(d), self.hidden, p(raw.flat), p(eps_item), p(self.item_feat), p(self.item_k),
+                  p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
+                  p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.scratch),
+                  p(self.loss), ops._stream(raw.flat.device))
         return self.loss
 
 
@@ -441,7 +432,7 @@ class FusedMeanTrainer(FusedTrainer):
     vibo_elbo_fwd_bwd in VIBO_POSTERIOR_GIVEN mode -> vibo_mean_encoder_backward_sets -> vibo_mtrain_epilogue (loss, the
     backward through u, v and mlp1 by hand, Adam on everything).  No PyTorch autograd node: the step replays from a hipGraph
     like FusedTrainer's (eight launches since the GIVEN call reads / writes the posterior itself: DESIGN 3.6).  Same interface (`FusedTrainer(model, ...)` returns this class for such models).
-    The packed row counts of the resident matrix are computed once (ops.row_counts keeps them while the same tensors come back).
+    The packed row counts of the resident matrix are computed once (ops.row_counts keeps them in the matrix's ops.ResidentMatrix record while the same tensors come back, under capture too).
     Person-sharded (round 5): `reduce_shards()` between the two halves all-reduces [scalars | item gradient | encoder gradient sums]
     in one collective; the per-person posterior gradients stay on their rank."""
 
@@ -483,26 +474,23 @@ class FusedMeanTrainer(FusedTrainer):
         dev = response.device
         A, H = model.ability_dim, self.hidden
         eps_item, eps_ab, native = self._choose_noise(B, dev, eps_item, eps_ability)
-        rc = lib.vibo_mtrain_prologue(ctypes.byref(d), H, p(self.par_flat), p(self.item_mu), p(self.item_lv), p(eps_item), self.seed,
-                                      1 if native else 0, p(eps_ab) if native else None, ab_stream, p(self.item_feat), p(self.uv),
-                                      p(self.saved), p(self.kl_parts), p(self._steps), stream)
-        _lib.check(rc, 'vibo_mtrain_prologue')
+        ops._call('vibo_mtrain_prologue', ctypes.byref(d), H, p(self.par_flat), p(self.item_mu), p(self.item_lv), p(eps_item), self.seed,
+                  1 if native else 0, p(eps_ab) if native else None, ab_stream, p(self.item_feat), p(self.uv),
+                  p(self.saved), p(self.kl_parts), p(self._steps), stream)
         if eps_ab is None:
             eps_ab = model._randn((B, A), self.item_mu, model._ability_gen)
         post = torch.empty(B, 2 * A, device=dev)
         dm = ops._mean_desc(counts, A)
-        rc = lib.vibo_mean_encoder_forward(ctypes.byref(dm), H, p(counts), p(self.uv[:H]), p(self.uv[H:]), p(self._w22), p(self._b22),
-                                           p(post), stream)
-        _lib.check(rc, 'vibo_mean_encoder_forward')
+        ops._call('vibo_mean_encoder_forward', ctypes.byref(dm), H, p(counts), p(self.uv[:H]), p(self.uv[H:]), p(self._w22), p(self._b22),
+                  p(post), stream)
         raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, post, self.item_feat, eps_ab, None, _lib.REG_KL, True, B)
         n_part = lib.vibo_mean_encoder_partials(ctypes.byref(dm))
         parts = self._parts.get(n_part)
         if parts is None:
             parts = self._parts[n_part] = torch.empty(n_part, 2 * H + 2 * A * H + 2 * A, device=dev)
         grad_sets = raw.flat[_lib.NUM_SCALARS:_lib.NUM_SCALARS + 2 * B * 2 * A]
-        rc = lib.vibo_mean_encoder_backward_sets(ctypes.byref(dm), H, p(counts), p(self.uv[:H]), p(self.uv[H:]), p(self._w22),
-                                                 p(grad_sets), p(self.beta), p(parts), n_part, stream)
-        _lib.check(rc, 'vibo_mean_encoder_backward_sets')
+        ops._call('vibo_mean_encoder_backward_sets', ctypes.byref(dm), H, p(counts), p(self.uv[:H]), p(self.uv[H:]), p(self._w22),
+                  p(grad_sets), p(self.beta), p(parts), n_part, stream)
         self._pending = (d, eps_item, raw, parts, n_part)
         self.last = raw
         return raw
@@ -537,13 +525,11 @@ class FusedMeanTrainer(FusedTrainer):
     @torch.no_grad()
     def update(self):
         d, eps_item, raw, parts, n_part = self._pending
-        lib, p = _lib.load(), ops._ptr
-        stream = ctypes.c_void_p(torch.cuda.current_stream(raw.flat.device).cuda_stream)
-        rc = lib.vibo_mtrain_epilogue(ctypes.byref(d), self.hidden, p(raw.flat), p(parts), n_part, p(self.grad_sums), p(self.saved),
-                                      p(self.kl_parts), p(eps_item), p(self.beta), p(self.lr), p(self._steps), p(self.par_flat),
-                                      p(self.par_m), p(self.par_v), p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v),
-                                      p(self.loss), stream)
-        _lib.check(rc, 'vibo_mtrain_epilogue')
+        p = ops._ptr
+        ops._call('vibo_mtrain_epilogue', ctypes.byref(d), self.hidden, p(raw.flat), p(parts), n_part, p(self.grad_sums), p(self.saved),
+                  p(self.kl_parts), p(eps_item), p(self.beta), p(self.lr), p(self._steps), p(self.par_flat),
+                  p(self.par_m), p(self.par_v), p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v),
+                  p(self.loss), ops._stream(raw.flat.device))
         return self.loss
 
 
@@ -649,9 +635,8 @@ class FusedDecoderTrainer(FusedTrainer):
         B, I = r.shape
         dev = r.device
         A, H = model.ability_dim, self.hidden
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        d = ops._make_desc(model.spec, B, I, _lib.MASK_NONE if m is None else _lib.MASK_U8, _lib.REG_KL, True, r.stride(0),
-                           m.stride(0) if m is not None else 0)
+        stream = ops._stream(dev)
+        d = ops._rows_desc(model.spec, B, r, m, _lib.MASK_NONE if m is None else _lib.MASK_U8, _lib.REG_KL, True)
         chunk = min(int(decoder.PERSON_CHUNK), B)
         scratch = self._scratch.get((B, chunk))
         if scratch is None:
@@ -661,15 +646,13 @@ class FusedDecoderTrainer(FusedTrainer):
             scratch = self._scratch[(B, chunk)] = torch.empty(n, device=dev)
             scratch[:_lib.NUM_SCALARS].zero_()
         eps_item, eps_ab, native = self._choose_noise(B, dev, eps_item, eps_ability)
-        rc = lib.vibo_dtrain_prologue(ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(self.item_mu), p(self.item_lv),
-                                      p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, 1, p(self.item_feat),
-                                      p(scratch), p(self._steps), stream)
-        _lib.check(rc, 'vibo_dtrain_prologue')
+        ops._call('vibo_dtrain_prologue', ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(self.item_mu), p(self.item_lv),
+                  p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, 1, p(self.item_feat),
+                  p(scratch), p(self._steps), stream)
         if eps_ab is None:
             eps_ab = model._randn((B, A), self.item_mu, model._ability_gen)
-        rc = lib.vibo_dtrain_forward_backward(ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts), p(eps_ab),
-                                              p(self.item_feat), p(scratch), stream)
-        _lib.check(rc, 'vibo_dtrain_forward_backward')
+        ops._call('vibo_dtrain_forward_backward', ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts), p(eps_ab),
+                  p(self.item_feat), p(scratch), stream)
         off = [int(lib.vibo_dtrain_scratch_offset(ctypes.byref(d), self.kind, H, chunk, w))
                for w in (_lib.DTRAIN_SCALARS, _lib.DTRAIN_POSTERIOR, _lib.DTRAIN_ABILITY)]
         post = scratch[off[1]:off[1] + B * 2 * A].view(B, 2 * A)
@@ -689,10 +672,8 @@ class FusedDecoderTrainer(FusedTrainer):
             raise RuntimeError('FusedDecoderTrainer.update(): no forward_backward() is pending')
         d, eps_item, scratch, chunk = self._pending
         self._pending = None
-        lib, p = _lib.load(), ops._ptr
-        stream = ctypes.c_void_p(torch.cuda.current_stream(scratch.device).cuda_stream)
-        rc = lib.vibo_dtrain_epilogue(ctypes.byref(d), self.kind, self.hidden, chunk, p(scratch), p(eps_item), p(self.item_feat),
-                                      p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
-                                      p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.loss), stream)
-        _lib.check(rc, 'vibo_dtrain_epilogue')
+        p = ops._ptr
+        ops._call('vibo_dtrain_epilogue', ctypes.byref(d), self.kind, self.hidden, chunk, p(scratch), p(eps_item), p(self.item_feat),
+                  p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
+                  p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.loss), ops._stream(scratch.device))
         return self.loss
