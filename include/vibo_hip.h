@@ -595,6 +595,43 @@ int vibo_dtrain_epilogue(const vibo_desc* d, int decoder, int hidden_dim, int pe
                          int32_t* step_count, float* params, float* adam_m, float* adam_v, float* item_mu,
                          float* item_logvar, float* item_m, float* item_v, float* loss_out, void* stream);
 
+/*
+ * The same step with the CONDITIONAL posterior q(ability | responses, items) of the product-of-experts encoder (d->posterior =
+ * VIBO_POSTERIOR_CONDITIONAL; models.py:695-710, utils.py:105-113): three twins of the calls above with the same arguments, plus
+ * the minibatch's 1-byte cell codes.  The calls above keep refusing such a descriptor (-6); these refuse an unconditional one.
+ *     vibo_dtrain_prologue_cond          as vibo_dtrain_prologue, without the 2-row table; then the encoder MLP
+ *                                        Linear(1 + D, H) -> ELU -> Linear(H, H) -> ELU -> Linear(H, 2A) over the 2 I rows
+ *                                        [c, item_feat_i] (activations kept) and the operand of the experts' contraction,
+ *                                        feature[c][i] = tau | mu tau | 0 ... (64 columns), tau = 1 / (exp(logvar) + 1e-8)
+ *     vibo_dtrain_forward_backward_cond  vibo_code_table_sum_forward over the whole minibatch -> [lambda | s] [B][64]; per chunk as
+ *                                        vibo_dtrain_forward_backward with lambda += (I - n_observed) / (1 + 1e-8) under
+ *                                        VIBO_MISSING_PRIOR (n_observed from `counts`), mu = s / lambda, logvar = log(1 / lambda)
+ *                                        (a person without an observed cell under VIBO_MISSING_DROP gets NaN, as in the reference),
+ *                                        the backward up to d [lambda | s] of d LL and of d KL; then vibo_code_table_sum_backward
+ *                                        over the whole minibatch -> d feature [2][I][64]
+ *     vibo_dtrain_epilogue_cond          d loss = -d LL + beta d KL -> the encoder MLP backward over the 2 I rows (one record per
+ *                                        workgroup, summed in fixed order with the other records; the gradient of the rows' item
+ *                                        columns joins d item_feat), then as vibo_dtrain_epilogue
+ *  codes [B][codes_row_stride] uint8: the minibatch's cells in the VIBO_MASK_CODES layout (0 wrong / 1 right / 2 missing, what
+ *  vibo_pack_codes writes; 4-byte aligned, stride a multiple of 4 and >= num_item, else -8), beside the dense rows the decoder reads.
+ *  params: as above with the encoder's first layer W0 [H][1 + D] (vibo_dtrain_param_floats follows d->posterior); scratch:
+ *  vibo_dtrain_scratch_floats / _scratch_offset follow d->posterior too (the conditional layout is the unconditional one with the
+ *  table's buffers behind it).  ability_dim 1..16, hidden_dim <= 64; flows, the other regulariser and int64 masks are refused as above.
+ *  The code-table calls run once per step whatever person_chunk is.  No atomics: bitwise reproducible, hipGraph-capturable.
+ */
+int vibo_dtrain_prologue_cond(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                              const float* item_mu, const float* item_logvar, float* eps_item, uint64_t seed, int draw_noise,
+                              float* eps_ability, uint32_t ability_stream_id, float* item_feat, float* scratch,
+                              int32_t* step_count, void* stream);
+int vibo_dtrain_forward_backward_cond(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                                      const float* response, const uint8_t* mask, const int32_t* counts,
+                                      const uint8_t* codes, int64_t codes_row_stride, const float* eps_ability,
+                                      const float* item_feat, float* scratch, void* stream);
+int vibo_dtrain_epilogue_cond(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, float* scratch,
+                              const float* eps_item, const float* item_feat, const float* beta, const float* lr,
+                              int32_t* step_count, float* params, float* adam_m, float* adam_v, float* item_mu,
+                              float* item_logvar, float* item_m, float* item_v, float* loss_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

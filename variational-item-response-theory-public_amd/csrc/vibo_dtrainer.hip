@@ -21,6 +21,23 @@
 // (row stride 65: "lane j walks row j" and "lane k walks column k" are both conflict-free), 16 rows per tile, a workgroup keeps
 // its tiles through all layers.  Every sum over persons / items / records has a fixed order: bitwise reproducible, no atomics.
 // Minibatches above `person_chunk` persons run the person kernels and the decoder once per chunk against per-chunk record slots.
+//
+// The conditional posterior q(ability | responses, items) (vibo_dtrain_*_cond; models.py:695-710, utils.py:105-113) runs beside that:
+//   dt_prologue_cond_kernel    the prologue without the 2-row table
+//   dt_table_fwd_kernel        the encoder MLP [1 + D -> H -> H -> 2A] over the 2 I rows [c, item_feat_i] (activations kept) and the
+//                              operand of the experts' contraction, feature[c][i] = tau | mu tau | 0 ... (64 columns)
+//   vibo_code_table_sum_forward    [lambda | s | 0] [B][64] = one-hot(codes) [B, 2I] x feature [2I, 64] (vibo_cmean.hip)
+//   dt_person_fwd_cond_kernel / dt_person_bwd_cond_kernel   the unconditional kernels' bodies with the posterior read from those
+//                              sums; the backward leaves d [lambda | s] of d LL (columns 0 .. 2A) and of d KL (2A .. 4A) per person
+//   vibo_code_table_sum_backward   d feature [2][I][64] (fixed-order sum over the persons)
+//   dt_table_bwd_kernel        d loss = -d LL + beta d KL -> d (mu, logvar) of the table, the encoder MLP backward: one record per
+//                              workgroup (summed by dt_reduce_kernel) + the gradient of the rows' inputs, whose item columns the
+//                              epilogue adds to d item_feat
+//   dt_epilogue_cond_kernel    block 0: the loss; Adam on the encoder parameters from the reduced records with the decoder's
+// The four kernels that exist once per posterior (prologue, person forward / backward, epilogue) live in vibo_dtrainer_kernels.inc,
+// included twice below: the unconditional ones are their own text, the conditional parts sit inside #if DT_COND.
+// The two code-table calls run ONCE per step over the whole minibatch, whatever the person chunks: they keep no per-chunk state
+// (the sums of all persons are formed before the first chunk, d [lambda | s] of all persons is complete after the last).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -39,14 +56,16 @@ constexpr int kDThreads = 256;
 constexpr int kDMaxGroups = 256;    // workgroups (= records) per row kernel
 constexpr int kDMaxSlices = 64;     // person slices (= records) of dt_ditem_kernel
 
-// a Linear -> ELU -> Linear -> ELU -> Linear stack [in -> H -> H -> H] in state_dict order (offsets into the flat parameters)
+// a Linear -> ELU -> Linear -> ELU -> Linear stack [in -> H -> H -> out] in state_dict order (offsets into the flat parameters);
+// out < 0: H
 struct Mlp3 {
     int w0, b0, w1, b1, w2, b2, total;
 };
-__host__ __device__ inline Mlp3 mlp3_at(const int base, const int in, const int H) {
+__host__ __device__ inline Mlp3 mlp3_at(const int base, const int in, const int H, const int out = -1) {
     Mlp3 m;
-    m.w0 = base; m.b0 = m.w0 + H * in; m.w1 = m.b0 + H; m.b1 = m.w1 + H * H; m.w2 = m.b1 + H; m.b2 = m.w2 + H * H;
-    m.total = m.b2 + H - base;
+    const int O = out < 0 ? H : out;
+    m.w0 = base; m.b0 = m.w0 + H * in; m.w1 = m.b0 + H; m.b1 = m.w1 + H * H; m.w2 = m.b1 + H; m.b2 = m.w2 + O * H;
+    m.total = m.b2 + O - base;
     return m;
 }
 
@@ -57,10 +76,11 @@ struct DParams {
     Mlp3 fi, fa;                              // mlp_item_feat / mlp_ability (deep, residual)
     int t0w, t0b, t2w, t2b, t4w, t4b, total;
 };
-__host__ __device__ inline DParams dparams(const int kind, const int H, const int A, const int D) {
+// xin: the encoder's input width, 1 (unconditional posterior) or 1 + D (conditional: the rows [c, item_feat_i])
+__host__ __device__ inline DParams dparams(const int kind, const int H, const int A, const int D, const int xin = 1) {
     DParams p;
     p.kind = kind; p.H = H; p.A = A; p.D = D;
-    p.enc = mlp_offsets(H, 2 * A).total;
+    p.enc = mlp3_at(0, xin, H, 2 * A).total;
     p.dec = p.enc;
     int o = p.enc;
     if (kind == VIBO_DECODER_LINK) {
@@ -94,7 +114,9 @@ __host__ __device__ inline DRec drec(const DParams& p) {
 struct DLayout {
     int B, I, A, D, H, kind, irt;
     int n_chunk, bc, dc, n_ib, n_wave, gp, gi, ns;      // chunks, persons per chunk, decoder person_chunks, ..., person / item groups, slices
-    bool has_l, has_g, mlp;
+    bool has_l, has_g, mlp, cond;
+    int xin, gt;                                        // conditional posterior: encoder input width, table workgroups (= records)
+    size_t cx, th1, th2, tout, feat, sums, dsum, dfeat, tda, tdb, tgx, trec, s_enc, ct, ct_bytes;
     size_t flat8, table, saved_h, kl_parts, w2p, b2p, w3p, w1p, b3p, guess, ih1, ih2, ihid, U, post, ability, ah1, ah2, ahid, V, L,
         dL, da, db, gab, ida, idb, gx, ll_part, dW2, dvec, dU, dguess, dV, prec, drec_item, irec, s_dW2, s_dvec, s_dU, s_dguess,
         s_p, s_ditem, total;
@@ -129,7 +151,10 @@ static DLayout dlayout(const vibo_desc* d, const int kind, const int H, int pers
     y.gp = (y.bc + kDRows - 1) / kDRows; if (y.gp > kDMaxGroups) y.gp = kDMaxGroups;
     y.gi = (I + kDRows - 1) / kDRows; if (y.gi > kDMaxGroups) y.gi = kDMaxGroups;
     y.ns = (y.bc + 63) / 64; if (y.ns > kDMaxSlices) y.ns = kDMaxSlices;
-    const DParams p = dparams(kind, H, A, D);
+    y.cond = d->posterior == VIBO_POSTERIOR_CONDITIONAL;
+    y.xin = y.cond ? 1 + D : 1;
+    y.gt = (2 * I + kDRows - 1) / kDRows; if (y.gt > kDMaxGroups) y.gt = kDMaxGroups;
+    const DParams p = dparams(kind, H, A, D, y.xin);
     const DRec r = drec(p);
     size_t o = 0;
     auto take = [&](size_t& field, const size_t n) { field = o; o += up4(n); };
@@ -156,6 +181,15 @@ static DLayout dlayout(const vibo_desc* d, const int kind, const int H, int pers
     take(y.irec, y.mlp ? (size_t)y.gi * r.itotal : 0);
     take(y.s_dW2, kDW * kDW); take(y.s_dvec, 4 * kDW); take(y.s_dU, y.mlp ? sI * kDW : 0); take(y.s_dguess, y.has_g ? sI : 0);
     take(y.s_p, r.ptotal); take(y.s_ditem, y.has_l ? sI * D : 0);
+    if (y.cond) {                                       // (behind everything else: the unconditional layout is a prefix)
+        const size_t rows = 2 * sI;
+        take(y.cx, rows * y.xin); take(y.th1, rows * kDW); take(y.th2, rows * kDW); take(y.tout, rows * kDW); take(y.feat, rows * kDW);
+        take(y.sums, sB * kDW); take(y.dsum, sB * kDW); take(y.dfeat, rows * kDW);
+        take(y.tda, rows * kDW); take(y.tdb, rows * kDW); take(y.tgx, rows * y.xin);
+        take(y.trec, (size_t)y.gt * p.enc); take(y.s_enc, p.enc);
+        y.ct_bytes = vibo_code_table_scratch_bytes(B, I, kDW);
+        take(y.ct, y.ct_bytes / 4 + 64);                // (the code-table calls want 256-byte alignment: found inside this slot)
+    }
     y.total = o;
     return y;
 }
@@ -259,6 +293,21 @@ __device__ void bwd_layer(float* Ws, float* Tin, float* Td, const float* __restr
     if (rec_b != nullptr && tid < n_out) rec_b[tid] = ab;
 }
 
+// ---- the conditional posterior's side argument -------------------------------------------------------------------------------------
+// What the *_cond kernels get beside the unconditional kernels' argument: the encoder stack e [xin -> H -> H -> 2A] over the
+// n = 2 I table rows and where its pieces live.
+struct DCond {
+    Mlp3 e;
+    int H, A, I, xin, nwg;
+    const float *P, *item_feat, *beta;
+    float *x, *h1, *h2, *out, *feat;          // table forward: input rows [2I][xin], activations / (mu | logvar) / feature [2I][64]
+    const float* sums;                        // person kernels: [lambda | s | 0] [nb][64] of this chunk
+    float* dsum;                              // ... d [lambda | s] of d LL | of d KL | 0 [nb][64]
+    const float* dfeat;                       // table backward: d feature [2I][64]
+    float *da, *db, *gx, *rec;                // ... [2I][64] x 2, d x [2I][xin], records [nwg][e.total]
+    const float* s_enc;                       // epilogue: the reduced records (d loss / d encoder parameters)
+};
+
 // ---- prologue --------------------------------------------------------------------------------------------------------------------
 struct DPrologue {
     DParams p;
@@ -269,48 +318,6 @@ struct DPrologue {
     uint32_t seed_lo, seed_hi, ab_stream;
     long long n_ab;
 };
-__global__ __launch_bounds__(kDThreads) void dt_prologue_kernel(const DPrologue a) {
-    __shared__ float h1[2 * kDW], h2[2 * kDW];
-    const int tid = threadIdx.x;
-    const DParams& p = a.p;
-    if (blockIdx.x == 0) {
-        if (tid == 0) a.step_count[0] += 1;
-        const int H = p.H, O = 2 * p.A;
-        const MlpOffsets o = mlp_offsets(H, O);
-        mlp2_layer0(a.P, o, H, O, h1, tid, kDThreads);
-        __syncthreads();
-        mlp2_layer1(a.P, o, H, O, h1, h2, tid, kDThreads);
-        __syncthreads();
-        mlp2_layer2(a.P, o, H, O, h1, h2, tid, kDThreads, a.table, a.saved_h);
-        // the per-term network's second and third layer, 64 wide (decoder._pad_hidden)
-        for (int e = tid; e < kDW * kDW; e += kDThreads) {
-            const int j = e >> 6, k = e & 63;
-            a.w2p[e] = (j < H && k < H) ? a.P[p.t2w + j * H + k] : 0.f;
-        }
-        if (tid < kDW) {
-            const bool in = tid < H;
-            a.b2p[tid] = in ? a.P[p.t2b + tid] : 0.f;
-            a.w3p[tid] = in ? a.P[p.t4w + tid] : 0.f;
-            a.w1p[tid] = (in && p.kind == VIBO_DECODER_LINK) ? a.P[p.t0w + tid] : 0.f;
-            if (tid == 0) a.b3p[0] = a.P[p.t4b];
-        }
-        return;
-    }
-    if ((int)blockIdx.x > a.n_item_blocks) {          // ability noise (stream ab_stream)
-        ability_noise_block(blockIdx.x - 1 - a.n_item_blocks, kDThreads, tid, a.eps_ab, a.n_ab, (uint32_t)a.step_count[1], a.ab_stream,
-                            a.seed_lo, a.seed_hi);
-        return;
-    }
-    item_prologue_block(blockIdx.x - 1, tid, a.I, p.D, a.mu, a.lv, a.eps, a.eps_w, a.gen, a.step_count + 1, a.seed_lo, a.seed_hi,
-                        a.item_feat, a.kl_parts);
-    if (a.guess != nullptr) {                         // 3PL: guess = sigmoid(item_feat[:, A + 1]) (this thread's own store)
-        const int k = (blockIdx.x - 1) * 256 + tid;
-        if (k < a.I * p.D) {
-            const int idx = item_entry_index(k, a.I, p.D);
-            if (idx % p.D == p.A + 1) a.guess[idx / p.D] = 1.0f / (1.0f + expf(-a.item_feat[idx]));
-        }
-    }
-}
 
 // ---- item side -------------------------------------------------------------------------------------------------------------------
 struct DItem {
@@ -380,164 +387,79 @@ __device__ __forceinline__ Poe poe_forward(const int c, const float* __restrict_
     return q;
 }
 
-__global__ __launch_bounds__(kDThreads) void dt_person_fwd_kernel(const DPerson a) {
+
+// the conditional product of experts of person row `row`, dimension a, from the experts' sums: lambda (with the prior experts of
+// the missing cells) and s  (models._conditional_posterior_poe); the per-code fields stay unset
+__device__ __forceinline__ Poe cpoe_forward(const DCond& c, const int row, const int a, const int count, const int I, const int prior) {
+    Poe q;
+    q.lam = c.sums[(size_t)row * kDW + a];
+    q.smu = c.sums[(size_t)row * kDW + c.A + a];
+    if (prior) q.lam += ((float)I - (float)(count & 0xffff)) * (1.0f / (1.0f + kPoeEps));
+    return q;
+}
+
+// ---- the conditional posterior's expert table ---------------------------------------------------------------------------------
+// row = c I + i of the 2 I table rows: input [c, item_feat_i] -> (mu | logvar) [2A] -> feature = tau | mu tau | 0 ... [64],
+// tau = 1 / (exp(logvar) + 1e-8)  (utils.py:105-113)
+__global__ __launch_bounds__(kDThreads) void dt_table_fwd_kernel(const DCond c) {
     __shared__ float Ws[kDW * kDLd], Ts[kDRows * kDW];
-    const DParams& p = a.p;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int H = p.H, A = p.A, D = p.D, I = a.I, wg = blockIdx.x;
-    const int r16 = tid >> 4, a16 = tid & 15;
-    for (int t = wg; t * kDRows < a.nb; t += a.nwg) {
-        const int row = t * kDRows + r16;
-        if (row < a.nb && a16 < A) {
-            const Poe q = poe_forward(a.counts[row], a.table, A, a16, I, a.prior);
-            const float mu = q.smu / q.lam, lv = logf(1.0f / q.lam);
-            a.post[(size_t)row * 2 * A + a16] = mu;
-            a.post[(size_t)row * 2 * A + A + a16] = lv;
-            a.ability[(size_t)row * A + a16] = fmaf(expf(0.5f * lv), a.eps[(size_t)row * A + a16], mu);
+    const int tid = threadIdx.x, wg = blockIdx.x;
+    const int H = c.H, A = c.A, I = c.I, xin = c.xin, n = 2 * c.I;
+    for (int t = wg; t * kDRows < n; t += c.nwg) {
+        for (int e = tid; e < kDRows * xin; e += kDThreads) {
+            const int row = t * kDRows + e / xin, k = e % xin;
+            if (row >= n) continue;
+            const int cc = row >= I ? 1 : 0, i = row - cc * I;
+            c.x[(size_t)row * xin + k] = k == 0 ? (float)cc : c.item_feat[(size_t)i * (xin - 1) + (k - 1)];
         }
     }
-    if (p.kind == VIBO_DECODER_LINK) {
-        for (int t = wg; t * kDRows < a.nb; t += a.nwg) {
-            for (int e = tid; e < kDRows * kDW; e += kDThreads) {
-                const int row = t * kDRows + (e >> 6), j = e & 63;
-                if (row < a.nb) a.V[(size_t)row * kDW + j] = j < H ? a.P[p.t0b + j] : 0.f;
+    // (fwd_layer starts with a barrier: this workgroup's input rows are visible to all of its threads)
+    fwd_layer(Ws, Ts, c.P + c.e.w0, xin, H, xin, c.P + c.e.b0, c.x, xin, xin, c.h1, n, true, wg, c.nwg);
+    fwd_layer(Ws, Ts, c.P + c.e.w1, H, H, H, c.P + c.e.b1, c.h1, kDW, kDW, c.h2, n, true, wg, c.nwg);
+    fwd_layer(Ws, Ts, c.P + c.e.w2, H, 2 * A, H, c.P + c.e.b2, c.h2, kDW, kDW, c.out, n, false, wg, c.nwg);
+    __syncthreads();
+    for (int t = wg; t * kDRows < n; t += c.nwg) {
+        for (int e = tid; e < kDRows * kDW; e += kDThreads) {
+            const int row = t * kDRows + (e >> 6), j = e & 63;
+            if (row >= n) continue;
+            float v = 0.f;
+            if (j < 2 * A) {
+                const int q = j < A ? j : j - A;
+                const float tau = 1.0f / (expf(c.out[(size_t)row * kDW + A + q]) + kPoeEps);
+                v = j < A ? tau : c.out[(size_t)row * kDW + q] * tau;
             }
-        }
-    } else {
-        // (fwd_layer starts with a barrier: this workgroup's ability rows are visible to all of its threads)
-        fwd_layer(Ws, Ts, a.P + p.fa.w0, A, H, A, a.P + p.fa.b0, a.ability, A, A, a.h1, a.nb, true, wg, a.nwg);
-        fwd_layer(Ws, Ts, a.P + p.fa.w1, H, H, H, a.P + p.fa.b1, a.h1, kDW, kDW, a.h2, a.nb, true, wg, a.nwg);
-        fwd_layer(Ws, Ts, a.P + p.fa.w2, H, H, H, a.P + p.fa.b2, a.h2, kDW, kDW, a.hid, a.nb, false, wg, a.nwg);
-        fwd_layer(Ws, Ts, a.P + p.t0w + H, 2 * H, H, H, a.P + p.t0b, a.hid, kDW, kDW, a.V, a.nb, false, wg, a.nwg);
-    }
-    if (a.L != nullptr) {                             // decoder.irt_logit: a wave per row, lanes over the items
-        __syncthreads();
-        for (int t = wg; t * kDRows < a.nb; t += a.nwg) {
-            for (int rr = 0; rr < 4; ++rr) {
-                const int row = t * kDRows + 4 * w + rr;
-                if (row >= a.nb) continue;
-                const float* ab = a.ability + (size_t)row * A;
-                for (int i = lane; i < I; i += 64) {
-                    float s;
-                    if (a.irt == VIBO_IRT_1PL) {
-                        s = 0.f;
-                        for (int q = 0; q < A; ++q) s += ab[q];
-                        s += a.item_feat[i];
-                    } else {
-                        s = 0.f;
-                        for (int q = 0; q < A; ++q) s = fmaf(ab[q], -a.item_feat[(size_t)i * D + q], s);
-                        s += a.item_feat[(size_t)i * D + A];
-                    }
-                    a.L[(size_t)row * I + i] = s;
-                }
-            }
+            c.feat[(size_t)row * kDW + j] = v;
         }
     }
 }
-
-__global__ __launch_bounds__(kDThreads) void dt_person_bwd_kernel(const DPerson a) {
+// d feature [2I][64] (columns 0 .. 2A: of d LL, 2A .. 4A: of d KL) -> d loss / d (mu | logvar) of the table -> the encoder MLP
+// backward: this workgroup's record in the encoder's parameter layout, and d x [2I][xin]
+__global__ __launch_bounds__(kDThreads) void dt_table_bwd_kernel(const DCond c) {
     __shared__ float Ws[kDW * kDLd], Tin[kDRows * kDW], Td[kDRows * kDW];
-    __shared__ float gl[kDRows * 16], wsum[4];
-    const DParams& p = a.p;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int H = p.H, A = p.A, D = p.D, I = a.I, wg = blockIdx.x;
-    float* rec = a.rec + (size_t)wg * a.rec_stride;
-    // d LL / d V = the fixed-order sum of the decoder kernel's records
-    float vb = 0.f;                                   // link: d link[0].bias = sum over the persons (column tid & 63, rows w, w + 4, ...)
-    for (int t = wg; t * kDRows < a.nb; t += a.nwg) {
+    const int tid = threadIdx.x, wg = blockIdx.x;
+    const int H = c.H, A = c.A, xin = c.xin, n = 2 * c.I;
+    const float beta = *c.beta;
+    for (int t = wg; t * kDRows < n; t += c.nwg) {
         for (int e = tid; e < kDRows * kDW; e += kDThreads) {
             const int row = t * kDRows + (e >> 6), j = e & 63;
-            if (row >= a.nb) continue;
-            float s = 0.f;
-            for (int k = 0; k < a.n_dv; ++k) s += a.dV[((size_t)k * a.nb + row) * kDW + j];
-            a.da[(size_t)row * kDW + j] = s;
-            vb += s;
-        }
-    }
-    if (p.kind == VIBO_DECODER_LINK) {
-        __syncthreads();
-        Td[tid] = vb;
-        __syncthreads();
-        if (tid < H) rec[a.r_vb + tid] = (Td[tid] + Td[64 + tid]) + (Td[128 + tid] + Td[192 + tid]);
-    } else {
-        float* rf = rec + a.r_fa - p.fa.w0;           // (mlp_ability in its parameter layout)
-        bwd_layer(Ws, Tin, Td, a.P + p.t0w + H, 2 * H, H, H, a.da, a.hid, kDW, kDW, false, a.db, kDW, a.nb, rec + a.r_wcp, H, rec + a.r_vb, wg,
-                  a.nwg);
-        bwd_layer(Ws, Tin, Td, a.P + p.fa.w2, H, H, H, a.db, a.h2, kDW, kDW, true, a.da, kDW, a.nb, rf + p.fa.w2, H, rf + p.fa.b2, wg, a.nwg);
-        bwd_layer(Ws, Tin, Td, a.P + p.fa.w1, H, H, H, a.da, a.h1, kDW, kDW, true, a.db, kDW, a.nb, rf + p.fa.w1, H, rf + p.fa.b1, wg, a.nwg);
-        bwd_layer(Ws, Tin, Td, a.P + p.fa.w0, A, H, A, a.db, a.ability, A, A, false, a.gab, A, a.nb, rf + p.fa.w0, A, rf + p.fa.b0, wg, a.nwg);
-    }
-    // d LL / d ability -> (mu, logvar) -> the 2-row table; KL and its gradient.  Thread (r16, a16) = (row of the tile, dimension).
-    const int r16 = tid >> 4, a16 = tid & 15;
-    float tg[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // [set][c][mu | logvar] of dimension a16
-    float kl = 0.f;
-    for (int t = wg; t * kDRows < a.nb; t += a.nwg) {
-        __syncthreads();
-        if (a.dL != nullptr) {                        // gl[r][q] = sum_i d L[row][i] (-item[i][q]): a wave per row, lanes over the items
-            for (int rr = 0; rr < 4; ++rr) {
-                const int r = 4 * w + rr, row = t * kDRows + r;
-                float acc[16];
-#pragma unroll
-                for (int q = 0; q < 16; ++q) acc[q] = 0.f;
-                if (row < a.nb) {
-                    for (int i = lane; i < I; i += 64) {
-                        const float g = a.dL[(size_t)row * I + i];
-                        if (a.irt == VIBO_IRT_1PL) {
-                            acc[0] += g;
-                        } else {
-#pragma unroll
-                            for (int q = 0; q < 16; ++q)
-                                if (q < A) acc[q] = fmaf(g, -a.item_feat[(size_t)i * D + q], acc[q]);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < 16; ++q) {
-                    if (q < A) {
-                        const float s = wave_total(acc[a.irt == VIBO_IRT_1PL ? 0 : q]);
-                        if (lane == 0) gl[r * 16 + q] = s;
-                    }
-                }
+            if (row >= n) continue;
+            float v = 0.f;
+            if (j < 2 * A) {
+                const int q = j < A ? j : j - A;
+                const float* g = c.dfeat + (size_t)row * kDW;
+                const float gt = fmaf(beta, g[2 * A + q], -g[q]);              // d loss / d tau
+                const float gm = fmaf(beta, g[3 * A + q], -g[A + q]);          // d loss / d (mu tau)
+                const float mu = c.out[(size_t)row * kDW + q], ev = expf(c.out[(size_t)row * kDW + A + q]);
+                const float tau = 1.0f / (ev + kPoeEps);
+                v = j < A ? gm * tau : fmaf(gm, mu, gt) * (-ev * tau * tau);
             }
-        }
-        __syncthreads();
-        const int row = t * kDRows + r16;
-        if (row < a.nb && a16 < A) {
-            float g = p.kind == VIBO_DECODER_LINK ? 0.f : a.gab[(size_t)row * A + a16];
-            if (a.dL != nullptr) g += gl[r16 * 16 + a16];
-            const Poe q = poe_forward(a.counts[row], a.table, A, a16, I, a.prior);
-            const float mu = a.post[(size_t)row * 2 * A + a16], lv = a.post[(size_t)row * 2 * A + A + a16];
-            const float var = expf(lv);
-            kl += -0.5f * (1.0f + lv - mu * mu - var);
-            const float inv = 1.0f / q.lam;
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                // set 0: d LL through the sample; set 1: d KL
-                const float dmu = s == 0 ? g : mu;
-                const float dlv = s == 0 ? g * a.eps[(size_t)row * A + a16] * (0.5f * expf(0.5f * lv)) : 0.5f * (var - 1.0f);
-                const float dsmu = dmu * inv;
-                const float dlam = -fmaf(dmu, mu, dlv) * inv;
-                tg[4 * s + 0] += q.n0 * q.tau0 * dsmu;
-                tg[4 * s + 1] += q.n0 * fmaf(dsmu, q.m0, dlam) * (-q.e0 * q.tau0 * q.tau0);
-                tg[4 * s + 2] += q.n1 * q.tau1 * dsmu;
-                tg[4 * s + 3] += q.n1 * fmaf(dsmu, q.m1, dlam) * (-q.e1 * q.tau1 * q.tau1);
-            }
+            c.da[(size_t)row * kDW + j] = v;
         }
     }
-    __syncthreads();
-#pragma unroll
-    for (int v = 0; v < 8; ++v) Ws[tid * 8 + v] = tg[v];
-    kl = wave_total(kl);
-    if (lane == 0) wsum[w] = kl;
-    __syncthreads();
-    if (tid < 8 * A) {
-        const int v = tid / A, q = tid % A;
-        float s = 0.f;
-        for (int r = 0; r < kDRows; ++r) s += Ws[(r * 16 + q) * 8 + v];
-        // v = 4 set + 2 c + part -> grad_table layout [set][c][part A + q]
-        rec[a.r_tab + (v >> 2) * 4 * A + ((v >> 1) & 1) * 2 * A + (v & 1) * A + q] = s;
-    }
-    if (tid == 0) rec[a.r_kl] = (wsum[0] + wsum[1]) + (wsum[2] + wsum[3]);
+    float* rec = c.rec + (size_t)wg * c.e.total;
+    bwd_layer(Ws, Tin, Td, c.P + c.e.w2, H, 2 * A, H, c.da, c.h2, kDW, kDW, true, c.db, kDW, n, rec + c.e.w2, H, rec + c.e.b2, wg, c.nwg);
+    bwd_layer(Ws, Tin, Td, c.P + c.e.w1, H, H, H, c.db, c.h1, kDW, kDW, true, c.da, kDW, n, rec + c.e.w1, H, rec + c.e.b1, wg, c.nwg);
+    bwd_layer(Ws, Tin, Td, c.P + c.e.w0, xin, H, xin, c.da, c.x, xin, xin, false, c.gx, xin, n, rec + c.e.w0, xin, rec + c.e.b0, wg, c.nwg);
 }
 
 // link / residual: d LL / d item_feat through the IRT logit, one record per person slice (grid: entries / 256 x slices)
@@ -596,90 +518,27 @@ struct DEpilogue {
     int32_t* step_count;
     float *P, *M, *V, *mu, *lv, *im, *iv, *loss;
 };
-__global__ __launch_bounds__(kEpiThreads) void dt_epilogue_kernel(const DEpilogue a) {
-    __shared__ EpiLds L;
-    const int tid = threadIdx.x;
-    const DParams& p = a.p;
-    const DRec& r = a.r;
-    const float beta = *a.beta, lr = *a.lr;
-    const AdamBias bc = adam_bias(a.step_count[0]);
-    constexpr int BS = kEpiThreads;
-    const int H = p.H;
-    if (blockIdx.x == 0) {
-        if (tid == 0) a.step_count[1] += 1;           // completed steps: the noise counter of the NEXT step
-        // the 2-row encoder: sc = [LL, KL_ability, ...], gtab = d LL / d table then d KL / d table (the person records' sums)
-        float pv[kEpiU], mv[kEpiU], vv[kEpiU];
-        const MlpOffsets o = mlp_offsets(H, 2 * p.A);
-        epi_mlp_prefetch(o.total, a.P, a.M, a.V, pv, mv, vv, tid);
-        if (H == 64) epi_mlp_block<64>(L, H, 2 * p.A, kl_part_count(a.n_item_entries), a.flat8, a.s_p + r.tab, a.saved_h, a.kl_parts, beta, lr,
-                                       bc, a.P, o, nullptr, a.P, a.M, a.V, pv, mv, vv, a.loss, tid);
-        else epi_mlp_block<0>(L, H, 2 * p.A, kl_part_count(a.n_item_entries), a.flat8, a.s_p + r.tab, a.saved_h, a.kl_parts, beta, lr, bc,
-                              a.P, o, nullptr, a.P, a.M, a.V, pv, mv, vv, a.loss, tid);
-        return;
-    }
-    if ((int)blockIdx.x <= a.n_dec_blocks) {          // Adam on the decoder parameters: d loss = -d LL
-        const int k = p.dec + ((int)blockIdx.x - 1) * BS + tid;
-        if (k >= p.total) return;
-        float g;
-        if (k >= p.t2w) {                             // the per-term network's second and third layer: the decoder kernel's records
-            if (k < p.t2b) {
-                const int e = k - p.t2w;
-                g = a.s_dW2[(e / H) * kDW + e % H];
-            } else if (k < p.t4w) {
-                g = a.s_dvec[k - p.t2b];
-            } else if (k < p.t4b) {
-                g = a.s_dvec[kDW + (k - p.t4w)];
-            } else {
-                g = a.s_dvec[3 * kDW];
-            }
-        } else if (p.kind == VIBO_DECODER_LINK) {
-            g = k < p.t0b ? a.s_dvec[2 * kDW + (k - p.t0w)] : a.s_p[r.vb + (k - p.t0b)];
-        } else if (k >= p.t0b) {
-            g = a.s_p[r.vb + (k - p.t0b)];
-        } else if (k >= p.fa.w0 && k < p.t0w) {
-            g = a.s_p[r.fa + (k - p.fa.w0)];
-        } else {
-            // mlp_item_feat, or the item half of mlp_concat[0].weight: the item workgroups' records, in order
-            int e;
-            if (k < p.fa.w0) {
-                e = r.fi + (k - p.fi.w0);
-            } else {
-                const int j = (k - p.t0w) / (2 * H), c = (k - p.t0w) % (2 * H);
-                e = c < H ? r.wci + j * H + c : -1;
-                if (e < 0) g = a.s_p[r.wcp + j * H + (c - H)];
-            }
-            if (e >= 0) {
-                g = 0.f;
-                for (int q = 0; q < a.n_irec; ++q) g += a.irec[(size_t)q * r.itotal + e];
-            }
-        }
-        float pv = a.P[k], mv = a.M[k], vv = a.V[k];
-        adam_update(pv, mv, vv, -g, lr, bc);
-        a.P[k] = pv; a.M[k] = mv; a.V[k] = vv;
-        return;
-    }
-    const int idx = ((int)blockIdx.x - 1 - a.n_dec_blocks) * BS + tid;
-    if (idx < a.n_item_entries) {                     // d loss / d item_feat = -d LL / d item_feat
-        float g = 0.f;
-        if (a.has_l) g += a.s_ditem[idx];
-        if (a.gx != nullptr) g += a.gx[idx];
-        if (a.has_g && idx % p.D == p.A + 1) {
-            const float gs = a.guess[idx / p.D];
-            g += a.s_dguess[idx / p.D] * gs * (1.0f - gs);
-        }
-        float pm, pl;
-        epi_item_update(idx, a.n_item_entries, -g, a.eps[idx], beta, lr, bc, a.mu, a.lv, a.im, a.iv, pm, pl);
-    }
-}
 
-static int dt_check(const vibo_desc* d, const int kind, const int H) {
+// dt_prologue / dt_person_fwd / dt_person_bwd / dt_epilogue: _kernel (unconditional posterior) and _cond_kernel (conditional)
+#define DT_COND 0
+#include "vibo_dtrainer_kernels.inc"
+#undef DT_COND
+#define DT_COND 1
+#include "vibo_dtrainer_kernels.inc"
+#undef DT_COND
+
+// which posterior an entry point serves: the vibo_dtrain_* calls the unconditional one, their *_cond twins the conditional one,
+// the size queries either
+enum { kPostUncond = 0, kPostCond = 1, kPostEither = 2 };
+static int dt_check(const vibo_desc* d, const int kind, const int H, const int post = kPostUncond) {
     if (!d || d->abi_version != VIBO_ABI_VERSION) return -2;
     if (d->ability_dim < 1 || d->ability_dim > VIBO_MAX_ABILITY_DIM_WIDE || d->num_item < 1 || d->num_person < 1) return -3;
     if (d->irt_model < VIBO_IRT_1PL || d->irt_model > VIBO_IRT_3PL) return -3;
     if (kind != VIBO_DECODER_LINK && kind != VIBO_DECODER_DEEP && kind != VIBO_DECODER_RESIDUAL) return -3;
     if (d->num_item > 65535) return -3;               // (the packed row counts)
     if (H < 1 || H > kDW) return -6;
-    if (d->posterior != VIBO_POSTERIOR_UNCONDITIONAL || d->n_flows != 0 || d->reg_mode != VIBO_REG_KL) return -6;
+    const bool uncond = d->posterior == VIBO_POSTERIOR_UNCONDITIONAL, cond = d->posterior == VIBO_POSTERIOR_CONDITIONAL;
+    if (!((uncond && post != kPostCond) || (cond && post != kPostUncond)) || d->n_flows != 0 || d->reg_mode != VIBO_REG_KL) return -6;
     if (d->mask_dtype != VIBO_MASK_U8 && d->mask_dtype != VIBO_MASK_NONE) return -8;
     return 0;
 }
@@ -691,16 +550,17 @@ using namespace vibo;
 extern "C" int64_t vibo_dtrain_param_floats(const vibo_desc* d, int decoder, int hidden_dim) {
     if (!d || hidden_dim < 1 || d->ability_dim < 1 || d->irt_model < VIBO_IRT_1PL || d->irt_model > VIBO_IRT_3PL) return 0;
     if (decoder != VIBO_DECODER_LINK && decoder != VIBO_DECODER_DEEP && decoder != VIBO_DECODER_RESIDUAL) return 0;
-    return dparams(decoder, hidden_dim, d->ability_dim, item_feat_dim(d->irt_model, d->ability_dim)).total;
+    const int D = item_feat_dim(d->irt_model, d->ability_dim);
+    return dparams(decoder, hidden_dim, d->ability_dim, D, d->posterior == VIBO_POSTERIOR_CONDITIONAL ? 1 + D : 1).total;
 }
 
 extern "C" int64_t vibo_dtrain_scratch_floats(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk) {
-    if (dt_check(d, decoder, hidden_dim)) return 0;
+    if (dt_check(d, decoder, hidden_dim, kPostEither)) return 0;
     return (int64_t)dlayout(d, decoder, hidden_dim, person_chunk).total;
 }
 
 extern "C" int64_t vibo_dtrain_scratch_offset(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, int which) {
-    if (dt_check(d, decoder, hidden_dim)) return -1;
+    if (dt_check(d, decoder, hidden_dim, kPostEither)) return -1;
     const DLayout y = dlayout(d, decoder, hidden_dim, person_chunk);
     switch (which) {
     case VIBO_DTRAIN_SCALARS: return (int64_t)y.flat8;
@@ -710,11 +570,27 @@ extern "C" int64_t vibo_dtrain_scratch_offset(const vibo_desc* d, int decoder, i
     }
 }
 
-extern "C" int vibo_dtrain_prologue(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
-                                    const float* item_mu, const float* item_logvar, float* eps_item, uint64_t seed, int draw_noise,
-                                    float* eps_ability, uint32_t ability_stream_id, float* item_feat, float* scratch,
-                                    int32_t* step_count, void* stream) {
-    const int rc = dt_check(d, decoder, hidden_dim);
+// the table's side argument of a step (every pointer but the per-chunk ones)
+static DCond dcond(const DLayout& y, const DParams& p, const float* params, const float* item_feat, float* scratch) {
+    DCond c;
+    memset(&c, 0, sizeof(c));
+    c.e = mlp3_at(0, y.xin, y.H, 2 * y.A);
+    c.H = y.H; c.A = y.A; c.I = y.I; c.xin = y.xin; c.nwg = y.gt;
+    c.P = params; c.item_feat = item_feat;
+    c.x = scratch + y.cx; c.h1 = scratch + y.th1; c.h2 = scratch + y.th2; c.out = scratch + y.tout; c.feat = scratch + y.feat;
+    c.sums = scratch + y.sums; c.dsum = scratch + y.dsum; c.dfeat = scratch + y.dfeat;
+    c.da = scratch + y.tda; c.db = scratch + y.tdb; c.gx = scratch + y.tgx; c.rec = scratch + y.trec; c.s_enc = scratch + y.s_enc;
+    return c;
+}
+static void* code_table_scratch(const DLayout& y, float* scratch) {
+    return (void*)(((uintptr_t)(scratch + y.ct) + 255) & ~(uintptr_t)255);
+}
+
+static int dt_prologue(const int post, const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                       const float* item_mu, const float* item_logvar, float* eps_item, uint64_t seed, int draw_noise,
+                       float* eps_ability, uint32_t ability_stream_id, float* item_feat, float* scratch, int32_t* step_count,
+                       void* stream) {
+    const int rc = dt_check(d, decoder, hidden_dim, post);
     if (rc) return rc;
     if (!params || !item_mu || !item_logvar || !eps_item || !item_feat || !scratch || !step_count) return -5;
     if (draw_noise && !eps_ability) return -5;
@@ -722,7 +598,7 @@ extern "C" int vibo_dtrain_prologue(const vibo_desc* d, int decoder, int hidden_
     hipStream_t s = (hipStream_t)stream;
     DPrologue a;
     memset(&a, 0, sizeof(a));
-    a.p = dparams(decoder, hidden_dim, y.A, y.D);
+    a.p = dparams(decoder, hidden_dim, y.A, y.D, y.xin);
     a.I = y.I; a.gen = draw_noise ? 1 : 0;
     a.n_item_blocks = (y.I * y.D + 255) / 256;
     a.P = params; a.mu = item_mu; a.lv = item_logvar; a.eps = eps_item; a.eps_w = eps_item; a.item_feat = item_feat;
@@ -733,7 +609,8 @@ extern "C" int vibo_dtrain_prologue(const vibo_desc* d, int decoder, int hidden_
     a.seed_lo = (uint32_t)seed; a.seed_hi = (uint32_t)(seed >> 32); a.ab_stream = ability_stream_id;
     a.n_ab = draw_noise ? (long long)y.B * y.A : 0;
     const long long ab_blocks = ((a.n_ab + 3) / 4 + kDThreads - 1) / kDThreads;
-    hipLaunchKernelGGL(dt_prologue_kernel, dim3((unsigned)(1 + a.n_item_blocks + ab_blocks)), dim3(kDThreads), 0, s, a);
+    if (y.cond) hipLaunchKernelGGL(dt_prologue_cond_kernel, dim3((unsigned)(1 + a.n_item_blocks + ab_blocks)), dim3(kDThreads), 0, s, a);
+    else hipLaunchKernelGGL(dt_prologue_kernel, dim3((unsigned)(1 + a.n_item_blocks + ab_blocks)), dim3(kDThreads), 0, s, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
     if (y.mlp) {
@@ -743,22 +620,55 @@ extern "C" int vibo_dtrain_prologue(const vibo_desc* d, int decoder, int hidden_
         it.h1 = scratch + y.ih1; it.h2 = scratch + y.ih2; it.hid = scratch + y.ihid; it.U = scratch + y.U;
         hipLaunchKernelGGL(dt_item_fwd_kernel, dim3((unsigned)y.gi), dim3(kDThreads), 0, s, it);
         e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    if (y.cond) {
+        const DCond c = dcond(y, a.p, params, item_feat, scratch);
+        hipLaunchKernelGGL(dt_table_fwd_kernel, dim3((unsigned)y.gt), dim3(kDThreads), 0, s, c);
+        e = hipGetLastError();
     }
     return (int)e;
 }
+extern "C" int vibo_dtrain_prologue(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                                    const float* item_mu, const float* item_logvar, float* eps_item, uint64_t seed, int draw_noise,
+                                    float* eps_ability, uint32_t ability_stream_id, float* item_feat, float* scratch,
+                                    int32_t* step_count, void* stream) {
+    return dt_prologue(kPostUncond, d, decoder, hidden_dim, person_chunk, params, item_mu, item_logvar, eps_item, seed, draw_noise,
+                       eps_ability, ability_stream_id, item_feat, scratch, step_count, stream);
+}
+extern "C" int vibo_dtrain_prologue_cond(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                                         const float* item_mu, const float* item_logvar, float* eps_item, uint64_t seed, int draw_noise,
+                                         float* eps_ability, uint32_t ability_stream_id, float* item_feat, float* scratch,
+                                         int32_t* step_count, void* stream) {
+    return dt_prologue(kPostCond, d, decoder, hidden_dim, person_chunk, params, item_mu, item_logvar, eps_item, seed, draw_noise,
+                       eps_ability, ability_stream_id, item_feat, scratch, step_count, stream);
+}
 
-extern "C" int vibo_dtrain_forward_backward(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
-                                            const float* response, const uint8_t* mask, const int32_t* counts,
-                                            const float* eps_ability, const float* item_feat, float* scratch, void* stream) {
-    const int rc = dt_check(d, decoder, hidden_dim);
+static int dt_forward_backward(const int post, const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                               const float* response, const uint8_t* mask, const int32_t* counts, const uint8_t* codes,
+                               int64_t codes_row_stride, const float* eps_ability, const float* item_feat, float* scratch,
+                               void* stream) {
+    const int rc = dt_check(d, decoder, hidden_dim, post);
     if (rc) return rc;
     if (!params || !response || !counts || !eps_ability || !item_feat || !scratch) return -5;
     if (d->mask_dtype == VIBO_MASK_U8 && !mask) return -5;
+    if (post == kPostCond) {
+        if (!codes) return -5;
+        if (codes_row_stride < d->num_item || codes_row_stride % 4 != 0 || ((uintptr_t)codes & 3)) return -8;
+    }
     const DLayout y = dlayout(d, decoder, hidden_dim, person_chunk);
-    const DParams p = dparams(decoder, hidden_dim, y.A, y.D);
+    const DParams p = dparams(decoder, hidden_dim, y.A, y.D, y.xin);
     const DRec r = drec(p);
     hipStream_t s = (hipStream_t)stream;
     const uint8_t* mk = d->mask_dtype == VIBO_MASK_U8 ? mask : nullptr;
+    DCond cd;
+    memset(&cd, 0, sizeof(cd));
+    if (y.cond) {                                     // the experts' sums of every person of the minibatch, whatever the chunks
+        cd = dcond(y, p, params, item_feat, scratch);
+        const int crc = vibo_code_table_sum_forward(y.B, y.I, kDW, codes, codes_row_stride, scratch + y.feat, scratch + y.sums,
+                                                    code_table_scratch(y, scratch), y.ct_bytes, stream);
+        if (crc) return crc;
+    }
     for (int c = 0; c < y.n_chunk; ++c) {
         const int p0 = c * y.bc;
         const int nb = (p0 + y.bc <= y.B ? y.bc : y.B - p0);
@@ -779,7 +689,12 @@ extern "C" int vibo_dtrain_forward_backward(const vibo_desc* d, int decoder, int
         a.da = scratch + y.da;
         a.rec = scratch + y.prec + (size_t)c * y.gp * r.ptotal; a.rec_stride = r.ptotal;
         a.r_tab = r.tab; a.r_kl = r.kl; a.r_vb = r.vb; a.r_fa = r.fa; a.r_wcp = r.wcp;
-        hipLaunchKernelGGL(dt_person_fwd_kernel, dim3((unsigned)y.gp), dim3(kDThreads), 0, s, a);
+        if (y.cond) {
+            cd.sums = scratch + y.sums + sp * kDW; cd.dsum = scratch + y.dsum + sp * kDW;
+            hipLaunchKernelGGL(dt_person_fwd_cond_kernel, dim3((unsigned)y.gp), dim3(kDThreads), 0, s, a, cd);
+        } else {
+            hipLaunchKernelGGL(dt_person_fwd_kernel, dim3((unsigned)y.gp), dim3(kDThreads), 0, s, a);
+        }
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
         vibo_decoder_desc dd;
@@ -795,7 +710,8 @@ extern "C" int vibo_dtrain_forward_backward(const vibo_desc* d, int decoder, int
             scratch + y.dV, y.has_l ? scratch + y.dL + sp * y.I : nullptr, y.has_g ? scratch + y.dguess + (size_t)c * y.dc * y.I : nullptr,
             scratch + y.dW2 + cw * kDW * kDW, scratch + y.dvec + cw * 4 * kDW, nullptr, stream);
         if (drc) return drc;
-        hipLaunchKernelGGL(dt_person_bwd_kernel, dim3((unsigned)y.gp), dim3(kDThreads), 0, s, a);
+        if (y.cond) hipLaunchKernelGGL(dt_person_bwd_cond_kernel, dim3((unsigned)y.gp), dim3(kDThreads), 0, s, a, cd);
+        else hipLaunchKernelGGL(dt_person_bwd_kernel, dim3((unsigned)y.gp), dim3(kDThreads), 0, s, a);
         e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
         if (y.has_l) {
@@ -806,22 +722,47 @@ extern "C" int vibo_dtrain_forward_backward(const vibo_desc* d, int decoder, int
             if (e != hipSuccess) return (int)e;
         }
     }
+    if (y.cond)                                       // d [lambda | s] of every person is complete: its transpose onto the table rows
+        return vibo_code_table_sum_backward(y.B, y.I, kDW, codes, codes_row_stride, scratch + y.dsum, scratch + y.dfeat,
+                                            code_table_scratch(y, scratch), y.ct_bytes, stream);
     return 0;
 }
+extern "C" int vibo_dtrain_forward_backward(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                                            const float* response, const uint8_t* mask, const int32_t* counts,
+                                            const float* eps_ability, const float* item_feat, float* scratch, void* stream) {
+    return dt_forward_backward(kPostUncond, d, decoder, hidden_dim, person_chunk, params, response, mask, counts, nullptr, 0, eps_ability,
+                               item_feat, scratch, stream);
+}
+extern "C" int vibo_dtrain_forward_backward_cond(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
+                                                 const float* response, const uint8_t* mask, const int32_t* counts,
+                                                 const uint8_t* codes, int64_t codes_row_stride, const float* eps_ability,
+                                                 const float* item_feat, float* scratch, void* stream) {
+    return dt_forward_backward(kPostCond, d, decoder, hidden_dim, person_chunk, params, response, mask, counts, codes, codes_row_stride,
+                               eps_ability, item_feat, scratch, stream);
+}
 
-extern "C" int vibo_dtrain_epilogue(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, float* scratch,
-                                    const float* eps_item, const float* item_feat, const float* beta, const float* lr,
-                                    int32_t* step_count, float* params, float* adam_m, float* adam_v, float* item_mu,
-                                    float* item_logvar, float* item_m, float* item_v, float* loss_out, void* stream) {
-    const int rc = dt_check(d, decoder, hidden_dim);
+static int dt_epilogue(const int post, const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, float* scratch,
+                       const float* eps_item, const float* item_feat, const float* beta, const float* lr, int32_t* step_count,
+                       float* params, float* adam_m, float* adam_v, float* item_mu, float* item_logvar, float* item_m,
+                       float* item_v, float* loss_out, void* stream) {
+    const int rc = dt_check(d, decoder, hidden_dim, post);
     if (rc) return rc;
     if (!scratch || !eps_item || !item_feat || !beta || !lr || !step_count || !params || !adam_m || !adam_v || !item_mu || !item_logvar ||
         !item_m || !item_v || !loss_out)
         return -5;
     const DLayout y = dlayout(d, decoder, hidden_dim, person_chunk);
-    const DParams p = dparams(decoder, hidden_dim, y.A, y.D);
+    const DParams p = dparams(decoder, hidden_dim, y.A, y.D, y.xin);
     const DRec r = drec(p);
     hipStream_t s = (hipStream_t)stream;
+    DCond cd;
+    memset(&cd, 0, sizeof(cd));
+    if (y.cond) {                                     // the table backward: its records join the sums below
+        cd = dcond(y, p, params, item_feat, scratch);
+        cd.beta = beta;
+        hipLaunchKernelGGL(dt_table_bwd_kernel, dim3((unsigned)y.gt), dim3(kDThreads), 0, s, cd);
+        const hipError_t te = hipGetLastError();
+        if (te != hipSuccess) return (int)te;
+    }
     DReduce q;
     memset(&q, 0, sizeof(q));
     int blk = 0;
@@ -839,6 +780,7 @@ extern "C" int vibo_dtrain_epilogue(const vibo_desc* d, int decoder, int hidden_
     if (y.mlp) seg(y.dU, y.s_dU, y.n_chunk * y.dc, (size_t)y.I * kDW, y.I * kDW);
     if (y.has_g) seg(y.dguess, y.s_dguess, y.n_chunk * y.dc, y.I, y.I);
     if (y.has_l) seg(y.drec_item, y.s_ditem, y.n_chunk * y.ns, (size_t)y.I * y.D, y.I * y.D);
+    if (y.cond) seg(y.trec, y.s_enc, y.gt, p.enc, p.enc);
     hipLaunchKernelGGL(dt_reduce_kernel, dim3((unsigned)blk), dim3(1024), 0, s, q);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return (int)e;
@@ -856,7 +798,7 @@ extern "C" int vibo_dtrain_epilogue(const vibo_desc* d, int decoder, int hidden_
     DEpilogue a;
     memset(&a, 0, sizeof(a));
     a.p = p; a.r = r; a.I = y.I; a.n_item_entries = y.I * y.D;
-    a.n_dec_blocks = (p.total - p.dec + kEpiThreads - 1) / kEpiThreads;
+    a.n_dec_blocks = (p.total - (y.cond ? 0 : p.dec) + kEpiThreads - 1) / kEpiThreads;
     a.n_irec = y.mlp ? y.gi : 0; a.has_l = y.has_l ? 1 : 0; a.has_g = y.has_g ? 1 : 0;
     a.flat8 = scratch + y.flat8; a.s_p = scratch + y.s_p; a.s_dW2 = scratch + y.s_dW2; a.s_dvec = scratch + y.s_dvec;
     a.s_ditem = scratch + y.s_ditem; a.s_dguess = scratch + y.s_dguess; a.guess = scratch + y.guess;
@@ -865,6 +807,21 @@ extern "C" int vibo_dtrain_epilogue(const vibo_desc* d, int decoder, int hidden_
     a.step_count = step_count; a.P = params; a.M = adam_m; a.V = adam_v; a.mu = item_mu; a.lv = item_logvar; a.im = item_m; a.iv = item_v;
     a.loss = loss_out;
     const int item_blocks = (a.n_item_entries + kEpiThreads - 1) / kEpiThreads;
-    hipLaunchKernelGGL(dt_epilogue_kernel, dim3((unsigned)(1 + a.n_dec_blocks + item_blocks)), dim3(kEpiThreads), 0, s, a);
+    if (y.cond) hipLaunchKernelGGL(dt_epilogue_cond_kernel, dim3((unsigned)(1 + a.n_dec_blocks + item_blocks)), dim3(kEpiThreads), 0, s, a, cd);
+    else hipLaunchKernelGGL(dt_epilogue_kernel, dim3((unsigned)(1 + a.n_dec_blocks + item_blocks)), dim3(kEpiThreads), 0, s, a);
     return (int)hipGetLastError();
+}
+extern "C" int vibo_dtrain_epilogue(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, float* scratch,
+                                    const float* eps_item, const float* item_feat, const float* beta, const float* lr,
+                                    int32_t* step_count, float* params, float* adam_m, float* adam_v, float* item_mu,
+                                    float* item_logvar, float* item_m, float* item_v, float* loss_out, void* stream) {
+    return dt_epilogue(kPostUncond, d, decoder, hidden_dim, person_chunk, scratch, eps_item, item_feat, beta, lr, step_count, params, adam_m,
+                       adam_v, item_mu, item_logvar, item_m, item_v, loss_out, stream);
+}
+extern "C" int vibo_dtrain_epilogue_cond(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, float* scratch,
+                                         const float* eps_item, const float* item_feat, const float* beta, const float* lr,
+                                         int32_t* step_count, float* params, float* adam_m, float* adam_v, float* item_mu,
+                                         float* item_logvar, float* item_m, float* item_v, float* loss_out, void* stream) {
+    return dt_epilogue(kPostCond, d, decoder, hidden_dim, person_chunk, scratch, eps_item, item_feat, beta, lr, step_count, params, adam_m,
+                       adam_v, item_mu, item_logvar, item_m, item_v, loss_out, stream);
 }

@@ -77,7 +77,8 @@ EXPORTED_SYMBOLS = ('vibo_version', 'vibo_last_error_string', 'vibo_workspace_by
                     'vibo_set_insitu_timer', 'vibo_insitu_timer_reset', 'vibo_selftest_lane_swaps', 'vibo_elbo_fwd_bwd_counts',
                     'vibo_train_step_draws_noise', 'vibo_elbo_fwd_bwd_step_noise',
                     'vibo_dtrain_param_floats', 'vibo_dtrain_scratch_floats', 'vibo_dtrain_scratch_offset', 'vibo_dtrain_prologue',
-                    'vibo_dtrain_forward_backward', 'vibo_dtrain_epilogue')
+                    'vibo_dtrain_forward_backward', 'vibo_dtrain_epilogue',
+                    'vibo_dtrain_prologue_cond', 'vibo_dtrain_forward_backward_cond', 'vibo_dtrain_epilogue_cond')
 
 _lib = None
 
@@ -209,6 +210,12 @@ def load():
     lib.vibo_dtrain_forward_backward.argtypes = [dp, ci, ci, ci, fp, fp, vp, vp, fp, fp, fp, vp]
     lib.vibo_dtrain_epilogue.restype = ctypes.c_int
     lib.vibo_dtrain_epilogue.argtypes = [dp, ci, ci, ci] + [fp] * 5 + [vp] + [fp] * 8 + [vp]
+    lib.vibo_dtrain_prologue_cond.restype = ctypes.c_int
+    lib.vibo_dtrain_prologue_cond.argtypes = lib.vibo_dtrain_prologue.argtypes
+    lib.vibo_dtrain_forward_backward_cond.restype = ctypes.c_int
+    lib.vibo_dtrain_forward_backward_cond.argtypes = [dp, ci, ci, ci, fp, fp, vp, vp, vp, ctypes.c_int64, fp, fp, fp, vp]
+    lib.vibo_dtrain_epilogue_cond.restype = ctypes.c_int
+    lib.vibo_dtrain_epilogue_cond.argtypes = lib.vibo_dtrain_epilogue.argtypes
     lib.vibo_selftest_lane_swaps.restype = ctypes.c_int
     lib.vibo_selftest_lane_swaps.argtypes = [fp, fp, vp]
     lib.vibo_set_insitu_timer.restype = ctypes.c_int

@@ -88,6 +88,10 @@ def build_parser():
                         'autograd, no torch.optim; replayed from a hipGraph unless --no-graph): needs --cuda, the product encoder with '
                         'the unconditional posterior, no flows, one GPU; without the flag these models train through the module + '
                         'torch.optim.Adam as before')
+    p.add_argument('--native-conditional-step', action='store_true', default=False,
+                   help='with --native-decoder-step: run --conditional-posterior models natively too (the encoder MLP over the '
+                        '2 x I table rows, the experts\' sums on the matrix pipe from the cell codes and the backward of both inside '
+                        'the native step); without it --native-decoder-step refuses --conditional-posterior as before')
     p.add_argument('--no-graph', action='store_true', default=False,
                    help='launch every fused train step eagerly instead of replaying a hipGraph (single-GPU runs)')
     p.add_argument('--store-predictive-samples', action='store_true', default=False,
@@ -148,8 +152,8 @@ def native_decoder_step_problem(args):
         return '--generative-model irt (the IRT decoder has its fused trainers already)'
     if args.ability_merge != 'product':
         return f'--ability-merge {args.ability_merge}'
-    if args.conditional_posterior:
-        return '--conditional-posterior'
+    if args.conditional_posterior and not getattr(args, 'native_conditional_step', False):
+        return '--conditional-posterior without --native-conditional-step'
     if args.n_norm_flows > 0:
         return '--n-norm-flows'
     return None
@@ -517,10 +521,11 @@ def main(argv=None):
     if args.native_decoder_step:
         # opt-in: the MLP decoders' whole step natively (FusedDecoderTrainer), replayed from a hipGraph below like the other trainers
         from ..trainer import FusedTrainer, fused_decoder_trainer_covers
-        if world > 1 or not fused_decoder_trainer_covers(model, args.hidden_dim):
+        native_cond = bool(getattr(args, 'native_conditional_step', False))
+        if world > 1 or not fused_decoder_trainer_covers(model, args.hidden_dim, conditional=native_cond):
             raise SystemExit('--native-decoder-step: ' + ('person sharding' if world > 1 else 'this model') + ' is not covered by '
                              'FusedDecoderTrainer (it trains through the module + torch.optim.Adam: drop the flag)')
-        trainer = FusedTrainer(model, lr=args.lr, rng=args.rng, seed=args.seed, max_batch=local_bs)
+        trainer = FusedTrainer(model, lr=args.lr, rng=args.rng, seed=args.seed, max_batch=local_bs, conditional=native_cond)
     graphed = None
     # The captured module step is opt-in (--graph-module-step): it is 3-4 x faster at small minibatches and follows the eager
     # step exactly in every configuration tests/test_gpu_trainer.py replays 60-150 times, but on this PyTorch / ROCm stack a

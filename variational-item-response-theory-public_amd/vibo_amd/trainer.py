@@ -33,9 +33,11 @@ FusedTrainer covers the unconditional posterior without flows; `FusedTrainer(mod
 FusedCondFlowTrainer (same interface, vibo_ctrain_* kernels) for --conditional-posterior / --n-norm-flows models.
 FusedMeanTrainer (vibo_mtrain_* kernels) is the same for --ability-merge mean with the unconditional posterior (person-sharded too).
 FusedDecoderTrainer (vibo_dtrain_* kernels around vibo_decoder_fwd_bwd) is the same for --generative-model link | deep | residual
-with the product encoder's unconditional posterior (`FusedTrainer(model)` returns it; fused_decoder_trainer_covers() tells which).
-Mean x conditional, and the MLP decoders with the conditional posterior / flows / mean merge, train through the module +
-torch.optim path (fused_trainer_covers() tells which of the IRT-decoder models are covered).
+with the product encoder's unconditional posterior (`FusedTrainer(model)` returns it; fused_decoder_trainer_covers() tells which)
+and, asked for with `conditional=True`, its conditional posterior (vibo_dtrain_*_cond; `FusedTrainer(model, conditional=True)`,
+fused_decoder_trainer_covers(model, conditional=True)).
+Mean x conditional, and the MLP decoders with flows / mean merge, train through the module + torch.optim path
+(fused_trainer_covers() tells which of the IRT-decoder models are covered).
 """
 import ctypes
 
@@ -63,14 +65,15 @@ def fused_trainer_covers(model, hidden_dim=None):
     return True
 
 
-def fused_decoder_trainer_covers(model, hidden_dim=None):
+def fused_decoder_trainer_covers(model, hidden_dim=None, conditional=False):
     """True when FusedDecoderTrainer runs the model's whole train step natively: --generative-model link | deep | residual on the
     product-of-experts encoder with the unconditional posterior, no flows, not person-sharded, hidden width <= 64, at most 65 535
-    items (the packed row counts).  Everything else with an MLP decoder trains through the module + torch.optim.Adam."""
+    items (the packed row counts).  conditional=True: the answer for FusedDecoderTrainer(model, conditional=True), which runs the
+    conditional posterior natively as well.  Everything else with an MLP decoder trains through the module + torch.optim.Adam."""
     if getattr(model, 'generative_model', 'irt') not in _lib.DECODER_KINDS:
         return False
     H = hidden_dim if hidden_dim is not None else model.ability_encoder.mlp[0].weight.shape[0] if model.ability_merge == 'product' else 0
-    return (model.ability_merge == 'product' and not model.conditional_posterior and model.n_norm_flows == 0
+    return (model.ability_merge == 'product' and (conditional or not model.conditional_posterior) and model.n_norm_flows == 0
             and model._reducer is None and H <= 64 and model.num_item <= 65535 and model.ability_dim <= _lib.MAX_ABILITY_DIM)
 
 
@@ -553,17 +556,21 @@ class FusedDecoderTrainer(FusedTrainer):
     autograd node and no torch.optim: the step replays from a hipGraph like FusedTrainer's, bitwise reproducible.  Same interface
     (`FusedTrainer(model, ...)` returns this class for such models).  The decoder kernel walks dense fp32 rows: a `row_index`
     minibatch is gathered into a persistent buffer (torch.index_select(out=)), cell codes are unpacked per step.
-    Covers the product encoder's unconditional posterior without flows, analytic KL, hidden width <= 64, one GPU."""
+    Covers the product encoder's unconditional posterior without flows, analytic KL, hidden width <= 64, one GPU.
+    conditional=True: the conditional posterior q(ability | responses, items) too (vibo_dtrain_*_cond: the encoder MLP over the
+    2 x I rows [c, item_i], the experts' sums as vibo_code_table_sum_forward / _backward on the minibatch's 1-byte cell codes --
+    the CellCodes rows themselves, gathered for a `row_index` minibatch, or packed from the dense rows by vibo_pack_codes into a
+    persistent buffer -- and the backward of both, in the same three calls).  The default keeps refusing such a model."""
 
-    def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None):
+    def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None, conditional=False):
         kind = getattr(model, 'generative_model', 'irt')
         why = None
         if kind not in _lib.DECODER_KINDS:
             why = 'an IRT-decoder model (FusedTrainer covers those)'
         elif model.ability_merge != 'product':
             why = '--ability-merge mean'
-        elif model.conditional_posterior:
-            why = 'the conditional posterior'
+        elif model.conditional_posterior and not conditional:
+            why = 'the conditional posterior (unless built with conditional=True)'
         elif model.n_norm_flows > 0:
             why = 'normalizing flows'
         elif model._reducer is not None:
@@ -574,6 +581,8 @@ class FusedDecoderTrainer(FusedTrainer):
             raise NotImplementedError(f'FusedDecoderTrainer does not cover {why}; use model.elbo_step + torch.optim.Adam')
         self.model = model
         self.kind = _lib.DECODER_KINDS[kind]
+        self.cond = bool(model.conditional_posterior)
+        self._sfx = '_cond' if self.cond else ''      # the three calls of a step: vibo_dtrain_* / vibo_dtrain_*_cond
         self.generation = 0                   # (no buffer of this step ever moves: see FusedTrainer.generation)
         self._primed_for, self._folded_open = None, False      # (FusedTrainer.invalidate's fields: every step starts from the parameters)
         mlp, dec = model.ability_encoder.mlp, model.decoder
@@ -594,6 +603,7 @@ class FusedDecoderTrainer(FusedTrainer):
         self.fused_noise = True
         self._scratch = {}                    # (persons, chunk) -> scratch buffer: never freed or replaced (captured graphs point at it)
         self._rows = {}                       # (persons, mask given) -> the gathered minibatch's dense rows: never replaced
+        self._codes = {}                      # (persons, source) -> the minibatch's cell codes (conditional posterior): never replaced
 
     def _dense_rows(self, response, mask, row_index):
         """The minibatch as the decoder kernel reads it: fp32 rows + u8 mask (or None), no autograd node."""
@@ -620,6 +630,28 @@ class FusedDecoderTrainer(FusedTrainer):
             torch.index_select(mask, 0, row_index, out=bufs[1])
         return bufs
 
+    def _cell_codes(self, response, row_index, r, m, d, stream):
+        """The minibatch's 1-byte cell codes (conditional posterior) -> (tensor, row stride): CellCodes rows as they are, gathered
+        for a `row_index` minibatch (torch.index_select(out=)), or packed from the dense rows by vibo_pack_codes -- into a buffer
+        that is kept per kind of call and never replaced (a captured graph points at it), padding cells 'missing'."""
+        B, I = r.shape
+        if isinstance(response, ops.CellCodes):
+            c = response.codes
+            if row_index is None:
+                return c, c.stride(0)
+            stride = c.stride(0)
+            buf = self._codes.get((B, 'gathered'))
+            if buf is None:
+                buf = self._codes[(B, 'gathered')] = torch.full((B, stride), 2, dtype=torch.uint8, device=c.device)
+            torch.index_select(c.as_strided((c.shape[0], stride), (stride, 1)), 0, row_index, out=buf)
+            return buf, stride
+        stride = (I + 15) // 16 * 16
+        buf = self._codes.get((B, 'packed'))
+        if buf is None:
+            buf = self._codes[(B, 'packed')] = torch.full((B, stride), 2, dtype=torch.uint8, device=r.device)
+        ops._call('vibo_pack_codes', ctypes.byref(d), ops._ptr(r), ops._ptr(m), ops._ptr(buf), ctypes.c_int64(stride), stream)
+        return buf, stride
+
     @torch.no_grad()
     def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
         from . import decoder
@@ -637,6 +669,7 @@ class FusedDecoderTrainer(FusedTrainer):
         A, H = model.ability_dim, self.hidden
         stream = ops._stream(dev)
         d = ops._rows_desc(model.spec, B, r, m, _lib.MASK_NONE if m is None else _lib.MASK_U8, _lib.REG_KL, True)
+        codes = self._cell_codes(response, row_index, r, m, d, stream) if self.cond else None
         chunk = min(int(decoder.PERSON_CHUNK), B)
         scratch = self._scratch.get((B, chunk))
         if scratch is None:
@@ -646,13 +679,17 @@ class FusedDecoderTrainer(FusedTrainer):
             scratch = self._scratch[(B, chunk)] = torch.empty(n, device=dev)
             scratch[:_lib.NUM_SCALARS].zero_()
         eps_item, eps_ab, native = self._choose_noise(B, dev, eps_item, eps_ability)
-        ops._call('vibo_dtrain_prologue', ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(self.item_mu), p(self.item_lv),
+        ops._call('vibo_dtrain_prologue' + self._sfx, ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(self.item_mu), p(self.item_lv),
                   p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, 1, p(self.item_feat),
                   p(scratch), p(self._steps), stream)
         if eps_ab is None:
             eps_ab = model._randn((B, A), self.item_mu, model._ability_gen)
-        ops._call('vibo_dtrain_forward_backward', ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts), p(eps_ab),
-                  p(self.item_feat), p(scratch), stream)
+        if self.cond:
+            ops._call('vibo_dtrain_forward_backward_cond', ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts),
+                      p(codes[0]), ctypes.c_int64(codes[1]), p(eps_ab), p(self.item_feat), p(scratch), stream)
+        else:
+            ops._call('vibo_dtrain_forward_backward', ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts), p(eps_ab),
+                      p(self.item_feat), p(scratch), stream)
         off = [int(lib.vibo_dtrain_scratch_offset(ctypes.byref(d), self.kind, H, chunk, w))
                for w in (_lib.DTRAIN_SCALARS, _lib.DTRAIN_POSTERIOR, _lib.DTRAIN_ABILITY)]
         post = scratch[off[1]:off[1] + B * 2 * A].view(B, 2 * A)
@@ -673,7 +710,7 @@ class FusedDecoderTrainer(FusedTrainer):
         d, eps_item, scratch, chunk = self._pending
         self._pending = None
         p = ops._ptr
-        ops._call('vibo_dtrain_epilogue', ctypes.byref(d), self.kind, self.hidden, chunk, p(scratch), p(eps_item), p(self.item_feat),
+        ops._call('vibo_dtrain_epilogue' + self._sfx, ctypes.byref(d), self.kind, self.hidden, chunk, p(scratch), p(eps_item), p(self.item_feat),
                   p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
                   p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.loss), ops._stream(scratch.device))
         return self.loss
