@@ -2,20 +2,20 @@
 conditional descriptor against the models' state_dict, argument validation (negative codes before any launch), the scratch size,
 the coverage predicates, the CLI flag and the new kernels' code-object notes."""
 import ctypes
-import glob
+import functools
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
 
+import decoder_trainer_common as common
+from decoder_trainer_common import CLS, _args, built_objects, kernel_notes
 from vibo_amd import _lib, ops
 from vibo_amd.torch_core import vibo as cli
-from vibo_amd.torch_core.models import VIBO_1PL, VIBO_2PL, VIBO_3PL
 from vibo_amd.trainer import fused_decoder_trainer_covers
 
-CLS = {1: VIBO_1PL, 2: VIBO_2PL, 3: VIBO_3PL}
+desc = functools.partial(common.desc, conditional=True)          # (this file's descriptors and models: the conditional posterior's)
+_model = functools.partial(common._model, cond=True)
 NEW_SYMBOLS = ('vibo_dtrain_prologue_cond', 'vibo_dtrain_forward_backward_cond', 'vibo_dtrain_epilogue_cond')
 COND_KERNELS = ('dt_prologue_cond_kernel', 'dt_table_fwd_kernel', 'dt_person_fwd_cond_kernel', 'dt_person_bwd_cond_kernel',
                 'dt_table_bwd_kernel', 'dt_epilogue_cond_kernel')
@@ -28,11 +28,6 @@ def test_new_symbols_are_exported():
         assert name in _lib.EXPORTED_SYMBOLS
         getattr(lib, name)
         assert re.search(r'\b' + name + r'\(', header), name
-
-
-def desc(irt, A, I=20, B=16, conditional=True, n_flows=0, mask=_lib.MASK_U8):
-    spec = ops.ElboSpec(irt_model=irt, ability_dim=A, conditional=conditional, n_flows=n_flows)
-    return ops._make_desc(spec, B, I, mask, _lib.REG_SAMPLED if n_flows else _lib.REG_KL, True, I, I)
 
 
 @pytest.mark.parametrize('kind', ['link', 'deep', 'residual'])
@@ -100,10 +95,6 @@ def test_scratch_grows_for_the_conditional_descriptor_and_keeps_the_unconditiona
         assert oc == ou >= 0
 
 
-def _model(gen='deep', merge='product', cond=True, flows=0, H=64, irt=2, A=2):
-    return CLS[irt](A, 12, hidden_dim=H, ability_merge=merge, conditional_posterior=cond, generative_model=gen, n_norm_flows=flows)
-
-
 def test_coverage_of_the_conditional_posterior_is_asked_for():
     for gen in ('link', 'deep', 'residual'):
         for irt in (1, 2, 3):
@@ -125,10 +116,6 @@ BASE = ['--irt-model', '2pl', '--dataset', '2pl_simulation', '--cuda', '--genera
         '--conditional-posterior']
 
 
-def _args(argv):
-    return cli.finalize_args(cli.build_parser().parse_args(argv))
-
-
 def test_cli_flag_for_the_native_conditional_step():
     assert _args(BASE).native_conditional_step is False
     with pytest.raises(SystemExit) as e:
@@ -148,22 +135,7 @@ def test_new_kernels_carry_no_scratch():
     """The conditional kernels of csrc/vibo_dtrainer.hip are built without spilled vector registers or private memory: read from
     the code-object notes of the in-tree object, the way test_new_unit_carries_no_scratch does; skipped when the build directory
     or the LLVM tools are not there."""
-    root = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-    objs = glob.glob(os.path.join(root, 'variational-item-response-theory-public_amd', 'csrc', 'build', 'vibo_dtrainer.o'))
-    llvm = '/opt/rocm/lib/llvm/bin'
-    if not objs or not os.path.exists(os.path.join(llvm, 'llvm-readelf')):
-        pytest.skip('no in-tree object / LLVM tools')
-    seen = set()
-    with tempfile.TemporaryDirectory() as tmp:
-        fat, co = os.path.join(tmp, 'fat.bin'), os.path.join(tmp, 'dev.co')
-        subprocess.run([os.path.join(llvm, 'llvm-objcopy'), '--dump-section', '.hip_fatbin=' + fat, objs[0]], check=True)
-        subprocess.run([os.path.join(llvm, 'clang-offload-bundler'), '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950',
-                        '--input=' + fat, '--output=' + co, '--unbundle'], check=True)
-        notes = subprocess.run([os.path.join(llvm, 'llvm-readelf'), '--notes', co], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split('  - .agpr_count:')[1:]:
-            name = re.search(r'\.name:\s+(\S+)', blk).group(1)
-            spill = int(re.search(r'\.vgpr_spill_count:\s+(\d+)', blk).group(1))
-            scratch = int(re.search(r'\.private_segment_fixed_size:\s+(\d+)', blk).group(1))
-            assert spill == 0 and scratch == 0, (name, spill, scratch)
-            seen.update(k for k in COND_KERNELS if k in name)
-    assert seen == set(COND_KERNELS)
+    notes = kernel_notes(built_objects('vibo_dtrainer.o')[0])
+    for name, (spill, scratch) in notes.items():
+        assert spill == 0 and scratch == 0, (name, spill, scratch)
+    assert {k for k in COND_KERNELS for name in notes if k in name} == set(COND_KERNELS)

@@ -1,21 +1,16 @@
 """FusedDecoderTrainer / vibo_dtrain_* without a GPU: the exported symbols, the flat parameter layout against the models'
 state_dict, argument validation (negative codes before any launch), the coverage predicates and the CLI flag."""
 import ctypes
-import glob
 import os
 import re
-import subprocess
-import tempfile
 
 import pytest
-import torch
 
+from decoder_trainer_common import CLS, _args, _model, built_objects, desc, kernel_notes
 from vibo_amd import _lib, ops
 from vibo_amd.torch_core import vibo as cli
-from vibo_amd.torch_core.models import VIBO_1PL, VIBO_2PL, VIBO_3PL
 from vibo_amd.trainer import fused_decoder_trainer_covers, fused_trainer_covers
 
-CLS = {1: VIBO_1PL, 2: VIBO_2PL, 3: VIBO_3PL}
 NEW_SYMBOLS = ('vibo_dtrain_param_floats', 'vibo_dtrain_scratch_floats', 'vibo_dtrain_scratch_offset', 'vibo_dtrain_prologue',
                'vibo_dtrain_forward_backward', 'vibo_dtrain_epilogue')
 
@@ -28,11 +23,6 @@ def test_new_symbols_are_exported():
     header = open(os.path.join(os.path.dirname(__file__), '..', 'include', 'vibo_hip.h')).read()
     for name in NEW_SYMBOLS:
         assert re.search(r'\b' + name + r'\(', header), name
-
-
-def desc(irt, A, I=20, B=16, conditional=False, n_flows=0, mask=_lib.MASK_U8):
-    spec = ops.ElboSpec(irt_model=irt, ability_dim=A, conditional=conditional, n_flows=n_flows)
-    return ops._make_desc(spec, B, I, mask, _lib.REG_SAMPLED if n_flows else _lib.REG_KL, True, I, I)
 
 
 @pytest.mark.parametrize('kind', ['link', 'deep', 'residual'])
@@ -80,10 +70,6 @@ def test_bad_descriptors_are_refused_before_any_launch():
     assert lib.vibo_dtrain_scratch_offset(ctypes.byref(desc(2, 2)), 2, 64, 0, 99) == -1
 
 
-def _model(gen='deep', merge='product', cond=False, flows=0, H=64, irt=2, A=2):
-    return CLS[irt](A, 12, hidden_dim=H, ability_merge=merge, conditional_posterior=cond, generative_model=gen, n_norm_flows=flows)
-
-
 def test_fused_decoder_trainer_covers_truth_table():
     for gen in ('link', 'deep', 'residual'):
         for irt in (1, 2, 3):
@@ -111,10 +97,6 @@ def test_fused_trainer_covers_is_unchanged():
 
 
 BASE = ['--irt-model', '2pl', '--dataset', '2pl_simulation', '--cuda', '--generative-model', 'deep']
-
-
-def _args(argv):
-    return cli.finalize_args(cli.build_parser().parse_args(argv))
 
 
 def test_cli_flag_is_parsed_and_off_by_default():
@@ -149,22 +131,7 @@ def test_new_unit_carries_no_scratch():
     """csrc/vibo_dtrainer.hip is built without spilled vector registers or private memory: read from the code-object notes of the
     in-tree object, the way test_matrix_kernel_instantiations_carry_no_scratch does; skipped when the build directory or the LLVM
     tools are not there."""
-    root = os.path.abspath(os.path.join(os.path.dirname(__file__), '..'))
-    objs = glob.glob(os.path.join(root, 'variational-item-response-theory-public_amd', 'csrc', 'build', 'vibo_dtrainer.o'))
-    llvm = '/opt/rocm/lib/llvm/bin'
-    if not objs or not os.path.exists(os.path.join(llvm, 'llvm-readelf')):
-        pytest.skip('no in-tree object / LLVM tools')
-    seen = 0
-    with tempfile.TemporaryDirectory() as tmp:
-        fat, co = os.path.join(tmp, 'fat.bin'), os.path.join(tmp, 'dev.co')
-        subprocess.run([os.path.join(llvm, 'llvm-objcopy'), '--dump-section', '.hip_fatbin=' + fat, objs[0]], check=True)
-        subprocess.run([os.path.join(llvm, 'clang-offload-bundler'), '--type=o', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950',
-                        '--input=' + fat, '--output=' + co, '--unbundle'], check=True)
-        notes = subprocess.run([os.path.join(llvm, 'llvm-readelf'), '--notes', co], check=True, capture_output=True, text=True).stdout
-        for blk in notes.split('  - .agpr_count:')[1:]:
-            name = re.search(r'\.name:\s+(\S+)', blk).group(1)
-            spill = int(re.search(r'\.vgpr_spill_count:\s+(\d+)', blk).group(1))
-            scratch = int(re.search(r'\.private_segment_fixed_size:\s+(\d+)', blk).group(1))
-            assert spill == 0 and scratch == 0, (name, spill, scratch)
-            seen += 1
-    assert seen >= 8
+    notes = kernel_notes(built_objects('vibo_dtrainer.o')[0])
+    for name, (spill, scratch) in notes.items():
+        assert spill == 0 and scratch == 0, (name, spill, scratch)
+    assert len(notes) >= 8

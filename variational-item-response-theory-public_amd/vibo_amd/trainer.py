@@ -582,7 +582,9 @@ class FusedDecoderTrainer(FusedTrainer):
         self.model = model
         self.kind = _lib.DECODER_KINDS[kind]
         self.cond = bool(model.conditional_posterior)
-        self._sfx = '_cond' if self.cond else ''      # the three calls of a step: vibo_dtrain_* / vibo_dtrain_*_cond
+        # the three calls of a step: vibo_dtrain_* / vibo_dtrain_*_cond
+        self._prologue, self._fwd_bwd, self._epilogue = ('vibo_dtrain_' + call + ('_cond' if self.cond else '')
+                                                         for call in ('prologue', 'forward_backward', 'epilogue'))
         self.generation = 0                   # (no buffer of this step ever moves: see FusedTrainer.generation)
         self._primed_for, self._folded_open = None, False      # (FusedTrainer.invalidate's fields: every step starts from the parameters)
         mlp, dec = model.ability_encoder.mlp, model.decoder
@@ -669,7 +671,10 @@ class FusedDecoderTrainer(FusedTrainer):
         A, H = model.ability_dim, self.hidden
         stream = ops._stream(dev)
         d = ops._rows_desc(model.spec, B, r, m, _lib.MASK_NONE if m is None else _lib.MASK_U8, _lib.REG_KL, True)
-        codes = self._cell_codes(response, row_index, r, m, d, stream) if self.cond else None
+        code_args = ()                                      # conditional posterior: the minibatch's cell codes and their row stride
+        if self.cond:
+            codes, stride = self._cell_codes(response, row_index, r, m, d, stream)
+            code_args = (p(codes), ctypes.c_int64(stride))
         chunk = min(int(decoder.PERSON_CHUNK), B)
         scratch = self._scratch.get((B, chunk))
         if scratch is None:
@@ -679,17 +684,13 @@ class FusedDecoderTrainer(FusedTrainer):
             scratch = self._scratch[(B, chunk)] = torch.empty(n, device=dev)
             scratch[:_lib.NUM_SCALARS].zero_()
         eps_item, eps_ab, native = self._choose_noise(B, dev, eps_item, eps_ability)
-        ops._call('vibo_dtrain_prologue' + self._sfx, ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(self.item_mu), p(self.item_lv),
+        ops._call(self._prologue, ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(self.item_mu), p(self.item_lv),
                   p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, 1, p(self.item_feat),
                   p(scratch), p(self._steps), stream)
         if eps_ab is None:
             eps_ab = model._randn((B, A), self.item_mu, model._ability_gen)
-        if self.cond:
-            ops._call('vibo_dtrain_forward_backward_cond', ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts),
-                      p(codes[0]), ctypes.c_int64(codes[1]), p(eps_ab), p(self.item_feat), p(scratch), stream)
-        else:
-            ops._call('vibo_dtrain_forward_backward', ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts), p(eps_ab),
-                      p(self.item_feat), p(scratch), stream)
+        ops._call(self._fwd_bwd, ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts), *code_args, p(eps_ab),
+                  p(self.item_feat), p(scratch), stream)
         off = [int(lib.vibo_dtrain_scratch_offset(ctypes.byref(d), self.kind, H, chunk, w))
                for w in (_lib.DTRAIN_SCALARS, _lib.DTRAIN_POSTERIOR, _lib.DTRAIN_ABILITY)]
         post = scratch[off[1]:off[1] + B * 2 * A].view(B, 2 * A)
@@ -710,7 +711,7 @@ class FusedDecoderTrainer(FusedTrainer):
         d, eps_item, scratch, chunk = self._pending
         self._pending = None
         p = ops._ptr
-        ops._call('vibo_dtrain_epilogue' + self._sfx, ctypes.byref(d), self.kind, self.hidden, chunk, p(scratch), p(eps_item), p(self.item_feat),
+        ops._call(self._epilogue, ctypes.byref(d), self.kind, self.hidden, chunk, p(scratch), p(eps_item), p(self.item_feat),
                   p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
                   p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.loss), ops._stream(scratch.device))
         return self.loss
