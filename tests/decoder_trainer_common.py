@@ -10,29 +10,48 @@ import tempfile
 import pytest
 import torch
 
+from gpu_common import CLS, dev, simulated          # (CLS: the host-side tests import it from here)
 from oracle import vibo_oracle as O
 from vibo_amd import _lib, ops
 from vibo_amd.torch_core import vibo as cli
-from vibo_amd.torch_core.models import VIBO_1PL, VIBO_2PL, VIBO_3PL
 
-CLS = {1: VIBO_1PL, 2: VIBO_2PL, 3: VIBO_3PL}
-TOL_ELBO, TOL_ADAM1, TOL_ADAM3 = 1e-4, 2e-4, 5e-4       # test_golden_adam_trajectory_through_the_fused_trainers' bounds
+TOL_ADAM1, TOL_ADAM3 = 2e-4, 5e-4                       # with gpu_common.TOL_ELBO: test_golden_adam_trajectory_through_the_fused_trainers' bounds
 # Adam normalises the step, so an entry whose gradient is at rounding level moves by a full +-lr either way: entries whose gradient
 # is below EXCLUDE_BELOW of the tensor's max-abs in any step are left out of a comparison, at most EXCLUDE_CAP of any tensor.
 EXCLUDE_BELOW, EXCLUDE_CAP = 1e-4, 0.02
 
 
-def dev():
-    assert torch.cuda.is_available(), 'these tests need the MI355X'
-    return torch.device('cuda:0')
-
-
 # ---------------------------------------------------------------------------
 # problems and the fp64 oracle
 # ---------------------------------------------------------------------------
+# The unconditional posterior.  (decoder, IRT, A, B, I, missing, hidden, drop_missing, seed).  The seeds were picked on the CPU with oracle_trajectory() below
+# (`python tests/test_gpu_decoder_trainer.py` prints the figures): seeds 1, 2, ... were tried per case until the float64
+# gradients left at most 1.5 % of any tensor under the exclusion threshold over the three steps -- inside the 2 % cap with room
+# for the fp32 gradients of the module-step test, which applies the same rule to the same problems.  Largest excluded share of
+# any tensor with the seeds below: 1.0 %, 1.3 %, 1.1 %, 1.5 %, 1.3 %.
+ORACLE_CASES = [('link', 3, 1, 33, 95, 0.3, 64, False, 1),
+                ('deep', 2, 8, 300, 130, 0.1, 64, False, 2),
+                ('residual', 1, 3, 77, 200, 0.2, 64, True, 8),
+                ('deep', 2, 2, 64, 64, 0.0, 32, False, 5),
+                ('residual', 3, 12, 40, 260, 0.1, 48, False, 9)]
+# The conditional posterior.  (decoder, IRT, A, B, I, missing, hidden, drop_missing, seed).  The inputs were picked on the CPU with oracle_trajectory() below
+# (`python tests/test_gpu_decoder_trainer.py` prints the figures) so that the float64 gradients leave at most 1.5 % of any
+# tensor under the exclusion threshold over the three steps -- inside the 2 % cap with room for the fp32 gradients of the
+# module-step test, which applies the same rule to the same problems.  The conditional table's wide last layer and the item
+# log-variances have many near-zero gradients at 8 and more ability dimensions: the unconditional file's shapes at A = 8 / 12
+# (130 / 260 items) left 3.5-50 % out with seeds 1-12, with 300-600 persons and missing fractions 0-0.1 still 3.5-51 %; at 30
+# items (not a multiple of 4; 60 table rows: four tiles, the last one ragged) and 100 persons (seven person tiles, the last one
+# ragged) seeds 1, 2, ... reached the bound at seed 6 (A = 8) and seed 15 (A = 12).  Largest excluded share of any tensor with
+# the inputs below: 0.70 %, 1.40 %, 1.04 %, 1.39 %, 0.87 %.
+COND_ORACLE_CASES = [('link', 3, 1, 33, 95, 0.3, 64, False, 10),
+                     ('residual', 1, 3, 77, 200, 0.2, 64, True, 4),
+                     ('deep', 2, 2, 64, 64, 0.0, 32, False, 2),
+                     ('deep', 2, 8, 100, 30, 0.1, 64, False, 6),
+                     ('residual', 3, 12, 100, 30, 0.1, 48, False, 15)]
+
+
 def make_problem(conditional, gen, irt, A, B, I, missing, H, drop, seed):
-    g = torch.Generator().manual_seed(seed)
-    resp, mask = O.simulate_responses(irt, B, I, A, generator=g, missing_frac=missing)
+    resp, mask, g = simulated(irt, B, I, A, missing, seed)
     D = O.item_feat_dim(irt, A)
     eps_item = torch.randn(3, I, D, generator=g)
     eps_ab = torch.randn(3, B, A, generator=g)
@@ -105,8 +124,7 @@ def print_excluded_shares(conditional, cases):
 # ---------------------------------------------------------------------------
 def resident(conditional, gen, irt, A, P, I, H=64, missing=0.15, seed=7, codes=False, drop=False):
     d = dev()
-    g = torch.Generator().manual_seed(seed)
-    resp, mask = O.simulate_responses(irt, P, I, A, generator=g, missing_frac=missing)
+    resp, mask, g = simulated(irt, P, I, A, missing, seed)
     resp, mask = ops.pad_rows(resp.to(d), mask.bool().to(d))
     if codes:
         resp, mask = ops.pack_cell_codes(resp, mask), None

@@ -33,7 +33,7 @@ def _worker(rank, world, port, case, out_path):
     dist.init_process_group('gloo', rank=rank, world_size=world)
     try:
         from oracle import cpu_backend
-        from test_host_logic import build_model
+        from golden_common import build_model
         from vibo_amd import ops
         cpu_backend.install(ops)
         g = Golden(os.path.join(GOLDEN_DIR, f'case_{case}.npz'))

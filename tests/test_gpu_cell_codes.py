@@ -6,7 +6,7 @@ import copy
 import pytest
 import torch
 
-from oracle import vibo_oracle as O
+from gpu_common import kernel_choice_fixture, random_problem, simulated
 from vibo_amd import _lib, ops
 from vibo_amd.ops import ElboSpec
 from vibo_amd.torch_core.models import VIBO_2PL, VIBO_3PL
@@ -15,47 +15,27 @@ from vibo_amd.trainer import FusedTrainer
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(autouse=True, params=[_lib.FLAG_KERNEL_MATRIX | _lib.FLAG_COND_MATRIX, _lib.FLAG_KERNEL_VALU | _lib.FLAG_COND_VALU,
-                        _lib.FLAG_KERNEL_MATRIX | _lib.FLAG_NO_EMIT_CODES | _lib.FLAG_COND_VALU, _lib.FLAG_KERNEL_VALU,
-                        _lib.FLAG_KERNEL_MATRIX | _lib.FLAG_COND_MATRIX | _lib.FLAG_COND_THREE_PASS],
-                ids=['matrix-kernels', 'valu-kernels', 'matrix-kernel-fp32-passes', 'valu-kernel-planned-posterior', 'matrix-kernels-three-pass'])
-def row_split_kernel_choice(request, monkeypatch):
-    """Every test here runs on both row-split kernels: the library's planner picks the matrix kernel (vibo_msplit_kernel.hpp)
-    above 2 048 persons per call and the VALU kernel (vibo_split_kernel.hpp) below; vibo_desc.flags pins one for the whole test
-    (ops.DESC_FLAGS: the library reads no environment variable).  Third run: the multi-pass paths (conditional posterior, more
-    than 1024 items) re-read the fp32 rows in every pass instead of the 1-byte cell codes their first pass leaves behind
-    (VIBO_FLAG_NO_EMIT_CODES).  The conditional posterior's two passes have a matrix-pipe form (vibo_cmean.hip, the default
-    from a call size that depends on ability_dim when the rows are cell codes, VIBO_FLAG_COND_MATRIX pins it) and a VALU form
-    (vibo_cond.hip, VIBO_FLAG_COND_VALU): the first run pins the matrix-pipe form, the second and third the VALU form, the fourth
-    runs the VALU row-split kernel around whatever the planner picks.  Fifth run (tests of the conditional posterior only): at
-    ability_dim 1 on fp32 rows the first run's matrix kernel gathers the experts itself (its XM == 3); VIBO_FLAG_COND_THREE_PASS keeps
-    the separate first pass it replaced."""
-    if request.param & _lib.FLAG_COND_THREE_PASS:
-        cs = getattr(request.node, 'callspec', None)
-        params = cs.params if cs is not None else {}
-        about_cond = 'cond' in request.node.name.lower() or bool(params.get('cond')) or 'cond' in str(params.get('golden', ''))
-        if not about_cond:
-            pytest.skip('the three-pass pin only differs for the conditional posterior')
-    monkeypatch.setattr(ops, 'DESC_FLAGS', request.param)
+# The pins of test_gpu_parity.py (described there); this file keeps its own list, so that a pin which only concerns one of the two
+# files adds no cases to the other.
+row_split_kernel_choice = kernel_choice_fixture(
+    [_lib.FLAG_KERNEL_MATRIX | _lib.FLAG_COND_MATRIX, _lib.FLAG_KERNEL_VALU | _lib.FLAG_COND_VALU,
+     _lib.FLAG_KERNEL_MATRIX | _lib.FLAG_NO_EMIT_CODES | _lib.FLAG_COND_VALU, _lib.FLAG_KERNEL_VALU,
+     _lib.FLAG_KERNEL_MATRIX | _lib.FLAG_COND_MATRIX | _lib.FLAG_COND_THREE_PASS],
+    ['matrix-kernels', 'valu-kernels', 'matrix-kernel-fp32-passes', 'valu-kernel-planned-posterior', 'matrix-kernels-three-pass'])
 dev = torch.device('cuda:0')
 
 
 def problem(irt, A, B, I, cond, n_flows, missing=0.2, seed=0):
-    g = torch.Generator().manual_seed(seed + 7 * I + A)
-    resp, mask = O.simulate_responses(irt, B, I, A, generator=g, missing_frac=missing)
+    resp, mask, table, item, eps, flow = random_problem(irt, A, B, I, missing, seed + 7 * I + A, cond=cond, scale=0.7, table_scale=0.6,
+                                                        n_flows=n_flows)
     spec = ElboSpec(irt_model=irt, ability_dim=A, n_flows=n_flows, conditional=cond)
-    table = (torch.randn(*spec.table_shape(I), generator=g) * 0.6).to(dev)
-    item = (torch.randn(I, spec.item_dim, generator=g) * 0.7).to(dev)
-    eps = torch.randn(B, A, generator=g).to(dev)
-    flow = (torch.randn(n_flows, 2 * A + 1, generator=g) * 0.5).to(dev) if n_flows else None
-    return spec, resp.to(dev), mask.bool().to(dev), table, item, eps, flow
+    return spec, resp.to(dev), mask.bool().to(dev), table.to(dev), item.to(dev), eps.to(dev), (flow.to(dev) if n_flows else None)
 
 
 @pytest.mark.parametrize('mask_kind', ['bool', 'int64', 'none'])
 @pytest.mark.parametrize('I', [1, 95, 100, 1028])
 def test_pack_codes_matches_the_layout_contract(I, mask_kind):
-    g = torch.Generator().manual_seed(I)
-    resp, mask = O.simulate_responses(2, 37, I, 1, generator=g, missing_frac=0.3)
+    resp, mask, _ = simulated(2, 37, I, 1, 0.3, seed=I)
     resp, mask = resp.to(dev), mask.bool().to(dev)
     if mask_kind == 'none':
         resp = resp.clamp(min=0)            # no mask: every cell is an answer
@@ -170,8 +150,7 @@ def test_codes_outside_the_row_split_paths_are_refused():
 def test_module_and_trainer_on_cell_codes(cls, A, I, kw):
     """Drop-in module (forward -> elbo -> backward, encode, log_marginal) and the fused trainer fed CellCodes rows
     follow the reference-layout run under the same noise."""
-    g = torch.Generator().manual_seed(5)
-    resp, mask = O.simulate_responses(cls.IRT, 300, I, A, generator=g, missing_frac=0.15)
+    resp, mask, g = simulated(cls.IRT, 300, I, A, 0.15, seed=5)
     resp, mask = resp.to(dev), mask.bool().to(dev)
     codes = ops.pack_cell_codes(resp, mask)
     resp, mask = ops.pad_rows(resp, mask)        # 95 items: padded rows keep the fp32 layout on the row-split path too

@@ -2,35 +2,11 @@
 against a plain PyTorch float64 statement of the same network with autograd."""
 import pytest
 import torch
-import torch.nn.functional as F
 
+from gpu_common import rel, torch_reference
 from vibo_amd import decoder as D
 
 pytestmark = pytest.mark.gpu
-EPS32 = 1.1920928955078125e-07
-
-
-def torch_reference(resp, mask, U, V, W2, b2, w3, b3, logit, w1, guess, resid):
-    """[B, I, 64] the slow way (float64)."""
-    z1 = V.unsqueeze(1) + (U.unsqueeze(0) if U is not None else 0.0)
-    if w1 is not None:
-        z1 = z1 + logit.unsqueeze(2) * w1
-    h2 = F.elu(F.elu(z1) @ W2.t() + b2)
-    o = h2 @ w3 + b3
-    if resid:
-        o = o + resid * logit
-    p = torch.sigmoid(o)
-    if guess is not None:
-        p = guess + (1 - guess) * p
-    pc = p.clamp(EPS32, 1 - EPS32)                       # torch.distributions.Bernoulli(probs=...) clamp (utils.py:46-49)
-    ll = torch.where(resp > 0.5, pc.log(), torch.log1p(-pc))
-    if mask is not None:
-        ll = ll * mask
-    return ll.sum(), p
-
-
-def rel(a, b):
-    return float((a - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
 
 @pytest.mark.parametrize('mode,B,I,missing,H', [('deep', 37, 130, 0.2, 64), ('residual', 16, 64, 0.0, 64), ('link', 33, 95, 0.3, 64),

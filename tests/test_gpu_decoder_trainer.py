@@ -10,10 +10,11 @@ import pytest
 import torch
 
 from conftest import GOLDEN_DIR, Golden, rel_err
-from decoder_trainer_common import (CLS, TOL_ADAM1, TOL_ADAM3, TOL_ELBO, assert_same_state, compare_kept, dev, keep_entries, make_problem,
+from decoder_trainer_common import (COND_ORACLE_CASES, ORACLE_CASES, TOL_ADAM1, TOL_ADAM3, assert_same_state, compare_kept, keep_entries, make_problem,
                                     oracle_of, print_excluded_shares, resident, state_of)
+from golden_common import build_model
+from gpu_common import CLS, TOL_ELBO, dev, scattered_rows, simulated
 from oracle import vibo_oracle as O
-from test_host_logic import build_model
 from vibo_amd import decoder, ops
 from vibo_amd.torch_core.models import VIBO_2PL
 from vibo_amd.trainer import FusedDecoderTrainer, FusedTrainer
@@ -35,12 +36,7 @@ def golden_rows(golden, rows, d):
     """The golden's minibatch as `rows` says -> response, mask, row_index: direct, gathered out of a larger resident matrix, or as
     cell codes."""
     if rows == 'gathered':
-        B, I = golden.response.shape
-        g = torch.Generator().manual_seed(B * I)
-        big_r = (torch.rand(3 * B + 5, I, generator=g) < 0.5).float()
-        big_m = torch.rand(3 * B + 5, I, generator=g) < 0.8
-        where = torch.randperm(3 * B + 5, generator=g)[:B]
-        big_r[where], big_m[where] = golden.response, golden.mask.bool()
+        big_r, big_m, where = scattered_rows(golden.response, golden.mask, 3 * golden.response.shape[0] + 5)
         return (*ops.pad_rows(big_r.to(d), big_m.to(d)), where.to(d))
     if rows == 'cell-codes':
         return ops.pack_cell_codes(golden.response.to(d), golden.mask.to(d).bool()), None, None
@@ -116,34 +112,8 @@ def test_the_default_trainer_still_refuses_the_conditional_posterior():
 
 
 # ---------------------------------------------------------------------------
-# 2. random shapes against the fp64 oracle
+# 2. random shapes against the fp64 oracle (decoder_trainer_common.ORACLE_CASES / COND_ORACLE_CASES)
 # ---------------------------------------------------------------------------
-# The unconditional posterior.  (decoder, IRT, A, B, I, missing, hidden, drop_missing, seed).  The seeds were picked on the CPU with decoder_trainer_common.oracle_trajectory()
-# (`python tests/test_gpu_decoder_trainer.py` prints the figures): seeds 1, 2, ... were tried per case until the float64
-# gradients left at most 1.5 % of any tensor under the exclusion threshold over the three steps -- inside the 2 % cap with room
-# for the fp32 gradients of the module-step test, which applies the same rule to the same problems.  Largest excluded share of
-# any tensor with the seeds below: 1.0 %, 1.3 %, 1.1 %, 1.5 %, 1.3 %.
-ORACLE_CASES = [('link', 3, 1, 33, 95, 0.3, 64, False, 1),
-                ('deep', 2, 8, 300, 130, 0.1, 64, False, 2),
-                ('residual', 1, 3, 77, 200, 0.2, 64, True, 8),
-                ('deep', 2, 2, 64, 64, 0.0, 32, False, 5),
-                ('residual', 3, 12, 40, 260, 0.1, 48, False, 9)]
-# The conditional posterior.  (decoder, IRT, A, B, I, missing, hidden, drop_missing, seed).  The inputs were picked on the CPU with decoder_trainer_common.oracle_trajectory()
-# (`python tests/test_gpu_decoder_trainer.py` prints the figures) so that the float64 gradients leave at most 1.5 % of any
-# tensor under the exclusion threshold over the three steps -- inside the 2 % cap with room for the fp32 gradients of the
-# module-step test, which applies the same rule to the same problems.  The conditional table's wide last layer and the item
-# log-variances have many near-zero gradients at 8 and more ability dimensions: the unconditional file's shapes at A = 8 / 12
-# (130 / 260 items) left 3.5-50 % out with seeds 1-12, with 300-600 persons and missing fractions 0-0.1 still 3.5-51 %; at 30
-# items (not a multiple of 4; 60 table rows: four tiles, the last one ragged) and 100 persons (seven person tiles, the last one
-# ragged) seeds 1, 2, ... reached the bound at seed 6 (A = 8) and seed 15 (A = 12).  Largest excluded share of any tensor with
-# the inputs below: 0.70 %, 1.40 %, 1.04 %, 1.39 %, 0.87 %.
-COND_ORACLE_CASES = [('link', 3, 1, 33, 95, 0.3, 64, False, 10),
-                     ('residual', 1, 3, 77, 200, 0.2, 64, True, 4),
-                     ('deep', 2, 2, 64, 64, 0.0, 32, False, 2),
-                     ('deep', 2, 8, 100, 30, 0.1, 64, False, 6),
-                     ('residual', 3, 12, 100, 30, 0.1, 48, False, 15)]
-
-
 @pytest.mark.parametrize('conditional,gen,irt,A,B,I,missing,H,drop,seed', both(ORACLE_CASES, COND_ORACLE_CASES))
 def test_random_shapes_against_the_fp64_oracle(conditional, gen, irt, A, B, I, missing, H, drop, seed):
     case = (gen, irt, A, B, I, missing, H, drop, seed)
@@ -378,8 +348,7 @@ def test_missing_data_modes_and_the_all_missing_row(codes):
     posterior is the observed experts' alone (against models._conditional_posterior_poe)."""
     gen, irt, A, I, B = 'deep', 2, 3, 45, 21
     d = dev()
-    g = torch.Generator().manual_seed(9)
-    resp, mask = O.simulate_responses(irt, B, I, A, generator=g, missing_frac=0.3)
+    resp, mask, g = simulated(irt, B, I, A, 0.3, seed=9)
     mask = mask.bool()
     mask[5] = False
     eps_i, eps_a = torch.randn(I, A + 1, generator=g).to(d), torch.randn(B, A, generator=g).to(d)

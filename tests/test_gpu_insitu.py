@@ -10,9 +10,8 @@ import ctypes
 import pytest
 import torch
 
-from test_gpu_parity import dev
+from gpu_common import coin_flip_rows, dev
 from vibo_amd import _lib, ops
-from vibo_amd.ops import ElboSpec
 
 pytestmark = pytest.mark.gpu
 
@@ -38,14 +37,9 @@ def test_lane_swap_sums_equal_the_shuffle_form():
         assert torch.equal(o[4].view(torch.int32), o[5].view(torch.int32)), 'chained swap sums differ from the chained shuffles'
 
 
-def _problem(P, I, A, d, seed=3):
-    g = torch.Generator(device=d).manual_seed(seed)
-    r = (torch.rand(P, I, device=d, generator=g) < 0.5).float()
-    mk = (torch.rand(P, I, device=d, generator=g) >= 0.1)
-    spec = ElboSpec(irt_model=2, ability_dim=A)
-    table = torch.randn(2, 2 * A, device=d, generator=g) * 0.5
-    item = torch.randn(I, A + 1, device=d, generator=g)
-    eps = torch.randn(P, A, device=d, generator=g)
+def _problem(P, I, A, seed=3):
+    spec, r, mk, table, item, g = coin_flip_rows(P, I, A, seed)
+    eps = torch.randn(P, A, device=r.device, generator=g)
     r2, m8, code = ops.prepare_rows(r, mk)
     return spec, r2, m8, code, table, item, eps
 
@@ -53,7 +47,7 @@ def _problem(P, I, A, d, seed=3):
 def test_insitu_timer_counts_launches_and_matches_events():
     d = dev()
     P, I, A = 200_000, 1000, 8
-    spec, r, m8, code, table, item, eps = _problem(P, I, A, d)
+    spec, r, m8, code, table, item, eps = _problem(P, I, A)
     assert ops.plan_kernel(spec, P, I, code, True).startswith('matrix')
     call = lambda: ops._hip_launch_elbo(spec, r, m8, code, None, table, item, eps, None, _lib.REG_KL, True, P)
     ref = call()                       # hook off
@@ -109,7 +103,7 @@ def test_insitu_timer_counts_narrow_kernel_launches():
     """The narrow-row kernel (BASELINE configs[0] / [3] widths) carries the same stamps."""
     d = dev()
     P, I, A = 100_000, 96, 1
-    spec, r, m8, code, table, item, eps = _problem(P, I, A, d, seed=5)
+    spec, r, m8, code, table, item, eps = _problem(P, I, A, seed=5)
     assert ops.plan_kernel(spec, P, I, code, True).startswith('narrow')
     call = lambda: ops._hip_launch_elbo(spec, r, m8, code, None, table, item, eps, None, _lib.REG_KL, True, P)
     ref = call()
@@ -130,7 +124,7 @@ def test_insitu_timer_inside_the_folded_train_step_graph():
     from vibo_amd.trainer import FusedTrainer
     d = dev()
     P, I, A = 65_536, 1000, 8
-    spec, r, m8, code, table, item, eps = _problem(P, I, A, d, seed=9)
+    spec, r, m8, code, table, item, eps = _problem(P, I, A, seed=9)
     torch.manual_seed(1)
     model = VIBO_2PL(A, I, ability_merge='product').to(d)
     tr = FusedTrainer(model, lr=5e-3, rng='native', seed=7)

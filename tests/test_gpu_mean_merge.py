@@ -5,6 +5,7 @@ import pytest
 import torch
 
 from conftest import rel_err
+from gpu_common import simulated
 from oracle import vibo_oracle as O
 from oracle import vibo_table_ref as T
 from vibo_amd import _lib, ops
@@ -18,8 +19,7 @@ dev = torch.device('cuda:0')
 @pytest.mark.parametrize('I', [1, 3, 95, 100, 1028, 6000])
 @pytest.mark.parametrize('layout', ['bool', 'int64', 'none', 'padded', 'codes', 'gather'])
 def test_row_counts(I, layout):
-    g = torch.Generator().manual_seed(I)
-    resp, mask = O.simulate_responses(2, 41, I, 1, generator=g, missing_frac=0.3)
+    resp, mask, g = simulated(2, 41, I, 1, 0.3, seed=I)
     resp, mask = resp.to(dev), mask.bool().to(dev)
     rows = None
     if layout == 'none':
@@ -60,9 +60,8 @@ CASES = [
 @pytest.mark.parametrize('irt,A,B,I,n_flows,missing,codes,gather', CASES)
 @pytest.mark.parametrize('want_grad', [True, False])
 def test_given_posterior_kernel_vs_oracle(irt, A, B, I, n_flows, missing, codes, gather, want_grad):
-    g = torch.Generator().manual_seed(B * 7 + I + A)
     P = B + 9 if gather else B
-    resp_all, mask_all = O.simulate_responses(irt, P, I, A, generator=g, missing_frac=missing)
+    resp_all, mask_all, g = simulated(irt, P, I, A, missing, seed=B * 7 + I + A)
     rows = torch.randperm(P, generator=g)[:B] if gather else None
     resp, mask = (resp_all[rows], mask_all[rows]) if gather else (resp_all, mask_all)
     spec = ElboSpec(irt_model=irt, ability_dim=A, n_flows=n_flows, given=True)
@@ -119,9 +118,8 @@ def test_given_posterior_needs_the_row_split_path():
 def test_mean_merge_module_vs_autograd_oracle(cls, A, I, kw):
     """forward -> elbo -> backward, encode and log_marginal of a mean-merge model against autograd through the op-by-op
     oracle (per-term mlp1, masked mean, mlp2) under the same noise; cell codes give the same numbers."""
-    g = torch.Generator().manual_seed(3)
     B = 48
-    resp, mask = O.simulate_responses(cls.IRT, B, I, A, generator=g, missing_frac=0.2)
+    resp, mask, g = simulated(cls.IRT, B, I, A, 0.2, seed=3)
     torch.manual_seed(2)
     model = cls(A, I, ability_merge='mean', **kw).to(dev)
     assert {k for k in model.state_dict() if k.startswith('ability_encoder')} == {
@@ -210,8 +208,7 @@ def test_mean_encoder_kernels_vs_torch(B, H, A):
 
 
 def test_row_counts_are_cached_per_resident_matrix():
-    g = torch.Generator().manual_seed(1)
-    resp, mask = O.simulate_responses(2, 300, 100, 1, generator=g, missing_frac=0.2)
+    resp, mask, _ = simulated(2, 300, 100, 1, 0.2, seed=1)
     resp, mask = resp.to(dev), mask.bool().to(dev)
     calls = []
     native = ops._BACKEND['counts']

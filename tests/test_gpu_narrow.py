@@ -17,9 +17,9 @@ import pytest
 import torch
 
 from conftest import GOLDEN_DIR, rel_err
+from golden_common import build_model, check_against_golden, run_reference_pattern
+from gpu_common import TOL_ELBO, compare_raw, dev, device_problem, launch_elbo, random_problem
 from oracle import vibo_table_ref as T
-from test_gpu_parity import (compare_raw, dev, random_problem, TOL_ELBO, _device_problem)
-from test_host_logic import build_model, check_against_golden, run_reference_pattern
 from vibo_amd import _lib, ops
 from vibo_amd.ops import ElboSpec
 
@@ -33,22 +33,10 @@ def is_narrow(spec, B, I, mcode=_lib.MASK_U8, grad=True):
 
 
 def launch(spec, resp, mask, table, item, eps, *, row_index=None, codes=False, want_grad=True):
-    """resp / mask on the host; rows padded to 16-byte strides (ops.pad_rows) as the CLI's resident splits are."""
-    d = dev()
+    """resp / mask on the host; rows padded to 16-byte strides (ops.pad_rows) as the CLI's resident splits are, or cell codes; the
+    planner's own choice has to be the narrow-row kernel."""
     assert ops.DESC_FLAGS == 0
-    if codes:
-        cells = ops.pack_cell_codes(resp.to(d), mask.to(d).bool() if mask is not None else None).codes
-        r, m, code = cells, cells, _lib.MASK_CODES
-    else:
-        rp, mp = ops.pad_rows(resp.to(d), mask.to(d).bool() if mask is not None else None)
-        r, m, code = ops.prepare_rows(rp, mp)
-    ri = row_index.to(d) if row_index is not None else None
-    B = int(ri.numel()) if ri is not None else resp.shape[0]
-    assert is_narrow(spec, B, resp.shape[1], code, want_grad), 'planner did not pick the narrow-row kernel'
-    raw = ops._hip_launch_elbo(spec, r, m, code, ri, table.to(d).contiguous(), item.to(d).contiguous(), eps.to(d).contiguous(),
-                               None, _lib.REG_KL, want_grad, B)
-    torch.cuda.synchronize()
-    return raw
+    return launch_elbo(spec, resp, mask, table, item, eps, row_index=row_index, pad=not codes, codes=codes, want_grad=want_grad, kernel=NARROW)
 
 
 SHAPES = [
@@ -197,7 +185,7 @@ def test_narrow_kernel_config4_shape_at_full_size():
     d = dev()
     spec = ElboSpec(irt_model=irt, ability_dim=A)
     assert is_narrow(spec, P, I)
-    resp, mask, table, item, eps = _device_problem(irt, A, P, I, 0.2, seed=44, cond=False)
+    resp, mask, table, item, eps = device_problem(irt, A, P, I, 0.2, seed=44, cond=False)
     rp, mp = ops.pad_rows(resp, mask)
 
     def run(rows=None, row_index=None):

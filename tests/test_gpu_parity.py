@@ -7,53 +7,40 @@
 
 Tolerances (fp32): ELBO <= 1e-4 relative (north_star), posterior
 mean / log-variance <= 2e-5, gradients <= 1e-4 of the tensor's max-abs against the fp64 analytic oracle (TOL_GRAD; measured
-maximum over the suite 6.1e-6) -- goldens: see check_against_golden.
+maximum over the suite 6.1e-6) -- goldens: see golden_common.check_against_golden.
 """
-import json
 import os
 
 import pytest
 import torch
 
 from conftest import rel_err
+from golden_common import build_model, check_against_golden, run_reference_pattern
+from gpu_common import (TOL_ELBO, TOL_GRAD, check, compare_raw, dev, device_problem, kernel_choice_fixture, launch_elbo, random_problem,
+                        scattered_rows)
 from oracle import vibo_oracle as O
 from oracle import vibo_table_ref as T
-from test_host_logic import build_model, check_against_golden, run_reference_pattern
 from vibo_amd import _lib, ops
 from vibo_amd.ops import ElboSpec
 
 pytestmark = pytest.mark.gpu
 
-
-@pytest.fixture(autouse=True, params=[_lib.FLAG_KERNEL_MATRIX | _lib.FLAG_COND_MATRIX, _lib.FLAG_KERNEL_VALU | _lib.FLAG_COND_VALU,
-                        _lib.FLAG_KERNEL_MATRIX | _lib.FLAG_NO_EMIT_CODES | _lib.FLAG_COND_VALU, _lib.FLAG_KERNEL_VALU,
-                        _lib.FLAG_KERNEL_MATRIX | _lib.FLAG_COND_MATRIX | _lib.FLAG_COND_THREE_PASS],
-                ids=['matrix-kernels', 'valu-kernels', 'matrix-kernel-fp32-passes', 'valu-kernel-planned-posterior', 'matrix-kernels-three-pass'])
-def row_split_kernel_choice(request, monkeypatch):
-    """Every test here runs on both row-split kernels: the library's planner picks the matrix kernel (vibo_msplit_kernel.hpp)
-    above 2 048 persons per call and the VALU kernel (vibo_split_kernel.hpp) below; vibo_desc.flags pins one for the whole test
-    (ops.DESC_FLAGS: the library reads no environment variable).  Third run: the multi-pass paths (conditional posterior, more
-    than 1024 items) re-read the fp32 rows in every pass instead of the 1-byte cell codes their first pass leaves behind
-    (VIBO_FLAG_NO_EMIT_CODES).  The conditional posterior's two passes have a matrix-pipe form (vibo_cmean.hip, the default
-    from a call size that depends on ability_dim when the rows are cell codes, VIBO_FLAG_COND_MATRIX pins it) and a VALU form
-    (vibo_cond.hip, VIBO_FLAG_COND_VALU): the first run pins the matrix-pipe form, the second and third the VALU form, the fourth
-    runs the VALU row-split kernel around whatever the planner picks.  Fifth run (tests of the conditional posterior only): at
-    ability_dim 1 on fp32 rows the first run's matrix kernel gathers the experts itself (its XM == 3); VIBO_FLAG_COND_THREE_PASS keeps
-    the separate first pass it replaced."""
-    if request.param & _lib.FLAG_COND_THREE_PASS:
-        cs = getattr(request.node, 'callspec', None)
-        params = cs.params if cs is not None else {}
-        about_cond = 'cond' in request.node.name.lower() or bool(params.get('cond')) or 'cond' in str(params.get('golden', ''))
-        if not about_cond:
-            pytest.skip('the three-pass pin only differs for the conditional posterior')
-    monkeypatch.setattr(ops, 'DESC_FLAGS', request.param)
-
-TOL_ELBO = 1e-4
-
-
-def dev():
-    assert torch.cuda.is_available(), 'these tests need the MI355X'
-    return torch.device('cuda:0')
+# Every test here runs on both row-split kernels: the library's planner picks the matrix kernel (vibo_msplit_kernel.hpp) above 2 048
+# persons per call and the VALU kernel (vibo_split_kernel.hpp) below; vibo_desc.flags pins one for the whole test.  Third run: the
+# multi-pass paths (conditional posterior, more than 1024 items) re-read the fp32 rows in every pass instead of the 1-byte cell codes
+# their first pass leaves behind (VIBO_FLAG_NO_EMIT_CODES).  The conditional posterior's two passes have a matrix-pipe form
+# (vibo_cmean.hip, the default from a call size that depends on ability_dim when the rows are cell codes, VIBO_FLAG_COND_MATRIX pins
+# it) and a VALU form (vibo_cond.hip, VIBO_FLAG_COND_VALU): the first run pins the matrix-pipe form, the second and third the VALU
+# form, the fourth runs the VALU row-split kernel around whatever the planner picks.  Fifth run (tests of the conditional posterior
+# only): at ability_dim 1 on fp32 rows the first run's matrix kernel gathers the experts itself (its XM == 3);
+# VIBO_FLAG_COND_THREE_PASS keeps the separate first pass it replaced.
+# (test_gpu_cell_codes.py holds the same five pins today; each file keeps its list, so that a pin which only concerns one of them
+# adds no cases to the other.)
+row_split_kernel_choice = kernel_choice_fixture(
+    [_lib.FLAG_KERNEL_MATRIX | _lib.FLAG_COND_MATRIX, _lib.FLAG_KERNEL_VALU | _lib.FLAG_COND_VALU,
+     _lib.FLAG_KERNEL_MATRIX | _lib.FLAG_NO_EMIT_CODES | _lib.FLAG_COND_VALU, _lib.FLAG_KERNEL_VALU,
+     _lib.FLAG_KERNEL_MATRIX | _lib.FLAG_COND_MATRIX | _lib.FLAG_COND_THREE_PASS],
+    ['matrix-kernels', 'valu-kernels', 'matrix-kernel-fp32-passes', 'valu-kernel-planned-posterior', 'matrix-kernels-three-pass'])
 
 
 # ---------------------------------------------------------------------------
@@ -108,12 +95,7 @@ def test_golden_adam_trajectory_through_the_fused_trainers(golden, rows):
     # row_index vector into a larger resident matrix (the golden's rows scattered among decoys), or as 1-byte cell codes
     row_index = None
     if rows == 'gathered':
-        B, I = golden.response.shape
-        g = torch.Generator().manual_seed(B * I)
-        big_r = (torch.rand(3 * B + 5, I, generator=g) < 0.5).float()
-        big_m = torch.rand(3 * B + 5, I, generator=g) < 0.8
-        where = torch.randperm(3 * B + 5, generator=g)[:B]
-        big_r[where], big_m[where] = golden.response, golden.mask.bool()
+        big_r, big_m, where = scattered_rows(golden.response, golden.mask, 3 * golden.response.shape[0] + 5)
         resp, mask = ops.pad_rows(big_r.to(d), big_m.to(d))
         row_index = where.to(d)
     elif rows == 'cell-codes':
@@ -131,65 +113,6 @@ def test_golden_adam_trajectory_through_the_fused_trainers(golden, rows):
 # ---------------------------------------------------------------------------
 # (2) raw kernel outputs vs the CPU analytic oracle
 # ---------------------------------------------------------------------------
-def random_problem(irt, A, B, I, missing, seed, cond=False, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    resp, mask = O.simulate_responses(irt, B, I, A, generator=g, missing_frac=missing)
-    D = O.item_feat_dim(irt, A)
-    table = torch.randn((2, I, 2 * A) if cond else (2, 2 * A), generator=g) * 0.7
-    item = torch.randn(I, D, generator=g) * scale
-    eps = torch.randn(B, A, generator=g)
-    return resp, mask, table, item, eps
-
-
-def run_kernel(spec, resp, mask, table, item, eps, reg_mode=_lib.REG_KL, mask_dtype=torch.bool,
-               row_index=None, want_grad=True, keep_int64=False):
-    d = dev()
-    r = ops.prepare_response(resp.to(d))
-    m, code = ops.prepare_mask(mask.to(d).to(mask_dtype) if mask is not None else None, keep_int64=keep_int64)
-    ri = row_index.to(d) if row_index is not None else None
-    B = int(ri.numel()) if ri is not None else r.shape[0]
-    raw = ops._hip_launch_elbo(spec, r, m, code, ri, table.to(d).contiguous(), item.to(d).contiguous(),
-                               eps.to(d).contiguous(), None, reg_mode, want_grad, B)
-    torch.cuda.synchronize()
-    return raw
-
-
-# Gradient tolerances (fractions of the tensor's max-abs against the fp64 analytic oracle).  SURVEY.md section 8c asks for <= 1e-4;
-# TOL_GRAD is that bound and the default everywhere.  Named wider bands exist only where the fp64 oracle cannot arbitrate to 1e-4,
-# each with the reason and the maximum measured on the GPU (VIBO_TOL_RECORD=path appends every observed error to a JSON-lines
-# file; gpurun_out/r6_tolerances.jsonl is the record these numbers come from):
-TOL_GRAD = 1e-4
-_OBSERVED = []
-
-
-def _check(kind, err, tol):
-    if os.environ.get('VIBO_TOL_RECORD'):
-        _OBSERVED.append((kind, float(err), float(tol), os.environ.get('PYTEST_CURRENT_TEST', '')))
-        with open(os.environ['VIBO_TOL_RECORD'], 'a') as f:
-            f.write(json.dumps({'kind': kind, 'err': float(err), 'tol': float(tol), 'test': os.environ.get('PYTEST_CURRENT_TEST', '')}) + '\n')
-    # record, then assert
-    assert err < tol, (kind, err, tol)
-
-
-def compare_raw(raw, ref, item_shape, want_grad=True, tol=TOL_GRAD):
-    sc = raw.scalars.cpu()
-    assert rel_err(sc[_lib.S_LL], ref['ll']) < 2e-5
-    assert abs(float(sc[_lib.S_REG]) - float(ref['reg'])) < 2e-5 * max(1.0, abs(float(ref['reg'])))
-    assert abs(float(sc[_lib.S_KL]) - float(ref['kl_ability'])) < 2e-5 * max(1.0, abs(float(ref['kl_ability'])))
-    assert abs(float(sc[_lib.S_LOGQ0]) - float(ref['logq0'])) < 2e-5 * max(1.0, abs(float(ref['logq0'])))
-    assert abs(float(sc[_lib.S_LOGP]) - float(ref['logp'])) < 2e-5 * max(1.0, abs(float(ref['logp'])))
-    for k, t in (('ability_mu', raw.ability_mu), ('ability_logvar', raw.ability_logvar), ('ability', raw.ability)):
-        assert (t.cpu() - ref[k].float()).abs().max() < 2e-5 * max(1.0, float(ref[k].abs().max())), k
-    if want_grad:
-        for s in range(2):
-            scale = float(ref['g_table'][s].abs().max())
-            if scale > 0:
-                _check(f'g_table[{s}]', rel_err(raw.grad_table(s).cpu(), ref['g_table'][s]), tol)
-            else:
-                assert float(raw.grad_table(s).abs().max()) < 1e-6
-        _check('g_item', rel_err(raw.grad_item(item_shape).cpu(), ref['g_item']), tol)
-
-
 SHAPES = [
     # irt, A, B, I, missing
     (2, 1, 64, 1000, 0.0),
@@ -233,7 +156,7 @@ def test_raw_kernel_vs_oracle(irt, A, B, I, missing, drop):
         resp[:, 0] = resp[:, 0].clamp(min=0)
     ref = T.fused_elbo_ref(table.double(), item.double(), resp.double(), mask, eps.double(),
                            irt_model=irt, ability_dim=A, replace_missing_with_prior=not drop, mode='kl')
-    raw = run_kernel(spec, resp, mask, table, item, eps)
+    raw = launch_elbo(spec, resp, mask, table, item, eps)
     compare_raw(raw, ref, (I, spec.item_dim))
 
 
@@ -248,7 +171,7 @@ def test_mask_dtypes(mask_dtype, keep_int64, I, A):
     resp, mask, table, item, eps = random_problem(irt, A, B, I, 0.0 if mask_dtype is None else 0.25, seed=7)
     ref = T.fused_elbo_ref(table.double(), item.double(), resp.double(), mask, eps.double(),
                            irt_model=irt, ability_dim=A, mode='kl')
-    raw = run_kernel(spec, resp, None if mask_dtype is None else mask, table, item, eps,
+    raw = launch_elbo(spec, resp, None if mask_dtype is None else mask, table, item, eps,
                      mask_dtype=mask_dtype or torch.bool, keep_int64=keep_int64)
     compare_raw(raw, ref, (I, spec.item_dim))
 
@@ -328,13 +251,7 @@ def test_general_kernel_vs_oracle(irt, A, B, I, missing, cond, n_flows, drop):
     ref = T.fused_elbo_ref(table.double(), item.double(), resp.double(), mask, eps.double(), irt_model=irt,
                            ability_dim=A, conditional_posterior=cond, replace_missing_with_prior=not drop,
                            mode=mode, flow_uhat_w_b=flows)
-    d = dev()
-    r = ops.prepare_response(resp.to(d))
-    m, code = ops.prepare_mask(mask.bool().to(d))
-    raw = ops._hip_launch_elbo(spec, r, m, code, None, table.to(d).contiguous(), item.to(d).contiguous(),
-                               eps.to(d).contiguous(), flow.to(d).contiguous() if flow is not None else None,
-                               _lib.REG_SAMPLED if n_flows else _lib.REG_KL, True, B)
-    torch.cuda.synchronize()
+    raw = launch_elbo(spec, resp, mask, table, item, eps, flow=flow, reg_mode=_lib.REG_SAMPLED if n_flows else _lib.REG_KL)
     compare_raw(raw, ref, (I, spec.item_dim))
     if n_flows:
         assert (raw.ability_k.cpu() - ref['ability_k'].float()).abs().max() < 5e-5
@@ -342,7 +259,7 @@ def test_general_kernel_vs_oracle(irt, A, B, I, missing, cond, n_flows, drop):
         assert abs(float(raw.scalars[_lib.S_LADJ]) - float(ref['ladj_sum'])) < 1e-4 * max(1.0, abs(float(ref['ladj_sum'])))
         for s_ in range(2):
             gref = torch.cat([torch.cat(gf) for gf in ref['g_flow'][s_]]).float()
-            _check(f'g_flow[{s_}]', rel_err(raw.grad_flow(s_).cpu(), gref), TOL_GRAD)
+            check(f'g_flow[{s_}]', rel_err(raw.grad_flow(s_).cpu(), gref), TOL_GRAD)
 
 
 def test_sampled_regulariser_mode():
@@ -351,7 +268,7 @@ def test_sampled_regulariser_mode():
     resp, mask, table, item, eps = random_problem(irt, A, B, I, 0.2, seed=11)
     ref = T.fused_elbo_ref(table.double(), item.double(), resp.double(), mask, eps.double(),
                            irt_model=irt, ability_dim=A, mode='sampled')
-    raw = run_kernel(spec, resp, mask, table, item, eps, reg_mode=_lib.REG_SAMPLED)
+    raw = launch_elbo(spec, resp, mask, table, item, eps, reg_mode=_lib.REG_SAMPLED)
     compare_raw(raw, ref, (I, spec.item_dim))
 
 
@@ -363,7 +280,7 @@ def test_row_index_gather_and_strided_rows():
     eps = torch.randn(130, A, generator=torch.Generator().manual_seed(2))
     ref = T.fused_elbo_ref(table.double(), item.double(), resp[idx].double(), mask[idx], eps.double(),
                            irt_model=irt, ability_dim=A, mode='kl')
-    raw = run_kernel(spec, resp, mask, table, item, eps, row_index=idx)
+    raw = launch_elbo(spec, resp, mask, table, item, eps, row_index=idx)
     compare_raw(raw, ref, (I, spec.item_dim))
 
 
@@ -377,16 +294,8 @@ def test_forward_only_matches_forward_of_train(irt, A, B, I, cond, n_flows):
     resp, mask, table, item, eps = random_problem(irt, A, B, I, 0.1, seed=3, cond=cond)
     g = torch.Generator().manual_seed(I)
     flow = torch.randn(n_flows, 2 * A + 1, generator=g) * 0.5 if n_flows else None
-    d = dev()
-    r = ops.prepare_response(resp.to(d))
-    m, code = ops.prepare_mask(mask.bool().to(d))
-    outs = []
-    for want_grad in (True, False):
-        outs.append(ops._hip_launch_elbo(spec, r, m, code, None, table.to(d).contiguous(), item.to(d).contiguous(),
-                                         eps.to(d).contiguous(), flow.to(d).contiguous() if flow is not None else None,
-                                         _lib.REG_SAMPLED if n_flows else _lib.REG_KL, want_grad, B))
-    torch.cuda.synchronize()
-    a, b = outs
+    a, b = (launch_elbo(spec, resp, mask, table, item, eps, flow=flow, reg_mode=_lib.REG_SAMPLED if n_flows else _lib.REG_KL,
+                        want_grad=want_grad) for want_grad in (True, False))
     assert rel_err(b.scalars[:7].cpu(), a.scalars[:7].cpu()) < 1e-6
     # two template instantiations of the same source: the compiler may contract a*b+c differently, so last-bit equal
     assert float((a.ability_mu - b.ability_mu).abs().max()) < 1e-6 and float((a.ability - b.ability).abs().max()) < 1e-6
@@ -409,7 +318,7 @@ def test_all_missing_rows_and_saturated_logits():
     ref = T.fused_elbo_ref(table, item, resp, mask, eps, irt_model=irt, ability_dim=A, mode='kl',
                            exact_saturation=True)
     assert float((ref['logit'].abs() > 17).float().mean()) > 0.02      # the clamp really is exercised
-    raw = run_kernel(spec, resp, mask, table, item, eps)
+    raw = launch_elbo(spec, resp, mask, table, item, eps)
     compare_raw(raw, ref, (I, spec.item_dim))
 
 
@@ -440,7 +349,7 @@ def test_item_scales_far_outside_the_f16_range(irt, A, scale):
     else:
         item[:, :A + 1] *= scale               # discriminations and difficulties (the 3PL guess logit stays O(1))
     ref = T.fused_elbo_ref(table, item, resp, mask, eps, irt_model=irt, ability_dim=A, mode='kl', exact_saturation=True)
-    raw = run_kernel(spec, resp, mask, table, item, eps)
+    raw = launch_elbo(spec, resp, mask, table, item, eps)
     assert torch.isfinite(raw.flat).all()
     compare_raw(raw, ref, (I, spec.item_dim), tol=max(TOL_GRAD, 1e-6 * scale))      # (measured: 2.1e-4 at scale 1e3, 1.5e-5 at 1e5, 8.5e-6 at 1e-4)
 
@@ -453,7 +362,7 @@ def test_operands_beyond_the_rescaling_range_fail_loudly():
     spec = ElboSpec(irt_model=irt, ability_dim=A)
     resp, mask, table, item, eps = random_problem(irt, A, B, I, 0.1, seed=5)
     item[3, A] = 3e9
-    raw = run_kernel(spec, resp, mask, table, item, eps)
+    raw = launch_elbo(spec, resp, mask, table, item, eps)
     if ops.DESC_FLAGS & _lib.FLAG_KERNEL_VALU:
         ref = T.fused_elbo_ref(table, item, resp, mask, eps, irt_model=irt, ability_dim=A, mode='kl', exact_saturation=True)
         assert rel_err(raw.scalars.cpu()[_lib.S_LL], ref['ll']) < 2e-5
@@ -477,7 +386,7 @@ def test_saturation_golden_through_kernel():
         resp = torch.full((1, I), float(x))
         mask = torch.ones(1, I, dtype=torch.bool)
         # table = 0 => tau = 1, mu = 0; eps = 0 => theta = 0 exactly
-        raw = run_kernel(spec, resp, mask, table, item, torch.zeros(1, 1))
+        raw = launch_elbo(spec, resp, mask, table, item, torch.zeros(1, 1))
         g_b = raw.grad_item((I, 2))[:, 1].cpu()
         ref_g = torch.from_numpy(z[f'dll_dlogit_x{x}'])[:2000:2]
         assert torch.equal(g_b == 0, ref_g == 0)
@@ -521,7 +430,7 @@ def test_saturation_3pl_golden_through_kernel():
             resp = torch.full((1, I4), float(x))
             mask = torch.zeros(1, I4, dtype=torch.bool)
             mask[:, :I] = True
-            raw = run_kernel(spec, resp, mask, table, item, torch.zeros(1, 1))
+            raw = launch_elbo(spec, resp, mask, table, item, torch.zeros(1, 1))
             g = raw.grad_item((I4, 3)).cpu()[:I]
             for col, key in ((1, 'dll_db'), (2, 'dll_dguess')):
                 ref = torch.from_numpy(z[f'{key}_g{gi}_x{x}'])
@@ -637,36 +546,6 @@ def test_full_size_shard_additivity_permutation_determinism(A, P):
     compare_raw(run(sl), ref, (I, A + 1))
 
 
-def _device_problem(irt, A, P, I, missing, seed, cond):
-    """A simulated response matrix built on the GPU in person slices (the full-size cases do not fit the host-side helper's
-    temporaries): responses from the model's own link (models.py:729-766), `missing` of the cells unobserved."""
-    d = dev()
-    g = torch.Generator(device=d).manual_seed(seed)
-    D = O.item_feat_dim(irt, A)
-    theta = torch.randn(P, A, device=d, generator=g)
-    item_true = torch.randn(I, D, device=d, generator=g)
-    resp = torch.empty(P, I, device=d)
-    mask = torch.empty(P, I, dtype=torch.bool, device=d)
-    step = max(1, 100_000_000 // I)
-    for s0 in range(0, P, step):
-        sl = slice(s0, min(P, s0 + step))
-        if irt == 1:
-            logit = theta[sl].sum(1, keepdim=True) + item_true[:, 0]
-        else:
-            logit = -(theta[sl] @ item_true[:, :A].t()) + item_true[:, A]
-        probs = torch.sigmoid(logit)
-        if irt == 3:
-            gs = torch.sigmoid(item_true[:, A + 1])
-            probs = gs + (1 - gs) * probs
-        resp[sl] = torch.bernoulli(probs, generator=g)
-        mask[sl] = torch.rand(probs.shape, device=d, generator=g) >= missing
-        del logit, probs
-    table = (torch.randn((2, I, 2 * A) if cond else (2, 2 * A), device=d, generator=g) * 0.5).contiguous()
-    item = torch.randn(I, D, device=d, generator=g)
-    eps = torch.randn(P, A, device=d, generator=g)
-    return resp, mask, table, item, eps
-
-
 @pytest.mark.parametrize('P', [100_000, 1_000_000], ids=['100k-persons', 'full-size-1M-persons'])
 @pytest.mark.parametrize('codes', [False, True], ids=['fp32-rows', 'cell-codes'])
 def test_config5_pipeline_at_the_planner_large_call_size(codes, P):
@@ -683,7 +562,7 @@ def test_config5_pipeline_at_the_planner_large_call_size(codes, P):
     if P * I > 2_000_000_000 and torch.cuda.mem_get_info(d)[0] < 150 * 2 ** 30:
         pytest.skip('the full-size case needs ~150 GB of free HBM')
     spec = ElboSpec(irt_model=irt, ability_dim=A, conditional=True, n_flows=n_flows)
-    resp, mask, table, item, eps = _device_problem(irt, A, P, I, 0.2, seed=55, cond=True)
+    resp, mask, table, item, eps = device_problem(irt, A, P, I, 0.2, seed=55, cond=True)
     g = torch.Generator().manual_seed(5)
     flow = (torch.randn(n_flows, 2 * A + 1, generator=g) * 0.5).to(d).contiguous()
     if codes:
@@ -746,7 +625,7 @@ def test_conditional_posterior_one_dim_at_full_size(irt, P, I, monkeypatch):
     A = 1
     d = dev()
     spec = ElboSpec(irt_model=irt, ability_dim=A, conditional=True)
-    resp, mask, table, item, eps = _device_problem(irt, A, P, I, 0.2, seed=66, cond=True)
+    resp, mask, table, item, eps = device_problem(irt, A, P, I, 0.2, seed=66, cond=True)
     rp, mp = ops.pad_rows(resp, mask)
 
     def run(rows=None, row_index=None, grad=True):
@@ -802,7 +681,7 @@ def test_resident_row_counts_change_nothing(codes, P, I, n_rows, second_stream, 
     irt, A = 2, 2
     d = dev()
     spec = ElboSpec(irt_model=irt, ability_dim=A)
-    resp, mask, table, item, eps = _device_problem(irt, A, P, I, 0.2, seed=77, cond=False)
+    resp, mask, table, item, eps = device_problem(irt, A, P, I, 0.2, seed=77, cond=False)
     if codes:
         r2 = m2 = ops.pack_cell_codes(resp, mask).codes
         code = _lib.MASK_CODES
@@ -848,8 +727,8 @@ def test_captured_whole_matrix_call_counts_inside_the_graph(gathered, monkeypatc
     irt, A, P, I = 2, 2, 64, 1028
     d = dev()
     spec = ElboSpec(irt_model=irt, ability_dim=A)
-    resp, mask, table, item, eps = _device_problem(irt, A, P, I, 0.2, seed=81, cond=False)
-    other, other_mask = _device_problem(irt, A, P, I, 0.2, seed=82, cond=False)[:2]
+    resp, mask, table, item, eps = device_problem(irt, A, P, I, 0.2, seed=81, cond=False)
+    other, other_mask = device_problem(irt, A, P, I, 0.2, seed=82, cond=False)[:2]
     rp, mp = ops.pad_rows(resp, mask)
     r2, m2, code = ops.prepare_rows(rp, mp)
     rows = torch.randperm(P, device=d, generator=torch.Generator(device=d).manual_seed(4))[:16].contiguous() if gathered else None
@@ -895,7 +774,7 @@ def test_resident_row_counts_through_the_module(monkeypatch):
     from vibo_amd.torch_core.models import VIBO_2PL
     A, P, I = 2, 900, 2100
     d = dev()
-    resp, mask, _, _, _ = _device_problem(2, A, P, I, 0.2, seed=78, cond=False)
+    resp, mask, _, _, _ = device_problem(2, A, P, I, 0.2, seed=78, cond=False)
     mask = mask.bool()
     torch.manual_seed(5)
     model = VIBO_2PL(A, I, ability_merge='product').to(d)
@@ -931,7 +810,7 @@ def test_config4_shape_at_full_size():
     irt, A, P, I = 2, 1, 535_598, 95
     d = dev()
     spec = ElboSpec(irt_model=irt, ability_dim=A)
-    resp, mask, table, item, eps = _device_problem(irt, A, P, I, 0.2, seed=44, cond=False)
+    resp, mask, table, item, eps = device_problem(irt, A, P, I, 0.2, seed=44, cond=False)
     rp, mp = ops.pad_rows(resp, mask)
 
     def run(rows=None, row_index=None):
@@ -981,7 +860,7 @@ def test_wide_conditional_posterior_is_deterministic(A, I, codes):
         run = lambda: ops._hip_launch_elbo(spec, cells, cells, _lib.MASK_CODES, None, table.to(d).contiguous(),
                                            item.to(d).contiguous(), eps.to(d).contiguous(), None, _lib.REG_KL, True, B)
     else:
-        run = lambda: run_kernel(spec, resp, mask, table, item, eps)
+        run = lambda: launch_elbo(spec, resp, mask, table, item, eps)
     a, b = run(), run()
     torch.cuda.synchronize()
     assert torch.equal(a.flat, b.flat) and torch.equal(a.grad_table(0), b.grad_table(0))

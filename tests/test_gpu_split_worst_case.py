@@ -29,13 +29,11 @@ shows that term.  Builds without theta_lo * a_hi, or with g_hi alone in the d LL
 VIBO_TOL_RECORD=path appends, per observable, the worst error / bound, the largest error, the fp64 model's worst ratio on the same
 cells and the bound's size against the plain fp32 bound as a JSON line; tools/split_record_table.py turns such a file into
 profiles/split_worst_case_record.txt.  The assertions hold either way."""
-import json
-import os
-
 import numpy as np
 import pytest
 import torch
 
+from gpu_common import launch_elbo, record, recording
 from oracle import split_model as M
 from oracle import vibo_table_ref as T
 from vibo_amd import _lib, ops
@@ -81,16 +79,12 @@ def _record(cls, kernel, observable, err, bound, **extra):
     ratio = float((err[~zero] / bound[~zero]).max()) if (~zero).any() else 0.0
     if zero.any() and float(err[zero].max()) > 0:
         ratio = float('inf')
-    if os.environ.get('VIBO_TOL_RECORD'):
-        with open(os.environ['VIBO_TOL_RECORD'], 'a') as f:
-            f.write(json.dumps({'kind': 'split_worst_case', 'class': cls, 'kernel': kernel, 'observable': observable, 'ratio': ratio,
-                                'err': float(err.max()), 'test': os.environ.get('PYTEST_CURRENT_TEST', ''), **extra}) + '\n')
+    record('split_worst_case', err.max(), **{'class': cls}, kernel=kernel, observable=observable, ratio=ratio, **extra)
     print(f'{cls:8s} {kernel:6s} {observable:8s} worst error / bound = {ratio:.3f}  (largest error {float(err.max()):.3e})')
     return ratio
 
 
 def _launch(case, posterior, rows, table, kernel, want_grad=True):
-    dev = torch.device('cuda:0')
     B, I = case['resp'].shape
     A = case['theta'].shape[1]
     spec = ElboSpec(irt_model=case['irt'], ability_dim=A, given=posterior == 'given')
@@ -102,15 +96,9 @@ def _launch(case, posterior, rows, table, kernel, want_grad=True):
         resp_all, mask_all = torch.zeros(P, I), torch.zeros(P, I, dtype=torch.bool)
         resp_all[index], mask_all[index] = resp, mask
         resp, mask = resp_all, mask_all
-    r_, m_ = ops.pad_rows(resp.to(dev), mask.to(dev))
-    if rows == 'codes':
-        r_, m_ = ops.pack_cell_codes(r_, m_), None
-    r, m, code = ops.prepare_rows(r_, m_)
     # the pin must really put the call on the kernel under test: any other kernel is true fp32 and would pass the split bound idly
-    assert ops.plan_kernel(spec, B, I, code, want_grad) == _lib.KERNEL_NAMES[1 if kernel == 'matrix' else 2]
-    raw = ops._hip_launch_elbo(spec, r, m, code, index.to(dev) if index is not None else None, table.to(dev).contiguous(),
-                               torch.from_numpy(M.item_tensor(case)).to(dev), torch.zeros(B, A, device=dev), None, _lib.REG_KL, want_grad, B)
-    torch.cuda.synchronize()
+    raw = launch_elbo(spec, resp, mask, table, torch.from_numpy(M.item_tensor(case)), torch.zeros(B, A), row_index=index, pad=True,
+                      codes=rows == 'codes', want_grad=want_grad, kernel=_lib.KERNEL_NAMES[1 if kernel == 'matrix' else 2])
     assert torch.isfinite(raw.scalars).all() and (not want_grad or torch.isfinite(raw.flat).all())
     return spec, raw
 
@@ -172,7 +160,7 @@ def _check(case, spec, raw, posterior, kernel, dense=False):
         sp = (M.sigmoid(l) * (1 - M.sigmoid(l)))[sel]
         el = e_l[case['p_obs'], idx][sel]
         extra = {}
-        if not fp32 and I <= M.PANEL and os.environ.get('VIBO_TOL_RECORD'):
+        if not fp32 and I <= M.PANEL and recording():
             # for the record: the fp64 model of the scheme on the same cells, and the bound's size against the plain fp32 bound
             model = np.abs(M.logit_model(theta, case['a'], case['b'], irt) - ref['logit'])[case['p_obs'], idx][sel]
             vs32 = (el / M.cell_bound(theta, case['a'], case['b'], irt, fp32=True)[case['p_obs'], idx][sel])

@@ -1,31 +1,22 @@
 """The folded train step on the matrix row-split kernel draws its ability noise in the kernel (vibo_elbo_fwd_bwd_step_noise
 with eps NULL) and may leave the posterior's mean / log-variance unwritten.  The drawn noise has to be, bit for bit, what
 vibo_fill_normal leaves in memory at the same counter, so the sample, the loss and every gradient stay what they were."""
-import copy
 import ctypes
 
 import pytest
 import torch
 
-from oracle import vibo_oracle as O
+from gpu_common import assert_same_parameters, coin_flip_rows, simulated, twin_trainers
 from vibo_amd import _lib, ops
-from vibo_amd.ops import ElboSpec
 from vibo_amd.torch_core.models import VIBO_2PL
-from vibo_amd.trainer import FusedTrainer
 
 SEED, STREAM = 0x1234_5678_9ABC, 3
 
 
 def _problem(B, I, A, gathered, seed=7, codes=False):
-    d = torch.device('cuda:0')
-    g = torch.Generator(device=d).manual_seed(seed)
     P = B + 37 if gathered else B
-    r = (torch.rand(P, I, device=d, generator=g) < 0.5).float()
-    mk = torch.rand(P, I, device=d, generator=g) >= 0.1
-    spec = ElboSpec(irt_model=2, ability_dim=A)
-    table = torch.randn(2, 2 * A, device=d, generator=g) * 0.5
-    item = torch.randn(I, A + 1, device=d, generator=g)
-    rows = torch.randperm(P, device=d, generator=g)[:B] if gathered else None
+    spec, r, mk, table, item, g = coin_flip_rows(P, I, A, seed)
+    rows = torch.randperm(P, device=r.device, generator=g)[:B] if gathered else None
     r2, m8, code = ops.prepare_rows(ops.pack_cell_codes(r, mk) if codes else r, None if codes else mk)
     return spec, r2, m8, code, rows, table, item
 
@@ -131,20 +122,15 @@ def test_drawing_step_survives_graph_replays_and_a_shorter_minibatch(pin, P, B):
     short one on the VALU kernel, which then has to fill the noise buffer itself (no epilogue does any more).  20 000 persons:
     625 batches over 256 workgroups (the batch loop's draws, the `late` workgroups) inside the captured step."""
     dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(4)
     I, A, n_short = 1000, 8, 45
-    resp, mask = O.simulate_responses(2, P, I, A, generator=g, missing_frac=0.1)
+    resp, mask, g = simulated(2, P, I, A, 0.1, seed=4)
     resp, mask = resp.to(dev), mask.bool().to(dev)
     rows = torch.randperm(P, generator=g)[:B].to(dev)
     short = torch.arange(P - n_short, P, device=dev)
-    torch.manual_seed(2)
-    m1 = VIBO_2PL(A, I, ability_merge='product').to(dev)
-    m2 = copy.deepcopy(m1)
     with ops.desc_flags(_lib.FLAG_KERNEL_MATRIX if pin else 0):
+        m1, m2, t1, t2 = twin_trainers(VIBO_2PL, A, I, 2, dict(rng='native', seed=3, max_batch=B), dict(rng='native', seed=3, fold=False))
         kinds = {ops.plan_kernel(m1.spec, n, I).split()[0] for n in (B, n_short)}
         assert kinds == ({'matrix'} if pin else {'matrix', 'VALU'}), kinds
-        t1 = FusedTrainer(m1, lr=5e-3, rng='native', seed=3, max_batch=B)
-        t2 = FusedTrainer(m2, lr=5e-3, rng='native', seed=3, fold=False)
         for k in range(3):
             rr = short if k == 1 else rows
             la, lb = t1.step(resp, mask, row_index=rr), t2.step(resp, mask, row_index=rr)
@@ -166,8 +152,7 @@ def test_drawing_step_survives_graph_replays_and_a_shorter_minibatch(pin, P, B):
                 graph.replay()
                 la, lb = lg, t2.step(resp, mask, row_index=rows)
             assert torch.equal(la, lb), it
-    for (k, a), (_, b) in zip(m1.state_dict().items(), m2.state_dict().items()):
-        assert torch.equal(a, b), k
+    assert_same_parameters(m1, m2)
 
 
 def test_drawing_entry_points_check_their_arguments():

@@ -5,39 +5,125 @@ import copy
 import pytest
 import torch
 
-from oracle import vibo_oracle as O
+from gpu_common import CLS, assert_same_parameters, dev, simulated, twin_trainers
+from vibo_amd import ops
 from vibo_amd.torch_core.models import VIBO_1PL, VIBO_2PL, VIBO_3PL
-from vibo_amd.trainer import FusedTrainer
+from vibo_amd.trainer import FusedCondFlowTrainer, FusedMeanTrainer, FusedTrainer
 
 pytestmark = pytest.mark.gpu
+
+
+def assert_follows_torch_adam(cls, A, I, B, beta, kw, *, trainer_class, merge='product', rows='all', tol_loss, tol_state, signs=None):
+    """Twin models; four steps of module + autograd + torch.optim.Adam (vibo.py:243-268) on one and of the native trainer on the
+    other at lr 5e-3, each pair under the same torch.manual_seed(100 + step) -> the same noise (rng='torch'): every loss within
+    tol_loss (relative), every state_dict tensor within tol_state at the end.  Data: seed 100 A + I, 15 % missing; model: seed 3.
+    rows='alternating': B + 20 persons in rows padded as the CLI's resident splits are (95 items: strides of 4 cells), the whole
+    matrix on even steps and B gathered rows on odd ones.  merge='mean': every person observes item 0 (a person without an observed
+    item has no mean: NaN in the reference too).
+    signs ('above-threshold' | 'and-share'): Adam's first step moves every parameter by lr * sign(g) (up to eps / |g|), so a wrong gradient SIGN anywhere shows as a
+    2 lr difference -- checked per tensor after step 0 so that a failure names the parameter, on the entries whose gradient is
+    above 1e-3 of the tensor's largest (the others' sign is the summation order's); 'and-share': and at most 2 % of ALL entries
+    of a tensor may have moved the other way."""
+    d = dev()
+    P = B + 20 if rows == 'alternating' else B
+    resp, mask, g = simulated(cls.IRT, P, I, A, 0.15, seed=A * 100 + I)
+    if merge == 'mean':
+        mask[:, 0] = 1
+        resp[:, 0] = resp[:, 0].clamp(min=0)
+    resp, mask = resp.to(d), mask.bool().to(d)
+    gathered = None
+    if rows == 'alternating':
+        resp, mask = ops.pad_rows(resp, mask)
+        gathered = torch.randperm(P, generator=g)[:B].to(d)
+    torch.manual_seed(3)
+    ref = cls(A, I, ability_merge=merge, **kw).to(d)
+    fus = copy.deepcopy(ref)
+    opt = torch.optim.Adam(ref.parameters(), lr=5e-3)
+    trainer = FusedTrainer(fus, lr=5e-3)
+    assert type(trainer) is trainer_class
+    assert list(fus.state_dict().keys()) == list(ref.state_dict().keys())
+    for step in range(4):
+        ri = gathered if step % 2 else None
+        torch.manual_seed(100 + step)
+        opt.zero_grad()
+        loss_ref = ref.elbo_step(resp, mask, annealing_factor=beta, row_index=ri)
+        loss_ref.backward()
+        if step == 0:
+            g_ref = {k: p.grad.clone() for k, p in ref.named_parameters()}
+        opt.step()
+        torch.manual_seed(100 + step)
+        loss_fus = trainer.step(resp, mask, beta=beta, row_index=ri)
+        assert abs(float(loss_fus) - float(loss_ref.detach())) < tol_loss * abs(float(loss_ref.detach())), step
+        if step == 0 and signs:
+            for (k, a), (_, b) in zip(ref.named_parameters(), fus.named_parameters()):
+                big = g_ref[k].abs() > 1e-3 * g_ref[k].abs().max()
+                diff = (a.detach() - b.detach()).abs()
+                assert (diff[big] < 1e-4).all(), (k, float(diff.max()), int((diff[big] >= 1e-4).sum()), int(big.sum()))
+                if signs == 'and-share':
+                    assert float((diff >= 1e-4).float().mean()) < 0.02, (k, 'more than 2 % of the entries moved the other way')
+    for (k, a), (_, b) in zip(ref.state_dict().items(), fus.state_dict().items()):
+        assert (a - b).abs().max() < tol_state, (k, float((a - b).abs().max()))
+    assert int(trainer.step_count) == 4
+
+
+def assert_replays_bitwise(irt, P, I, A, B, model_seed, trainer_seed, replays, *, side_stream_warm_up, check_losses, **model_kw):
+    """Twin trainers with native noise (the counters live on the device) over a resident matrix (data seed 5, 10 % missing): one
+    captures its step once and replays it, the other launches the same steps eagerly, the row-index buffer refreshed between
+    replays -- bitwise the same finite parameters at the end.  Three eager warm-up steps of both come first.
+    side_stream_warm_up=False: the warm-up runs on the current stream, all three steps on the first B rows of the permutation;
+    replay `it` (from 0) reads the window at it B mod (P - B).  True: it runs on a side stream, each step on its own window; after
+    the capture one replay / eager pair repeats the last window, then replay `it` counts on from 4.
+    check_losses: compare the two losses on every 20th replay and the last."""
+    d = dev()
+    resp, mask, g = simulated(irt, P, I, A, 0.1, seed=5)
+    resp, mask = resp.to(d), mask.bool().to(d)
+    m1, m2, t1, t2 = twin_trainers(CLS[irt], A, I, model_seed, dict(rng='native', seed=trainer_seed), **model_kw)
+    rows = torch.zeros(B, dtype=torch.int64, device=d)
+    perm = torch.randperm(P, generator=g).to(d)
+
+    def window(it):
+        lo = (it * B) % (P - B)
+        rows.copy_(perm[lo:lo + B])
+
+    def warm_up():
+        for it in range(3):
+            window(it if side_stream_warm_up else 0)
+            t1.step(resp, mask, row_index=rows)
+            t2.step(resp, mask, row_index=rows)
+
+    if side_stream_warm_up:
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            warm_up()
+        torch.cuda.current_stream().wait_stream(side)
+    else:
+        warm_up()
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr):
+        lg = t1.step(resp, mask, row_index=rows)               # capture only: nothing runs
+    first = 0
+    if side_stream_warm_up:
+        t2.step(resp, mask, row_index=rows)
+        gr.replay()
+        first = 4
+    for it in range(first, first + replays):
+        window(it)
+        gr.replay()
+        l2 = t2.step(resp, mask, row_index=rows)
+        if check_losses and (it % 20 == 0 or it == replays - 1):
+            assert torch.equal(lg, l2), it
+    torch.cuda.synchronize()
+    for k, a in m1.state_dict().items():
+        assert torch.isfinite(a).all(), k
+    assert_same_parameters(m1, m2)
 
 
 @pytest.mark.parametrize('cls,A,I,B,beta', [(VIBO_2PL, 1, 1000, 300, 1.0), (VIBO_2PL, 8, 200, 130, 0.5),
                                             (VIBO_3PL, 2, 95, 77, 1.0), (VIBO_1PL, 3, 64, 50, 0.7)])
 def test_fused_trainer_matches_torch_adam(cls, A, I, B, beta):
-    dev = torch.device('cuda:0')
-    irt = cls.IRT
-    g = torch.Generator().manual_seed(A * 100 + I)
-    resp, mask = O.simulate_responses(irt, B, I, A, generator=g, missing_frac=0.15)
-    resp, mask = resp.to(dev), mask.bool().to(dev)
-    torch.manual_seed(3)
-    ref = cls(A, I, ability_merge='product').to(dev)
-    fus = copy.deepcopy(ref)
-    opt = torch.optim.Adam(ref.parameters(), lr=5e-3)
-    trainer = FusedTrainer(fus, lr=5e-3)
-    assert list(fus.state_dict().keys()) == list(ref.state_dict().keys())
-    for step in range(4):
-        torch.manual_seed(100 + step)
-        opt.zero_grad()
-        loss_ref = ref.elbo_step(resp, mask, annealing_factor=beta)
-        loss_ref.backward()
-        opt.step()
-        torch.manual_seed(100 + step)
-        loss_fus = trainer.step(resp, mask, beta=beta)
-        assert abs(float(loss_fus) - float(loss_ref.detach())) < 2e-5 * abs(float(loss_ref.detach())), step
-    for (k, a), (_, b) in zip(ref.state_dict().items(), fus.state_dict().items()):
-        assert (a - b).abs().max() < 2e-5, k
-    assert int(trainer.step_count) == 4
+    assert_follows_torch_adam(cls, A, I, B, beta, {}, trainer_class=FusedTrainer, tol_loss=2e-5, tol_state=2e-5)
 
 
 @pytest.mark.gpu
@@ -53,11 +139,10 @@ def test_folded_step_equals_the_unfolded_step(cls, A, I, B, rng, kernel, rows):
     moment and loss BIT FOR BIT over six steps -- both row-split kernels, fp32 rows in order / gathered by row_index / cell
     codes, both noise sources, a shorter minibatch in between (the epoch's last one) -- and again as captured hipGraphs.
     1 032 items do not take the folded step (panel mode), nor does rng='torch': fold=True runs the four-launch form there."""
-    from vibo_amd import _lib, ops
+    from vibo_amd import _lib
     dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(A * 1000 + I)
     P = B + 40
-    resp, mask = O.simulate_responses(cls.IRT, P, I, A, generator=g, missing_frac=0.12)
+    resp, mask, g = simulated(cls.IRT, P, I, A, 0.12, seed=A * 1000 + I)
     resp, mask = resp.to(dev), mask.bool().to(dev)
     if rows == 'codes':
         resp, mask = ops.pack_cell_codes(resp, mask), None
@@ -69,13 +154,9 @@ def test_folded_step_equals_the_unfolded_step(cls, A, I, B, rng, kernel, rows):
             pytest.skip('cell codes are exercised through row_index')
         resp, mask = resp[:B].contiguous(), mask[:B].contiguous()
         short = torch.arange(B - n_short, B, device=dev)
-    torch.manual_seed(11)
-    m_a = cls(A, I, ability_merge='product').to(dev)
-    m_b = copy.deepcopy(m_a)
     flags = _lib.FLAG_KERNEL_MATRIX if kernel == 'matrix' else _lib.FLAG_KERNEL_VALU
     with ops.desc_flags(flags):
-        t_a = FusedTrainer(m_a, lr=5e-3, rng=rng, seed=5, fold=True)
-        t_b = FusedTrainer(m_b, lr=5e-3, rng=rng, seed=5, fold=False)
+        m_a, m_b, t_a, t_b = twin_trainers(cls, A, I, 11, dict(rng=rng, seed=5, fold=True), dict(rng=rng, seed=5, fold=False))
         lib = _lib.load()
         d = ops._make_desc(m_a.spec, B, I, _lib.MASK_CODES if rows == 'codes' else _lib.MASK_U8, _lib.REG_KL, True, (I + 3) & ~3, (I + 3) & ~3)
         assert lib.vibo_train_step_supported(__import__('ctypes').byref(d)) == (3 if I <= 1024 else 0)
@@ -91,8 +172,7 @@ def test_folded_step_equals_the_unfolded_step(cls, A, I, B, rng, kernel, rows):
 
         for k in range(6):
             both(k, short if k == 3 else idx, 1.0 if k < 4 else 0.6)
-        for (ka, a), (_, b) in zip(m_a.state_dict().items(), m_b.state_dict().items()):
-            assert torch.equal(a, b), ka
+        assert_same_parameters(m_a, m_b)
         assert torch.equal(t_a.mlp_m, t_b.mlp_m) and torch.equal(t_a.mlp_v, t_b.mlp_v)
         assert torch.equal(t_a.item_m, t_b.item_m) and torch.equal(t_a.item_v, t_b.item_v)
         assert torch.equal(t_a._steps, t_b._steps) and int(t_a.step_count) == 6
@@ -113,8 +193,7 @@ def test_folded_step_equals_the_unfolded_step(cls, A, I, B, rng, kernel, rows):
                 gr.replay()
                 la, lb = loss_g, t_b.step(resp, mask, row_index=idx)
             assert torch.equal(la, lb), k
-        for (ka, a), (_, b) in zip(m_a.state_dict().items(), m_b.state_dict().items()):
-            assert torch.equal(a, b), ka
+        assert_same_parameters(m_a, m_b)
 
 
 @pytest.mark.gpu
@@ -146,7 +225,6 @@ def test_fill_normal_moments_determinism_and_step_dependence():
 
 @pytest.mark.gpu
 def test_fused_trainer_native_rng_trains():
-    from vibo_amd.trainer import FusedTrainer
     torch.manual_seed(0)
     dev = torch.device('cuda:0')
     B, I, A = 4096, 256, 2
@@ -198,18 +276,12 @@ def test_cli_end_to_end_on_the_gpu(tmp_path, monkeypatch, extra):
 def test_noise_drawn_in_the_prologue_equals_separate_fills(A, I, B):
     """vibo_train_prologue_noise draws exactly the streams vibo_fill_normal gives (item: stream 0, ability: stream
     1 + rank, step = completed steps): the two trainers stay bitwise identical, eagerly and replayed from a hipGraph."""
-    import copy
     dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(A + I)
-    resp, mask = O.simulate_responses(2, B, I, A, generator=g, missing_frac=0.1)
-    from vibo_amd import ops
+    resp, mask, _ = simulated(2, B, I, A, 0.1, seed=A + I)
     resp, mask = ops.pad_rows(resp.to(dev), mask.bool().to(dev))
-    torch.manual_seed(5)
-    m1 = VIBO_2PL(A, I, ability_merge='product').to(dev)
-    m2 = copy.deepcopy(m1)
     # (fold=False: the four-launch form, whose prologue draws; the folded form is pinned to it by test_folded_step_equals_the_unfolded_step)
-    t1 = FusedTrainer(m1, lr=5e-3, rng='native', seed=11, fused_noise=True, fold=False)
-    t2 = FusedTrainer(m2, lr=5e-3, rng='native', seed=11, fused_noise=False, fold=False)
+    m1, m2, t1, t2 = twin_trainers(VIBO_2PL, A, I, 5, dict(rng='native', seed=11, fused_noise=True, fold=False),
+                                   dict(rng='native', seed=11, fused_noise=False, fold=False))
     for step in range(3):
         l1, l2 = t1.step(resp, mask), t2.step(resp, mask)
         assert torch.equal(l1, l2), step
@@ -225,8 +297,7 @@ def test_noise_drawn_in_the_prologue_equals_separate_fills(A, I, B):
         l2 = t2.step(resp, mask)
         assert torch.equal(lg, l2), step
     assert not torch.equal(first, t1._eps_ab[B])    # fresh noise on every replay (the step counters live on the device)
-    for (k, a), (_, b) in zip(m1.state_dict().items(), m2.state_dict().items()):
-        assert torch.equal(a, b), k
+    assert_same_parameters(m1, m2)
 
 
 @pytest.mark.gpu
@@ -331,17 +402,12 @@ def test_graph_replay_survives_a_shorter_eager_minibatch_with_native_noise():
     """An epoch's last, shorter minibatch runs eagerly between replays of the captured full-size step.  The noise buffer the
     graph recorded must stay alive and untouched by that (it used to be freed and re-allocated: replays then wrote Philox
     noise into whatever the allocator had handed out in between)."""
-    import copy
     dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(9)
     P, I, A, B = 1000, 64, 2, 128
-    resp, mask = O.simulate_responses(2, P, I, A, generator=g, missing_frac=0.1)
+    resp, mask, _ = simulated(2, P, I, A, 0.1, seed=9)
     resp, mask = resp.to(dev), mask.bool().to(dev)
-    torch.manual_seed(5)
-    m1 = VIBO_2PL(A, I, ability_merge='product').to(dev)
-    m2 = copy.deepcopy(m1)
-    t1 = FusedTrainer(m1, lr=5e-3, rng='native', seed=3)                    # the folded step: its noise buffer has a fixed capacity
-    t2 = FusedTrainer(m2, lr=5e-3, rng='native', seed=3, fold=False)        # the four-launch form, eager throughout
+    # t1: the folded step, whose noise buffer has a fixed capacity; t2: the four-launch form, eager throughout
+    m1, m2, t1, t2 = twin_trainers(VIBO_2PL, A, I, 5, dict(rng='native', seed=3), dict(rng='native', seed=3, fold=False))
     rows = torch.arange(B, device=dev)
     tail = torch.arange(P - 40, P, device=dev)
     for _ in range(2):
@@ -360,8 +426,7 @@ def test_graph_replay_survives_a_shorter_eager_minibatch_with_native_noise():
         assert torch.equal(la, lb), it
         del junk
     assert t1._eps_cap.data_ptr() == ptr and t1._eps_cap.numel() == B * A
-    for (k, a), (_, b) in zip(m1.state_dict().items(), m2.state_dict().items()):
-        assert torch.equal(a, b), k
+    assert_same_parameters(m1, m2)
 
 
 @pytest.mark.gpu
@@ -377,16 +442,14 @@ def test_graphed_module_step_follows_the_eager_module_step(cls, kw):
     vibo.py:243-268 for --conditional-posterior / --n-norm-flows / --ability-merge mean) from a hipGraph.  Same seed ->
     the same noise stream as the eager loop, so both models must follow the same trajectory; rows and beta are refreshed
     between replays through device buffers."""
-    import copy
     from vibo_amd.torch_core.vibo import GraphedModuleStep
 
     class Data:
         pass
     dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(11)
     kw = dict(kw)
     P, I, A, B = 640, kw.pop('_items', 120), 2, 64
-    resp, mask = O.simulate_responses(cls.IRT, P, I, A, generator=g, missing_frac=0.1)
+    resp, mask, g = simulated(cls.IRT, P, I, A, 0.1, seed=11)
     data = Data()
     data.response, data.mask, data.device = resp.to(dev), mask.bool().to(dev), dev
     torch.manual_seed(2)
@@ -443,15 +506,13 @@ def test_graphed_module_step_survives_the_epochs_short_last_minibatch():
     """num_person % batch_size != 0: the epoch's last, shorter minibatch runs eagerly between the replays.  Its zero_grad
     must not free the gradient buffers the captured graph was recorded with (set_to_none=True there was a
     use-after-free -- later replays wrote their gradients into memory the allocator had handed to someone else)."""
-    import copy
     from vibo_amd.torch_core.vibo import GraphedModuleStep
 
     class Data:
         pass
     dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(3)
     P, I, A, B = 672, 120, 2, 64                       # 10 full minibatches + one of 32 rows
-    resp, mask = O.simulate_responses(2, P, I, A, generator=g, missing_frac=0.1)
+    resp, mask, _ = simulated(2, P, I, A, 0.1, seed=3)
     data = Data()
     data.response, data.mask, data.device = resp.to(dev), mask.bool().to(dev), dev
     torch.manual_seed(2)
@@ -511,43 +572,7 @@ def test_fused_cond_flow_trainer_matches_torch_adam(cls, A, I, B, beta, kw):
     """FusedTrainer on --conditional-posterior / --n-norm-flows models (FusedCondFlowTrainer: vibo_ctrain_prologue, the ELBO
     kernel, vibo_ctrain_epilogue -- no autograd) follows module + autograd + torch.optim.Adam: same seeds -> the same noise
     (rng='torch'), so losses and every parameter must agree after several steps.  Reference loop: vibo.py:243-268."""
-    dev = torch.device('cuda:0')
-    irt = cls.IRT
-    g = torch.Generator().manual_seed(A * 100 + I)
-    resp, mask = O.simulate_responses(irt, B, I, A, generator=g, missing_frac=0.15)
-    resp, mask = resp.to(dev), mask.bool().to(dev)
-    kw = dict(kw)
-    torch.manual_seed(kw.pop('_seed', 3))
-    ref = cls(A, I, ability_merge='product', **kw).to(dev)
-    fus = copy.deepcopy(ref)
-    opt = torch.optim.Adam(ref.parameters(), lr=5e-3)
-    trainer = FusedTrainer(fus, lr=5e-3)
-    assert type(trainer).__name__ == 'FusedCondFlowTrainer'
-    assert list(fus.state_dict().keys()) == list(ref.state_dict().keys())
-    for step in range(4):
-        torch.manual_seed(100 + step)
-        opt.zero_grad()
-        loss_ref = ref.elbo_step(resp, mask, annealing_factor=beta)
-        loss_ref.backward()
-        if step == 0:
-            g_ref = {k: p.grad.clone() for k, p in ref.named_parameters()}
-            p_before = {k: p.detach().clone() for k, p in ref.named_parameters()}
-        opt.step()
-        torch.manual_seed(100 + step)
-        loss_fus = trainer.step(resp, mask, beta=beta)
-        assert abs(float(loss_fus) - float(loss_ref.detach())) < 3e-5 * abs(float(loss_ref.detach())), step
-        if step == 0:
-            # Adam's first step moves every parameter by lr * sign(g) (up to eps / |g|): a wrong gradient SIGN anywhere shows
-            # as a 2 lr difference -- checked per tensor so that a failure names the parameter
-            # (entries whose gradient is below 1e-3 of the tensor's largest are left out: their sign is the summation order's)
-            for (k, a), (_, b) in zip(ref.named_parameters(), fus.named_parameters()):
-                big = g_ref[k].abs() > 1e-3 * g_ref[k].abs().max()
-                diff = (a.detach() - b.detach()).abs()
-                assert (diff[big] < 1e-4).all(), (k, float(diff.max()), int((diff[big] >= 1e-4).sum()), int(big.sum()))
-                assert float((diff >= 1e-4).float().mean()) < 0.02, (k, 'more than 2 % of the entries moved the other way')
-    for (k, a), (_, b) in zip(ref.state_dict().items(), fus.state_dict().items()):
-        assert (a - b).abs().max() < 2e-4, (k, float((a - b).abs().max()))
-    assert int(trainer.step_count) == 4
+    assert_follows_torch_adam(cls, A, I, B, beta, kw, trainer_class=FusedCondFlowTrainer, tol_loss=3e-5, tol_state=2e-4, signs='and-share')
 
 
 @pytest.mark.gpu
@@ -560,41 +585,8 @@ def test_fused_mean_trainer_matches_torch_adam(cls, A, I, B, beta, kw):
     kernel with the caller-supplied posterior, vibo_mean_encoder_backward_sets, vibo_mtrain_epilogue -- no autograd) follows
     module + autograd + torch.optim.Adam: same seeds -> the same noise (rng='torch'), so losses and every parameter must agree
     after several steps, on the whole matrix and on a gathered minibatch.  Reference: vibo.py:243-268, models.py:584-594, 631-650."""
-    dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(A * 100 + I)
-    resp, mask = O.simulate_responses(cls.IRT, B + 20, I, A, generator=g, missing_frac=0.15)
-    mask[:, 0] = 1                      # (a person without an observed item has no mean: NaN in the reference too)
-    resp[:, 0] = resp[:, 0].clamp(min=0)
-    from vibo_amd import ops
-    resp, mask = ops.pad_rows(resp.to(dev), mask.bool().to(dev))      # (95 items: row strides padded to 4 cells, as the CLI's resident splits)
-    rows = torch.randperm(B + 20, generator=g)[:B].to(dev)
-    torch.manual_seed(3)
-    ref = cls(A, I, ability_merge='mean', **kw).to(dev)
-    fus = copy.deepcopy(ref)
-    opt = torch.optim.Adam(ref.parameters(), lr=5e-3)
-    trainer = FusedTrainer(fus, lr=5e-3)
-    assert type(trainer).__name__ == 'FusedMeanTrainer'
-    assert list(fus.state_dict().keys()) == list(ref.state_dict().keys())
-    for step in range(4):
-        ri = rows if step % 2 else None
-        torch.manual_seed(100 + step)
-        opt.zero_grad()
-        loss_ref = ref.elbo_step(resp, mask, annealing_factor=beta, row_index=ri)
-        loss_ref.backward()
-        if step == 0:
-            g_ref = {k: p.grad.clone() for k, p in ref.named_parameters()}
-        opt.step()
-        torch.manual_seed(100 + step)
-        loss_fus = trainer.step(resp, mask, beta=beta, row_index=ri)
-        assert abs(float(loss_fus) - float(loss_ref.detach())) < 3e-5 * abs(float(loss_ref.detach())), step
-        if step == 0:       # Adam's first step moves every parameter by lr * sign(g): a wrong gradient sign shows as 2 lr
-            for (k, a), (_, b) in zip(ref.named_parameters(), fus.named_parameters()):
-                big = g_ref[k].abs() > 1e-3 * g_ref[k].abs().max()
-                diff = (a.detach() - b.detach()).abs()
-                assert (diff[big] < 1e-4).all(), (k, float(diff.max()), int((diff[big] >= 1e-4).sum()), int(big.sum()))
-    for (k, a), (_, b) in zip(ref.state_dict().items(), fus.state_dict().items()):
-        assert (a - b).abs().max() < 2e-4, (k, float((a - b).abs().max()))
-    assert int(trainer.step_count) == 4
+    assert_follows_torch_adam(cls, A, I, B, beta, kw, trainer_class=FusedMeanTrainer, merge='mean', rows='alternating', tol_loss=3e-5,
+                              tol_state=2e-4, signs='above-threshold')
 
 
 @pytest.mark.gpu
@@ -602,33 +594,7 @@ def test_fused_mean_trainer_replays_bitwise_from_a_hipgraph():
     """The mean-merge step captured once and replayed (native noise: the counters live on the device) against the same steps
     launched eagerly: bitwise, 200 replays over changing row-index vectors -- the captured autograd step this replaces is the
     kind that went wrong after a dozen replays on this stack."""
-    dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(5)
-    P, I, A, B = 512, 1000, 2, 16
-    resp, mask = O.simulate_responses(2, P, I, A, generator=g, missing_frac=0.1)
-    resp, mask = resp.to(dev), mask.bool().to(dev)
-    torch.manual_seed(1)
-    m1 = VIBO_2PL(A, I, ability_merge='mean').to(dev)
-    m2 = copy.deepcopy(m1)
-    t1 = FusedTrainer(m1, lr=5e-3, rng='native', seed=7)
-    t2 = FusedTrainer(m2, lr=5e-3, rng='native', seed=7)
-    rows = torch.zeros(B, dtype=torch.int64, device=dev)
-    perm = torch.randperm(P, generator=g).to(dev)
-    for _ in range(3):
-        rows.copy_(perm[:B]); t1.step(resp, mask, row_index=rows); t2.step(resp, mask, row_index=rows)
-    torch.cuda.synchronize()
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
-        lg = t1.step(resp, mask, row_index=rows)
-    for it in range(200):
-        s0 = (it * B) % (P - B)
-        rows.copy_(perm[s0:s0 + B])
-        gr.replay()
-        l2 = t2.step(resp, mask, row_index=rows)
-        if it % 20 == 0 or it == 199:
-            assert torch.equal(lg, l2), it
-    for (k, a), (_, b) in zip(m1.state_dict().items(), m2.state_dict().items()):
-        assert torch.equal(a, b), k
+    assert_replays_bitwise(2, 512, 1000, 2, 16, 1, 7, 200, side_stream_warm_up=False, check_losses=True, ability_merge='mean')
 
 
 @pytest.mark.gpu
@@ -639,41 +605,8 @@ def test_fused_cond_flow_trainer_replays_bitwise_from_a_hipgraph(P, I, A, B, rep
     same steps launched eagerly (native noise: the counters live on the device), 200 replays -- the captured autograd step
     this replaces went wrong after a dozen replays on the same stack.  Second case: a minibatch the
     planner's large-call paths see -- three 1024-item panels in one launch per pass, the matrix-pipe table-gradient pass."""
-    dev = torch.device('cuda:0')
-    g = torch.Generator().manual_seed(5)
-    resp, mask = O.simulate_responses(3, P, I, A, generator=g, missing_frac=0.1)
-    resp, mask = resp.to(dev), mask.bool().to(dev)
-    torch.manual_seed(4)
-    m1 = VIBO_3PL(A, I, ability_merge='product', conditional_posterior=True, n_norm_flows=4).to(dev)
-    m2 = copy.deepcopy(m1)
-    t1 = FusedTrainer(m1, lr=5e-3, rng='native', seed=9)
-    t2 = FusedTrainer(m2, lr=5e-3, rng='native', seed=9)
-    rows = torch.zeros(B, dtype=torch.int64, device=dev)
-    perm = torch.randperm(P, generator=g).to(dev)
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        for it in range(3):
-            lo = (it * B) % (P - B)
-            rows.copy_(perm[lo:lo + B])
-            t1.step(resp, mask, row_index=rows)
-            t2.step(resp, mask, row_index=rows)
-    torch.cuda.current_stream().wait_stream(side)
-    torch.cuda.synchronize()
-    gr = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(gr):
-        t1.step(resp, mask, row_index=rows)
-    t2.step(resp, mask, row_index=rows)                    # (the capture ran step 4 once for t1 as well? no: capture records only)
-    gr.replay()
-    for it in range(4, 4 + replays):
-        lo = (it * B) % (P - B)
-        rows.copy_(perm[lo:lo + B])
-        gr.replay()
-        t2.step(resp, mask, row_index=rows)
-    torch.cuda.synchronize()
-    for (k, a), (_, b) in zip(m1.state_dict().items(), m2.state_dict().items()):
-        assert torch.isfinite(a).all(), k
-        assert torch.equal(a, b), (k, float((a - b).abs().max()))
+    assert_replays_bitwise(3, P, I, A, B, 4, 9, replays, side_stream_warm_up=True, check_losses=False, conditional_posterior=True,
+                           n_norm_flows=4)
 
 
 @pytest.mark.gpu

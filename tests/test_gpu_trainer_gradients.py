@@ -4,117 +4,36 @@ and Adam divides the gradient by its own running magnitude: a gradient tensor wr
 trajectory as a right one.  Here the gradient of each of three steps is read back from Adam's first moments
 (trainer_gradient_common.native_gradients) and compared with oracle.vibo_oracle.elbo_loss_and_grads in float64 AT THE PARAMETERS
 THE KERNEL STARTED THAT STEP FROM (read from the device), tensor by tensor: max|g - g64| <= tol max|g64|, tol = 1e-4
-(test_gpu_parity.TOL_GRAD) for the three IRT-decoder trainers and 2e-4 (test_gpu_decoder.py's bound on vibo_decoder_fwd_bwd) for
+(gpu_common.TOL_GRAD) for the three IRT-decoder trainers and 2e-4 (test_gpu_decoder.py's bound on vibo_decoder_fwd_bwd) for
 FusedDecoderTrainer, no entry left out.  Steps 1 and 2 run at beta = 0.7, step 3 at 1.0 through set_beta.  After each step the loss
 is compared to 1e-4 relative and the parameter update to Adam's formula in float64 within 1e-4 lr + 2^-23 |p|.
 
 Input selection (CPU): `python tests/test_gpu_trainer_gradients.py` prints, per case, the worst per-tensor distance between the
 oracle in float32 -- the reference's own arithmetic -- and in float64 on the case's inputs; a case is admitted only at a quarter
 of its bound or less (2.5e-5 / 5e-5).  Seeds 1, 2, ... were tried per case until that held; the seed and the distance it reached
-stand beside each case (measured with one CPU thread: long float32 sums depend on how many threads split them).
-test_trainer_gradient_helper.py asserts the condition over all the lists below."""
-import collections
+stand beside each case in trainer_gradient_common.py (measured with one CPU thread: long float32 sums depend on how many threads split them).
+test_trainer_gradient_helper.py asserts the condition over all of those lists."""
 import ctypes
 import os
 
 import pytest
-import torch
 
 from conftest import Golden, golden_case_files, rel_err
-from decoder_trainer_common import CLS, dev, make_problem
-from oracle import vibo_oracle as O
-from test_gpu_decoder_trainer import COND_ORACLE_CASES, ORACLE_CASES
-from test_host_logic import build_model
-from trainer_gradient_common import (BETAS, TOL_DECODER, TOL_IRT, TOL_LOSS, _record, assert_adam, assert_gradients,
-                                     assert_second_moment_saw_the_same_gradient, family, float32_oracle_distance, moments,
-                                     native_gradients, oracle_gradients, parameters)
+from golden_common import build_model
+from gpu_common import dev, record, scattered_rows
+from trainer_gradient_common import (ALL_PROBLEMS, CHUNK_CASES, COND_FLOW_CASES, DECODER_CASES, MEAN_CASES, PLAIN_CASES, TOL_DECODER, TOL_IRT,
+                                     TOL_LOSS, assert_adam, assert_gradients, assert_second_moment_saw_the_same_gradient, decoder_problem,
+                                     family, float32_oracle_distance, ident, irt_problem, moments, native_gradients, oracle_gradients,
+                                     parameters, steps_of)
 from vibo_amd import _lib, decoder, ops
 from vibo_amd.trainer import (FusedCondFlowTrainer, FusedDecoderTrainer, FusedMeanTrainer, FusedTrainer, fused_decoder_trainer_covers,
                               fused_trainer_covers)
 
 pytestmark = pytest.mark.gpu
 
-Problem = collections.namedtuple('Problem', 'model resp mask rows eps_item eps_ab')      # rows / eps_ab: one entry per step
-
-
-# ---------------------------------------------------------------------------
-# the cases.  Behind each: the seed's float32-oracle distance (worst tensor over the three steps), at most a quarter of the bound
-# ---------------------------------------------------------------------------
-# FusedTrainer, four-launch form (the folded step is tied to it bit for bit, moments included: test_folded_step_equals_the_unfolded_step)
-# (IRT, A, I, B, model kwargs, seed)
-# (1000 items x 300 persons: the [64, 1] first-layer gradient is one float32 sum over 3e5 rows in the reference's arithmetic -- 1.2e-4
-#  from fp64 summed by one thread, 3e-6 by 32 -- and still 2.3e-5 to 4.9e-5 at 1000 x 48 and 1000 x 24; 520 x 33 has room)
-PLAIN_CASES = [(2, 1, 520, 33, {}, 1),                                                          # seed 1: 1.3e-5
-               (2, 8, 200, 130, {}, 1),                                                         # seed 1: 4.8e-6
-               (3, 2, 95, 77, {}, 1),                                                           # seed 1: 1.7e-5
-               (1, 3, 64, 50, {}, 1)]                                                           # seed 1: 3.2e-6
-COND = dict(conditional_posterior=True)
-COND_FLOW_CASES = [(2, 1, 200, 130, COND, 2),                                                   # seed 2: 1.1e-6
-                   (2, 2, 1100, 48, COND, 1),                                                   # seed 1: 9.4e-7; two panels
-                   (2, 3, 95, 50, dict(n_norm_flows=2), 1),                                     # seed 1: 4.0e-6; flows only
-                   (3, 1, 120, 77, dict(COND, n_norm_flows=4), 2),                              # seed 2: 1.8e-6
-                   # (wide ability + flows: at 200 items x 48 persons no seed up to 20 keeps every cell out of the probability clamp
-                   #  band -- 1.0 to 9.7 on the flows' b; at 100 x 33 seed 15 does)
-                   (2, 8, 100, 33, dict(COND, n_norm_flows=2), 15),                             # seed 15: 7.1e-6
-                   (2, 3, 130, 60, dict(COND, n_norm_flows=2, hidden_dim=48, replace_missing_with_prior=False), 6),      # seed 6: 3.6e-6; --drop-missing
-                   (3, 1, 37, 20, dict(COND, hidden_dim=10), 1)]                                # seed 1: 2.0e-6; zero-padded tile
-# FusedMeanTrainer: the whole matrix (B + 20 persons) on steps 1 and 3, B gathered rows on step 2.  The mean encoder's posterior is
-# wide before training (sd ~ 1 per dimension): at 8 dimensions x 200 items x 150 persons, 3PL at 95 x 97 and hidden 32 at
-# 4 dimensions x 130 x 80 every seed up to 20 has cells in the clamp band (1e-2 to 0.7 on the item tensors); the shapes below are the
-# largest tried that have a seed which does not.
-MEAN_CASES = [(2, 1, 520, 33, {}, 9),                                                           # seed 9: 1.4e-5 (1000 x 300: as for the plain trainer)
-              (2, 8, 37, 20, {}, 10),                                                           # seed 10: 1.1e-6
-              (3, 2, 37, 33, {}, 6),                                                            # seed 6: 2.2e-5
-              (1, 3, 64, 50, dict(replace_missing_with_prior=False), 1),                        # seed 1: 1.4e-6
-              (2, 4, 130, 33, dict(hidden_dim=32), 17),                                         # seed 17: 1.9e-6
-              (2, 2, 130, 60, dict(hidden_dim=128), 1)]                                         # seed 1: 2.3e-6
-# FusedDecoderTrainer: the problems of test_gpu_decoder_trainer's two lists -- (decoder, IRT, A, B, I, missing, hidden, drop, seed) --
-# with seeds of this file's own rule (the last conditional one sits at 6.0e-5 with that list's seed 15 and has no seed up to 20 at
-# 100 persons x 30 items: 3PL at 12 dimensions; 20 x 12 has), and 301 persons for the person chunks
-DECODER_SEEDS = [1, 1, 1, 1, 9]                                                                 # 1.0e-5, 3.0e-6, 2.3e-6, 1.0e-6, 6.4e-6
-COND_DECODER_SEEDS = [1, 1, 1, 2]                                                               # 3.7e-6, 5.8e-7, 7.4e-7, 3.4e-6
-DECODER_CASES = ([(False, c[:-1] + (s,)) for c, s in zip(ORACLE_CASES, DECODER_SEEDS)] +
-                 [(True, c[:-1] + (s,)) for c, s in zip(COND_ORACLE_CASES, COND_DECODER_SEEDS)] +
-                 [(True, ('residual', 3, 12, 20, 12, 0.1, 48, False, 14))])                     # seed 14: 2.2e-5
-CHUNK_CASES = [(False, ('residual', 3, 3, 301, 130, 0.15, 64, False, 3)),                       # seed 3: 2.4e-5
-               (True, ('deep', 2, 3, 301, 130, 0.15, 64, False, 1))]                            # seed 1: 4.7e-6
-
-
-def irt_problem(irt, A, I, B, kw, seed, mean=False):
-    """The data and noise of an IRT-decoder case, as make_problem draws them: responses with 15 % missing, three steps' noise."""
-    g = torch.Generator().manual_seed(seed)
-    P = B + 20 if mean else B
-    resp, mask = O.simulate_responses(irt, P, I, A, generator=g, missing_frac=0.15)
-    if mean:
-        mask[:, 0] = 1                  # (a person without an observed item has no mean: NaN in the reference too)
-        resp[:, 0] = resp[:, 0].clamp(min=0)
-    rows = [None, torch.randperm(P, generator=g)[:B], None] if mean else [None] * 3
-    eps_item = torch.randn(3, I, O.item_feat_dim(irt, A), generator=g)
-    eps_ab = [torch.randn(P if r is None else B, A, generator=g) for r in rows]
-    torch.manual_seed(seed)
-    model = CLS[irt](A, I, ability_merge='mean' if mean else 'product', **kw)
-    return Problem(model, resp, mask, rows, eps_item, eps_ab)
-
-
-def decoder_problem(conditional, case):
-    model, resp, mask, eps_item, eps_ab = make_problem(conditional, *case)
-    return Problem(model, resp, mask, [None] * 3, eps_item, list(eps_ab))
-
-
-def steps_of(p):
-    """Per step what the oracle sees: (resp, mask, eps_item, eps_ab, beta)."""
-    return [(p.resp if r is None else p.resp[r], p.mask if r is None else p.mask[r], p.eps_item[t], p.eps_ab[t], BETAS[t])
-            for t, r in enumerate(p.rows)]
-
-
-ALL_PROBLEMS = ([('plain', TOL_IRT, c, lambda c=c: irt_problem(*c)) for c in PLAIN_CASES] +
-                [('cond/flow', TOL_IRT, c, lambda c=c: irt_problem(*c)) for c in COND_FLOW_CASES] +
-                [('mean', TOL_IRT, c, lambda c=c: irt_problem(*c, mean=True)) for c in MEAN_CASES] +
-                [('decoder', TOL_DECODER, c, lambda c=c: decoder_problem(*c)) for c in DECODER_CASES + CHUNK_CASES])
-
 
 def print_float32_oracle_distances():
-    """Input selection for every list above (CPU only)."""
+    """Input selection for every list of trainer_gradient_common.py (CPU only)."""
     for kind, tol, case, make in ALL_PROBLEMS:
         p = make()
         dist, name, step = float32_oracle_distance(p.model, steps_of(p))
@@ -132,12 +51,7 @@ def resident_rows(p, rows_mode, d):
         r, m = ops.pad_rows(p.resp.to(d), p.mask.bool().to(d))
         return r, m, [None if x is None else x.to(d) for x in p.rows]
     assert all(x is None for x in p.rows)
-    B, I = p.resp.shape
-    g = torch.Generator().manual_seed(B * I)
-    big_r = (torch.rand(2 * B + 5, I, generator=g) < 0.5).float()
-    big_m = torch.rand(2 * B + 5, I, generator=g) < 0.8
-    where = torch.randperm(2 * B + 5, generator=g)[:B]
-    big_r[where], big_m[where] = p.resp, p.mask.bool()
+    big_r, big_m, where = scattered_rows(p.resp, p.mask, 2 * p.resp.shape[0] + 5)
     r, m = ops.pad_rows(big_r.to(d), big_m.to(d))
     if rows_mode == 'codes':
         r, m = ops.pack_cell_codes(r, m), None
@@ -167,10 +81,6 @@ def run_three_steps(p, what, tol, want_class, lr=5e-3, rows_mode='dense', kernel
             assert_second_moment_saw_the_same_gradient(got, what)
         assert_adam(tr, p_before, before, got, lr, t, what)
     return tr
-
-
-def ident(case):
-    return '-'.join(str(x) if not isinstance(x, dict) else '+'.join(f'{k}={v}' for k, v in x.items()) or 'plain' for x in case)
 
 
 @pytest.mark.parametrize('rows_mode', ['dense', 'gathered', 'codes'])
@@ -252,7 +162,7 @@ def golden_trainer(golden, model):
 @pytest.mark.parametrize('path', golden_case_files(), ids=lambda p: os.path.basename(p)[5:-4])
 def test_reference_gradients_through_the_native_step(path):
     """One native step with the golden's noise and annealing factor; native_gradients against the reference's own fp32 gradient
-    (grad.*) by the rule test_host_logic.check_against_golden(strict=True) holds the module path to: within the bound of the fp64
+    (grad.*) by the rule golden_common.check_against_golden(strict=True) holds the module path to: within the bound of the fp64
     gradient or of the reference's; where the reference itself is >= 1e-2 from fp64 (3PL cells in the probability clamp band),
     within 6 % of the reference's own distance."""
     golden = Golden(path)
@@ -279,8 +189,8 @@ def test_reference_gradients_through_the_native_step(path):
         e_truth, e_ref, ref_off = rel_err(g, truth[name]), rel_err(g, g_ref), rel_err(g_ref, truth[name])
         tol = tol_grad if ref_off < 1e-2 else max(tol_grad, 0.06 * ref_off)
         print(f'{name}: to fp64 {e_truth:.3e}  to the reference {e_ref:.3e}  reference to fp64 {ref_off:.3e}  bound {tol:.1e}')
-        _record({'kind': 'trainer_grad_golden', 'what': type(tr).__name__, 'name': name, 'family': family(name), 'err': min(e_truth, e_ref),
-                 'e_truth': e_truth, 'e_ref': e_ref, 'ref_off': ref_off, 'tol': tol})
+        record('trainer_grad_golden', min(e_truth, e_ref), tol, what=type(tr).__name__, name=name, family=family(name), e_truth=e_truth,
+               e_ref=e_ref, ref_off=ref_off)
         if not min(e_truth, e_ref) < tol:
             bad.append((name, e_truth, e_ref, ref_off))
     assert not bad, bad

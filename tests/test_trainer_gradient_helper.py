@@ -5,9 +5,8 @@ import torch
 
 from decoder_trainer_common import CLS
 from oracle import vibo_oracle as O
-from test_gpu_trainer_gradients import ALL_PROBLEMS, ident, steps_of
-from trainer_gradient_common import (BETAS, _by_name, adam_step_error, assert_gradients, float32_oracle_distance, layout, moments, native_gradients,
-                                     oracle_gradients, parameters)
+from trainer_gradient_common import (ALL_PROBLEMS, BETAS, _by_name, adam_step_error, assert_gradients, float32_oracle_distance, ident, layout, moments,
+                                     native_gradients, oracle_gradients, parameters, steps_of)
 from vibo_amd.trainer import FusedTrainer
 
 

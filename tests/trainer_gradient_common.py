@@ -1,14 +1,15 @@
 """The native trainers' gradients and Adam arithmetic, read back from Adam's own moments (test_gpu_trainer_gradients.py,
-test_trainer_gradient_helper.py).  Every fused trainer keeps the moments in tensors a test can read (`mlp_m` / `par_m`, `mlp_v` /
-`par_v`, `item_m`, `item_v`), and adam_update (csrc/vibo_train_hook.hpp) sets m = fma(0.9f, m, 0.1f g), v = fma(0.999f, v, (0.001f g) g):
+test_trainer_gradient_helper.py), and the cases both files run over.  Every fused trainer keeps the moments in tensors a test can
+read (`mlp_m` / `par_m`, `mlp_v` / `par_v`, `item_m`, `item_v`), and adam_update (csrc/vibo_train_hook.hpp) sets m = fma(0.9f, m, 0.1f g), v = fma(0.999f, v, (0.001f g) g):
 after the first step of a fresh trainer m = 0.1f g gives g back to one ulp, later g_t = (m_t - 0.9f m_{t-1}) / 0.1f.  The gradient is
 thus compared by MAGNITUDE with the fp64 oracle at the parameters the kernel itself differentiated at -- no trajectory, no exclusion
 rule -- and Adam's update is checked from the kernel's own m, v and parameters."""
-import json
-import os
+import collections
 
 import torch
 
+from decoder_trainer_common import COND_ORACLE_CASES, ORACLE_CASES, make_problem
+from gpu_common import CLS, record, simulated
 from oracle import vibo_oracle as O
 
 _f32 = lambda x: float(torch.tensor(x, dtype=torch.float32))
@@ -16,8 +17,90 @@ B1, W1, B2, W2 = _f32(0.9), _f32(0.1), _f32(0.999), _f32(0.001)      # adam_upda
 U = 2.0 ** -24                                                       # half an fp32 ulp, relative
 DENORM = 2.0 ** -149
 TOL_LOSS = 1e-4                                                      # TOL_ELBO of the trajectory tests
-TOL_IRT, TOL_DECODER = 1e-4, 2e-4                                    # test_gpu_parity.TOL_GRAD; test_gpu_decoder.py's bound on vibo_decoder_fwd_bwd
+TOL_IRT, TOL_DECODER = 1e-4, 2e-4                                    # gpu_common.TOL_GRAD; test_gpu_decoder.py's bound on vibo_decoder_fwd_bwd
 BETAS = (0.7, 0.7, 1.0)                                              # the KL weight of the three steps
+
+
+Problem = collections.namedtuple('Problem', 'model resp mask rows eps_item eps_ab')      # rows / eps_ab: one entry per step
+
+
+# ---------------------------------------------------------------------------
+# the cases.  Behind each: the seed's float32-oracle distance (worst tensor over the three steps), at most a quarter of the bound
+# ---------------------------------------------------------------------------
+# FusedTrainer, four-launch form (the folded step is tied to it bit for bit, moments included: test_folded_step_equals_the_unfolded_step)
+# (IRT, A, I, B, model kwargs, seed)
+# (1000 items x 300 persons: the [64, 1] first-layer gradient is one float32 sum over 3e5 rows in the reference's arithmetic -- 1.2e-4
+#  from fp64 summed by one thread, 3e-6 by 32 -- and still 2.3e-5 to 4.9e-5 at 1000 x 48 and 1000 x 24; 520 x 33 has room)
+PLAIN_CASES = [(2, 1, 520, 33, {}, 1),                                                          # seed 1: 1.3e-5
+               (2, 8, 200, 130, {}, 1),                                                         # seed 1: 4.8e-6
+               (3, 2, 95, 77, {}, 1),                                                           # seed 1: 1.7e-5
+               (1, 3, 64, 50, {}, 1)]                                                           # seed 1: 3.2e-6
+COND = dict(conditional_posterior=True)
+COND_FLOW_CASES = [(2, 1, 200, 130, COND, 2),                                                   # seed 2: 1.1e-6
+                   (2, 2, 1100, 48, COND, 1),                                                   # seed 1: 9.4e-7; two panels
+                   (2, 3, 95, 50, dict(n_norm_flows=2), 1),                                     # seed 1: 4.0e-6; flows only
+                   (3, 1, 120, 77, dict(COND, n_norm_flows=4), 2),                              # seed 2: 1.8e-6
+                   # (wide ability + flows: at 200 items x 48 persons no seed up to 20 keeps every cell out of the probability clamp
+                   #  band -- 1.0 to 9.7 on the flows' b; at 100 x 33 seed 15 does)
+                   (2, 8, 100, 33, dict(COND, n_norm_flows=2), 15),                             # seed 15: 7.1e-6
+                   (2, 3, 130, 60, dict(COND, n_norm_flows=2, hidden_dim=48, replace_missing_with_prior=False), 6),      # seed 6: 3.6e-6; --drop-missing
+                   (3, 1, 37, 20, dict(COND, hidden_dim=10), 1)]                                # seed 1: 2.0e-6; zero-padded tile
+# FusedMeanTrainer: the whole matrix (B + 20 persons) on steps 1 and 3, B gathered rows on step 2.  The mean encoder's posterior is
+# wide before training (sd ~ 1 per dimension): at 8 dimensions x 200 items x 150 persons, 3PL at 95 x 97 and hidden 32 at
+# 4 dimensions x 130 x 80 every seed up to 20 has cells in the clamp band (1e-2 to 0.7 on the item tensors); the shapes below are the
+# largest tried that have a seed which does not.
+MEAN_CASES = [(2, 1, 520, 33, {}, 9),                                                           # seed 9: 1.4e-5 (1000 x 300: as for the plain trainer)
+              (2, 8, 37, 20, {}, 10),                                                           # seed 10: 1.1e-6
+              (3, 2, 37, 33, {}, 6),                                                            # seed 6: 2.2e-5
+              (1, 3, 64, 50, dict(replace_missing_with_prior=False), 1),                        # seed 1: 1.4e-6
+              (2, 4, 130, 33, dict(hidden_dim=32), 17),                                         # seed 17: 1.9e-6
+              (2, 2, 130, 60, dict(hidden_dim=128), 1)]                                         # seed 1: 2.3e-6
+# FusedDecoderTrainer: the problems of decoder_trainer_common's two lists -- (decoder, IRT, A, B, I, missing, hidden, drop, seed) --
+# with seeds of this file's own rule (the last conditional one sits at 6.0e-5 with that list's seed 15 and has no seed up to 20 at
+# 100 persons x 30 items: 3PL at 12 dimensions; 20 x 12 has), and 301 persons for the person chunks
+DECODER_SEEDS = [1, 1, 1, 1, 9]                                                                 # 1.0e-5, 3.0e-6, 2.3e-6, 1.0e-6, 6.4e-6
+COND_DECODER_SEEDS = [1, 1, 1, 2]                                                               # 3.7e-6, 5.8e-7, 7.4e-7, 3.4e-6
+DECODER_CASES = ([(False, c[:-1] + (s,)) for c, s in zip(ORACLE_CASES, DECODER_SEEDS)] +
+                 [(True, c[:-1] + (s,)) for c, s in zip(COND_ORACLE_CASES, COND_DECODER_SEEDS)] +
+                 [(True, ('residual', 3, 12, 20, 12, 0.1, 48, False, 14))])                     # seed 14: 2.2e-5
+CHUNK_CASES = [(False, ('residual', 3, 3, 301, 130, 0.15, 64, False, 3)),                       # seed 3: 2.4e-5
+               (True, ('deep', 2, 3, 301, 130, 0.15, 64, False, 1))]                            # seed 1: 4.7e-6
+
+
+def irt_problem(irt, A, I, B, kw, seed, mean=False):
+    """The data and noise of an IRT-decoder case, as make_problem draws them: responses with 15 % missing, three steps' noise."""
+    P = B + 20 if mean else B
+    resp, mask, g = simulated(irt, P, I, A, 0.15, seed)
+    if mean:
+        mask[:, 0] = 1                  # (a person without an observed item has no mean: NaN in the reference too)
+        resp[:, 0] = resp[:, 0].clamp(min=0)
+    rows = [None, torch.randperm(P, generator=g)[:B], None] if mean else [None] * 3
+    eps_item = torch.randn(3, I, O.item_feat_dim(irt, A), generator=g)
+    eps_ab = [torch.randn(P if r is None else B, A, generator=g) for r in rows]
+    torch.manual_seed(seed)
+    model = CLS[irt](A, I, ability_merge='mean' if mean else 'product', **kw)
+    return Problem(model, resp, mask, rows, eps_item, eps_ab)
+
+
+def decoder_problem(conditional, case):
+    model, resp, mask, eps_item, eps_ab = make_problem(conditional, *case)
+    return Problem(model, resp, mask, [None] * 3, eps_item, list(eps_ab))
+
+
+def steps_of(p):
+    """Per step what the oracle sees: (resp, mask, eps_item, eps_ab, beta)."""
+    return [(p.resp if r is None else p.resp[r], p.mask if r is None else p.mask[r], p.eps_item[t], p.eps_ab[t], BETAS[t])
+            for t, r in enumerate(p.rows)]
+
+
+ALL_PROBLEMS = ([('plain', TOL_IRT, c, lambda c=c: irt_problem(*c)) for c in PLAIN_CASES] +
+                [('cond/flow', TOL_IRT, c, lambda c=c: irt_problem(*c)) for c in COND_FLOW_CASES] +
+                [('mean', TOL_IRT, c, lambda c=c: irt_problem(*c, mean=True)) for c in MEAN_CASES] +
+                [('decoder', TOL_DECODER, c, lambda c=c: decoder_problem(*c)) for c in DECODER_CASES + CHUNK_CASES])
+
+
+def ident(case):
+    return '-'.join(str(x) if not isinstance(x, dict) else '+'.join(f'{k}={v}' for k, v in x.items()) or 'plain' for x in case)
 
 
 # ---------------------------------------------------------------------------
@@ -117,12 +200,6 @@ def family(name):
     return 'decoder stacks' if name.startswith('decoder.') else 'encoder MLP'
 
 
-def _record(entry):
-    if os.environ.get('VIBO_TOL_RECORD'):
-        with open(os.environ['VIBO_TOL_RECORD'], 'a') as f:
-            f.write(json.dumps(dict(entry, test=os.environ.get('PYTEST_CURRENT_TEST', ''))) + '\n')
-
-
 def assert_gradients(got, want, tol, what):
     """Tensor by tensor: max|got - want| <= tol * max|want|; a tensor whose oracle gradient is identically zero must be exactly
     zero.  No entry is left out.  Every tensor is printed and recorded (VIBO_TOL_RECORD, kind 'trainer_grad') before the assert."""
@@ -135,7 +212,7 @@ def assert_gradients(got, want, tol, what):
         ok = err <= tol * top                              # (top == 0: only an exactly zero gradient passes)
         rel = err / top if top > 0 else (0.0 if err == 0 else float('inf'))
         print(f'{what} {k}: max|g| {top:.3e}  err/max {rel:.3e}  err/bound {rel / tol:.3f}')
-        _record({'kind': 'trainer_grad', 'what': what, 'name': k, 'family': family(k), 'err': rel, 'tol': tol})
+        record('trainer_grad', rel, tol, what=what, name=k, family=family(k))
         if not ok:
             bad.append((k, rel))
     assert not bad, (what, tol, bad)
@@ -174,7 +251,7 @@ def assert_adam(tr, p_before, before, g, lr, t, what):
         err, bound = adam_step_error(p_before[b], p_after[b], now[b + '_m'], now[b + '_v'], lr, t)
         worst = float((err / bound).max())
         print(f'{what} step {t} {b}: Adam update, worst error / bound {worst:.3f} (largest error {float(err.max()):.3e})')
-        _record({'kind': 'trainer_adam', 'what': what, 'name': b, 'step': t, 'err': float(err.max()), 'ratio': worst, 'tol': 1e-4 * lr})
+        record('trainer_adam', err.max(), 1e-4 * lr, what=what, name=b, step=t, ratio=worst)
         assert bool((err <= bound).all()), (what, b, t, worst, int((err > bound).sum()))
         v_want = B2 * before[b + '_v'] + W2 * g.flat[b] ** 2
         # From the second step on g_t itself is known only to U (|g_t| + 10 |m_t|) -- m_t's own rounding, divided by 0.1 -- and

@@ -13,7 +13,7 @@ for p in (ROOT, os.path.join(ROOT, 'variational-item-response-theory-public_amd'
 import torch
 from vibo_amd import decoder as D
 from vibo_amd import ops
-from test_gpu_decoder import torch_reference, rel
+from gpu_common import torch_reference, rel
 
 ap = argparse.ArgumentParser()
 ap.add_argument('--seconds', type=float, default=120)
