@@ -479,8 +479,14 @@ int vibo_code_table_sum_backward(int64_t num_person, int num_item, int hidden_di
  * Standard-normal fill for the reparameterisation noise (replaces the torch.randn_like calls of utils.py:85-88 as
  * used at models.py:361,368 when the caller does not need PyTorch's generator stream):
  *     out[i] ~ N(0,1),  Philox4x32-10 keyed by `seed`, counter (i / 4, *step_count, stream_id), Box-Muller.
- * The step number is read on the device, so a captured hipGraph draws fresh noise on every replay (the prologue
- * increments step_count).  Deterministic: same (seed, step, stream_id, i) -> same value.
+ * Word by word: group g = i / 4 has the counter (g & 0xffffffff, g >> 32, (uint32_t)*step_count, stream_id) and the key
+ * (seed & 0xffffffff, seed >> 32); of its four output words, u0 = ((c0 >> 8) + 1) / 2^24 and u2 (likewise from c2) in (0, 1]
+ * are the radius uniforms, u1 = (c1 >> 8) / 2^24 and u3 (from c3) in [0, 1) the angles, and
+ *     out[4g .. 4g + 3] = r0 cos 2 pi u1, r0 sin 2 pi u1, r1 cos 2 pi u3, r1 sin 2 pi u3,  r0 = sqrt(-2 ln u0), r1 = sqrt(-2 ln u2).
+ * (oracle/philox_ref.py is this paragraph in numpy; tests/test_gpu_noise.py holds the kernel to it entry by entry.)
+ * The step number is read on the device, so a captured hipGraph draws fresh noise on every replay: the trainers pass
+ * step_count + 1, the number of completed steps, which the train step's epilogue increments (the prologue increments
+ * step_count[0], Adam's step).  Deterministic: same (seed, step, stream_id, i) -> same value.
  */
 int vibo_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* step_count, uint32_t stream_id, void* stream);
 

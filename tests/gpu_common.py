@@ -1,6 +1,6 @@
 """What the GPU tests share, once each: the device, the seeded random ELBO problems, the one launch of the ELBO kernel, the
-comparison with the fp64 table oracle and its tolerances, the VIBO_TOL_RECORD writer, the kernel-pin fixture, twin trainers, and
-the float64 statement of the MLP decoder.  A plain module (tools/ import it too), importable without a GPU: only calling dev() needs one."""
+comparison with the fp64 table oracle and its tolerances, the VIBO_TOL_RECORD writer, the kernel-pin fixture, twin trainers, the
+native noise at a counter of the test's own, and the float64 statement of the MLP decoder.  A plain module (tools/ import it too), importable without a GPU: only calling dev() needs one."""
 import copy
 import json
 import os
@@ -211,6 +211,25 @@ def twin_trainers(cls, A, I, model_seed, kw_a, kw_b=None, **model_kw):
 def assert_same_parameters(m_a, m_b):
     for (k, a), (_, b) in zip(m_a.state_dict().items(), m_b.state_dict().items()):
         assert torch.equal(a, b), (k, float((a - b).abs().max()))
+
+
+# ---------------------------------------------------------------------------
+# the native noise at a counter of the test's own (test_gpu_noise.py)
+# ---------------------------------------------------------------------------
+def noise_counter(step):
+    """The int32 device word vibo_fill_normal reads its step from, holding `step` (as uint32 bits: 2^31 ... 2^32 - 1 wrap)."""
+    step = int(step) & 0xFFFFFFFF
+    return torch.tensor([step - (1 << 32) if step >= 1 << 31 else step], dtype=torch.int32, device=dev())
+
+
+def fill_normal(n, seed, counter, stream_id, out=None):
+    """vibo_fill_normal(out, n, seed, counter, stream_id) on torch's current stream -> out: a fresh float32 tensor [n], or the
+    caller's (a contiguous float32 view of at least n entries, wherever it starts)."""
+    if out is None:
+        out = torch.empty(n, device=counter.device)
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= n and counter.dtype == torch.int32
+    ops._call('vibo_fill_normal', ops._ptr(out), n, int(seed), ops._ptr(counter), int(stream_id), ops._stream(counter.device))
+    return out
 
 
 # ---------------------------------------------------------------------------
