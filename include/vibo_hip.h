@@ -498,13 +498,35 @@ int vibo_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* step_c
  *     out_scalars[s][VIBO_NUM_SCALARS]   same heads as vibo_elbo_fwd_bwd's out_scalars, per sample
  * Posterior outputs and gradients are not produced.  Returns -8 when nothing can be shared between the samples or
  * the descriptor is not on the row-split path (conditional posterior: its table depends on the item sample; int64
- * masks; unaligned rows): loop over vibo_elbo_fwd_bwd instead.
+ * masks; unaligned rows): loop over vibo_elbo_fwd_bwd instead.  VIBO_POSTERIOR_GIVEN descriptors are refused with -8 too:
+ * vibo_elbo_multi_forward_given below is their call.
  * Workspace: vibo_multi_workspace_bytes(d, num_samples) bytes, 256-byte aligned.
  */
 size_t vibo_multi_workspace_bytes(const vibo_desc* d, int num_samples);
 int vibo_elbo_multi_forward(const vibo_desc* d, int num_samples, const float* response, const void* mask,
                             const int64_t* row_index, const float* table, const float* item, const float* eps,
                             const float* flow, float* out_scalars, void* workspace, size_t workspace_bytes, void* stream);
+
+/*
+ * The same pass for a caller-supplied posterior (d->posterior must be VIBO_POSTERIOR_GIVEN: --ability-merge mean with or without
+ * the conditional posterior, VI_1PL/2PL/3PL), which vibo_elbo_multi_forward refuses with -8.  `posterior` holds mu | logvar rows
+ * [num_person][2 ability_dim] in minibatch order (like eps; row_index gathers the response rows only), sample s at
+ * posterior + s * posterior_sample_stride:
+ *     posterior_sample_stride == 0                              one posterior for all samples (mean merge from the row counts, VI's
+ *                                                               embedding rows): its per-person part is computed once per batch of rows
+ *     posterior_sample_stride == num_person * 2 * ability_dim   one posterior per sample, [num_samples][num_person][2 ability_dim]
+ *                                                               (mean merge x conditional posterior)
+ * Any other stride returns -3.  The heads are those of num_samples vibo_elbo_fwd_bwd calls with that posterior (lam = exp(-logvar),
+ * every cell counted as observed: no missing-prior expert, NOBS = num_person * num_item).  Shapes: those of VIBO_POSTERIOR_GIVEN
+ * (4..32767 items, rows chunkable in 4 cells, no int64 mask, ability_dim <= 8; rows of more than 1024 items run as panels, without a
+ * pre-pass); outside them -8 as above.
+ * Workspace: vibo_multi_given_workspace_bytes(d, num_samples) bytes, 256-byte aligned (0: no plan for the descriptor).
+ */
+size_t vibo_multi_given_workspace_bytes(const vibo_desc* d, int num_samples);
+int vibo_elbo_multi_forward_given(const vibo_desc* d, int num_samples, const float* response, const void* mask,
+                                  const int64_t* row_index, const float* posterior, int64_t posterior_sample_stride,
+                                  const float* item, const float* eps, const float* flow, float* out_scalars,
+                                  void* workspace, size_t workspace_bytes, void* stream);
 
 /*
  * The per-term MLP decoders of --generative-model link | deep | residual (LinkedIRT / DeepIRT / ResidualIRT,

@@ -404,17 +404,23 @@ def critlangacq_case(out_dir):
     np.savez_compressed(os.path.join(out_dir, 'critlangacq_loader.npz'), **rec)
 
 
-def log_marginal_case(ref_models, out_dir):
+def log_marginal_case(ref_models, out_dir, only=''):
     """log_marginal (models.py:445-504) with S=8 under a fixed seed; the eps
     sequence (item then ability, per sample) is stored so it can be replayed."""
-    for name, irt, A, B, I, cond, missing, flows in (
-            ('logmarg_2pl_a2', 2, 2, 16, 20, False, 0.2, 0),
-            ('logmarg_3pl_a1_cond_flows2', 3, 1, 16, 20, True, 0.0, 2)):
+    for name, irt, A, B, I, cond, missing, flows, merge in (
+            ('logmarg_2pl_a2', 2, 2, 16, 20, False, 0.2, 0, 'product'),
+            ('logmarg_3pl_a1_cond_flows2', 3, 1, 16, 20, True, 0.0, 2, 'product'),
+            # --ability-merge mean: the posterior reaches the kernel as given (vibo_elbo_multi_forward_given)
+            ('logmarg_2pl_a2_mean', 2, 2, 16, 20, False, 0.2, 0, 'mean'),
+            ('logmarg_2pl_a2_cond_mean', 2, 2, 16, 20, True, 0.2, 0, 'mean'),
+            ('logmarg_3pl_a1_mean_flows2', 3, 1, 16, 20, False, 0.0, 2, 'mean')):
+        if only and name != only:
+            continue
         seed = 77 + len(name)
         resp, mask = make_data(irt, B, I, A, missing, seed)
         cls = {1: ref_models.VIBO_1PL, 2: ref_models.VIBO_2PL, 3: ref_models.VIBO_3PL}[irt]
         torch.manual_seed(seed)
-        model = cls(A, I, ability_merge='product', conditional_posterior=cond, n_norm_flows=flows)
+        model = cls(A, I, ability_merge=merge, conditional_posterior=cond, n_norm_flows=flows)
         D = model.item_feat_dim
         S = 8
         torch.manual_seed(seed + 5)
@@ -428,7 +434,7 @@ def log_marginal_case(ref_models, out_dir):
             'meta': json.dumps(dict(name=name, irt_model=irt, ability_dim=A, num_person=B, num_item=I,
                                     conditional_posterior=cond, missing_frac=missing,
                                     replace_missing_with_prior=True, n_norm_flows=flows,
-                                    num_samples=S, hidden_dim=64)),
+                                    num_samples=S, hidden_dim=64, **({} if merge == 'product' else {'ability_merge': merge}))),
             'response': resp.numpy().astype(np.int8), 'mask': mask.numpy().astype(np.uint8),
             'eps_item': torch.stack(ei).numpy(), 'eps_ability': torch.stack(ea).numpy(),
             'out.logp': logp.detach().numpy(),
@@ -477,6 +483,8 @@ def main():
         print(f'{case[0]:34s} loss={run_mle_case(ref_models, case, out_dir):.6f}')
     if args.only == 'saturation_3pl':         # MKL_CBWR=COMPATIBLE python tools/gen_golden.py --only saturation_3pl
         saturation_3pl_case(ref_models, ref_utils, out_dir)
+    if args.only.startswith('logmarg_'):      # one log_marginal golden by its full name
+        log_marginal_case(ref_models, out_dir, only=args.only)
     if not args.only:
         saturation_case(ref_utils, out_dir)
         saturation_3pl_case(ref_models, ref_utils, out_dir)

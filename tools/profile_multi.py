@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Multi-sample forward (log_marginal's loop body) vs one forward launch per sample.
-   python tools/profile_multi.py [--persons P] [--items I] [--ability-dim A] [--samples S]"""
+   python tools/profile_multi.py [--persons P] [--items I] [--ability-dim A] [--samples S] [--given [--per-sample]]
+--given: a caller-supplied posterior (VIBO_POSTERIOR_GIVEN: --ability-merge mean, VI_*PL) through vibo_elbo_multi_forward_given,
+one [P, 2A] posterior for all samples, or with --per-sample one per sample ([S, P, 2A]: mean merge x conditional posterior); the
+singles leg is then one GIVEN forward launch (want_grad = 0) per sample."""
 import argparse
 import os
 import sys
@@ -21,14 +24,20 @@ ap.add_argument('--samples', type=int, default=16)
 ap.add_argument('--irt', type=int, default=2)
 ap.add_argument('--codes', action='store_true', help='rows as 1-byte cell codes (VIBO_MASK_CODES)')
 ap.add_argument('--gather', action='store_true')
+ap.add_argument('--given', action='store_true', help='caller-supplied posterior, shared by the samples')
+ap.add_argument('--per-sample', action='store_true', help='with --given: one posterior per sample')
+ap.add_argument('--reps', type=int, default=3)
 a = ap.parse_args()
 d = torch.device('cuda:0')
 g = torch.Generator(device=d).manual_seed(0)
 P, I, A, S = a.persons, a.items, a.ability_dim, a.samples
-spec = ElboSpec(irt_model=a.irt, ability_dim=A)
+spec = ElboSpec(irt_model=a.irt, ability_dim=A, given=a.given)
 resp = (torch.rand(P, I, device=d, generator=g) < 0.5).float()
 mask = torch.rand(P, I, device=d, generator=g) >= 0.1
 table = torch.randn(2, 2 * A, device=d, generator=g) * 0.5
+if a.given:      # mu = 0.5 randn | logvar = -1 + 0.5 randn
+    shape = (S, P, A) if a.per_sample else (P, A)
+    table = torch.cat([0.5 * torch.randn(shape, device=d, generator=g), -1.0 + 0.5 * torch.randn(shape, device=d, generator=g)], dim=-1)
 items = torch.randn(S, I, spec.item_dim, device=d, generator=g)
 eps = torch.randn(S, P, A, device=d, generator=g)
 m, code = ops.prepare_mask(mask)
@@ -42,17 +51,19 @@ def multi():
 
 
 def singles():
-    return [ops._hip_launch_elbo(spec, resp, m, code, ridx, table, items[s], eps[s], None, _lib.REG_SAMPLED, False, P).scalars
-            for s in range(S)]
+    return [ops._hip_launch_elbo(spec, resp, m, code, ridx, table[s] if a.given and a.per_sample else table, items[s], eps[s], None,
+                                 _lib.REG_SAMPLED, False, P).scalars for s in range(S)]
 
 
 for name, f in (('multi-sample kernel', multi), ('one launch per sample', singles)):
-    f()
+    if f() is None:
+        print(f'{name}: this library does not cover the configuration')
+        continue
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    for _ in range(3):
+    for _ in range(a.reps):
         f()
     torch.cuda.synchronize()
-    dt = (time.perf_counter() - t0) / 3
-    print(f'P={P} I={I} A={A} S={S} codes={a.codes} gather={a.gather} {name:24s}: {dt * 1e3:8.3f} ms = {dt * 1e3 / S:6.3f} ms per sample, '
+    dt = (time.perf_counter() - t0) / a.reps
+    print(f'P={P} I={I} A={A} S={S} codes={a.codes} gather={a.gather} given={a.given} per_sample={a.per_sample} {name:24s}: {dt * 1e3:8.3f} ms = {dt * 1e3 / S:6.3f} ms per sample, '
           f'{P * I * S / dt / 1e12:.3f} T sample-terms/s')

@@ -569,9 +569,19 @@ size_t vibo_multi_workspace_bytes(const vibo_desc* d, int num_samples) {
     return pl.total_bytes + 4 * prep;
 }
 
-int vibo_elbo_multi_forward(const vibo_desc* d, int num_samples, const float* response, const void* mask,
-                            const int64_t* row_index, const float* table, const float* item, const float* eps,
-                            const float* flow, float* out_scalars, void* workspace, size_t workspace_bytes, void* stream) {
+size_t vibo_multi_given_workspace_bytes(const vibo_desc* d, int num_samples) {
+    if (check_desc(d) != 0 || num_samples < 1) return 0;
+    vibo_desc d0;
+    Plan pl;
+    size_t prep = 0;
+    if (multi_plan(d, device_cus(), &d0, &pl, &prep, true) != 0) return 0;
+    return pl.total_bytes + 4 * prep;
+}
+
+// both multi-sample calls: `table` is the 2-row expert table, or (given) the caller's posterior with post_sstride floats between the samples'
+static int multi_forward_impl(const vibo_desc* d, bool given, int num_samples, const float* response, const void* mask,
+                              const int64_t* row_index, const float* table, long long post_sstride, const float* item, const float* eps,
+                              const float* flow, float* out_scalars, void* workspace, size_t workspace_bytes, void* stream) {
     const int num_cu = device_cus();
     int rc = check_desc(d);
     if (rc) return rc;
@@ -582,8 +592,10 @@ int vibo_elbo_multi_forward(const vibo_desc* d, int num_samples, const float* re
     vibo_desc d0;
     Plan pl;
     size_t prep = 0;
-    rc = multi_plan(d, num_cu, &d0, &pl, &prep);
+    rc = multi_plan(d, num_cu, &d0, &pl, &prep, given);
     if (rc) return rc;
+    if (given && post_sstride != 0 && post_sstride != (long long)d->num_person * 2 * d->ability_dim)
+        return fail(-3, "posterior_sample_stride must be 0 (one posterior for all samples) or num_person * 2 * ability_dim");
     if (!workspace || workspace_bytes < pl.total_bytes + 4 * prep) return fail(-7, "workspace too small");
     if ((uintptr_t)workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
     const int I = d->num_item, A = d->ability_dim;
@@ -605,8 +617,9 @@ int vibo_elbo_multi_forward(const vibo_desc* d, int num_samples, const float* re
     p.flow = flow; p.n_flows = d->n_flows; p.lay = pl.lay; p.I_total = I; p.primary = 1;
     mp.item_sstride = (long long)(prep / 4);
     mp.eps_sstride = (long long)d->num_person * A;
+    mp.post_sstride = given ? post_sstride : 0;
     hipError_t e = hipSuccess;
-    if (pl.path == Path::Panels) {             // sample-independent: whole-row counts
+    if (pl.path == Path::Panels && !given) {   // sample-independent: whole-row counts (given: the slot lanes read the posterior themselves)
         int* cnt = reinterpret_cast<int*>(wsb + pl.off_cnt);
         e = launch_row_counts(d, num_cu, response, mask, row_index, cnt, nullptr, 0, s);
         p.row_cnt = cnt;
@@ -620,12 +633,13 @@ int vibo_elbo_multi_forward(const vibo_desc* d, int num_samples, const float* re
             (void)launch_item_prep(item + (size_t)(s0 + k) * I * pl.D, item_prep + (size_t)k * (prep / 4), I, A, pl.AT, pl.D, pl.DP,
                                    d->irt_model, s);      // (a failed launch shows at the next check)
         p.eps = eps + (size_t)s0 * d->num_person * A;
+        if (given) p.given_post = table + (size_t)s0 * post_sstride;
         for (int pn = 0; pn < panels && e == hipSuccess; ++pn) {
             p.item0 = pn * 1024;
             p.I = pl.panels > 0 ? (I - p.item0 < 1024 ? I - p.item0 : 1024) : I;
             p.primary = pn == 0 ? 1 : 0;
             p.partial = partial + (size_t)pn * nblk * pl.lay.stride;
-            e = launch_elbo_multi(mp, pl.AT, d->irt_model, sc, (p.I + 255) / 256, nblk, s);
+            e = (given ? launch_elbo_multi_given : launch_elbo_multi)(mp, pl.AT, d->irt_model, sc, (p.I + 255) / 256, nblk, s);
         }
         if (e != hipSuccess) return hip_fail(e, "multi-sample forward launch");
         e = launch_multi_finalize(partial, out_scalars + (size_t)s0 * VIBO_NUM_SCALARS, panels * nblk, pl.lay.stride, sc, d->reg_mode, s);
@@ -633,6 +647,21 @@ int vibo_elbo_multi_forward(const vibo_desc* d, int num_samples, const float* re
         s0 += sc;
     }
     return 0;
+}
+
+int vibo_elbo_multi_forward(const vibo_desc* d, int num_samples, const float* response, const void* mask,
+                            const int64_t* row_index, const float* table, const float* item, const float* eps,
+                            const float* flow, float* out_scalars, void* workspace, size_t workspace_bytes, void* stream) {
+    return multi_forward_impl(d, false, num_samples, response, mask, row_index, table, 0, item, eps, flow, out_scalars, workspace,
+                              workspace_bytes, stream);
+}
+
+int vibo_elbo_multi_forward_given(const vibo_desc* d, int num_samples, const float* response, const void* mask,
+                                  const int64_t* row_index, const float* posterior, int64_t posterior_sample_stride,
+                                  const float* item, const float* eps, const float* flow, float* out_scalars,
+                                  void* workspace, size_t workspace_bytes, void* stream) {
+    return multi_forward_impl(d, true, num_samples, response, mask, row_index, posterior, (long long)posterior_sample_stride, item, eps,
+                              flow, out_scalars, workspace, workspace_bytes, stream);
 }
 
 int vibo_decode_mean(const vibo_desc* d, int num_samples, const float* ability, const float* item,

@@ -12,6 +12,11 @@
 //   item parameters: SC prepped tables, sample s at item_prep + s * item_sstride (floats)
 //   noise:           eps[s][B][A], sample s at eps + s * eps_sstride
 //   partial record:  scalars of sample s at out[8 s + {ll, kl, logq0, logp, ladj, nobs}]
+// GIVEN (VIBO_POSTERIOR_GIVEN: --ability-merge mean, VI_*PL): the posterior is the caller's, p.given_post = mu | logvar rows [B][2A]
+// in minibatch order, sample s at given_post + s * post_sstride.  post_sstride == 0: one posterior for all samples, the per-person
+// part is computed once per batch; post_sstride == B 2A: lam, mu, sigma, the KL head and logq0 are per sample.  The slot lanes of
+// every panel read the posterior themselves (the row-split kernel's GIVEN statements: lam = exp(-logvar), s = mu lam, nobs =
+// I_total) a batch ahead, with the noise: no counts, no pre-pass, nothing shared between the waves -- so no barrier in the batch loop.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vibo_multi.hpp"
@@ -32,7 +37,7 @@ struct alignas(16) MultiCommonLds {
 };
 inline size_t multi_lds_bytes(int nq) { return sizeof(MultiCommonLds) + (size_t)nq * sizeof(MultiWaveLds); }
 
-template <int AT, int IRT, bool FLOWS, int SC>
+template <int AT, int IRT, bool FLOWS, int SC, bool GIVEN = false>
 __global__ __launch_bounds__(256, 2) void multi_forward_kernel(const MultiParams mp) {
     const ElboParams& p = mp.e;
     constexpr int R = kSplitRows;
@@ -54,7 +59,7 @@ __global__ __launch_bounds__(256, 2) void multi_forward_kernel(const MultiParams
     const bool chunk_ok = chunk < n4;
     const uint32_t tail_mask = ((I & 3) && chunk == (I >> 2)) ? ((1u << (8 * (I & 3))) - 1u) : 0xFFFFFFFFu;
 
-    if (tid < 2 * AT) {
+    if (!GIVEN && tid < 2 * AT) {
         const int c = tid / AT, a = tid % AT;
         float m = 0.f, s = 0.f;
         if (a < A) { m = p.table[c * 2 * A + a]; s = p.table[c * 2 * A + A + a]; }
@@ -101,17 +106,27 @@ __global__ __launch_bounds__(256, 2) void multi_forward_kernel(const MultiParams
     float s_log[SC], s_logq0[SC], s_logp[SC], s_ladj[SC];
 #pragma unroll
     for (int s = 0; s < SC; ++s) s_log[s] = s_logq0[s] = s_logp[s] = s_ladj[s] = 0.f;
-    float s_kl = 0.f, s_nobs = 0.f;
+    constexpr int SK = GIVEN ? SC : 1;                    // KL heads: one per sample where the posterior is per sample
+    float s_kl[SK], s_nobs = 0.f;
+#pragma unroll
+    for (int s = 0; s < SK; ++s) s_kl[s] = 0.f;
     int unobs = 0;
     __syncthreads();
-    const float tau0 = cl.ctab[(0 * 2 + 0) * AT + ed], tau1 = cl.ctab[(0 * 2 + 1) * AT + ed];
-    const float mt0 = cl.ctab[(1 * 2 + 0) * AT + ed], mt1 = cl.ctab[(1 * 2 + 1) * AT + ed];
+    float tau0 = 0.f, tau1 = 0.f, mt0 = 0.f, mt1 = 0.f;
+    if constexpr (!GIVEN) {
+        tau0 = cl.ctab[(0 * 2 + 0) * AT + ed]; tau1 = cl.ctab[(0 * 2 + 1) * AT + ed];
+        mt0 = cl.ctab[(1 * 2 + 0) * AT + ed]; mt1 = cl.ctab[(1 * 2 + 1) * AT + ed];
+    }
+    const bool per_sample = GIVEN && mp.post_sstride != 0;      // (uniform)
 
     const long long n_batches = ((long long)p.B + R - 1) / R;
     const bool cell_codes = p.mask_dtype == 3;          // VIBO_MASK_CODES: 1-byte cell codes through p.mask
     float4 x[R];
     uint32_t m[R];
     float epn[SC];
+    float pmn[SK], pvn[SK];              // GIVEN: mu / logvar of (person er, dim ed) of the next batch
+#pragma unroll
+    for (int s = 0; s < SK; ++s) pmn[s] = pvn[s] = 0.f;
     auto load_batch = [&](const long long bt) {
         const long long row0 = bt * R;
         long long srcs[R];               // (row indices first: see the row-split kernel)
@@ -139,6 +154,16 @@ __global__ __launch_bounds__(256, 2) void multi_forward_kernel(const MultiParams
         const long long erow = row0 + er;
 #pragma unroll
         for (int s = 0; s < SC; ++s) epn[s] = (e_ok && erow < p.B) ? p.eps[s * mp.eps_sstride + erow * A + ed] : 0.f;
+        if constexpr (GIVEN) {           // (posterior and eps are in minibatch order: row_index gathers the response rows only)
+#pragma unroll
+            for (int s = 0; s < SC; ++s) {
+                if (s == 0 || per_sample) {
+                    const float* po = p.given_post + s * mp.post_sstride + erow * 2 * A;
+                    pmn[s] = (e_ok && erow < p.B) ? po[ed] : 0.f;
+                    pvn[s] = (e_ok && erow < p.B) ? po[A + ed] : 0.f;
+                }
+            }
+        }
     };
 
     long long bt = blockIdx.x;
@@ -155,11 +180,16 @@ __global__ __launch_bounds__(256, 2) void multi_forward_kernel(const MultiParams
         float eps_c[SC];
 #pragma unroll
         for (int s = 0; s < SC; ++s) eps_c[s] = epn[s];
+        float pm_c[SK], pv_c[SK];
+#pragma unroll
+        for (int s = 0; s < SK; ++s) { pm_c[s] = pmn[s]; pv_c[s] = pvn[s]; }
         if (bt + gridDim.x < n_batches) load_batch(bt + gridDim.x);
         __builtin_amdgcn_sched_barrier(0);
         {
-            const int tot = bfly8(pk, lane);
-            if ((lane & 7) == 0) wl.cntp[par][lane >> 3] = tot;
+            if constexpr (!GIVEN) {
+                const int tot = bfly8(pk, lane);
+                if ((lane & 7) == 0) wl.cntp[par][lane >> 3] = tot;
+            }
             if constexpr (IRT != 3) {      // this lane's unobserved cells: each adds exactly log2(1 + 2^0) = 1 below
                 int obs8 = 0;
 #pragma unroll
@@ -167,43 +197,61 @@ __global__ __launch_bounds__(256, 2) void multi_forward_kernel(const MultiParams
                 unobs += 4 * R - (obs8 & 0xffff);
             }
         }
-        __syncthreads();
+        if constexpr (!GIVEN) __syncthreads();      // (GIVEN: codes and theta are wave-private, the waves share nothing per batch)
 
         // ---- product of experts (sample independent), then SC reparameterised samples + flows ----
         const bool live = e_ok && (row0 + er) < p.B;
-        int cnt = 0;
-        if (p.row_cnt) {
-            cnt = live ? p.row_cnt[row0 + er] : 0;
-        } else {
-            for (int w = 0; w < nq; ++w) cnt += wls[w].cntp[par][er];
-        }
-        const float n1 = (float)(cnt >> 16);
-        float nobs = (float)(cnt & 0xffff);
-        const float n0 = nobs - n1;
-        float lam = n0 * tau0 + n1 * tau1, smu = n0 * mt0 + n1 * mt1;
-        if (p.pre_stats) {
-            lam = 0.f; smu = 0.f; nobs = 0.f;
-            if (live) {
-                for (int pn = 0; pn < p.pre_panels; ++pn) {
-                    const float* st = p.pre_stats + ((size_t)pn * p.B + (row0 + er)) * (2 * A + 1);
-                    lam += st[ed]; smu += st[A + ed]; nobs += st[2 * A];
+        const bool head = q == 0 && live && p.primary;
+        float amu = 0.f, sig = 1.f, alv = 0.f;
+        if constexpr (!GIVEN) {
+            int cnt = 0;
+            if (p.row_cnt) {
+                cnt = live ? p.row_cnt[row0 + er] : 0;
+            } else {
+                for (int w = 0; w < nq; ++w) cnt += wls[w].cntp[par][er];
+            }
+            const float n1 = (float)(cnt >> 16);
+            float nobs = (float)(cnt & 0xffff);
+            const float n0 = nobs - n1;
+            float lam = n0 * tau0 + n1 * tau1, smu = n0 * mt0 + n1 * mt1;
+            if (p.pre_stats) {
+                lam = 0.f; smu = 0.f; nobs = 0.f;
+                if (live) {
+                    for (int pn = 0; pn < p.pre_panels; ++pn) {
+                        const float* st = p.pre_stats + ((size_t)pn * p.B + (row0 + er)) * (2 * A + 1);
+                        lam += st[ed]; smu += st[A + ed]; nobs += st[2 * A];
+                    }
                 }
             }
+            const float nmiss = (float)p.I_total - nobs;
+            if (p.missing_mode == 0) lam += nmiss * (1.0f / (1.0f + kPoeEps));
+            if (!live) lam = 1.0f;
+            const float inv_lam = 1.0f / lam;
+            amu = smu * inv_lam;
+            sig = fast_rsq(lam);
+            alv = -kLn2 * fast_log2(lam);
+            if (head) {
+                s_kl[0] += -0.5f * (1.0f + alv - amu * amu - inv_lam);
+                if (ed == 0) s_nobs += nobs;
+            }
+        } else {
+            if (head && ed == 0) s_nobs += (float)p.I_total;      // (every cell counts as observed: no missing-prior term)
         }
-        const float nmiss = (float)p.I_total - nobs;
-        if (p.missing_mode == 0) lam += nmiss * (1.0f / (1.0f + kPoeEps));
-        if (!live) lam = 1.0f;
-        const float inv_lam = 1.0f / lam;
-        const float amu = smu * inv_lam;
-        const float sig = fast_rsq(lam);
-        const float alv = -kLn2 * fast_log2(lam);
-        const bool head = q == 0 && live && p.primary;
-        if (head) {
-            s_kl += -0.5f * (1.0f + alv - amu * amu - inv_lam);
-            if (ed == 0) s_nobs += nobs;
-        }
+        float klv = 0.f;
 #pragma unroll
         for (int s = 0; s < SC; ++s) {
+            if constexpr (GIVEN) {
+                if (s == 0 || per_sample) {      // the row-split kernel's GIVEN branch (vibo_split_kernel.hpp)
+                    const float lam = live ? expf(-pv_c[s]) : 1.0f;      // rows past the end / padded dims: keep the arithmetic finite
+                    const float smu = live ? pm_c[s] * lam : 0.f;
+                    const float inv_lam = 1.0f / lam;
+                    amu = smu * inv_lam;
+                    sig = fast_rsq(lam);
+                    alv = -kLn2 * fast_log2(lam);
+                    klv = -0.5f * (1.0f + alv - amu * amu - inv_lam);
+                }
+                if (head) s_kl[s] += klv;
+            }
             float thv = live ? amu + sig * eps_c[s] : 0.f;
             float ladj = 0.f;
             if constexpr (FLOWS) {
@@ -275,9 +323,10 @@ __global__ __launch_bounds__(256, 2) void multi_forward_kernel(const MultiParams
 
     // ================= workgroup reduction -> partial record: 8 scalars per sample ======
     float* out = p.partial + (size_t)blockIdx.x * p.lay.stride;
-    const float t_kl = wave_total(s_kl), t_no = wave_total(s_nobs);
+    const float t_kl0 = wave_total(s_kl[0]), t_no = wave_total(s_nobs);
 #pragma unroll
     for (int s = 0; s < SC; ++s) {
+        const float t_kl = (GIVEN && s > 0) ? wave_total(s_kl[GIVEN ? s : 0]) : t_kl0;
         const float ll = (IRT == 3) ? kLn2 * wave_total(s_log[s]) : -kLn2 * wave_total(s_log[s] - (float)unobs);
         const float t_q0 = wave_total(s_logq0[s]), t_lp = wave_total(s_logp[s]), t_la = wave_total(s_ladj[s]);
         if (lane == 0) {
@@ -293,21 +342,21 @@ __global__ __launch_bounds__(256, 2) void multi_forward_kernel(const MultiParams
     }
 }
 
-template <int AT, int IRT, int SC>
+template <int AT, int IRT, int SC, bool GIVEN>
 static hipError_t launch_multi_flows(const MultiParams& mp, int nq, int grid, hipStream_t s) {
     const size_t lds = multi_lds_bytes(nq);
-    if (mp.e.n_flows > 0) hipLaunchKernelGGL((multi_forward_kernel<AT, IRT, true, SC>), dim3(grid), dim3(64 * nq), lds, s, mp);
-    else hipLaunchKernelGGL((multi_forward_kernel<AT, IRT, false, SC>), dim3(grid), dim3(64 * nq), lds, s, mp);
+    if (mp.e.n_flows > 0) hipLaunchKernelGGL((multi_forward_kernel<AT, IRT, true, SC, GIVEN>), dim3(grid), dim3(64 * nq), lds, s, mp);
+    else hipLaunchKernelGGL((multi_forward_kernel<AT, IRT, false, SC, GIVEN>), dim3(grid), dim3(64 * nq), lds, s, mp);
     return hipGetLastError();
 }
 
 // sc in {1, 2, 4} (4 only for template widths <= 4)
-template <int AT>
+template <int AT, bool GIVEN = false>
 static hipError_t launch_multi_at(const MultiParams& mp, int irt, int sc, int nq, int grid, hipStream_t s) {
 #define VIBO_MULTI_IRT(SCV)                                                              \
-    if (irt == 1) return launch_multi_flows<AT, 1, SCV>(mp, nq, grid, s);                  \
-    if (irt == 2) return launch_multi_flows<AT, 2, SCV>(mp, nq, grid, s);                  \
-    return launch_multi_flows<AT, 3, SCV>(mp, nq, grid, s);
+    if (irt == 1) return launch_multi_flows<AT, 1, SCV, GIVEN>(mp, nq, grid, s);                  \
+    if (irt == 2) return launch_multi_flows<AT, 2, SCV, GIVEN>(mp, nq, grid, s);                  \
+    return launch_multi_flows<AT, 3, SCV, GIVEN>(mp, nq, grid, s);
     if (sc == 1) { VIBO_MULTI_IRT(1) }
     if (sc == 2) { VIBO_MULTI_IRT(2) }
     if constexpr (AT <= 4) {

@@ -420,14 +420,18 @@ int make_plan(const vibo_desc* d, int num_cu, Plan* pl, bool allow_msplit) {
     return 0;
 }
 
-int multi_plan(const vibo_desc* d, int num_cu, vibo_desc* d0, Plan* pl, size_t* prep_bytes) {
+int multi_plan(const vibo_desc* d, int num_cu, vibo_desc* d0, Plan* pl, size_t* prep_bytes, bool given_call) {
     *d0 = *d;
     d0->want_grad = 0;
+    if (given_call && d->posterior != VIBO_POSTERIOR_GIVEN)
+        return fail(-3, "vibo_elbo_multi_forward_given: the descriptor's posterior must be VIBO_POSTERIOR_GIVEN");
+    // (GIVEN outside the row-split shapes -- 4..32767 items, rows chunkable in 4 cells, no int64 mask, ability_dim <= 8 -- has no plan: -8)
     const int rc = make_plan(d0, num_cu, pl, false);
     if (rc < 0) return rc;
     // conditional posterior: the expert table itself depends on the item sample, nothing is shared between samples
     if (d->posterior == VIBO_POSTERIOR_CONDITIONAL) return fail(-8, "multi-sample forward: conditional posterior (one table per sample)");
-    if (d->posterior == VIBO_POSTERIOR_GIVEN) return fail(-8, "multi-sample forward: caller-supplied posterior");
+    if (d->posterior == VIBO_POSTERIOR_GIVEN && !given_call)
+        return fail(-8, "multi-sample forward: caller-supplied posterior (use vibo_elbo_multi_forward_given)");
     if (!pl->row_split()) return fail(-8, "multi-sample forward: shape is not on the row-split path");
     *prep_bytes = ((size_t)((d->num_item + 15) & ~15) * pl->DP * 4 + 255) & ~(size_t)255;
     return 0;

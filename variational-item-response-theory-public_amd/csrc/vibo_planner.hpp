@@ -99,8 +99,9 @@ int plan_cond_pass_bits(const Plan& pl);     // vibo_plan_cond_passes
 bool step_plan_ok(const vibo_desc* d, const Plan& pl);
 // ... and where that step runs the matrix kernel, it may draw its own ability noise and skip the posterior's mean / log-variance
 bool step_draws_noise(const vibo_desc* d, const Plan& pl);
-// plan of a multi-sample forward: the single-launch plan with want_grad = 0, restricted to the row-split paths
-int multi_plan(const vibo_desc* d, int num_cu, vibo_desc* d0, Plan* pl, size_t* prep_bytes);
+// plan of a multi-sample forward: the single-launch plan with want_grad = 0, restricted to the row-split paths.
+// given_call: vibo_elbo_multi_forward_given (VIBO_POSTERIOR_GIVEN descriptors only; the plain call refuses those)
+int multi_plan(const vibo_desc* d, int num_cu, vibo_desc* d0, Plan* pl, size_t* prep_bytes, bool given_call = false);
 
 bool encode_on_matrix_pipe(const vibo_desc* d);
 // scratch the fast encode path needs (0: not applicable -> wave-per-person encode_kernel)

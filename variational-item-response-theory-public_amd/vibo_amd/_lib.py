@@ -67,7 +67,7 @@ class ViboDecoderDesc(ctypes.Structure):
 
 EXPORTED_SYMBOLS = ('vibo_version', 'vibo_last_error_string', 'vibo_workspace_bytes', 'vibo_plan_kernel', 'vibo_plan_cond_passes',
                     'vibo_elbo_fwd_bwd', 'vibo_encode', 'vibo_decode', 'vibo_train_prologue', 'vibo_train_epilogue', 'vibo_fill_normal', 'vibo_multi_workspace_bytes',
-                    'vibo_elbo_multi_forward', 'vibo_decode_mean', 'vibo_pack_codes', 'vibo_row_counts', 'vibo_mean_encoder_partials',
+                    'vibo_elbo_multi_forward', 'vibo_multi_given_workspace_bytes', 'vibo_elbo_multi_forward_given', 'vibo_decode_mean', 'vibo_pack_codes', 'vibo_row_counts', 'vibo_mean_encoder_partials',
                     'vibo_mean_encoder_forward', 'vibo_mean_encoder_backward', 'vibo_train_prologue_noise',
                     'vibo_decoder_person_chunks', 'vibo_decoder_fwd_bwd', 'vibo_flow_stack_forward', 'vibo_flow_stack_backward',
                     'vibo_ctrain_param_floats', 'vibo_ctrain_scratch_floats', 'vibo_ctrain_prologue', 'vibo_ctrain_epilogue',
@@ -136,6 +136,10 @@ def load():
     lib.vibo_multi_workspace_bytes.argtypes = [dp, ctypes.c_int]
     lib.vibo_elbo_multi_forward.restype = ctypes.c_int
     lib.vibo_elbo_multi_forward.argtypes = [dp, ctypes.c_int, fp, vp, i64p, fp, fp, fp, fp, fp, vp, ctypes.c_size_t, vp]
+    lib.vibo_multi_given_workspace_bytes.restype = ctypes.c_size_t
+    lib.vibo_multi_given_workspace_bytes.argtypes = [dp, ctypes.c_int]
+    lib.vibo_elbo_multi_forward_given.restype = ctypes.c_int
+    lib.vibo_elbo_multi_forward_given.argtypes = [dp, ctypes.c_int, fp, vp, i64p, fp, ctypes.c_int64, fp, fp, fp, fp, vp, ctypes.c_size_t, vp]
     lib.vibo_row_counts.restype = ctypes.c_int
     lib.vibo_row_counts.argtypes = [dp, fp, vp, i64p, vp, vp]
     lib.vibo_mean_encoder_partials.restype = ctypes.c_int

@@ -504,23 +504,34 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
 
 def _hip_multi_forward(spec, response, mask, mask_code, row_index, table, items, eps, flow, reg_mode, num_person):
     """vibo_elbo_multi_forward: S forward evaluations in one pass.  items [S,I,D], eps [S,B,A] -> scalars [S,8], or
-    None when the configuration is not on the row-split path (the caller then loops over single launches)."""
+    None when the configuration is not on the row-split path (the caller then loops over single launches).
+    spec.given (vibo_elbo_multi_forward_given): `table` is the caller's posterior (mu | logvar) in minibatch order, [B, 2A] shared
+    by the samples or [S, B, 2A] one per sample."""
     lib = _lib.load()
     _require_device(response, mask, table, items, eps)
     S, B, I = int(items.shape[0]), int(num_person), response.shape[1]
+    given = bool(getattr(spec, 'given', False))
     d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, False)
-    ws_bytes = lib.vibo_multi_workspace_bytes(ctypes.byref(d), S)
+    ws_bytes = (lib.vibo_multi_given_workspace_bytes if given else lib.vibo_multi_workspace_bytes)(ctypes.byref(d), S)
     if ws_bytes == 0:
         return None
     dev = response.device
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(S, _lib.NUM_SCALARS, dtype=torch.float32, device=dev)
-    rc = lib.vibo_elbo_multi_forward(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table),
-                                     _ptr(items), _ptr(eps), _ptr(flow), _ptr(out), _ptr(ws), ctypes.c_size_t(ws_bytes),
-                                     _stream(dev))
+    tail = (_ptr(items), _ptr(eps), _ptr(flow), _ptr(out), _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(dev))
+    if given:
+        A = spec.ability_dim
+        if tuple(table.shape) not in ((B, 2 * A), (S, B, 2 * A)) or not table.is_contiguous():
+            raise ValueError('multi-sample forward: the posterior is a contiguous [B, 2A] or [S, B, 2A] tensor, got %s' % (tuple(table.shape),))
+        name, stride = 'vibo_elbo_multi_forward_given', (B * 2 * A if table.dim() == 3 else 0)
+        rc = lib.vibo_elbo_multi_forward_given(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table),
+                                               ctypes.c_int64(stride), *tail)
+    else:
+        name = 'vibo_elbo_multi_forward'
+        rc = lib.vibo_elbo_multi_forward(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table), *tail)
     if rc == -8:
         return None
-    _lib.check(rc, 'vibo_elbo_multi_forward')
+    _lib.check(rc, name)
     return out
 
 

@@ -372,9 +372,10 @@ class VIBO_1PL(nn.Module):
         item_feat = eps_item * torch.exp(0.5 * item_lv) + item_mu
         return item_feat, item_mu, item_lv
 
-    def _run_fused(self, response, mask, *, eps_item=None, eps_ability=None, reg_mode=None, row_index=None):
+    def _run_fused(self, response, mask, *, eps_item=None, eps_ability=None, reg_mode=None, row_index=None, posterior=None):
         """Item sample -> expert table -> fused kernel.  Draw order: item eps, then
-        ability eps (models.py:361,368)."""
+        ability eps (models.py:361,368).  posterior: the mean-merge posterior [B, 2A] of these rows (and this item noise) where
+        the caller has it already (log_marginal's loop after _log_weights_multi)."""
         item_feat, item_mu, item_lv = self._item_side(eps_item)
         if self.n_norm_flows > 0:
             item_k, item_ladj = self.item_norm_flows(item_feat)
@@ -390,7 +391,7 @@ class VIBO_1PL(nn.Module):
                     if row_index is not None:
                         response, m2, row_index = response[row_index], (m2[row_index] if m2 is not None else None), None
                     response, mask = ops.pad_rows(response, m2)
-            table = self._mean_posterior(response, mask, row_index, item_feat)
+            table = posterior if posterior is not None else self._mean_posterior(response, mask, row_index, item_feat)
         else:
             table = self.ability_encoder.expert_table(item_feat if self.conditional_posterior else None)
         B = int(row_index.numel()) if row_index is not None else response.shape[0]
@@ -606,8 +607,11 @@ class VIBO_1PL(nn.Module):
     def log_marginal(self, response, mask, num_samples=100, eps_item=None, eps_ability=None):
         """Importance-weighted bound with batch-level weights (models.py:445-504).  eps_item [S,I,D] / eps_ability
         [S,B,A] replay a fixed noise sequence (tests); by default it is drawn item-then-ability per sample like the
-        reference's loop.  Unconditional posterior: the S forwards share one pass over the responses
-        (vibo_elbo_multi_forward); otherwise one forward launch per sample."""
+        reference's loop.  The S forwards share one pass over the responses where nothing per sample needs the rows: the
+        unconditional product of experts (vibo_elbo_multi_forward) and --ability-merge mean, whose posterior reaches the kernel as
+        given (vibo_elbo_multi_forward_given: one [B, 2A] posterior for all samples, or with --conditional-posterior one per
+        sample).  Otherwise -- product of experts x conditional posterior, a person-sharded mean-merge model (its heads go through
+        the collective), a backend that answers None -- one forward launch per sample."""
         with torch.no_grad():
             S = int(num_samples)
             if self.generative_model != 'irt':
@@ -617,21 +621,27 @@ class VIBO_1PL(nn.Module):
                                             eps_ability=None if eps_ability is None else eps_ability[s])
                     log_w.append(-self._decoder_elbo(ctx, 1.0, False))
                 return torch.logsumexp(torch.stack(log_w), 0) - math.log(S)
-            if not self.conditional_posterior and self.ability_merge == 'product':
+            mean_merge = self.ability_merge == 'mean'
+            posts = None      # mean merge: the posteriors _log_weights_multi computed before the backend answered None
+            # (person-sharded mean merge: the loop reduces its heads through the collective)
+            if (mean_merge and self._reducer is None) or (not mean_merge and not self.conditional_posterior):
                 if not isinstance(response, ops.CellCodes):
                     response = ops.prepare_response(response)
                     if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
-                        # (a compact copy of e.g. 95-item rows: pad the minibatch so the multi-sample kernel applies)
+                        # (a compact copy of e.g. 95-item rows: pad the minibatch so the multi-sample kernel applies; the mean
+                        #  path of _run_fused pads the same way)
                         response, mask = ops.pad_rows(response, ops.prepare_mask(mask)[0])
-                log_w, eps_item, eps_ability = self._log_weights_multi(response, mask, S, eps_item, eps_ability)
+                log_w, eps_item, eps_ability, posts = self._log_weights_multi(response, mask, S, eps_item, eps_ability)
                 if log_w is not None:
                     return torch.logsumexp(log_w, 0) - math.log(S)
-                # not covered (fewer than 4 items, ...): the loop below replays the noise already drawn
+                # not covered (fewer than 4 items, ...): the loop below replays the noise already drawn and, for mean merge,
+                # takes the posteriors already computed from it
             log_w = []
             for s in range(S):
                 ctx = self._run_fused(response, mask, reg_mode=_lib.REG_SAMPLED,
                                       eps_item=None if eps_item is None else eps_item[s],
-                                      eps_ability=None if eps_ability is None else eps_ability[s])
+                                      eps_ability=None if eps_ability is None else eps_ability[s],
+                                      posterior=None if posts is None else (posts[s] if posts.dim() == 3 else posts))
                 log_q_d = _normal_logpdf(ctx.item_feat, ctx.item_mu, ctx.item_lv).sum()
                 if ctx.item_ladj is not None:
                     log_q_d = log_q_d - ctx.item_ladj.sum()
@@ -641,13 +651,20 @@ class VIBO_1PL(nn.Module):
             return torch.logsumexp(log_w, 0) - math.log(S)
 
     def _log_weights_multi(self, response, mask, S, eps_item, eps_ability):
-        """log w_s for s < S through the multi-sample forward kernel, or None if the configuration is not covered."""
+        """log w_s for s < S through the multi-sample forward kernel, or None if the configuration is not covered.
+        --ability-merge mean: the posterior goes to the kernel as given -- _mean_posterior once for all samples, or (conditional
+        posterior: it depends on the item sample) once per sample, stacked to [S, B, 2A].  Memory: the stacked noise is S B A floats
+        and the per-sample posteriors S B 2A (1M persons, A = 8, S = 16: 0.5 + 1 GB): a caller with a whole resident split and many
+        samples passes it in minibatches.
+        -> (log_w or None, eps_item, eps_ability, posteriors or None): after None the caller's loop replays the last three."""
+        rows, mask_in = response, mask
         response, mask2, code = ops.prepare_rows(response, mask)
         if code == _lib.MASK_I64:
-            return None, eps_item, eps_ability
+            return None, eps_item, eps_ability, None
         B = response.shape[0]
+        mean_merge = self.ability_merge == 'mean'
         item_mu, item_lv = self.item_encoder()
-        items, log_qd, log_pd, eps_ab, drawn_items = [], [], [], [], []
+        items, log_qd, log_pd, eps_ab, drawn_items, posts = [], [], [], [], [], []
         for s in range(S):                      # draw order of the reference's loop: item eps, then ability eps
             e_i = self._randn(item_mu.shape, item_mu, self._item_gen) if eps_item is None else eps_item[s]
             drawn_items.append(e_i)
@@ -657,19 +674,27 @@ class VIBO_1PL(nn.Module):
             if self.n_norm_flows > 0:
                 item_k, item_ladj = self.item_norm_flows(item_feat)
                 lq = lq - item_ladj.sum()
+            if mean_merge and self.conditional_posterior:      # (from the item sample in front of the item flows, as _run_fused)
+                posts.append(self._mean_posterior(rows, mask_in, None, item_feat))
             items.append(item_k)
             log_qd.append(lq)
             log_pd.append(_std_normal_logpdf(item_k).sum())
             eps_ab.append(self._randn((B, self.ability_dim), item_mu, self._ability_gen)
                           if eps_ability is None else eps_ability[s])
-        table = self.ability_encoder.expert_table(None)
+        if not mean_merge:
+            table = self.ability_encoder.expert_table(None)
+        elif self.conditional_posterior:
+            table = torch.stack(posts)
+            posts = None          # (one copy)
+        else:
+            table = self._mean_posterior(rows, mask_in, None, None)
         flow_packed = self.ability_norm_flows.packed() if self.n_norm_flows > 0 else None
+        eps_ab = torch.stack(eps_ab)
         sc = ops._BACKEND['multi'](self.spec, response, mask2, code, None, table.contiguous(),
-                                   torch.stack(items).contiguous(), torch.stack(eps_ab).contiguous(), flow_packed,
-                                   _lib.REG_SAMPLED, B)
+                                   torch.stack(items).contiguous(), eps_ab, flow_packed, _lib.REG_SAMPLED, B)
         if sc is None:
-            return None, (torch.stack(drawn_items) if eps_item is None else eps_item), torch.stack(eps_ab)
-        return sc[:, _lib.S_LL] - sc[:, _lib.S_REG] + torch.stack(log_pd) - torch.stack(log_qd), eps_item, eps_ability
+            return None, (torch.stack(drawn_items) if eps_item is None else eps_item), eps_ab, (table if mean_merge else None)
+        return sc[:, _lib.S_LL] - sc[:, _lib.S_REG] + torch.stack(log_pd) - torch.stack(log_qd), eps_item, eps_ability, None
 
     # ---- fast path for training loops (no tuple round trip) -------------------
     def elbo_step(self, response, mask, annealing_factor=1.0, row_index=None):
@@ -797,11 +822,42 @@ class VI_1PL(nn.Module):
         """Batch-level importance-weighted bound (models.py:174-207; the reference's own loop there omits `index` in its
         forward call and cannot run -- this is the same estimator with the index passed)."""
         with torch.no_grad():
-            log_w = []
-            for _ in range(int(num_samples)):
-                outs = self.forward(index, response, mask)
-                log_w.append(-self.elbo(*outs, annealing_factor=1, use_kl_divergence=False))
-            return torch.logsumexp(torch.stack(log_w), 0) - math.log(int(num_samples))
+            S = int(num_samples)
+            log_w, eps = self._log_weights_multi(index, response, mask, S)
+            if log_w is None:      # not covered by the multi-sample kernel: one forward per sample on the noise already drawn
+                log_w = []
+                for s in range(S):
+                    outs = self.forward(index, response, mask, eps_item=eps[0][s], eps_ability=eps[1][s])
+                    log_w.append(-self.elbo(*outs, annealing_factor=1, use_kl_divergence=False))
+                log_w = torch.stack(log_w)
+            return torch.logsumexp(log_w, 0) - math.log(S)
+
+    def _log_weights_multi(self, index, response, mask, S):
+        """log w_s for s < S in one pass over the responses (vibo_elbo_multi_forward_given: the looked-up (mu | logvar) rows are
+        the posterior of every sample), or None and the noise drawn where the backend does not cover the call.  The noise comes
+        from the default generator in _run's order: item randn_like, then randn(B, A), per sample."""
+        item_mu, item_lv = self.item_mu_lookup.weight, self.item_logvar_lookup.weight
+        amu, alv = self._posterior_rows(index)
+        B = amu.shape[0]
+        std = torch.exp(0.5 * item_lv)
+        eps_item, eps_ab = [], []
+        for _ in range(S):
+            eps_item.append(torch.randn_like(std))
+            eps_ab.append(torch.randn(B, self.ability_dim, dtype=amu.dtype, device=amu.device))
+        eps_item, eps_ab = torch.stack(eps_item), torch.stack(eps_ab)
+        items = eps_item * std + item_mu                                              # [S, I, D]
+        log_qd = _normal_logpdf(items, item_mu, item_lv).sum((1, 2))
+        log_pd = _std_normal_logpdf(items).sum((1, 2))
+        if not isinstance(response, ops.CellCodes):
+            response = ops.prepare_response(response)
+            if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
+                response, mask = ops.pad_rows(response, ops.prepare_mask(mask)[0])      # (as _run pads compact ragged rows)
+        response, mask2, code = ops.prepare_rows(response, mask)
+        sc = ops._BACKEND['multi'](self.spec, response, mask2, code, None, torch.cat([amu, alv], dim=1).contiguous(),
+                                   items.contiguous(), eps_ab, None, _lib.REG_SAMPLED, B)
+        if sc is None:
+            return None, (eps_item, eps_ab)
+        return sc[:, _lib.S_LL] - sc[:, _lib.S_REG] + log_pd - log_qd, None
 
 
 class VI_2PL(VI_1PL):
