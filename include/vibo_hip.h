@@ -463,7 +463,8 @@ int vibo_mtrain_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, 
  * over a person's observed cells.  The sum over the cells -- one-hot(codes) [B, 2I] x feature [2I, H], the path's one dense
  * encoder contraction -- and its transpose for the backward run on the matrix pipe from the 1-byte cell codes
  * (VIBO_MASK_CODES layout: 0 wrong / 1 right / 2 missing; rows 4-byte aligned, stride % 4 == 0), the dense operand as
- * hi + lo f16 pieces with fp32 accumulation (fp32-grade):
+ * three truncated bf16 pieces hi + mid + lo of 0.5 x (exact: 8 + 8 + 8 significant bits) with fp32 accumulation -- a person
+ * who observes one cell gets that cell's row back bit for bit (tests/test_gpu_onehot_contractions.py):
  *     vibo_code_table_sum_forward    out_sum [B][H]          = sum_i [observed] feature[code_pi][i][:]
  *     vibo_code_table_sum_backward   grad_feature [2][I][H]  = sum_p [code_pi == c] grad_sum[p][:]      (fixed-order: reproducible)
  * H = 64.  scratch: vibo_code_table_scratch_bytes(B, I, H) bytes, 256-byte aligned, need not survive between the two calls.

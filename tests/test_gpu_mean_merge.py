@@ -235,7 +235,7 @@ def test_row_counts_are_cached_per_resident_matrix():
 @pytest.mark.parametrize('B,I,missing', [(64, 64, 0.0), (200, 1000, 0.2), (77, 95, 0.3), (1, 7, 0.0), (513, 130, 0.1), (4099, 1000, 0.1)])
 def test_code_table_sum_kernels_match_dense_products(B, I, missing):
     """vibo_code_table_sum_forward / _backward (--ability-merge mean with --conditional-posterior, models.py:631-650 +
-    695-710: the one-hot [B, 2I] x [2I, H] contraction on the matrix pipe from the cell codes, hi + lo f16 operands) against
+    695-710: the one-hot [B, 2I] x [2I, H] contraction on the matrix pipe from the cell codes, three bf16 pieces per operand value) against
     the same sums as float64 products on materialised indicator matrices: fp32-grade, bitwise run to run, ragged shapes."""
     from vibo_amd import ops
     dev = torch.device('cuda:0')
