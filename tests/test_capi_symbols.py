@@ -4,6 +4,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 from conftest import ROOT
 from vibo_amd import _lib
 
@@ -167,3 +169,69 @@ def test_matrix_kernel_instantiations_carry_no_scratch():
             assert spill == 0 and scratch == 0, (os.path.basename(o), name, spill, scratch)
             seen += 1
     assert seen >= 216
+
+
+# ---------------------------------------------------------------------------
+# the binding is derived from the header (_lib.parse_prototypes): counts, spot checks, constants, structs
+# ---------------------------------------------------------------------------
+def header_text():
+    src = open(os.path.join(ROOT, 'include', 'vibo_hip.h')).read()
+    return re.sub(r'/\*.*?\*/', '', src, flags=re.S)
+
+
+def test_every_function_is_typed_with_the_header_s_parameter_count():
+    lib, src = _lib.load(), header_text()
+    assert list(_lib.EXPORTED_SYMBOLS) == re.findall(r'\b(vibo_[a-z_0-9]+)\s*\(', src) and len(_lib.EXPORTED_SYMBOLS) == 56      # header order
+    for name in _lib.EXPORTED_SYMBOLS:
+        params = re.search(r'\b' + name + r'\s*\(([^()]*)\)\s*;', src).group(1).strip()
+        want = 0 if params in ('', 'void') else params.count(',') + 1
+        fn = getattr(lib, name)
+        assert fn.argtypes is not None and len(fn.argtypes) == want, (name, want, fn.argtypes)
+        assert fn.restype in (ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_char_p), (name, fn.restype)
+
+
+def test_derived_argument_lists_spot_checks():
+    lib = _lib.load()
+    vp, dp, ci, i64, u64, u32, sz = (ctypes.c_void_p, ctypes.POINTER(_lib.ViboDesc), ctypes.c_int, ctypes.c_int64, ctypes.c_uint64,
+                                     ctypes.c_uint32, ctypes.c_size_t)
+    assert lib.vibo_elbo_fwd_bwd.restype is ci
+    assert lib.vibo_elbo_fwd_bwd.argtypes == [dp, vp, vp, vp, vp, vp, vp, vp,          # rows, table, item, eps, flow
+                                              vp, vp, vp, vp, vp, vp,                  # scalars + posterior outputs
+                                              vp, vp, vp,                              # gradients
+                                              vp, sz, vp]                              # workspace, its bytes, stream
+    assert lib.vibo_train_epilogue_fused.argtypes == [dp, ci, vp, vp, vp, vp, vp, vp, vp, vp,      # workspace .. step_count
+                                                      vp, vp, vp, vp, vp, vp, vp, vp,              # parameters, moments, loss
+                                                      u64, vp, vp, vp, i64, u32, vp]               # seed .. stream
+    assert lib.vibo_dtrain_forward_backward_cond.argtypes == [dp, ci, ci, ci, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp]
+    assert [len(f.argtypes) for f in (lib.vibo_elbo_fwd_bwd, lib.vibo_train_epilogue_fused, lib.vibo_dtrain_forward_backward_cond)] == [20, 25, 14]
+    assert lib.vibo_decoder_fwd_bwd.argtypes[0] is ctypes.POINTER(_lib.ViboDecoderDesc)
+    assert lib.vibo_last_error_string.restype is ctypes.c_char_p and lib.vibo_ctrain_param_floats.restype is i64
+    assert lib.vibo_workspace_bytes.restype is sz and lib.vibo_fill_normal.argtypes == [vp, i64, u64, vp, u32, vp]
+
+
+def test_an_unknown_c_type_is_an_error_that_names_it():
+    ok = _lib.parse_prototypes('/* int vibo_hidden(double x); */\nconst char* vibo_a(void);\nsize_t vibo_b(const vibo_desc* d, const float* x,\n int64_t n);')
+    assert ok == [('vibo_a', ctypes.c_char_p, []), ('vibo_b', ctypes.c_size_t, [ctypes.POINTER(_lib.ViboDesc), ctypes.c_void_p, ctypes.c_int64])]
+    for text, word in (('int vibo_c(const vibo_desc* d, double scale);', 'double'), ('int vibo_c(unsigned n);', 'unsigned'),
+                       ('float vibo_c(void);', 'float'), ('float* vibo_c(int n);', 'float*'), ('int vibo_c(short n, void* stream);', 'short')):
+        with pytest.raises(_lib.ViboLibraryError) as e:
+            _lib.parse_prototypes(text)
+        assert 'vibo_c' in str(e.value) and word in str(e.value)
+
+
+def test_constants_mirror_the_header():
+    src = header_text()
+    header = {k: int(v) for k, v in re.findall(r'\bVIBO_([A-Z0-9_]+)\s*=\s*(\d+)', src) + re.findall(r'#define\s+VIBO_([A-Z0-9_]+)\s+(\d+)', src)}
+    # the two ability_dim limits go by other names in the binding; every other constant by the header's name without VIBO_
+    assert _lib.MAX_ABILITY_DIM_FAST == header.pop('MAX_ABILITY_DIM') and _lib.MAX_ABILITY_DIM == header.pop('MAX_ABILITY_DIM_WIDE')
+    mirrored = {k for k in header if hasattr(_lib, k)}
+    for k in mirrored:
+        assert getattr(_lib, k) == header[k], k
+    assert _lib.DECODER_KINDS == {k[8:].lower(): v for k, v in header.items() if k.startswith('DECODER_')}
+    assert set(_lib.KERNEL_NAMES) == {v for k, v in header.items() if k.startswith('KERNEL_')}
+    for k, word in (('KERNEL_MATRIX', 'matrix'), ('KERNEL_VALU', 'VALU'), ('KERNEL_NARROW', 'narrow')):
+        assert word in _lib.KERNEL_NAMES[header[k]]
+    rest = {k for k in header if k not in mirrored and not k.startswith(('DECODER_', 'KERNEL_'))}
+    assert rest == {'S_RESERVED'}, rest                 # nothing else in the header goes unmirrored
+    assert mirrored >= {'ABI_VERSION', 'NUM_SCALARS', 'MAX_FLOWS', 'S_LL', 'S_NOBS', 'IRT_3PL', 'POSTERIOR_GIVEN', 'MISSING_DROP',
+                        'MASK_CODES', 'REG_SAMPLED', 'FLAG_COND_THREE_PASS', 'DTRAIN_ABILITY'} and len(mirrored) == 33

@@ -509,10 +509,8 @@ def main(argv=None):
     if world > 1:
         model.enable_person_sharding(lambda flat: dist.all_reduce(flat), seed=args.seed, rank=rank)
     trainer = None
-    plain = args.ability_merge == 'product' and not args.conditional_posterior and args.n_norm_flows == 0
     from ..trainer import fused_trainer_covers
-    if (args.cuda and not args.torch_optimizer and fused_trainer_covers(model, args.hidden_dim)
-            and (args.hidden_dim <= 256 or not plain)):      # (else: module + torch.optim.Adam)
+    if args.cuda and not args.torch_optimizer and fused_trainer_covers(model, args.hidden_dim):      # (else: module + torch.optim.Adam)
         # the whole step natively: FusedTrainer's kernels, (conditional posterior / planar flows) FusedCondFlowTrainer's, or
         # (--ability-merge mean, unconditional posterior) FusedMeanTrainer's -- same Adam arithmetic, 2-12 launches
         # per step, no PyTorch autograd inside the replayed graph

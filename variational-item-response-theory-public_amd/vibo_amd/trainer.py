@@ -29,15 +29,11 @@ short minibatch on the VALU kernel) fills it itself in front of its ELBO launch,
 vibo_elbo_fwd_bwd = kernel + finalize -> vibo_train_epilogue); the two forms agree bit for bit (tests/test_gpu_trainer.py).
 Same arithmetic as the PyTorch path (tests/test_gpu_trainer.py compares parameters after several steps); `.grad` fields are not
 populated.
-FusedTrainer covers the unconditional posterior without flows; `FusedTrainer(model)` returns its sibling
-FusedCondFlowTrainer (same interface, vibo_ctrain_* kernels) for --conditional-posterior / --n-norm-flows models.
-FusedMeanTrainer (vibo_mtrain_* kernels) is the same for --ability-merge mean with the unconditional posterior (person-sharded too).
-FusedDecoderTrainer (vibo_dtrain_* kernels around vibo_decoder_fwd_bwd) is the same for --generative-model link | deep | residual
-with the product encoder's unconditional posterior (`FusedTrainer(model)` returns it; fused_decoder_trainer_covers() tells which)
-and, asked for with `conditional=True`, its conditional posterior (vibo_dtrain_*_cond; `FusedTrainer(model, conditional=True)`,
-fused_decoder_trainer_covers(model, conditional=True)).
-Mean x conditional, and the MLP decoders with flows / mean merge, train through the module + torch.optim path
-(fused_trainer_covers() tells which of the IRT-decoder models are covered).
+One entry point: `FusedTrainer(model, ...)` returns the class that runs the model's step natively -- fused_trainer_for() is the
+table: FusedTrainer itself (plain), FusedCondFlowTrainer (vibo_ctrain_*: --conditional-posterior / --n-norm-flows), FusedMeanTrainer
+(vibo_mtrain_*: --ability-merge mean), FusedDecoderTrainer (vibo_dtrain_*[_cond]: --generative-model link | deep | residual; the
+conditional posterior asked for with `conditional=True`) -- or says why none does: those train through the module + torch.optim.
+All four share _FusedStep: the state, the noise, and step() = forward_backward() -> reduce_shards() -> update().
 """
 import ctypes
 
@@ -45,76 +41,102 @@ import torch
 
 from . import _lib, ops
 
+_MODULE_PATH = 'use model.elbo_step + torch.optim.Adam otherwise'
+
+
+def fused_trainer_for(model, hidden_dim=None, conditional=False):
+    """THE coverage table -> (the trainer class that runs the model's whole train step natively, None), or (None, why none does:
+    the constructors' NotImplementedError).  hidden_dim: the encoder's width when the caller knows it (else read from the model);
+    conditional: FusedDecoderTrainer was asked for the conditional posterior (conditional=True).  Reads the model's
+    generative_model, ability_merge, conditional_posterior, n_norm_flows, ability_dim, num_item and _reducer, nothing else."""
+    kind, merge, A = getattr(model, 'generative_model', 'irt'), model.ability_merge, model.ability_dim
+    cond, flows = bool(model.conditional_posterior), model.n_norm_flows > 0
+
+    def hidden():
+        if hidden_dim is not None:
+            return hidden_dim
+        enc = model.ability_encoder
+        return (enc.mlp1 if merge == 'mean' else enc.mlp)[0].weight.shape[0]
+
+    if kind in _lib.DECODER_KINDS:
+        # product encoder, no flows, one GPU, the packed row counts' 65 535 items, the decoder kernel's width
+        why = (f'--ability-merge {merge}' if merge != 'product' else
+               'the conditional posterior (unless built with conditional=True)' if cond and not conditional else
+               'normalizing flows' if flows else
+               'person sharding' if model._reducer is not None else
+               'more than 65 535 items (the packed row counts)' if model.num_item > 65535 else
+               f'ability_dim above {_lib.MAX_ABILITY_DIM}' if A > _lib.MAX_ABILITY_DIM else None)
+        if why is not None:
+            return None, f'FusedDecoderTrainer does not cover {why}; use model.elbo_step + torch.optim.Adam'
+        if hidden() > 64:
+            return None, f"FusedDecoderTrainer: hidden_dim <= 64 (the per-term decoder kernel's width); {_MODULE_PATH}"
+        return FusedDecoderTrainer, None
+    if kind != 'irt' or merge not in ('product', 'mean'):
+        return None, f'the fused trainers cover the product-of-experts encoder with the IRT decoder; {_MODULE_PATH}'
+    if merge == 'mean':
+        if cond or flows or hidden() > 128 or A > _lib.MAX_ABILITY_DIM_FAST:
+            return None, ('FusedMeanTrainer: --ability-merge mean with the unconditional posterior, the IRT decoder, no flows, '
+                          f'hidden_dim <= 128, ability_dim <= 8; {_MODULE_PATH}')
+        return FusedMeanTrainer, None
+    if cond or flows:
+        if hidden() > 64:
+            return None, f'FusedCondFlowTrainer: hidden_dim <= 64 (one 64-wide tile of the matrix-pipe table MLP); {_MODULE_PATH}'
+        if A > _lib.MAX_ABILITY_DIM_FAST:
+            return None, f'FusedCondFlowTrainer: ability_dim <= 8 (the row-split kernels of vibo_ctrain_*); {_MODULE_PATH}'
+        return FusedCondFlowTrainer, None
+    if hidden() > 256:
+        return None, f'FusedTrainer: hidden_dim <= 256; {_MODULE_PATH}'
+    return FusedTrainer, None
+
 
 def fused_trainer_covers(model, hidden_dim=None):
-    """True when one of the fused trainers of this module runs the model's whole train step natively: the product-of-experts
-    encoder with the IRT decoder -- plain (FusedTrainer's kernels), or with the conditional posterior and / or planar flows
-    (FusedCondFlowTrainer's, hidden width <= 64) -- or the --ability-merge mean encoder with the unconditional posterior
-    (FusedMeanTrainer's; person-sharded too since round 5).  The MLP decoders and mean x conditional train through the module + torch.optim.Adam."""
-    if getattr(model, 'generative_model', 'irt') != 'irt':
-        return False
-    if model.ability_merge == 'mean':          # FusedMeanTrainer: unconditional posterior, no flows, hidden width <= 128
-        H = hidden_dim if hidden_dim is not None else model.ability_encoder.mlp1[0].weight.shape[0]
-        return (not model.conditional_posterior and model.n_norm_flows == 0 and H <= 128
-                and model.ability_dim <= _lib.MAX_ABILITY_DIM_FAST)
-    if model.ability_merge != 'product':
-        return False
-    if model.conditional_posterior or model.n_norm_flows > 0:
-        H = hidden_dim if hidden_dim is not None else model.ability_encoder.mlp[0].weight.shape[0]
-        return H <= 64 and model.ability_dim <= _lib.MAX_ABILITY_DIM_FAST      # (vibo_ctrain_*: one 64-wide tile, 8 ability dims)
-    return True
+    """True when FusedTrainer, FusedCondFlowTrainer or FusedMeanTrainer runs the model's whole train step natively (the IRT decoder)."""
+    return fused_trainer_for(model, hidden_dim)[0] not in (None, FusedDecoderTrainer)
 
 
 def fused_decoder_trainer_covers(model, hidden_dim=None, conditional=False):
-    """True when FusedDecoderTrainer runs the model's whole train step natively: --generative-model link | deep | residual on the
-    product-of-experts encoder with the unconditional posterior, no flows, not person-sharded, hidden width <= 64, at most 65 535
-    items (the packed row counts).  conditional=True: the answer for FusedDecoderTrainer(model, conditional=True), which runs the
-    conditional posterior natively as well.  Everything else with an MLP decoder trains through the module + torch.optim.Adam."""
-    if getattr(model, 'generative_model', 'irt') not in _lib.DECODER_KINDS:
-        return False
-    H = hidden_dim if hidden_dim is not None else model.ability_encoder.mlp[0].weight.shape[0] if model.ability_merge == 'product' else 0
-    return (model.ability_merge == 'product' and (conditional or not model.conditional_posterior) and model.n_norm_flows == 0
-            and model._reducer is None and H <= 64 and model.num_item <= 65535 and model.ability_dim <= _lib.MAX_ABILITY_DIM)
+    """True when FusedDecoderTrainer(model, conditional=conditional) runs the model's whole train step natively (the MLP decoders)."""
+    return fused_trainer_for(model, hidden_dim, conditional)[0] is FusedDecoderTrainer
 
 
-class FusedTrainer:
-    def __new__(cls, model=None, *args, **kwargs):
-        # one entry point: the conditional posterior / planar flows are served by the sibling class below
-        # (model=None: copy / pickle re-create the object through cls.__new__(cls) and fill __dict__ themselves)
-        if cls is FusedTrainer and model is not None and getattr(model, 'generative_model', 'irt') != 'irt':
-            return super().__new__(FusedDecoderTrainer)
-        if cls is FusedTrainer and model is not None and model.ability_merge == 'mean':
-            return super().__new__(FusedMeanTrainer)
-        if cls is FusedTrainer and model is not None and (model.conditional_posterior or model.n_norm_flows > 0):
-            return super().__new__(FusedCondFlowTrainer)
-        return super().__new__(cls)
+class _FusedStep:
+    """What the four trainers share: the state every step reads, the noise, and the step protocol."""
 
-    def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None):
-        if model.ability_merge != 'product' or getattr(model, 'generative_model', 'irt') != 'irt':
-            raise NotImplementedError('the fused trainers cover the product-of-experts encoder with the IRT decoder; '
-                                      'use model.elbo_step + torch.optim.Adam otherwise')
+    def __init__(self, model, lr, rng, seed, fold=False, conditional=False, keep_item_noise=True):
+        covering, why = fused_trainer_for(model, conditional=conditional)
+        if covering is None or not isinstance(self, covering):
+            raise NotImplementedError(why or f'{type(self).__name__} does not cover this model ({covering.__name__} does)')
+        if rng not in ('torch', 'native'):
+            raise ValueError("rng must be 'torch' or 'native'")
         self.model = model
-        self.fold = bool(fold)                # two launches per step (train hook + fused epilogue) where the shape allows
-        self._primed_for = None               # folded step: (noise capacity, parameter versions) the next step's head was prepared for
-        self._eps_cap = None                  # ... the ability-noise buffer [capacity] every step's epilogue refills
-        self._eps_keep = []                   # (outgrown buffers stay alive: a captured graph may still write to them)
-        self._max_batch = int(max_batch) if max_batch else 0      # persons of the largest minibatch to expect (sizes _eps_cap once)
         self.generation = 0                   # bumped when a buffer a captured hipGraph points at was replaced (re-capture then)
+        self.fold = bool(fold)                # FusedTrainer: two launches per step (train hook + fused epilogue) where the shape allows
+        self._primed_for = None               # folded step: (noise capacity, parameter versions) the next step's head was prepared for
         self._folded_open = False             # a folded forward_backward() whose update() has not run yet
-        self._draw_mode = False               # a folded step drew its own ability noise: epilogues no longer fill _eps_cap
-        mlp = model.ability_encoder.mlp
-        self.hidden = mlp[0].weight.shape[0]
-        if self.hidden > 256:
-            raise NotImplementedError('hidden_dim > 256')
-        plist = [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, mlp[4].weight, mlp[4].bias]
-        self.mlp_flat, self.mlp_m, self.mlp_v = self._flatten(plist)      # W0 | b0 | W1 | b1 | W2 | b2
-        dev, n_item = self._init_state(model, lr)
-        self._watched = plist + [self.mlp_flat, self.item_mu, self.item_lv]
-        self.table = torch.empty(2, 2 * model.ability_dim, device=dev)
-        self.saved_h = torch.empty(4 * self.hidden, device=dev)
-        self.kl_parts = torch.empty(2 * ((n_item + 63) // 64), device=dev)      # (two halves: the folded step double-buffers them)
-        self._init_rng(rng, seed, keep_item_noise=rng == 'native')
-        self.fused_noise = bool(fused_noise)      # rng='native': draw the noise inside the prologue launch (2 launches fewer)
+        self._pending = None                  # what forward_backward() leaves for update(): the arguments of the class's _update()
+        self.last = None                      # RawElbo of the last step (posterior outputs, scalars)
+        enc = model.ability_encoder
+        self.hidden = (enc.mlp1 if model.ability_merge == 'mean' else enc.mlp)[0].weight.shape[0]
+        # the item tensors and their moments, Adam's counters and scalars, the item sample, the loss
+        self.item_mu = model.item_encoder.mu_lookup.weight
+        self.item_lv = model.item_encoder.logvar_lookup.weight
+        assert self.item_mu.is_contiguous() and self.item_lv.is_contiguous()
+        dev, n_item = self.item_mu.device, self.item_mu.numel()
+        self.item_m = torch.zeros(2 * n_item, device=dev)
+        self.item_v = torch.zeros(2 * n_item, device=dev)
+        self._steps = torch.zeros(2, dtype=torch.int32, device=dev)      # [Adam step t, completed steps (noise counter)]
+        self.lr = torch.tensor(float(lr), device=dev)
+        self.beta = torch.tensor(1.0, device=dev)
+        self._beta_host = 1.0
+        self.item_feat = torch.empty_like(self.item_mu)
+        self.loss = torch.zeros((), device=dev)
+        # Reparameterisation noise: 'torch' = torch.randn on the model's generators (the reference's stream for a given seed),
+        # 'native' = Philox4x32-10 keyed by `seed` (vibo_fill_normal's streams, ~5x faster on [1M, 8]).
+        # (person-sharded: item noise is the same on every rank, ability noise uses stream 1 + rank)
+        self.rng, self.seed = rng, int(seed)
+        self.fused_noise = True               # rng='native': the noise is drawn inside the prologue launch
+        self._eps_item = torch.empty_like(self.item_mu) if keep_item_noise else None
+        self._eps_ab = {}
 
     @staticmethod
     def _flatten(plist):
@@ -128,34 +150,9 @@ class FusedTrainer:
             off += n
         return flat, torch.zeros_like(flat), torch.zeros_like(flat)
 
-    def _init_state(self, model, lr):
-        """What every fused trainer keeps: the item tensors and their moments, Adam's counters and scalars, the item sample, the
-        loss and the step's bookkeeping.  Returns (device, item entries)."""
-        self.item_mu = model.item_encoder.mu_lookup.weight
-        self.item_lv = model.item_encoder.logvar_lookup.weight
-        assert self.item_mu.is_contiguous() and self.item_lv.is_contiguous()
-        dev, n_item = self.item_mu.device, self.item_mu.numel()
-        self.item_m = torch.zeros(2 * n_item, device=dev)
-        self.item_v = torch.zeros(2 * n_item, device=dev)
-        self._steps = torch.zeros(2, dtype=torch.int32, device=dev)      # [Adam step t, completed steps (noise counter)]
-        self.lr = torch.tensor(float(lr), device=dev)
-        self.beta = torch.tensor(1.0, device=dev)
-        self._beta_host = 1.0
-        self.item_feat = torch.empty_like(self.item_mu)
-        self.loss = torch.zeros((), device=dev)
-        self.last = None                      # RawElbo of the last step (posterior outputs, scalars)
-        self._pending = None
-        return dev, n_item
-
-    def _init_rng(self, rng, seed, keep_item_noise=True):
-        """Reparameterisation noise: 'torch' = torch.randn on the model's generators (the reference's stream for a given seed),
-        'native' = Philox4x32-10 keyed by `seed` (vibo_fill_normal's streams, ~5x faster on [1M, 8]).
-        (person-sharded: item noise is the same on every rank, ability noise uses stream 1 + rank)"""
-        if rng not in ('torch', 'native'):
-            raise ValueError("rng must be 'torch' or 'native'")
-        self.rng, self.seed = rng, int(seed)
-        self._eps_item = torch.empty_like(self.item_mu) if keep_item_noise else None
-        self._eps_ab = {}
+    def _check_layout(self, param_floats):
+        if param_floats != self.par_flat.numel():
+            raise RuntimeError(f'{type(self).__name__}: parameter layout mismatch')
 
     def _begin(self, response, mask, beta, row_index, reg_mode):
         """What every forward_backward() starts with: the KL weight, the rows as the kernels read them, the descriptor of this
@@ -179,16 +176,19 @@ class FusedTrainer:
         return eps_ab
 
     def _choose_noise(self, B, dev, eps_item, eps_ability):
-        """The noise of a step of the two sibling trainers -> (eps_item, eps_ab, native): the caller's (given), this trainer's
-        buffers for the prologue launch to fill (native), or torch's generators in the reference's draw order, item eps then
-        ability eps (models.py:361,368) -- the item draw happens here, eps_ab is None and the caller draws it after the prologue."""
-        if eps_item is not None:
-            if eps_ability is None:
+        """The noise of a step -> (eps_item, eps_ab, native): the caller's (given), this trainer's buffers for the native draws to
+        fill (native), or torch's generators in the reference's draw order, item eps then ability eps (models.py:361,368) -- the
+        item draw happens here, eps_ab is None and the caller draws it after the prologue (_draw_ability)."""
+        if eps_item is not None or eps_ability is not None:
+            if eps_item is None or eps_ability is None:
                 raise ValueError('pass both eps_item and eps_ability, or neither')
             return eps_item.contiguous().float(), eps_ability.contiguous().float(), False
         if self.rng == 'native':
             return self._eps_item, self._ab_buffer(B, dev), True
         return self.model._randn(self.item_mu.shape, self.item_mu, self.model._item_gen), None, False
+
+    def _draw_ability(self, B):
+        return self.model._randn((B, self.model.ability_dim), self.item_mu, self.model._ability_gen)
 
     def set_beta(self, beta):
         """KL weight (vibo.py:223-230).  A device scalar: update it between graph replays when annealing."""
@@ -209,66 +209,98 @@ class FusedTrainer:
 
     reprime = invalidate
 
+    @property
+    def step_count(self):
+        """Adam's step number (device int32 scalar)."""
+        return self._steps[0]
+
     @torch.no_grad()
     def step(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
-        """One train step; returns the loss (device scalar).  = forward_backward(); [all-reduce]; update().
+        """One train step; returns the loss (device scalar).  = forward_backward(); reduce_shards(); update().
         eps_item [I, D] / eps_ability [B, A]: replay given reparameterisation noise instead of drawing it (parity tests against
-        the reference's recorded steps; takes the four-launch form)."""
-        raw = self.forward_backward(response, mask, beta=beta, row_index=row_index, eps_item=eps_item, eps_ability=eps_ability)
-        if self.model._reducer is not None:
-            self.model._reducer(raw.flat)     # person-sharded: ONE all-reduce per step
-        return self.update()
+        the reference's recorded steps; FusedTrainer takes the four-launch form)."""
+        self._forward_backward(response, mask, beta, row_index, eps_item, eps_ability)
+        self.reduce_shards()
+        return self._finish()
 
     @torch.no_grad()
     def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
-        """Noise, prologue and the fused ELBO forward+backward of this rank's persons.  Returns the RawElbo whose
-        `.flat` buffer [scalars | grads] a person-sharded caller all-reduces before `update()`.  (Split from
-        `update()` so that a multi-GPU loop can replay the two halves as hipGraphs around an eager collective.)"""
-        model, spec, lib, p = self.model, self.model.spec, _lib.load(), ops._ptr
+        """Noise, prologue and the fused ELBO forward+backward of this rank's persons (the class's _forward_backward).  Returns the
+        step's outputs (`trainer.last`), whose `.flat` buffer [scalars | grads] a person-sharded caller all-reduces before `update()`.
+        (Split from `update()` so that a multi-GPU loop can replay the two halves as hipGraphs around an eager collective.)"""
+        return self._forward_backward(response, mask, beta, row_index, eps_item, eps_ability)
+
+    def reduce_shards(self):
+        """Person-sharded: ONE all-reduce per step, of the flat buffer [scalars | grads] forward_backward() returned."""
+        if self.model._reducer is not None:
+            self.model._reducer(self.last.flat)
+
+    @torch.no_grad()
+    def update(self):
+        """Loss, backward of everything outside the ELBO call and Adam from the (all-reduced) buffers of forward_backward()
+        (the class's _update)."""
+        return self._finish()
+
+    def _finish(self):
+        if self._pending is None:
+            raise RuntimeError(f'{type(self).__name__}.update(): no forward_backward() is pending')
+        return self._update(*self._pending)
+
+
+class FusedTrainer(_FusedStep):
+    def __new__(cls, model=None, *args, **kwargs):
+        # one entry point: the class the coverage table names is built and returned (not an instance of this one: no second __init__)
+        # (model=None: copy / pickle re-create the object through cls.__new__(cls) and fill __dict__ themselves)
+        if cls is FusedTrainer and model is not None:
+            covering, why = fused_trainer_for(model, conditional=kwargs.get('conditional', False))
+            if covering is None:
+                raise NotImplementedError(why)
+            if covering is not cls:
+                return covering(model, *args, **kwargs)
+        return super().__new__(cls)
+
+    def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None):
+        super().__init__(model, lr, rng, seed, fold=fold, keep_item_noise=rng == 'native')
+        self._eps_cap = None                  # folded step: the ability-noise buffer [capacity] every step's epilogue refills
+        self._eps_keep = []                   # (outgrown buffers stay alive: a captured graph may still write to them)
+        self._max_batch = int(max_batch) if max_batch else 0      # persons of the largest minibatch to expect (sizes _eps_cap once)
+        self._draw_mode = False               # a folded step drew its own ability noise: epilogues no longer fill _eps_cap
+        mlp = model.ability_encoder.mlp
+        plist = [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, mlp[4].weight, mlp[4].bias]
+        self.mlp_flat, self.mlp_m, self.mlp_v = self._flatten(plist)      # W0 | b0 | W1 | b1 | W2 | b2
+        self._watched = plist + [self.mlp_flat, self.item_mu, self.item_lv]
+        dev, n_item = self.item_mu.device, self.item_mu.numel()
+        self.table = torch.empty(2, 2 * model.ability_dim, device=dev)
+        self.saved_h = torch.empty(4 * self.hidden, device=dev)
+        self.kl_parts = torch.empty(2 * ((n_item + 63) // 64), device=dev)      # (two halves: the folded step double-buffers them)
+        self.fused_noise = bool(fused_noise)      # rng='native': draw the noise inside the prologue launch (2 launches fewer)
+
+    def _forward_backward(self, response, mask, beta, row_index, eps_item, eps_ability):
+        model, lib, p = self.model, _lib.load(), ops._ptr
         response, mask, code, B, I, stream, d, ab_stream = self._begin(response, mask, beta, row_index, _lib.REG_KL)
-        given = eps_item is not None or eps_ability is not None
-        if given and (eps_item is None or eps_ability is None):
-            raise ValueError('pass both eps_item and eps_ability, or neither')
+        given = eps_item is not None or eps_ability is not None      # (given noise: the four-launch form; _choose_noise checks it)
         step_bits = lib.vibo_train_step_supported(ctypes.byref(d)) if (self.fold and self.rng == 'native' and self.fused_noise and not given) else 0
         if step_bits & 1:
             return self._forward_backward_folded(d, step_bits, response, mask, code, row_index, B, ab_stream, stream)
         # ---- the four-launch form ----
-        if given:
-            eps_item, eps_ab = eps_item.contiguous().float(), eps_ability.contiguous().float()
-            self._primed_for = None
-            ops._call('vibo_train_prologue', ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
-                      p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
-                      p(self._steps), stream)
-            raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, eps_ab, None,
-                                       _lib.REG_KL, True, B)
-            self._pending = (d, eps_item, raw, None)
-            self._folded_open = False             # (a four-launch step replaces whatever was pending)
-            self.last = raw
-            return raw
-        # reference draw order: item eps, then ability eps (models.py:361,368)
-        if self.rng == 'native':
-            eps_item, eps_ab = self._eps_item, self._ab_buffer(B, response.device)
-            self._primed_for = None           # (these draws move on without refilling the folded step's buffers)
+        eps_item, eps_ab, native = self._choose_noise(B, response.device, eps_item, eps_ability)
+        self._primed_for = None               # (these draws move on without refilling the folded step's buffers)
+        prologue = (ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv), p(eps_item), p(self.item_feat),
+                    p(self.table), p(self.saved_h), p(self.kl_parts), p(self._steps))
+        if native and self.fused_noise:       # noise drawn inside the prologue launch
+            ops._call('vibo_train_prologue_noise', *prologue, self.seed, p(eps_ab), ab_stream, stream)
         else:
-            eps_item = model._randn(self.item_mu.shape, self.item_mu, model._item_gen)
-        if self.rng == 'native' and self.fused_noise:       # noise drawn inside the prologue launch
-            ops._call('vibo_train_prologue_noise', ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
-                      p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
-                      p(self._steps), self.seed, p(eps_ab), ab_stream, stream)
-        else:
-            noise_step = ctypes.c_void_p(self._steps.data_ptr() + 4)          # completed steps (step_count[1])
-            if self.rng == 'native':
+            if native:
+                noise_step = ctypes.c_void_p(self._steps.data_ptr() + 4)          # completed steps (step_count[1])
                 ops._call('vibo_fill_normal', p(eps_item), eps_item.numel(), self.seed, noise_step, 0, stream)
                 ops._call('vibo_fill_normal', p(eps_ab), eps_ab.numel(), self.seed, noise_step, ab_stream, stream)
-            ops._call('vibo_train_prologue', ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv),
-                      p(eps_item), p(self.item_feat), p(self.table), p(self.saved_h), p(self.kl_parts),
-                      p(self._steps), stream)
-            if self.rng != 'native':
-                eps_ab = model._randn((B, model.ability_dim), self.item_mu, model._ability_gen)
-        raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, eps_ab, None,
+            ops._call('vibo_train_prologue', *prologue, stream)
+        if eps_ab is None:
+            eps_ab = self._draw_ability(B)
+        raw = ops._BACKEND['elbo'](model.spec, response, mask, code, row_index, self.table, self.item_feat, eps_ab, None,
                                    _lib.REG_KL, True, B)
         self._pending = (d, eps_item, raw, None)
-        self._folded_open = False
+        self._folded_open = False             # (a four-launch step replaces whatever was pending)
         self.last = raw
         return raw
 
@@ -327,17 +359,7 @@ class FusedTrainer:
         self.last = raw
         return raw
 
-    @property
-    def step_count(self):
-        """Adam's step number (device int32 scalar)."""
-        return self._steps[0]
-
-    @torch.no_grad()
-    def update(self):
-        """Loss, encoder-MLP / item backward and Adam from the (all-reduced) flat buffer of forward_backward()."""
-        if self._pending is None:
-            raise RuntimeError('FusedTrainer.update(): no forward_backward() is pending')
-        d, eps_item, raw, folded_stream = self._pending
+    def _update(self, d, eps_item, raw, folded_stream):
         p = ops._ptr
         stream = ops._stream(raw.flat.device)
         if folded_stream is not None:
@@ -356,7 +378,7 @@ class FusedTrainer:
         return self.loss
 
 
-class FusedCondFlowTrainer(FusedTrainer):
+class FusedCondFlowTrainer(_FusedStep):
     """The fused train step for --conditional-posterior and / or --n-norm-flows models (vibo.py:243-268 with
     models.py:337-354, 380-443, 664-710, flows.py:21-66): vibo_ctrain_prologue (item sample, item-side flows, ability-flow
     packing, the encoder MLP on the 2 x I rows [c, item_i] -> expert table; optionally the Philox noise) -> vibo_elbo_fwd_bwd
@@ -366,16 +388,11 @@ class FusedCondFlowTrainer(FusedTrainer):
 
     def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None):
         # (fold: FusedTrainer's two-launch form; this class's step is prologue / ELBO call / epilogue either way)
-        if model.ability_merge != 'product' or getattr(model, 'generative_model', 'irt') != 'irt':
-            raise NotImplementedError('the fused trainers cover the product-of-experts encoder with the IRT decoder; '
-                                      'use model.elbo_step + torch.optim.Adam otherwise')
-        self.model = model
-        self.generation = 0                   # (no buffer of this step ever moves: see FusedTrainer.generation)
+        super().__init__(model, lr, rng, seed)
+        if not fused_noise:
+            raise NotImplementedError('FusedCondFlowTrainer draws the native noise inside vibo_ctrain_prologue (there is no '
+                                      'separate vibo_fill_normal form of this step): fused_noise=False is not available')
         mlp = model.ability_encoder.mlp
-        self.hidden = mlp[0].weight.shape[0]
-        if self.hidden > 64:
-            raise NotImplementedError('FusedCondFlowTrainer: hidden_dim <= 64 (one 64-wide tile of the matrix-pipe table MLP); '
-                                      'use model.elbo_step + torch.optim.Adam otherwise')
         plist = [mlp[0].weight, mlp[0].bias, mlp[2].weight, mlp[2].bias, mlp[4].weight, mlp[4].bias]
         F = model.n_norm_flows
         if F > 0:
@@ -383,24 +400,16 @@ class FusedCondFlowTrainer(FusedTrainer):
                 for fl in st.flows:
                     plist += [fl.u, fl.w, fl.b]
         self.par_flat, self.par_m, self.par_v = self._flatten(plist)      # (the layout of include/vibo_hip.h: vibo_ctrain_*)
-        dev, _ = self._init_state(model, lr)
-        I, A = self.item_mu.shape[0], model.ability_dim
+        dev, I, A = self.item_mu.device, self.item_mu.shape[0], model.ability_dim
         self.item_k = torch.empty_like(self.item_mu) if F > 0 else self.item_feat
         self.table = torch.empty((2, I, 2 * A) if model.conditional_posterior else (2, 2 * A), device=dev)
         self.flow_packed = torch.empty(F, 2 * A + 1, device=dev) if F > 0 else None
         self._desc0 = ops._make_desc(model.spec, 1, I, _lib.MASK_NONE, _lib.REG_SAMPLED if F > 0 else _lib.REG_KL, True, I, 0)
         lib = _lib.load()
-        if lib.vibo_ctrain_param_floats(ctypes.byref(self._desc0), self.hidden) != self.par_flat.numel():
-            raise RuntimeError('FusedCondFlowTrainer: parameter layout mismatch')
+        self._check_layout(lib.vibo_ctrain_param_floats(ctypes.byref(self._desc0), self.hidden))
         self.scratch = torch.empty(int(lib.vibo_ctrain_scratch_floats(ctypes.byref(self._desc0), self.hidden)), device=dev)
-        self._init_rng(rng, seed)
-        if not fused_noise:
-            raise NotImplementedError('FusedCondFlowTrainer draws the native noise inside vibo_ctrain_prologue (there is no '
-                                      'separate vibo_fill_normal form of this step): fused_noise=False is not available')
-        self.fused_noise = True
 
-    @torch.no_grad()
-    def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
+    def _forward_backward(self, response, mask, beta, row_index, eps_item, eps_ability):
         model, spec, p = self.model, self.model.spec, ops._ptr
         reg_mode = _lib.REG_SAMPLED if model.n_norm_flows > 0 else _lib.REG_KL
         response, mask, code, B, I, stream, d, ab_stream = self._begin(response, mask, beta, row_index, reg_mode)
@@ -410,16 +419,14 @@ class FusedCondFlowTrainer(FusedTrainer):
                   p(self.item_feat), p(self.item_k), p(self.table), p(self.flow_packed), p(self.scratch),
                   p(self._steps), stream)
         if eps_ab is None:
-            eps_ab = model._randn((B, model.ability_dim), self.item_mu, model._ability_gen)
+            eps_ab = self._draw_ability(B)
         raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_k, eps_ab, self.flow_packed,
                                    reg_mode, True, B)
         self._pending = (d, eps_item, raw)
         self.last = raw
         return raw
 
-    @torch.no_grad()
-    def update(self):
-        d, eps_item, raw = self._pending
+    def _update(self, d, eps_item, raw):
         p = ops._ptr
         ops._call('vibo_ctrain_epilogue', ctypes.byref(d), self.hidden, p(raw.flat), p(eps_item), p(self.item_feat), p(self.item_k),
                   p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
@@ -428,7 +435,7 @@ class FusedCondFlowTrainer(FusedTrainer):
         return self.loss
 
 
-class FusedMeanTrainer(FusedTrainer):
+class FusedMeanTrainer(_FusedStep):
     """The fused train step for --ability-merge mean models with the unconditional posterior (vibo.py:243-268 with
     models.py:584-594, 631-650): vibo_mtrain_prologue (item sample, item KL, the 2-row mlp1 forward and the u, v collapse of
     mlp2[0]; optionally the Philox noise) -> vibo_mean_encoder_forward (per-person posterior from the row counts) ->
@@ -440,22 +447,16 @@ class FusedMeanTrainer(FusedTrainer):
     in one collective; the per-person posterior gradients stay on their rank."""
 
     def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None):
-        if not fused_trainer_covers(model):
-            raise NotImplementedError('FusedMeanTrainer: --ability-merge mean with the unconditional posterior, the IRT decoder, no '
-                                      'flows, hidden_dim <= 128, ability_dim <= 8; use model.elbo_step + torch.optim.Adam otherwise')
-        self.model = model
-        self.generation = 0
+        super().__init__(model, lr, rng, seed)
         enc = model.ability_encoder
-        self.hidden = enc.mlp1[0].weight.shape[0]
         plist = [enc.mlp1[0].weight, enc.mlp1[0].bias, enc.mlp1[2].weight, enc.mlp1[2].bias,
                  enc.mlp2[0].weight, enc.mlp2[0].bias, enc.mlp2[2].weight, enc.mlp2[2].bias]
         self.par_flat, self.par_m, self.par_v = self._flatten(plist)      # (the layout of include/vibo_hip.h: vibo_mtrain_*)
-        dev, n_item = self._init_state(model, lr)
+        dev, n_item = self.item_mu.device, self.item_mu.numel()
         I, A, H = self.item_mu.shape[0], model.ability_dim, self.hidden
         self._desc0 = ops._make_desc(model.spec, 1, I, _lib.MASK_NONE, _lib.REG_KL, True, I, 0)
         lib = _lib.load()
-        if lib.vibo_mtrain_param_floats(ctypes.byref(self._desc0), H) != self.par_flat.numel():
-            raise RuntimeError('FusedMeanTrainer: parameter layout mismatch')
+        self._check_layout(lib.vibo_mtrain_param_floats(ctypes.byref(self._desc0), H))
         self.uv = torch.empty(2 * H, device=dev)
         self.saved = torch.empty(4 * H, device=dev)
         self.grad_sums = torch.empty(2 * H + 2 * A * H + 2 * A, device=dev)
@@ -463,12 +464,9 @@ class FusedMeanTrainer(FusedTrainer):
         o = 2 * H + H * H + H + H * H + H
         self._w22 = self.par_flat[o:o + 2 * A * H]
         self._b22 = self.par_flat[o + 2 * A * H:o + 2 * A * H + 2 * A]
-        self._init_rng(rng, seed)
-        self.fused_noise = True
         self._parts = {}
 
-    @torch.no_grad()
-    def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
+    def _forward_backward(self, response, mask, beta, row_index, eps_item, eps_ability):
         model, spec, lib, p = self.model, self.model.spec, _lib.load(), ops._ptr
         counts = ops.row_counts(response, mask)             # packed (n_correct << 16 | n_observed) of every resident row, cached
         if row_index is not None:
@@ -481,7 +479,7 @@ class FusedMeanTrainer(FusedTrainer):
                   1 if native else 0, p(eps_ab) if native else None, ab_stream, p(self.item_feat), p(self.uv),
                   p(self.saved), p(self.kl_parts), p(self._steps), stream)
         if eps_ab is None:
-            eps_ab = model._randn((B, A), self.item_mu, model._ability_gen)
+            eps_ab = self._draw_ability(B)
         post = torch.empty(B, 2 * A, device=dev)
         dm = ops._mean_desc(counts, A)
         ops._call('vibo_mean_encoder_forward', ctypes.byref(dm), H, p(counts), p(self.uv[:H]), p(self.uv[H:]), p(self._w22), p(self._b22),
@@ -519,15 +517,7 @@ class FusedMeanTrainer(FusedTrainer):
         psum.copy_(buf[ns + n_item:].view_as(psum))
         self._pending = (d, eps_item, raw, psum, 1)
 
-    @torch.no_grad()
-    def step(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
-        self.forward_backward(response, mask, beta=beta, row_index=row_index, eps_item=eps_item, eps_ability=eps_ability)
-        self.reduce_shards()
-        return self.update()
-
-    @torch.no_grad()
-    def update(self):
-        d, eps_item, raw, parts, n_part = self._pending
+    def _update(self, d, eps_item, raw, parts, n_part):
         p = ops._ptr
         ops._call('vibo_mtrain_epilogue', ctypes.byref(d), self.hidden, p(raw.flat), p(parts), n_part, p(self.grad_sums), p(self.saved),
                   p(self.kl_parts), p(eps_item), p(self.beta), p(self.lr), p(self._steps), p(self.par_flat),
@@ -547,7 +537,7 @@ class _DecoderStep:
     scalars = property(lambda self: self.flat)
 
 
-class FusedDecoderTrainer(FusedTrainer):
+class FusedDecoderTrainer(_FusedStep):
     """The fused train step for --generative-model link | deep | residual (vibo.py:243-268 with models.py:337-443, 596-629,
     769-919): vibo_dtrain_prologue (item sample, item KL, 2-row encoder table, mlp_item_feat and U; optionally the Philox noise) ->
     vibo_dtrain_forward_backward (per chunk of decoder.PERSON_CHUNK persons: product of experts from the packed row counts, ability
@@ -563,46 +553,21 @@ class FusedDecoderTrainer(FusedTrainer):
     persistent buffer -- and the backward of both, in the same three calls).  The default keeps refusing such a model."""
 
     def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None, conditional=False):
-        kind = getattr(model, 'generative_model', 'irt')
-        why = None
-        if kind not in _lib.DECODER_KINDS:
-            why = 'an IRT-decoder model (FusedTrainer covers those)'
-        elif model.ability_merge != 'product':
-            why = '--ability-merge mean'
-        elif model.conditional_posterior and not conditional:
-            why = 'the conditional posterior (unless built with conditional=True)'
-        elif model.n_norm_flows > 0:
-            why = 'normalizing flows'
-        elif model._reducer is not None:
-            why = 'person sharding'
-        elif model.num_item > 65535:
-            why = 'more than 65 535 items (the packed row counts)'
-        if why is not None:
-            raise NotImplementedError(f'FusedDecoderTrainer does not cover {why}; use model.elbo_step + torch.optim.Adam')
-        self.model = model
+        super().__init__(model, lr, rng, seed, conditional=conditional)
+        kind = model.generative_model
         self.kind = _lib.DECODER_KINDS[kind]
         self.cond = bool(model.conditional_posterior)
         # the three calls of a step: vibo_dtrain_* / vibo_dtrain_*_cond
         self._prologue, self._fwd_bwd, self._epilogue = ('vibo_dtrain_' + call + ('_cond' if self.cond else '')
                                                          for call in ('prologue', 'forward_backward', 'epilogue'))
-        self.generation = 0                   # (no buffer of this step ever moves: see FusedTrainer.generation)
-        self._primed_for, self._folded_open = None, False      # (FusedTrainer.invalidate's fields: every step starts from the parameters)
         mlp, dec = model.ability_encoder.mlp, model.decoder
-        self.hidden = mlp[0].weight.shape[0]
-        if self.hidden > 64 or dec.hidden_dim != self.hidden:
-            raise NotImplementedError('FusedDecoderTrainer: hidden_dim <= 64 (the per-term decoder kernel\'s width); '
-                                      'use model.elbo_step + torch.optim.Adam otherwise')
         stacks = [dec.link] if kind == 'link' else [dec.mlp_item_feat, dec.mlp_ability, dec.mlp_concat]
         plist = [t for st in [mlp] + stacks for k in (0, 2, 4) for t in (st[k].weight, st[k].bias)]
         self.par_flat, self.par_m, self.par_v = self._flatten(plist)      # (the layout of include/vibo_hip.h: vibo_dtrain_*)
-        dev, _ = self._init_state(model, lr)
         I = self.item_mu.shape[0]
         self._desc0 = ops._make_desc(model.spec, 1, I, _lib.MASK_NONE, _lib.REG_KL, True, I, 0)
         lib = _lib.load()
-        if lib.vibo_dtrain_param_floats(ctypes.byref(self._desc0), self.kind, self.hidden) != self.par_flat.numel():
-            raise RuntimeError('FusedDecoderTrainer: parameter layout mismatch')
-        self._init_rng(rng, seed)
-        self.fused_noise = True
+        self._check_layout(lib.vibo_dtrain_param_floats(ctypes.byref(self._desc0), self.kind, self.hidden))
         self._scratch = {}                    # (persons, chunk) -> scratch buffer: never freed or replaced (captured graphs point at it)
         self._rows = {}                       # (persons, mask given) -> the gathered minibatch's dense rows: never replaced
         self._codes = {}                      # (persons, source) -> the minibatch's cell codes (conditional posterior): never replaced
@@ -654,8 +619,7 @@ class FusedDecoderTrainer(FusedTrainer):
         ops._call('vibo_pack_codes', ctypes.byref(d), ops._ptr(r), ops._ptr(m), ops._ptr(buf), ctypes.c_int64(stride), stream)
         return buf, stride
 
-    @torch.no_grad()
-    def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
+    def _forward_backward(self, response, mask, beta, row_index, eps_item, eps_ability):
         from . import decoder
         model, lib, p = self.model, _lib.load(), ops._ptr
         if beta is not None:
@@ -688,7 +652,7 @@ class FusedDecoderTrainer(FusedTrainer):
                   p(eps_item), self.seed, 1 if native else 0, p(eps_ab) if native else None, 1, p(self.item_feat),
                   p(scratch), p(self._steps), stream)
         if eps_ab is None:
-            eps_ab = model._randn((B, A), self.item_mu, model._ability_gen)
+            eps_ab = self._draw_ability(B)
         ops._call(self._fwd_bwd, ctypes.byref(d), self.kind, H, chunk, p(self.par_flat), p(r), p(m), p(counts), *code_args, p(eps_ab),
                   p(self.item_feat), p(scratch), stream)
         off = [int(lib.vibo_dtrain_scratch_offset(ctypes.byref(d), self.kind, H, chunk, w))
@@ -699,16 +663,10 @@ class FusedDecoderTrainer(FusedTrainer):
         self._pending = (d, eps_item, scratch, chunk)
         return self.last
 
-    @torch.no_grad()
-    def step(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None):
-        self.forward_backward(response, mask, beta=beta, row_index=row_index, eps_item=eps_item, eps_ability=eps_ability)
-        return self.update()
+    def reduce_shards(self):
+        """Nothing to reduce: this trainer refuses person sharding."""
 
-    @torch.no_grad()
-    def update(self):
-        if self._pending is None:
-            raise RuntimeError('FusedDecoderTrainer.update(): no forward_backward() is pending')
-        d, eps_item, scratch, chunk = self._pending
+    def _update(self, d, eps_item, scratch, chunk):
         self._pending = None
         p = ops._ptr
         ops._call(self._epilogue, ctypes.byref(d), self.kind, self.hidden, chunk, p(scratch), p(eps_item), p(self.item_feat),
