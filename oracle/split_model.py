@@ -214,6 +214,11 @@ def sigmoid(l):
     return 0.5 * (1.0 + np.tanh(0.5 * np.asarray(l, np.float64)))
 
 
+def sigmoid_rel(l):
+    """sigmoid with a small RELATIVE error on both tails (the tanh form above is good to 1e-16 absolute: a guess of 1e-13 needs more)."""
+    return np.exp(-np.logaddexp(0.0, -np.asarray(l, np.float64)))
+
+
 def g_bound(logit, e_logit, dgdl=None, c_eval=C_SIGMA):
     """Bound of the error of g = d ll/d l evaluated in fp32 from a logit that is off by at most e_logit.  dgdl: |d g/d l| where it
     is not sigmoid' (3PL)."""
@@ -292,7 +297,7 @@ def _grad_bounds_panel(theta, a, b, g, obs, e_logit, irt, fp32, dgdl, c_eval):
 HOSTILE_MANTISSAS = (0x7FFFFF, 0x7FF001, 0x7FEFFF, 0x7FF000, 0x001FFF, 0x000000, 0x7FE000, 0x400000, 0x7FFFFE, 0x2AAAAA, 0x555555,
                      0x0007FF, 0x000001, 0x3FF800)
 DELTAS = (1e-3, -1e-3, 0.1, -0.1, 1.0, -1.0, 3.0, -3.0)
-CLASSES = ('cancel', 'hostile', 'bias', 'mixed_a', 'mixed_b', 'clamp3', 'onepl')
+CLASSES = ('cancel', 'hostile', 'bias', 'mixed_a', 'mixed_b', 'clamp3', 'onepl', 'threepl')
 
 
 def from_bits(sign, exponent, mantissa):
@@ -323,9 +328,11 @@ def make_case(cls, A, B, I, seed, theta=None, shift=0, outliers=(), same_tile=Fa
     clamp3 (3PL): cancelling logits as in 'cancel', placed so that p = c + (1 - c) sigmoid(l) of the observed cell lies within 1e-6 of a
     probability clamp value: just inside 1 - eps32 (1 - p = 4 ... 8 eps32), on both sides of eps32 (c < eps32: guess logits -16.5 ...
     -30, l = -15.94 +- 0.02 ... 1; where the logit is below -15.94 the guess is so small that the exact p is below eps32 as well, so the
-    reference's logit clamp and its probability clamp agree), and about 1 % of the items within 4 ulp of eps32 (guess logit -40)."""
+    reference's logit clamp and its probability clamp agree), and about 1 % of the items within 4 ulp of eps32 (guess logit -40).
+    threepl (3PL): an ordinary 3PL problem -- logits as in 'cancel', guess logits uniform in (-2, 1): p = 0.12 ... 1 - 1e-2, far from both
+    probability clamps, so the guess gradient is alive in every observed cell."""
     rng = np.random.default_rng(seed)
-    irt = 1 if cls == 'onepl' else 3 if cls == 'clamp3' else 2
+    irt = 1 if cls == 'onepl' else 3 if cls in ('clamp3', 'threepl') else 2
     own_theta = theta is None
     sgn = lambda shape: rng.choice([-1.0, 1.0], size=shape)
     if own_theta:
@@ -372,6 +379,8 @@ def make_case(cls, A, B, I, seed, theta=None, shift=0, outliers=(), same_tile=Fa
         gamma[kind == 99] = -40.0                                                     # ... within 4 ulp of eps32: excluded cells
         target[dead_lo] = -LOGIT_LO - rng.choice([0.02, 0.1, 0.5], int(dead_lo.sum()))
         gamma = f32(gamma)
+    if cls == 'threepl':
+        gamma = f32(rng.uniform(-2.0, 1.0, I))
     at = np.einsum('ik,ik->i', np.asarray(a, np.float64), np.asarray(theta, np.float64)[p_obs])
     if cls == 'bias':
         b = _hostile(rng, (I,), -3, 2)               # |b| in [1/8, 8)
@@ -412,7 +421,8 @@ def ulp32(x):
 
 def reference(case, theta=None):
     """fp64 reference of a case on the fp32 theta the kernel used: exact logits, ll and g = d ll/d l per cell (zero where
-    unobserved), |d g/d l|, the three gradients, and `excluded` (3PL cells within 4 fp32 ulp of a probability clamp value).
+    unobserved), |d g/d l|, the three gradients, g_c = d LL / d guess-logit per item with its per-cell terms gc and |d gc/d l| (3PL;
+    zeros otherwise), and `excluded` (3PL cells within 4 fp32 ulp of a probability clamp value).
     Saturation as in vibo_table_ref.fused_elbo_ref(exact_saturation=True): the logit held to +-LOGIT_LO for the value, gradient zero
     outside [-LOGIT_LO, LOGIT_HI] and, 3PL, where p leaves [eps32, 1 - eps32]."""
     theta = case['theta'] if theta is None else f32(theta)
@@ -434,10 +444,16 @@ def reference(case, theta=None):
         p1, p2 = (1.0 - c) * sg * (1.0 - sg), (1.0 - c) * sg * (1.0 - sg) * (1.0 - 2.0 * sg)
         g = np.where(x == 1, p1 / pc, -sg)
         dgdl = np.where(x == 1, np.abs(p2 / pc - (p1 / pc) ** 2), sg * (1.0 - sg))
+        # d ll / d guess-logit = (x / p - (1 - x) / (1 - p)) (1 - sigmoid(l)) c (1 - c): c (1 - c) (1 - sg) / p answered right, -c wrong
+        cr = sigmoid_rel(np.asarray(case['gamma'], np.float64))[None, :]
+        gc = np.where(x == 1, cr * (1.0 - c) * (1.0 - sg) / pc, -cr * np.ones_like(sg))
+        dgcdl = np.where(x == 1, cr * (1.0 - c) * sg * (1.0 - sg) * (1.0 / pc + (1.0 - c) * (1.0 - sg) / pc ** 2), 0.0)
     else:
         ll = x * lc - np.maximum(lc, 0.0) - np.log1p(np.exp(-np.abs(lc)))
         g = x - sg
         dgdl = sg * (1.0 - sg)
+        gc, dgcdl = np.zeros_like(l), np.zeros_like(l)
     g = np.where(obs, g, 0.0) * live
+    gc = np.where(obs, gc, 0.0) * live
     return dict(logit=l, g=g, dgdl=dgdl, ll=np.where(obs, ll, 0.0), g_b=g.sum(0), g_a=-(g.T @ t64), g_theta=-(g @ a64), live=live,
-                excluded=excluded)
+                excluded=excluded, gc=gc, dgcdl=dgcdl, g_c=gc.sum(0))

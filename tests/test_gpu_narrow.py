@@ -9,6 +9,7 @@ configs[0]'s 100 items and configs[3]'s CritLangAcq rows of 95; the planner's ch
 The other GPU modules pin one of the row-split kernels per fixture run (vibo_desc.flags), so their shapes never reach this
 kernel; here ops.DESC_FLAGS stays 0 and every case asserts that the planner picked it.
 Tolerances: ELBO <= 1e-4 relative, posterior <= 2e-5, gradients <= 1e-4 of the tensor's max-abs.
+tests/test_gpu_narrow_cells.py holds the same kernel entry by entry to derived bounds: every width 4..128, padding, several units per wave.
 """
 import os
 

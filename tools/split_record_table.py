@@ -1,7 +1,10 @@
-"""VIBO_TOL_RECORD file of tests/test_gpu_split_worst_case.py -> the table kept in profiles/split_worst_case_record.txt.
+"""VIBO_TOL_RECORD file of a cell-by-cell GPU test -> the table kept under profiles/.  The record kind is the second argument:
 
     VIBO_TOL_RECORD=record.jsonl python -m pytest tests/test_gpu_split_worst_case.py -q -m gpu
-    python tools/split_record_table.py record.jsonl > profiles/split_worst_case_record.txt
+    python tools/split_record_table.py record.jsonl split_worst_case > profiles/split_worst_case_record.txt
+
+    VIBO_TOL_RECORD=record.jsonl python -m pytest tests/test_gpu_narrow_cells.py -q -m gpu
+    python tools/split_record_table.py record.jsonl narrow_cells > profiles/narrow_cells_record.txt
 """
 import collections
 import json
@@ -9,8 +12,7 @@ import re
 import sys
 
 
-def main(path):
-    recs = [r for r in map(json.loads, open(path)) if r.get('kind') == 'split_worst_case']
+def split_worst_case(recs):
     worst, model = collections.defaultdict(float), collections.defaultdict(float)
     for r in recs:
         k = (r['class'], r['kernel'], r['observable'])
@@ -34,5 +36,35 @@ def main(path):
             print(f'{cid:60s} {r["bound_over_fp32_median"]:17.1f} {r["bound_over_fp32_max"]:9.1f} {r["ratio"]:17.3f} {r["err"]:17.2e}')
 
 
+def narrow_cells(recs):
+    parts = ('sweep', 'sweep-forward', 'units', 'dense')
+    worst = collections.defaultdict(float)
+    for r in recs:
+        worst[(r['part'], r['class'], r['observable'])] = max(worst[(r['part'], r['class'], r['observable'])], r['ratio'])
+    obs = sorted({k[2] for k in worst})
+    print(f'Worst error / a-priori bound per part, input class and observable ({len(recs)} records of tests/test_gpu_narrow_cells.py on one MI355X;')
+    print('bounds: oracle/narrow_model.py).  sweep: all item counts 4..128, ability_dim 1..4, three row modes (/drop: --drop-missing at')
+    print('ability_dim 3); sweep-forward: the forward-only launches of the same cases; units: 32 645 persons, one observer per item, at the')
+    print('first unit, a later unit and the ragged end; dense: 32 645 persons, 30 % missing, summed bounds with the counted chain.')
+    print('S_NOBS is exact or the ratio is infinite.')
+    print()
+    for part in parts:
+        classes = sorted({k[1] for k in worst if k[0] == part})
+        if not classes:
+            continue
+        print(f'{part:14s} ' + ' '.join(f'{c:>13s}' for c in classes))
+        for o in obs:
+            if any((part, c, o) in worst for c in classes):
+                print(f'  {o:12s} ' + ' '.join(f'{worst[(part, c, o)]:13.3f}' if (part, c, o) in worst else f'{"-":>13s}' for c in classes))
+        print()
+
+
+KINDS = {'split_worst_case': split_worst_case, 'narrow_cells': narrow_cells}
+
+
+def main(path, kind='split_worst_case'):
+    KINDS[kind]([r for r in map(json.loads, open(path)) if r.get('kind') == kind])
+
+
 if __name__ == '__main__':
-    main(sys.argv[1])
+    main(*sys.argv[1:3])
