@@ -500,7 +500,7 @@ int vibo_fill_normal(float* out, int64_t n, uint64_t seed, const int32_t* step_c
  * Posterior outputs and gradients are not produced.  Returns -8 when nothing can be shared between the samples or
  * the descriptor is not on the row-split path (conditional posterior: its table depends on the item sample; int64
  * masks; unaligned rows): loop over vibo_elbo_fwd_bwd instead.  VIBO_POSTERIOR_GIVEN descriptors are refused with -8 too:
- * vibo_elbo_multi_forward_given below is their call.
+ * vibo_elbo_multi_forward_given below is their call; the conditional posterior's is declared in vibo_hip_multi_cond.h.
  * Workspace: vibo_multi_workspace_bytes(d, num_samples) bytes, 256-byte aligned.
  */
 size_t vibo_multi_workspace_bytes(const vibo_desc* d, int num_samples);

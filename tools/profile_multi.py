@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """Multi-sample forward (log_marginal's loop body) vs one forward launch per sample.
-   python tools/profile_multi.py [--persons P] [--items I] [--ability-dim A] [--samples S] [--given [--per-sample]]
+   python tools/profile_multi.py [--persons P] [--items I] [--ability-dim A] [--samples S] [--given [--per-sample] | --cond]
 --given: a caller-supplied posterior (VIBO_POSTERIOR_GIVEN: --ability-merge mean, VI_*PL) through vibo_elbo_multi_forward_given,
 one [P, 2A] posterior for all samples, or with --per-sample one per sample ([S, P, 2A]: mean merge x conditional posterior); the
-singles leg is then one GIVEN forward launch (want_grad = 0) per sample."""
+singles leg is then one GIVEN forward launch (want_grad = 0) per sample.
+--cond: the product of experts of the conditional posterior through vibo_elbo_multi_forward_cond, one encoder table per sample
+([S, 2, I, 2A]); the singles leg is one conditional forward launch per sample.
+--log-marginal: the module instead of the kernel legs -- VIBO_*PL(...).log_marginal of this checkout's package on the same rows
+(with --minibatch N: summed over minibatches of N persons, as the reference's evaluation pass), torch.manual_seed(7) in front of
+every call; prints `log_marginal <ms median> <min> <max> <value>`.  Run from two checkouts for a parent / new comparison."""
 import argparse
 import os
 import sys
@@ -26,24 +31,57 @@ ap.add_argument('--codes', action='store_true', help='rows as 1-byte cell codes 
 ap.add_argument('--gather', action='store_true')
 ap.add_argument('--given', action='store_true', help='caller-supplied posterior, shared by the samples')
 ap.add_argument('--per-sample', action='store_true', help='with --given: one posterior per sample')
+ap.add_argument('--cond', action='store_true', help='product of experts x conditional posterior: one encoder table per sample')
+ap.add_argument('--log-marginal', action='store_true', help='time model.log_marginal instead of the kernel legs')
+ap.add_argument('--minibatch', type=int, default=0, help='with --log-marginal: persons per call (0: all)')
 ap.add_argument('--reps', type=int, default=3)
 a = ap.parse_args()
 d = torch.device('cuda:0')
 g = torch.Generator(device=d).manual_seed(0)
 P, I, A, S = a.persons, a.items, a.ability_dim, a.samples
-spec = ElboSpec(irt_model=a.irt, ability_dim=A, given=a.given)
+spec = ElboSpec(irt_model=a.irt, ability_dim=A, given=a.given, conditional=a.cond)
 resp = (torch.rand(P, I, device=d, generator=g) < 0.5).float()
 mask = torch.rand(P, I, device=d, generator=g) >= 0.1
+
+if a.log_marginal:
+    from vibo_amd.torch_core import models
+    torch.manual_seed(3)
+    model = {1: models.VIBO_1PL, 2: models.VIBO_2PL, 3: models.VIBO_3PL}[a.irt](
+        A, I, ability_merge='mean' if a.given else 'product', conditional_posterior=a.cond or a.per_sample).to(d)
+    rows = ops.pack_cell_codes(resp, mask) if a.codes else resp
+    step = a.minibatch or P
+
+    def one_pass():
+        torch.manual_seed(7)
+        total = 0.0
+        for p0 in range(0, P, step):
+            r = rows.rows(torch.arange(p0, min(P, p0 + step), device=d)) if a.codes else rows[p0:p0 + step]
+            total += float(model.log_marginal(r, None if a.codes else mask[p0:p0 + step], num_samples=S))      # (float() synchronises)
+        return total
+
+    value = one_pass()
+    times = []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        value = one_pass()
+        times.append((time.perf_counter() - t0) * 1e3)
+    times.sort()
+    print(f'log_marginal {times[len(times) // 2]:.3f} {times[0]:.3f} {times[-1]:.3f} {value!r}')
+    sys.exit(0)
+
 table = torch.randn(2, 2 * A, device=d, generator=g) * 0.5
 if a.given:      # mu = 0.5 randn | logvar = -1 + 0.5 randn
     shape = (S, P, A) if a.per_sample else (P, A)
     table = torch.cat([0.5 * torch.randn(shape, device=d, generator=g), -1.0 + 0.5 * torch.randn(shape, device=d, generator=g)], dim=-1)
+if a.cond:
+    table = torch.randn(S, 2, I, 2 * A, device=d, generator=g) * 0.5
 items = torch.randn(S, I, spec.item_dim, device=d, generator=g)
 eps = torch.randn(S, P, A, device=d, generator=g)
 m, code = ops.prepare_mask(mask)
 if a.codes:
     resp, m, code = ops.prepare_rows(ops.pack_cell_codes(resp, mask), None)
 ridx = torch.randperm(P, device=d) if a.gather else None
+per_sample_table = a.cond or (a.given and a.per_sample)
 
 
 def multi():
@@ -51,7 +89,7 @@ def multi():
 
 
 def singles():
-    return [ops._hip_launch_elbo(spec, resp, m, code, ridx, table[s] if a.given and a.per_sample else table, items[s], eps[s], None,
+    return [ops._hip_launch_elbo(spec, resp, m, code, ridx, table[s] if per_sample_table else table, items[s], eps[s], None,
                                  _lib.REG_SAMPLED, False, P).scalars for s in range(S)]
 
 
@@ -65,5 +103,5 @@ for name, f in (('multi-sample kernel', multi), ('one launch per sample', single
         f()
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / a.reps
-    print(f'P={P} I={I} A={A} S={S} codes={a.codes} gather={a.gather} given={a.given} per_sample={a.per_sample} {name:24s}: {dt * 1e3:8.3f} ms = {dt * 1e3 / S:6.3f} ms per sample, '
+    print(f'P={P} I={I} A={A} S={S} codes={a.codes} gather={a.gather} given={a.given} per_sample={a.per_sample} cond={a.cond} {name:24s}: {dt * 1e3:8.3f} ms = {dt * 1e3 / S:6.3f} ms per sample, '
           f'{P * I * S / dt / 1e12:.3f} T sample-terms/s')

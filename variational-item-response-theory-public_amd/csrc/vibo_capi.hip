@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/vibo_hip.h"
+#include "../../include/vibo_hip_multi_cond.h"
 #include "vibo_cond.hpp"
 #include "vibo_general.hpp"
 #include "vibo_helpers.hpp"
@@ -662,6 +663,109 @@ int vibo_elbo_multi_forward_given(const vibo_desc* d, int num_samples, const flo
                                   void* workspace, size_t workspace_bytes, void* stream) {
     return multi_forward_impl(d, true, num_samples, response, mask, row_index, posterior, (long long)posterior_sample_stride, item, eps,
                               flow, out_scalars, workspace, workspace_bytes, stream);
+}
+
+// vibo_elbo_multi_forward_cond: the GIVEN pass's descriptor and plan, and the blocks behind that plan's own workspace
+struct MultiCondPlan {
+    vibo_desc dg;              // the rows as the GIVEN pass reads them: the caller's cell codes, or the ones packed into the workspace
+    size_t given_bytes;        // vibo_multi_given_workspace_bytes(&dg)
+    size_t off_image, off_sums, off_post, off_codes, total_bytes;
+    long long codes_stride;    // 0: the caller's rows are cell codes already
+    int group, ldc;            // samples per contraction pass; floats per row of the sums (group * 2A + the count)
+};
+static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+static int multi_cond_plan(const vibo_desc* d, int num_samples, int num_cu, MultiCondPlan* m) {
+    if (d->posterior != VIBO_POSTERIOR_CONDITIONAL)
+        return fail(-3, "vibo_elbo_multi_forward_cond: the descriptor's posterior must be VIBO_POSTERIOR_CONDITIONAL");
+    if (num_samples < 1) return fail(-3, "num_samples must be >= 1");
+    // the shapes of VIBO_POSTERIOR_GIVEN, asked of the caller's own rows first
+    vibo_desc dq = *d;
+    dq.posterior = VIBO_POSTERIOR_GIVEN;
+    Plan pl;
+    size_t prep = 0;
+    int rc = check_desc(&dq);
+    if (rc == 0) rc = multi_plan(&dq, num_cu, &m->dg, &pl, &prep, true);
+    if (rc) return rc;
+    const int I = d->num_item, A = d->ability_dim;
+    // Measured against the loop (profiles/r09_multi_cond.txt, 1M x 1k, 16 samples): fp32 rows win at 1 and 8 dims (the loop re-reads
+    // 5 B per cell and sample), cell codes at 1 and 2 dims (12.8 -> 11.2 / 12.9 -> 11.9 ms); from 3 dims the loop's 16-column pass
+    // per sample over the 1-byte codes beats this call's share of a 64-column pass (13.0 -> 13.8 ms at 3 dims, 13.5 -> 18.5 at 8):
+    // those callers keep looping.  VIBO_FLAG_COND_MATRIX pins the stacked form (tests, A/B runs)
+    if (d->mask_dtype == VIBO_MASK_CODES && A >= 3 && !(d->flags & VIBO_FLAG_COND_MATRIX))
+        return fail(-8, "multi-sample forward: cell codes at ability_dim >= 3 -- one launch per sample is faster (VIBO_FLAG_COND_MATRIX pins this call)");
+    m->dg = dq;
+    m->codes_stride = 0;
+    if (d->mask_dtype != VIBO_MASK_CODES) {      // packed once, minibatch order, rows of whole 64-byte steps
+        m->codes_stride = ((long long)I + 63) / 64 * 64;
+        m->dg.mask_dtype = VIBO_MASK_CODES;
+        m->dg.mask_row_stride = m->codes_stride;
+        m->dg.response_row_stride = 0;
+        vibo_desc d0;
+        if ((rc = multi_plan(&m->dg, num_cu, &d0, &pl, &prep, true)) != 0) return rc;
+    }
+    m->given_bytes = up256(pl.total_bytes + 4 * prep);
+    m->group = cond_stack_group(A);
+    m->ldc = m->group * 2 * A + 1;
+    const size_t B = (size_t)d->num_person;
+    size_t off = m->given_bytes;
+    m->off_image = off; off += up256(cond_stack_image_bytes(I));
+    m->off_sums = off;  off += up256(B * m->ldc * 4);
+    m->off_post = off;  off += up256((size_t)num_samples * B * 2 * A * 4);
+    m->off_codes = off; off += up256(B * (size_t)m->codes_stride);
+    m->total_bytes = off;
+    return 0;
+}
+
+size_t vibo_multi_cond_workspace_bytes(const vibo_desc* d, int num_samples) {
+    MultiCondPlan m;
+    if (check_desc(d) != 0 || multi_cond_plan(d, num_samples, device_cus(), &m) != 0) return 0;
+    return m.total_bytes;
+}
+
+int vibo_elbo_multi_forward_cond(const vibo_desc* d, int num_samples, const float* response, const void* mask, const int64_t* row_index,
+                                 const float* tables, const float* item, const float* eps, const float* flow, float* out_scalars,
+                                 float* posterior_out, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = check_desc(d);
+    if (rc) return rc;
+    MultiCondPlan m;
+    if ((rc = multi_cond_plan(d, num_samples, device_cus(), &m)) != 0) return rc;
+    if (!tables || !item || !eps || !out_scalars) return fail(-5, "null required pointer");
+    if ((rc = require_rows(d, response, mask)) != 0) return rc;
+    if (d->n_flows > 0 && !flow) return fail(-5, "flows need flow");
+    if (!workspace || workspace_bytes < m.total_bytes) return fail(-7, "workspace too small: %zu < %zu", workspace_bytes, m.total_bytes);
+    if ((uintptr_t)workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
+    if (!rows_vec_ok(d, response, mask)) return fail(-8, "multi-sample forward: rows are not 16-byte chunkable");
+    const int I = d->num_item, A = d->ability_dim;
+    const long long B = d->num_person;
+    hipStream_t s = (hipStream_t)stream;
+    char* wsb = static_cast<char*>(workspace);
+    float* sums = reinterpret_cast<float*>(wsb + m.off_sums);
+    float* post = posterior_out ? posterior_out : reinterpret_cast<float*>(wsb + m.off_post);
+    // 1. the minibatch's cell codes
+    const uint8_t* codes = static_cast<const uint8_t*>(mask);
+    long long stride = d->mask_row_stride;
+    const int64_t* ridx = row_index;
+    if (m.codes_stride) {
+        uint8_t* packed = reinterpret_cast<uint8_t*>(wsb + m.off_codes);
+        const hipError_t e = launch_pack_codes(d, response, mask, packed, m.codes_stride, true, s, row_index);
+        if (e != hipSuccess) return hip_fail(e, "multi-sample forward: pack_codes launch");
+        codes = packed; stride = m.codes_stride; ridx = nullptr;
+    }
+    // 2.-4. per group of samples: stacked table image, one contraction pass over the codes, the per-person finish.  The first
+    // group's pass leaves the rows' observed counts in the sums' last column, which no later (never wider) group writes
+    const size_t n_table = (size_t)2 * I * 2 * A;
+    const int cnt_col = (num_samples < m.group ? num_samples : m.group) * 2 * A;
+    for (int s0 = 0; s0 < num_samples; s0 += m.group) {
+        const int G = num_samples - s0 < m.group ? num_samples - s0 : m.group;
+        hipError_t e = launch_cond_stack_sums(codes, stride, ridx, B, I, A, tables + (size_t)s0 * n_table, (long long)n_table, G, s0 == 0, sums,
+                                              m.ldc, wsb + m.off_image, s);
+        if (e != hipSuccess) return hip_fail(e, "multi-sample forward: experts' sums launch");
+        e = launch_cond_stack_finish(sums, m.ldc, cnt_col, post + (size_t)s0 * B * 2 * A, B, I, A, G, d->missing_mode, s);
+        if (e != hipSuccess) return hip_fail(e, "multi-sample forward: posterior finish launch");
+    }
+    // 5. the GIVEN multi-sample pass on the codes
+    return multi_forward_impl(&m.dg, true, num_samples, nullptr, codes, ridx, post, B * 2 * A, item, eps, flow, out_scalars, workspace,
+                              m.given_bytes, stream);
 }
 
 int vibo_decode_mean(const vibo_desc* d, int num_samples, const float* ability, const float* item,

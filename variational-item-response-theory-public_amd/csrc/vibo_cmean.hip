@@ -115,6 +115,38 @@ __global__ __launch_bounds__(256) void cm_table_image_kernel(const float* __rest
     img[o + 64] = mid;
     img[o + 128] = lo;
 }
+// cm_table_image_kernel<true> for the tables of G item samples side by side (the multi-sample forward of the conditional
+// posterior): column n = g 2A + j is tau (j < A) or mu tau (j >= A) of the table at src + g sstride -- a sample's columns may
+// straddle a 16-column tile (2A = 6, 10) --, column ones_col (if >= 0) is the column of ones, every other column is zero
+__global__ __launch_bounds__(256) void cm_table_image_stack_kernel(const float* __restrict__ src, long long sstride, uint4* __restrict__ img, int I,
+                                                                   int nS, int NT, int A, int G, int ones_col) {
+    const int t = blockIdx.x * 256 + threadIdx.x;
+    if (t >= nS * 4 * NT * 64) return;
+    const int lane = t & 63, nt = (t >> 6) % NT, j = ((t >> 6) / NT) & 3, S = (t >> 6) / (NT * 4);
+    const int n = 16 * nt + (lane & 15), g = lane >> 4;
+    const int gs = n / (2 * A), jn = n - gs * 2 * A, a = jn < A ? jn : jn - A;
+    float v[8];
+#pragma unroll
+    for (int kk = 0; kk < 8; ++kk) {
+        const int item = 64 * S + 16 * g + 4 * j + (kk >> 1), c = kk & 1;
+        float x = 0.f;
+        if (item < I) {
+            if (n == ones_col) x = 1.0f;
+            else if (gs < G) {
+                const float* te = src + (size_t)gs * sstride + ((size_t)c * I + item) * 2 * A;
+                const float tau = 1.0f / (expf(te[A + a]) + kPoeEps);
+                x = jn < A ? tau : te[a] * tau;
+            }
+        }
+        v[kk] = x;
+    }
+    uint4 hi, mid, lo;
+    cm_split3(v, hi, mid, lo);
+    const size_t o = ((size_t)((S * 4 + j) * NT + nt) * kCmNP) * 64 + lane;
+    img[o] = hi;
+    img[o + 64] = mid;
+    img[o + 128] = lo;
+}
 // backward B operand: gimg[((c32 * NT + nt) * 3 + piece) * 64 + lane] = 8 pieces over kk of G[32 c32 + 8 g + kk][16 nt + (lane & 15)]
 // (G row stride = ncols; columns >= ncols are zero)
 __global__ __launch_bounds__(256) void cm_grad_image_kernel(const float* __restrict__ G, uint4* __restrict__ gimg, long long B, long long n32,
@@ -905,6 +937,24 @@ hipError_t launch_cond_pre_mfma_fp32(const float* response, const void* mask, lo
     else { if (mal) CM_FWD32(false, true); else CM_FWD32(false, false); }
 #undef CM_FWD32
     return hipGetLastError();
+}
+// the multi-sample forward of the conditional posterior: lam | s of G item samples' tables in one pass over the code rows.
+// NT = the G 2A columns' tiles rounded up to an instantiation (1, 2, 4).  The observed count (count: the first group of a call)
+// comes out at column G 2A either way: a column of ones where the last tile has room, cm_forward_kernel's COUNT form where it has none
+size_t cond_stack_image_bytes(int I) { return cm_timg_bytes((I + 63) / 64, 4); }
+hipError_t launch_cond_stack_sums(const uint8_t* codes, long long stride, const int64_t* row_index, long long B, int I, int A,
+                                  const float* tables, long long table_sstride, int G, bool count, float* sums, int ldc, void* image,
+                                  hipStream_t s) {
+    const int nS = (I + 63) / 64, cols = G * 2 * A;
+    const int tiles = (cols + 15) / 16, NT = tiles <= 1 ? 1 : tiles <= 2 ? 2 : 4;
+    const bool ones = count && cols < 16 * NT;
+    uint4* img = static_cast<uint4*>(image);
+    hipLaunchKernelGGL(cm_table_image_stack_kernel, dim3((nS * 4 * NT * 64 + 255) / 256), dim3(256), 0, s, tables, table_sstride, img, I, nS, NT, A, G,
+                       ones ? cols : -1);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    if (count && !ones) return cm_launch_forward<true>(NT, codes, stride, row_index, B, I, nS, img, sums, ldc, cols, s);
+    return cm_launch_forward<false>(NT, codes, stride, row_index, B, I, nS, img, sums, ldc, ones ? cols + 1 : cols, s);
 }
 // grad_table[2 heads][2][I][2A] from the per-person coefficients coef[B][4A] = [head][P1 | P2][dim]
 hipError_t launch_cond_post_mfma(const uint8_t* codes, long long stride, const int64_t* row_index, long long B, int I, int A,

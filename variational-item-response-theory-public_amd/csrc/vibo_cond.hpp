@@ -40,4 +40,13 @@ hipError_t launch_cond_post_mfma(const uint8_t* codes, long long stride, const i
                                  const float* table, const float* coef, float* grad_table, void* scratch, hipStream_t s,
                                  CondFinTail* defer = nullptr);
 
+// the first of those passes for a group of G <= cond_stack_group(A) item samples in ONE pass over the code rows (the multi-sample
+// forward of the conditional posterior): tables = G encoder tables [2][I][2A], table_sstride floats apart;
+// sums[p][ldc]: column g 2A + j = lam (j < A) | s (j >= A) of sample g; count: the rows' observed counts at column G 2A
+inline int cond_stack_group(int A) { return 64 / (2 * A); }
+size_t cond_stack_image_bytes(int I);
+hipError_t launch_cond_stack_sums(const uint8_t* codes, long long stride, const int64_t* row_index, long long B, int I, int A,
+                                  const float* tables, long long table_sstride, int G, bool count, float* sums, int ldc, void* image,
+                                  hipStream_t s);
+
 }  // namespace vibo

@@ -182,10 +182,12 @@ __global__ __launch_bounds__(256) void pack_codes_kernel(const float* __restrict
     }
 }
 
-// the same for 4-cell chunks of aligned rows (thread = one chunk: float4 + mask word in, one code word out)
+// the same for 4-cell chunks of aligned rows (thread = one chunk: float4 + mask word in, one code word out); row_index: code row
+// k is source row row_index[k] (a minibatch's rows, packed in its order)
 __global__ __launch_bounds__(256) void pack_codes4_kernel(const float* __restrict__ response, const void* __restrict__ mask,
                                                           uint32_t* __restrict__ codes, long long resp_stride, long long mask_stride,
-                                                          long long chunks_per_row, long long B, int I, int mask_dtype) {
+                                                          long long chunks_per_row, long long B, int I, int mask_dtype,
+                                                          const int64_t* __restrict__ row_index) {
     const long long n = B * chunks_per_row;
     const int n4 = (I + 3) >> 2;
     for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
@@ -193,9 +195,10 @@ __global__ __launch_bounds__(256) void pack_codes4_kernel(const float* __restric
         const int c = (int)(e - row * chunks_per_row);
         uint32_t w = kAllMissing4;
         if (c < n4) {
-            const float4 x = reinterpret_cast<const float4*>(response + row * resp_stride)[c];
+            const long long src = row_index ? row_index[row] : row;
+            const float4 x = reinterpret_cast<const float4*>(response + src * resp_stride)[c];
             uint32_t m = mask_dtype == VIBO_MASK_U8
-                             ? reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(mask) + row * mask_stride)[c]
+                             ? reinterpret_cast<const uint32_t*>(static_cast<const uint8_t*>(mask) + src * mask_stride)[c]
                              : 0x01010101u;
             m = ((m | (m >> 1) | (m >> 2) | (m >> 3) | (m >> 4) | (m >> 5) | (m >> 6) | (m >> 7)) & 0x01010101u);   // any bit -> 1
             if ((I & 3) && c == (I >> 2)) m &= (1u << (8 * (I & 3))) - 1u;
@@ -413,6 +416,24 @@ __global__ __launch_bounds__(256) void encode_finish_kernel(const int* __restric
     ability_logvar[e] = logf(1.0f / lam);
 }
 
+// the same finish for a group of G item samples of the conditional posterior (launch_cond_stack_sums: row p of `sums` holds
+// lam | s of sample g at columns g 2A .., the row's observed count at column cnt_col): thread = (person, sample, dim), so a row's
+// sums are read once; post[g][p] = mu | logvar, [G][B][2A].  The statements are encode_finish_kernel's: the same bits from the same sums
+__global__ __launch_bounds__(256) void cond_stack_finish_kernel(const float* __restrict__ sums, int ldc, int cnt_col, float* __restrict__ post,
+                                                                long long B, int I, int A, int G, int missing_mode) {
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= B * G * A) return;
+    const long long row = e / (G * A);
+    const int c = (int)(e - row * (G * A)), g = c / A, a = c - g * A;
+    const float* st = sums + row * ldc;
+    float lam = st[g * 2 * A + a];
+    const float smu = st[g * 2 * A + A + a], nobs = st[cnt_col];
+    if (missing_mode == VIBO_MISSING_PRIOR) lam += ((float)I - nobs) * (1.0f / (1.0f + kPoeEps));
+    float* po = post + ((long long)g * B + row) * 2 * A;
+    po[a] = smu / lam;
+    po[A + a] = logf(1.0f / lam);
+}
+
 // posterior-predictive mean: thread = one item x 8 persons; per sample the item row is loaded once and reused for the
 // 8 persons (ability rows are wave-uniform scalar loads)
 __global__ __launch_bounds__(256) void decode_mean_kernel_strided(const float* __restrict__ ability, const float* __restrict__ item,
@@ -528,14 +549,14 @@ hipError_t launch_given_post(const float* post, const float* coef, int panels, f
 }
 
 hipError_t launch_pack_codes(const vibo_desc* d, const float* response, const void* mask, uint8_t* codes, long long codes_row_stride,
-                             bool chunks, hipStream_t s) {
+                             bool chunks, hipStream_t s, const int64_t* row_index) {
     if (chunks) {      // aligned rows, 4 cells per thread (16 B of responses + 4 B of mask -> one code word)
         const long long n = (long long)d->num_person * (codes_row_stride / 4);
         long long grid = (n + 255) / 256;
         if (grid > 262144) grid = 262144;
         hipLaunchKernelGGL(pack_codes4_kernel, dim3((unsigned)grid), dim3(256), 0, s, response, mask, reinterpret_cast<uint32_t*>(codes),
                            (long long)d->response_row_stride, (long long)d->mask_row_stride, (long long)(codes_row_stride / 4),
-                           (long long)d->num_person, d->num_item, d->mask_dtype);
+                           (long long)d->num_person, d->num_item, d->mask_dtype, row_index);
         return hipGetLastError();
     }
     const long long n = (long long)d->num_person * codes_row_stride;
@@ -571,6 +592,11 @@ hipError_t launch_encode(const EncodeParams& p, hipStream_t s) {
 hipError_t launch_encode_finish(const int* cnt, const float* pre, int panels, const float* table, float* ability_mu, float* ability_logvar,
                                 long long B, int I, int A, int missing_mode, hipStream_t s) {
     return launch_elementwise(encode_finish_kernel, B * A, s, cnt, pre, panels, table, ability_mu, ability_logvar, B, I, A, missing_mode);
+}
+
+hipError_t launch_cond_stack_finish(const float* sums, int ldc, int cnt_col, float* post, long long B, int I, int A, int G, int missing_mode,
+                                    hipStream_t s) {
+    return launch_elementwise(cond_stack_finish_kernel, B * G * A, s, sums, ldc, cnt_col, post, B, I, A, G, missing_mode);
 }
 
 hipError_t launch_decode(const float* ability, const float* item, float* response_mu, long long B, int I, int A, int D, int irt,

@@ -27,9 +27,10 @@ hipError_t launch_panel_sum(float* buf, long long n, int panels, hipStream_t s);
 hipError_t launch_given_pre(const float* post, float* pre, long long B, int A, int I, hipStream_t s);
 hipError_t launch_given_post(const float* post, const float* coef, int panels, float* grad, long long B, int A, hipStream_t s);
 
-// fp32 rows + mask -> 1-byte cell codes; chunks: 4 cells per thread (aligned rows, codes_row_stride % 4 == 0)
+// fp32 rows + mask -> 1-byte cell codes; chunks: 4 cells per thread (aligned rows, codes_row_stride % 4 == 0).
+// row_index (chunks only): the code rows are the minibatch's, in its order
 hipError_t launch_pack_codes(const vibo_desc* d, const float* response, const void* mask, uint8_t* codes, long long codes_row_stride,
-                             bool chunks, hipStream_t s);
+                             bool chunks, hipStream_t s, const int64_t* row_index = nullptr);
 
 // fixed-order sum of the partial records (+ f.tail in the same launch); sets f.n_fin
 hipError_t launch_finalize(FinalizeParams& f, hipStream_t s);
@@ -48,6 +49,10 @@ struct EncodeParams {
 hipError_t launch_encode(const EncodeParams& p, hipStream_t s);
 hipError_t launch_encode_finish(const int* cnt, const float* pre, int panels, const float* table, float* ability_mu, float* ability_logvar,
                                 long long B, int I, int A, int missing_mode, hipStream_t s);
+
+// the same finish for G item samples' stacked sums (launch_cond_stack_sums) -> post[G][B][2A] = mu | logvar
+hipError_t launch_cond_stack_finish(const float* sums, int ldc, int cnt_col, float* post, long long B, int I, int A, int G, int missing_mode,
+                                    hipStream_t s);
 
 hipError_t launch_decode(const float* ability, const float* item, float* response_mu, long long B, int I, int A, int D, int irt,
                          hipStream_t s);

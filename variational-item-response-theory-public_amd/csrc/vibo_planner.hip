@@ -428,8 +428,10 @@ int multi_plan(const vibo_desc* d, int num_cu, vibo_desc* d0, Plan* pl, size_t* 
     // (GIVEN outside the row-split shapes -- 4..32767 items, rows chunkable in 4 cells, no int64 mask, ability_dim <= 8 -- has no plan: -8)
     const int rc = make_plan(d0, num_cu, pl, false);
     if (rc < 0) return rc;
-    // conditional posterior: the expert table itself depends on the item sample, nothing is shared between samples
-    if (d->posterior == VIBO_POSTERIOR_CONDITIONAL) return fail(-8, "multi-sample forward: conditional posterior (one table per sample)");
+    // conditional posterior: the expert table itself depends on the item sample; its call stacks the samples' tables and comes back
+    // here with the posteriors as given
+    if (d->posterior == VIBO_POSTERIOR_CONDITIONAL)
+        return fail(-8, "multi-sample forward: conditional posterior, one table per sample (use vibo_elbo_multi_forward_cond)");
     if (d->posterior == VIBO_POSTERIOR_GIVEN && !given_call)
         return fail(-8, "multi-sample forward: caller-supplied posterior (use vibo_elbo_multi_forward_given)");
     if (!pl->row_split()) return fail(-8, "multi-sample forward: shape is not on the row-split path");

@@ -502,17 +502,34 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     return raw
 
 
+def multi_forward_declined(spec, response, mask, mask_code, num_samples, num_person):
+    """True where the native multi-sample backend is installed and its workspace query already says that it does not cover the
+    call (vibo_multi_cond_workspace_bytes == 0: cell codes at ability_dim >= 3, int64 masks, ...) -- asked from the descriptor
+    alone, before a caller draws noise or stacks S tables for a call that would answer None.  False for any other backend (the CPU
+    stand-in, a test's fake: they answer for themselves) and for rows off the device."""
+    if _BACKEND['multi'] is not _hip_multi_forward or not (spec.conditional and not getattr(spec, 'given', False)) or not response.is_cuda:
+        return False
+    d = _rows_desc(spec, int(num_person), response, mask, mask_code, _lib.REG_SAMPLED, False)
+    return _lib.load().vibo_multi_cond_workspace_bytes(ctypes.byref(d), int(num_samples)) == 0
+
+
 def _hip_multi_forward(spec, response, mask, mask_code, row_index, table, items, eps, flow, reg_mode, num_person):
     """vibo_elbo_multi_forward: S forward evaluations in one pass.  items [S,I,D], eps [S,B,A] -> scalars [S,8], or
     None when the configuration is not on the row-split path (the caller then loops over single launches).
     spec.given (vibo_elbo_multi_forward_given): `table` is the caller's posterior (mu | logvar) in minibatch order, [B, 2A] shared
-    by the samples or [S, B, 2A] one per sample."""
+    by the samples or [S, B, 2A] one per sample.
+    spec.conditional without given (vibo_elbo_multi_forward_cond): `table` is the encoder's table of every item sample,
+    [S, 2, I, 2A]; rows that are not on the device also answer None (the caller's loop then meets its own backend)."""
+    given = bool(getattr(spec, 'given', False))
+    cond = bool(spec.conditional) and not given
+    if cond and not response.is_cuda:
+        return None
     lib = _lib.load()
     _require_device(response, mask, table, items, eps)
     S, B, I = int(items.shape[0]), int(num_person), response.shape[1]
-    given = bool(getattr(spec, 'given', False))
     d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, False)
-    ws_bytes = (lib.vibo_multi_given_workspace_bytes if given else lib.vibo_multi_workspace_bytes)(ctypes.byref(d), S)
+    query = lib.vibo_multi_given_workspace_bytes if given else lib.vibo_multi_cond_workspace_bytes if cond else lib.vibo_multi_workspace_bytes
+    ws_bytes = query(ctypes.byref(d), S)
     if ws_bytes == 0:
         return None
     dev = response.device
@@ -526,6 +543,13 @@ def _hip_multi_forward(spec, response, mask, mask_code, row_index, table, items,
         name, stride = 'vibo_elbo_multi_forward_given', (B * 2 * A if table.dim() == 3 else 0)
         rc = lib.vibo_elbo_multi_forward_given(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table),
                                                ctypes.c_int64(stride), *tail)
+    elif cond:
+        A = spec.ability_dim
+        if tuple(table.shape) != (S, 2, I, 2 * A) or not table.is_contiguous():
+            raise ValueError('multi-sample forward: the conditional posterior takes a contiguous [S, 2, I, 2A] table, got %s' % (tuple(table.shape),))
+        name = 'vibo_elbo_multi_forward_cond'
+        rc = lib.vibo_elbo_multi_forward_cond(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table), *tail[:4],
+                                              None, *tail[4:])
     else:
         name = 'vibo_elbo_multi_forward'
         rc = lib.vibo_elbo_multi_forward(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table), *tail)

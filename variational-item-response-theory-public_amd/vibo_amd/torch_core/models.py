@@ -607,11 +607,13 @@ class VIBO_1PL(nn.Module):
     def log_marginal(self, response, mask, num_samples=100, eps_item=None, eps_ability=None):
         """Importance-weighted bound with batch-level weights (models.py:445-504).  eps_item [S,I,D] / eps_ability
         [S,B,A] replay a fixed noise sequence (tests); by default it is drawn item-then-ability per sample like the
-        reference's loop.  The S forwards share one pass over the responses where nothing per sample needs the rows: the
-        unconditional product of experts (vibo_elbo_multi_forward) and --ability-merge mean, whose posterior reaches the kernel as
-        given (vibo_elbo_multi_forward_given: one [B, 2A] posterior for all samples, or with --conditional-posterior one per
-        sample).  Otherwise -- product of experts x conditional posterior, a person-sharded mean-merge model (its heads go through
-        the collective), a backend that answers None -- one forward launch per sample."""
+        reference's loop.  The S forwards share one pass over the responses: the unconditional product of experts
+        (vibo_elbo_multi_forward); --ability-merge mean, whose posterior reaches the kernel as given
+        (vibo_elbo_multi_forward_given: one [B, 2A] posterior for all samples, or with --conditional-posterior one per sample);
+        product of experts x conditional posterior, whose per-sample encoder tables go in stacked (vibo_elbo_multi_forward_cond:
+        the experts' sums of up to 64 / 2A samples per contraction pass over the cell codes).  Otherwise -- a person-sharded
+        mean-merge or conditional model (its heads go through the collective), a backend that answers None -- one forward launch
+        per sample."""
         with torch.no_grad():
             S = int(num_samples)
             if self.generative_model != 'irt':
@@ -623,8 +625,8 @@ class VIBO_1PL(nn.Module):
                 return torch.logsumexp(torch.stack(log_w), 0) - math.log(S)
             mean_merge = self.ability_merge == 'mean'
             posts = None      # mean merge: the posteriors _log_weights_multi computed before the backend answered None
-            # (person-sharded mean merge: the loop reduces its heads through the collective)
-            if (mean_merge and self._reducer is None) or (not mean_merge and not self.conditional_posterior):
+            # (person-sharded mean merge or conditional posterior: the loop reduces its heads through the collective)
+            if self._reducer is None or not (mean_merge or self.conditional_posterior):
                 if not isinstance(response, ops.CellCodes):
                     response = ops.prepare_response(response)
                     if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
@@ -653,7 +655,9 @@ class VIBO_1PL(nn.Module):
     def _log_weights_multi(self, response, mask, S, eps_item, eps_ability):
         """log w_s for s < S through the multi-sample forward kernel, or None if the configuration is not covered.
         --ability-merge mean: the posterior goes to the kernel as given -- _mean_posterior once for all samples, or (conditional
-        posterior: it depends on the item sample) once per sample, stacked to [S, B, 2A].  Memory: the stacked noise is S B A floats
+        posterior: it depends on the item sample) once per sample, stacked to [S, B, 2A].  Product of experts x conditional
+        posterior: the encoder's table of every item sample (expert_table of the sample in front of the item flows, as _run_fused),
+        stacked to [S, 2, I, 2A]; the kernel forms the posteriors.  Memory: the stacked noise is S B A floats
         and the per-sample posteriors S B 2A (1M persons, A = 8, S = 16: 0.5 + 1 GB): a caller with a whole resident split and many
         samples passes it in minibatches.
         -> (log_w or None, eps_item, eps_ability, posteriors or None): after None the caller's loop replays the last three."""
@@ -663,8 +667,10 @@ class VIBO_1PL(nn.Module):
             return None, eps_item, eps_ability, None
         B = response.shape[0]
         mean_merge = self.ability_merge == 'mean'
+        if ops.multi_forward_declined(self.spec, response, mask2, code, S, B):
+            return None, eps_item, eps_ability, None      # (nothing drawn, nothing stacked: the loop runs as it always did)
         item_mu, item_lv = self.item_encoder()
-        items, log_qd, log_pd, eps_ab, drawn_items, posts = [], [], [], [], [], []
+        items, log_qd, log_pd, eps_ab, drawn_items, posts, tables = [], [], [], [], [], [], []
         for s in range(S):                      # draw order of the reference's loop: item eps, then ability eps
             e_i = self._randn(item_mu.shape, item_mu, self._item_gen) if eps_item is None else eps_item[s]
             drawn_items.append(e_i)
@@ -676,13 +682,15 @@ class VIBO_1PL(nn.Module):
                 lq = lq - item_ladj.sum()
             if mean_merge and self.conditional_posterior:      # (from the item sample in front of the item flows, as _run_fused)
                 posts.append(self._mean_posterior(rows, mask_in, None, item_feat))
+            elif self.conditional_posterior:
+                tables.append(self.ability_encoder.expert_table(item_feat))
             items.append(item_k)
             log_qd.append(lq)
             log_pd.append(_std_normal_logpdf(item_k).sum())
             eps_ab.append(self._randn((B, self.ability_dim), item_mu, self._ability_gen)
                           if eps_ability is None else eps_ability[s])
         if not mean_merge:
-            table = self.ability_encoder.expert_table(None)
+            table = torch.stack(tables) if self.conditional_posterior else self.ability_encoder.expert_table(None)
         elif self.conditional_posterior:
             table = torch.stack(posts)
             posts = None          # (one copy)
