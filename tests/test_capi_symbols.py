@@ -181,7 +181,7 @@ def header_text():
 
 def test_every_function_is_typed_with_the_header_s_parameter_count():
     lib, src = _lib.load(), header_text()
-    assert list(_lib.EXPORTED_SYMBOLS) == re.findall(r'\b(vibo_[a-z_0-9]+)\s*\(', src) and len(_lib.EXPORTED_SYMBOLS) == 56      # header order
+    assert list(_lib.EXPORTED_SYMBOLS) == re.findall(r'\b(vibo_[a-z_0-9]+)\s*\(', src) and len(_lib.EXPORTED_SYMBOLS) == 58      # header order
     for name in _lib.EXPORTED_SYMBOLS:
         params = re.search(r'\b' + name + r'\s*\(([^()]*)\)\s*;', src).group(1).strip()
         want = 0 if params in ('', 'void') else params.count(',') + 1
@@ -207,6 +207,8 @@ def test_derived_argument_lists_spot_checks():
     assert lib.vibo_decoder_fwd_bwd.argtypes[0] is ctypes.POINTER(_lib.ViboDecoderDesc)
     assert lib.vibo_last_error_string.restype is ctypes.c_char_p and lib.vibo_ctrain_param_floats.restype is i64
     assert lib.vibo_workspace_bytes.restype is sz and lib.vibo_fill_normal.argtypes == [vp, i64, u64, vp, u32, vp]
+    assert lib.vibo_elbo_multi_forward_cond.argtypes == [dp, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp,      # rows .. posterior_out
+                                                         vp, sz, vp]                                 # workspace, its bytes, stream
 
 
 def test_an_unknown_c_type_is_an_error_that_names_it():

@@ -409,3 +409,44 @@ def test_bookkeeping_on_callers_tensors_is_not_saved_with_them(count_calls, tmp_
         torch.save(t, tmp_path / f'{k}.pt')
         back = torch.load(tmp_path / f'{k}.pt', weights_only=False)
         assert torch.equal(back, t) and not any(vars(back).values()) and not any(vars(copy.deepcopy(t)).values())
+
+
+def test_chunkable_rows_is_the_one_padding_idiom():
+    """ops.chunkable_rows: compact rows whose width is no multiple of 4 come back as padded copies (row stride a multiple of 4, zeros
+    behind column I, a row index gathered first and returned as None); everything the kernels can chunk already comes back as it is."""
+    g = torch.Generator().manual_seed(31)
+    P, I = 13, 95
+    resp = (torch.rand(P, I, generator=g) < 0.5).float()
+    mask = torch.rand(P, I, generator=g) < 0.8
+    idx = torch.tensor([5, 0, 5, 12, 3, 3])
+
+    def check_padded(r, want):
+        assert tuple(r.shape) == tuple(want.shape) and torch.equal(r, want) and r.stride(0) % 4 == 0 and r.stride(1) == 1
+        whole = r.as_strided((r.shape[0], r.stride(0)), (r.stride(0), 1))
+        assert r.stride(0) >= 96 and not whole[:, I:].any()
+
+    for m in (mask, None):
+        r2, m2 = ops.chunkable_rows(resp, m)
+        check_padded(r2, resp)
+        assert (m2 is None) if m is None else (check_padded(m2, ops.prepare_mask(mask)[0]) is None)
+        # a row index that permutes and repeats rows: gathered before the padding, gone afterwards
+        r3, m3, i3 = ops.chunkable_rows(resp, m, idx)
+        check_padded(r3, resp[idx])
+        assert i3 is None and ((m3 is None) if m is None else (check_padded(m3, ops.prepare_mask(mask)[0][idx]) is None))
+        r4, m4, i4 = ops.chunkable_rows(resp, m, None)
+        check_padded(r4, resp)
+        assert i4 is None and (m4 is None) == (m is None)
+    # [B, I, 1] input as the reference's loaders yield it
+    r5, m5 = ops.chunkable_rows(resp.unsqueeze(2), mask.unsqueeze(2))
+    check_padded(r5, resp)
+    check_padded(m5, ops.prepare_mask(mask)[0])
+    # nothing to do: 96-item rows and 95-item views of padded rows are the same storage, mask and row index pass through
+    wide_r, wide_m = torch.cat([resp, resp[:, :1]], 1), torch.cat([mask, mask[:, :1]], 1)
+    for r, m in ((wide_r, wide_m), (r2, m2), ops.pad_rows(resp, mask)):
+        ra, ma, ia = ops.chunkable_rows(r, m, idx)
+        assert ra.data_ptr() == r.data_ptr() and ra.stride() == r.stride() and ma is m and ia is idx
+        rb, mb = ops.chunkable_rows(r, m)
+        assert rb.data_ptr() == r.data_ptr() and mb is m
+    codes = ops.CellCodes(torch.zeros(P, 96, dtype=torch.uint8)[:, :I])
+    c3 = ops.chunkable_rows(codes, None, idx)
+    assert ops.chunkable_rows(codes, None)[0] is codes and c3[0] is codes and c3[1] is None and c3[2] is idx

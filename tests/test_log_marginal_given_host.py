@@ -11,38 +11,17 @@ import torch
 from conftest import GOLDEN_DIR, Golden
 from golden_common import build_model
 from oracle import cpu_backend
-from oracle import vibo_table_ref as T
+from recording_multi import RecordingMulti
 from vibo_amd import _lib, ops
 from vibo_amd.torch_core.models import VI_2PL, VIBO_2PL
 
 NEW_GOLDENS = ['logmarg_2pl_a2_mean', 'logmarg_2pl_a2_cond_mean', 'logmarg_3pl_a1_mean_flows2']
 
 
-class RecordingMulti:
-    """ops._BACKEND['multi'] evaluated sample by sample on the fp32 table oracle; keeps every call's arguments."""
-
-    def __init__(self):
-        self.calls = []
-
-    def __call__(self, spec, response, mask, mask_code, row_index, table, items, eps, flow, reg_mode, num_person):
-        self.calls.append(dict(spec=spec, table=table, items=items, eps=eps, flow=flow, reg_mode=reg_mode, num_person=num_person))
-        assert spec.given and reg_mode == _lib.REG_SAMPLED and row_index is None
-        S, A = items.shape[0], spec.ability_dim
-        resp, msk = cpu_backend._rows(response, mask, mask_code, None)
-        flows = [(f[:A], f[A:2 * A], f[2 * A:2 * A + 1]) for f in flow] if flow is not None else None
-        out = torch.zeros(S, _lib.NUM_SCALARS)
-        for s in range(S):
-            post = table[s] if table.dim() == 3 else table
-            o = T.fused_elbo_ref(post, items[s], resp, msk, eps[s], flow_uhat_w_b=flows, want_grad=False, **cpu_backend._cfg(spec, reg_mode))
-            out[s, _lib.S_LL], out[s, _lib.S_REG], out[s, _lib.S_KL] = o['ll'], o['reg'], o['kl_ability']
-            out[s, _lib.S_LOGQ0], out[s, _lib.S_LOGP], out[s, _lib.S_LADJ] = o['logq0'], o['logp'], o['ladj_sum']
-        return out
-
-
 @pytest.fixture()
 def multi():
     restore = cpu_backend.install(ops)
-    fake = RecordingMulti()
+    fake = RecordingMulti(given=True)
     ops._BACKEND['multi'] = fake
     yield fake
     restore()
@@ -157,7 +136,7 @@ def test_vi_log_marginal_shares_the_looked_up_rows(multi):
 
 @pytest.mark.parametrize('cond', [False, True])
 def test_loop_fallback_reuses_the_posteriors_already_computed(cond, cpu_ops, monkeypatch):
-    """The backend answers None after _log_weights_multi has computed the posteriors: the loop takes those, it does not encode the
+    """The backend answers None after _draw_samples has computed the posteriors: the loop takes those, it does not encode the
     rows a second time (one _mean_posterior call for the shared posterior, S for the conditional one)."""
     torch.manual_seed(13)
     model = VIBO_2PL(2, 20, ability_merge='mean', conditional_posterior=cond)

@@ -11,33 +11,9 @@ import torch
 from conftest import GOLDEN_DIR, Golden
 from golden_common import build_model
 from oracle import cpu_backend
-from oracle import vibo_table_ref as T
+from recording_multi import RecordingMulti
 from vibo_amd import _lib, ops
 from vibo_amd.torch_core.models import VIBO_2PL, VIBO_3PL
-
-
-class RecordingMulti:
-    """ops._BACKEND['multi'] evaluated sample by sample on the fp32 table oracle (table s is the conditional encoder's of item
-    sample s); keeps every call's arguments.  answer=False: records and answers None, as a backend that does not cover the call."""
-
-    def __init__(self, answer=True):
-        self.calls, self.answer = [], answer
-
-    def __call__(self, spec, response, mask, mask_code, row_index, table, items, eps, flow, reg_mode, num_person):
-        self.calls.append(dict(spec=spec, mask=mask, mask_code=mask_code, table=table, items=items, eps=eps, flow=flow, reg_mode=reg_mode,
-                               num_person=num_person))
-        assert reg_mode == _lib.REG_SAMPLED and row_index is None
-        if not self.answer:
-            return None
-        S, A = items.shape[0], spec.ability_dim
-        resp, msk = cpu_backend._rows(response, mask, mask_code, None)
-        flows = [(f[:A], f[A:2 * A], f[2 * A:2 * A + 1]) for f in flow] if flow is not None else None
-        out = torch.zeros(S, _lib.NUM_SCALARS)
-        for s in range(S):
-            o = T.fused_elbo_ref(table[s], items[s], resp, msk, eps[s], flow_uhat_w_b=flows, want_grad=False, **cpu_backend._cfg(spec, reg_mode))
-            out[s, _lib.S_LL], out[s, _lib.S_REG], out[s, _lib.S_KL] = o['ll'], o['reg'], o['kl_ability']
-            out[s, _lib.S_LOGQ0], out[s, _lib.S_LOGP], out[s, _lib.S_LADJ] = o['logq0'], o['logp'], o['ladj_sum']
-        return out
 
 
 @pytest.fixture()
@@ -170,14 +146,14 @@ def test_an_int64_mask_never_reaches_the_backend_with_a_conditional_table(multi)
     assert close(a, b) and len(multi.calls) == 2
     for c in multi.calls:
         assert c['table'].dim() == 4 and c['mask_code'] == _lib.MASK_U8 and c['mask'].dtype == torch.uint8
-    # _log_weights_multi itself, were a caller to keep the int64 form: None, no call, no draw
+    # _draw_samples itself, were a caller to keep the int64 form: None, no call, no draw
     multi.calls.clear()
     state = torch.get_rng_state()
     seen = []
     real = ops.prepare_rows
     try:
         ops.prepare_rows = lambda r, m, keep_int64=False: seen.append(1) or real(r, m, keep_int64=True)
-        out = model._log_weights_multi(resp, mask.long(), 4, None, None)
+        out = model._draw_samples(resp, mask.long(), 4, None, None)
     finally:
         ops.prepare_rows = real
-    assert seen and out[0] is None and multi.calls == [] and torch.equal(torch.get_rng_state(), state)
+    assert seen and out is None and multi.calls == [] and torch.equal(torch.get_rng_state(), state)

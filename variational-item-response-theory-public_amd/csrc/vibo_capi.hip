@@ -6,7 +6,6 @@
 #include <string.h>
 
 #include "../../include/vibo_hip.h"
-#include "../../include/vibo_hip_multi_cond.h"
 #include "vibo_cond.hpp"
 #include "vibo_general.hpp"
 #include "vibo_helpers.hpp"
@@ -561,22 +560,32 @@ int vibo_train_epilogue_fused(const vibo_desc* d, int hidden_dim, const void* wo
     return 0;
 }
 
-size_t vibo_multi_workspace_bytes(const vibo_desc* d, int num_samples) {
+static size_t multi_workspace_bytes(const vibo_desc* d, int num_samples, bool given) {
     if (check_desc(d) != 0 || num_samples < 1) return 0;
     vibo_desc d0;
     Plan pl;
     size_t prep = 0;
-    if (multi_plan(d, device_cus(), &d0, &pl, &prep) != 0) return 0;
+    if (multi_plan(d, device_cus(), &d0, &pl, &prep, given) != 0) return 0;
     return pl.total_bytes + 4 * prep;
 }
 
-size_t vibo_multi_given_workspace_bytes(const vibo_desc* d, int num_samples) {
-    if (check_desc(d) != 0 || num_samples < 1) return 0;
-    vibo_desc d0;
-    Plan pl;
-    size_t prep = 0;
-    if (multi_plan(d, device_cus(), &d0, &pl, &prep, true) != 0) return 0;
-    return pl.total_bytes + 4 * prep;
+size_t vibo_multi_workspace_bytes(const vibo_desc* d, int num_samples) { return multi_workspace_bytes(d, num_samples, false); }
+
+size_t vibo_multi_given_workspace_bytes(const vibo_desc* d, int num_samples) { return multi_workspace_bytes(d, num_samples, true); }
+
+// The argument checks that the multi-sample calls share, in their one order of precedence.  plan_rc / need: what the call's plan
+// answered (its refusal is reported behind the pointer, row and flow checks) and the workspace bytes it asks for.
+static int multi_check_args(const vibo_desc* d, bool have_pointers, const float* response, const void* mask, const float* flow,
+                            int plan_rc, size_t need, void* workspace, size_t workspace_bytes) {
+    int rc;
+    if (!have_pointers) return fail(-5, "null required pointer");
+    if ((rc = require_rows(d, response, mask)) != 0) return rc;
+    if (d->n_flows > 0 && !flow) return fail(-5, "flows need flow");
+    if (plan_rc) return plan_rc;
+    if (!workspace || workspace_bytes < need) return fail(-7, "workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
+    if (!rows_vec_ok(d, response, mask)) return fail(-8, "multi-sample forward: rows are not 16-byte chunkable");
+    return 0;
 }
 
 // both multi-sample calls: `table` is the 2-row expert table, or (given) the caller's posterior with post_sstride floats between the samples'
@@ -587,20 +596,16 @@ static int multi_forward_impl(const vibo_desc* d, bool given, int num_samples, c
     int rc = check_desc(d);
     if (rc) return rc;
     if (num_samples < 1) return fail(-3, "num_samples must be >= 1");
-    if (!table || !item || !eps || !out_scalars) return fail(-5, "null required pointer");
-    if ((rc = require_rows(d, response, mask)) != 0) return rc;
-    if (d->n_flows > 0 && !flow) return fail(-5, "flows need flow");
     vibo_desc d0;
     Plan pl;
     size_t prep = 0;
-    rc = multi_plan(d, num_cu, &d0, &pl, &prep, given);
+    int plan_rc = multi_plan(d, num_cu, &d0, &pl, &prep, given);
+    if (plan_rc == 0 && given && post_sstride != 0 && post_sstride != (long long)d->num_person * 2 * d->ability_dim)
+        plan_rc = fail(-3, "posterior_sample_stride must be 0 (one posterior for all samples) or num_person * 2 * ability_dim");
+    rc = multi_check_args(d, table && item && eps && out_scalars, response, mask, flow, plan_rc, plan_rc ? 0 : pl.total_bytes + 4 * prep,
+                          workspace, workspace_bytes);
     if (rc) return rc;
-    if (given && post_sstride != 0 && post_sstride != (long long)d->num_person * 2 * d->ability_dim)
-        return fail(-3, "posterior_sample_stride must be 0 (one posterior for all samples) or num_person * 2 * ability_dim");
-    if (!workspace || workspace_bytes < pl.total_bytes + 4 * prep) return fail(-7, "workspace too small");
-    if ((uintptr_t)workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
     const int I = d->num_item, A = d->ability_dim;
-    if (!rows_vec_ok(d, response, mask)) return fail(-8, "multi-sample forward: rows are not 16-byte chunkable");
     hipStream_t s = (hipStream_t)stream;
     char* wsb = static_cast<char*>(workspace);
     float* partial = reinterpret_cast<float*>(wsb + pl.off_partial);
@@ -729,12 +734,8 @@ int vibo_elbo_multi_forward_cond(const vibo_desc* d, int num_samples, const floa
     if (rc) return rc;
     MultiCondPlan m;
     if ((rc = multi_cond_plan(d, num_samples, device_cus(), &m)) != 0) return rc;
-    if (!tables || !item || !eps || !out_scalars) return fail(-5, "null required pointer");
-    if ((rc = require_rows(d, response, mask)) != 0) return rc;
-    if (d->n_flows > 0 && !flow) return fail(-5, "flows need flow");
-    if (!workspace || workspace_bytes < m.total_bytes) return fail(-7, "workspace too small: %zu < %zu", workspace_bytes, m.total_bytes);
-    if ((uintptr_t)workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
-    if (!rows_vec_ok(d, response, mask)) return fail(-8, "multi-sample forward: rows are not 16-byte chunkable");
+    rc = multi_check_args(d, tables && item && eps && out_scalars, response, mask, flow, 0, m.total_bytes, workspace, workspace_bytes);
+    if (rc) return rc;
     const int I = d->num_item, A = d->ability_dim;
     const long long B = d->num_person;
     hipStream_t s = (hipStream_t)stream;

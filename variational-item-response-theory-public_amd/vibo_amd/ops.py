@@ -259,6 +259,26 @@ def prepare_response(response):
         response = response.contiguous()
     return response
 
+_NOT_GIVEN = object()
+
+
+def chunkable_rows(response, mask, row_index=_NOT_GIVEN):
+    """-> (response, mask), or with a `row_index` argument (a tensor or None) -> (response, mask, row_index): rows that the kernels
+    can read in chunks of 4 cells.  The caller-supplied-posterior modes (mean merge, VI, MLE) and the multi-sample forward have no
+    fallback kernel for unchunkable rows, so a compact copy of rows whose width is no multiple of 4 (CritLangAcq: 95 items) is
+    padded here (pad_rows); a row index is gathered first -- only the minibatch is copied -- and comes back as None.  CellCodes,
+    widths that are multiples of 4 and rows that are padded already come back as they are."""
+    if not isinstance(response, CellCodes):
+        response = prepare_response(response)
+        if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
+            mask = prepare_mask(mask)[0]
+            if row_index is not _NOT_GIVEN and row_index is not None:
+                response, mask, row_index = response[row_index], (mask[row_index] if mask is not None else None), None
+            response, mask = pad_rows(response, mask)
+    return (response, mask) if row_index is _NOT_GIVEN else (response, mask, row_index)
+
+
+
 
 # vibo_desc.flags of every descriptor this module builds (_lib.FLAG_*): 0 = the planner chooses.  Tests and A/B tools
 # pin one row-split kernel here; the library itself reads no environment variable.
@@ -507,10 +527,28 @@ def multi_forward_declined(spec, response, mask, mask_code, num_samples, num_per
     call (vibo_multi_cond_workspace_bytes == 0: cell codes at ability_dim >= 3, int64 masks, ...) -- asked from the descriptor
     alone, before a caller draws noise or stacks S tables for a call that would answer None.  False for any other backend (the CPU
     stand-in, a test's fake: they answer for themselves) and for rows off the device."""
-    if _BACKEND['multi'] is not _hip_multi_forward or not (spec.conditional and not getattr(spec, 'given', False)) or not response.is_cuda:
+    if _BACKEND['multi'] is not _hip_multi_forward or _multi_mode(spec) != 'cond' or not response.is_cuda:
         return False
     d = _rows_desc(spec, int(num_person), response, mask, mask_code, _lib.REG_SAMPLED, False)
     return _lib.load().vibo_multi_cond_workspace_bytes(ctypes.byref(d), int(num_samples)) == 0
+
+
+# The three multi-sample entries by posterior mode: workspace query, entry, what `table` must be (None: unchecked) and the shapes
+# that means, and the arguments that entry alone takes: (those after `table`, those after `out_scalars`)
+_MULTI_CALLS = {
+    'plain': ('vibo_multi_workspace_bytes', 'vibo_elbo_multi_forward', None, None,
+              lambda table, B, A: ((), ())),
+    'given': ('vibo_multi_given_workspace_bytes', 'vibo_elbo_multi_forward_given',
+              'the posterior is a contiguous [B, 2A] or [S, B, 2A] tensor', lambda S, B, I, A: ((B, 2 * A), (S, B, 2 * A)),
+              lambda table, B, A: ((ctypes.c_int64(B * 2 * A if table.dim() == 3 else 0),), ())),      # posterior_sample_stride
+    'cond': ('vibo_multi_cond_workspace_bytes', 'vibo_elbo_multi_forward_cond',
+             'the conditional posterior takes a contiguous [S, 2, I, 2A] table', lambda S, B, I, A: ((S, 2, I, 2 * A),),
+             lambda table, B, A: ((), (None,))),                                                        # posterior_out
+}
+
+
+def _multi_mode(spec):
+    return 'given' if getattr(spec, 'given', False) else 'cond' if spec.conditional else 'plain'
 
 
 def _hip_multi_forward(spec, response, mask, mask_code, row_index, table, items, eps, flow, reg_mode, num_person):
@@ -520,39 +558,25 @@ def _hip_multi_forward(spec, response, mask, mask_code, row_index, table, items,
     by the samples or [S, B, 2A] one per sample.
     spec.conditional without given (vibo_elbo_multi_forward_cond): `table` is the encoder's table of every item sample,
     [S, 2, I, 2A]; rows that are not on the device also answer None (the caller's loop then meets its own backend)."""
-    given = bool(getattr(spec, 'given', False))
-    cond = bool(spec.conditional) and not given
-    if cond and not response.is_cuda:
+    mode = _multi_mode(spec)
+    query, name, table_rule, table_shapes, extra = _MULTI_CALLS[mode]
+    if mode == 'cond' and not response.is_cuda:
         return None
     lib = _lib.load()
     _require_device(response, mask, table, items, eps)
-    S, B, I = int(items.shape[0]), int(num_person), response.shape[1]
+    S, B, I, A = int(items.shape[0]), int(num_person), response.shape[1], spec.ability_dim
     d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, False)
-    query = lib.vibo_multi_given_workspace_bytes if given else lib.vibo_multi_cond_workspace_bytes if cond else lib.vibo_multi_workspace_bytes
-    ws_bytes = query(ctypes.byref(d), S)
+    ws_bytes = getattr(lib, query)(ctypes.byref(d), S)
     if ws_bytes == 0:
         return None
+    if table_rule is not None and (tuple(table.shape) not in table_shapes(S, B, I, A) or not table.is_contiguous()):
+        raise ValueError('multi-sample forward: %s, got %s' % (table_rule, tuple(table.shape)))
+    after_table, after_out = extra(table, B, A)
     dev = response.device
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     out = torch.empty(S, _lib.NUM_SCALARS, dtype=torch.float32, device=dev)
-    tail = (_ptr(items), _ptr(eps), _ptr(flow), _ptr(out), _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(dev))
-    if given:
-        A = spec.ability_dim
-        if tuple(table.shape) not in ((B, 2 * A), (S, B, 2 * A)) or not table.is_contiguous():
-            raise ValueError('multi-sample forward: the posterior is a contiguous [B, 2A] or [S, B, 2A] tensor, got %s' % (tuple(table.shape),))
-        name, stride = 'vibo_elbo_multi_forward_given', (B * 2 * A if table.dim() == 3 else 0)
-        rc = lib.vibo_elbo_multi_forward_given(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table),
-                                               ctypes.c_int64(stride), *tail)
-    elif cond:
-        A = spec.ability_dim
-        if tuple(table.shape) != (S, 2, I, 2 * A) or not table.is_contiguous():
-            raise ValueError('multi-sample forward: the conditional posterior takes a contiguous [S, 2, I, 2A] table, got %s' % (tuple(table.shape),))
-        name = 'vibo_elbo_multi_forward_cond'
-        rc = lib.vibo_elbo_multi_forward_cond(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table), *tail[:4],
-                                              None, *tail[4:])
-    else:
-        name = 'vibo_elbo_multi_forward'
-        rc = lib.vibo_elbo_multi_forward(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table), *tail)
+    rc = getattr(lib, name)(ctypes.byref(d), S, _ptr(response), _ptr(mask), _ptr(row_index), _ptr(table), *after_table,
+                            _ptr(items), _ptr(eps), _ptr(flow), _ptr(out), *after_out, _ptr(ws), ctypes.c_size_t(ws_bytes), _stream(dev))
     if rc == -8:
         return None
     _lib.check(rc, name)

@@ -16,6 +16,7 @@ The only piece of forward()'s tuple that is not materialised is ``response_mu``
 ([B,I,1], as large as the input): it is a :class:`DeferredResponseMu` that
 ``elbo`` recognises; call ``.materialize()`` (or ``model.decode``) for the values.
 """
+import dataclasses
 import math
 
 import torch
@@ -375,7 +376,7 @@ class VIBO_1PL(nn.Module):
     def _run_fused(self, response, mask, *, eps_item=None, eps_ability=None, reg_mode=None, row_index=None, posterior=None):
         """Item sample -> expert table -> fused kernel.  Draw order: item eps, then
         ability eps (models.py:361,368).  posterior: the mean-merge posterior [B, 2A] of these rows (and this item noise) where
-        the caller has it already (log_marginal's loop after _log_weights_multi)."""
+        the caller has it already (log_marginal's loop after _draw_samples)."""
         item_feat, item_mu, item_lv = self._item_side(eps_item)
         if self.n_norm_flows > 0:
             item_k, item_ladj = self.item_norm_flows(item_feat)
@@ -383,14 +384,7 @@ class VIBO_1PL(nn.Module):
         else:
             item_k, item_ladj, flow_packed = item_feat, None, None
         if self.ability_merge == 'mean':      # per-person posterior from the row counts; the kernel takes it as given
-            if not isinstance(response, ops.CellCodes):
-                response = ops.prepare_response(response)
-                if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
-                    # compact ragged rows (e.g. 95 items): this path has no fallback kernel, so pad the minibatch
-                    m2 = ops.prepare_mask(mask)[0]
-                    if row_index is not None:
-                        response, m2, row_index = response[row_index], (m2[row_index] if m2 is not None else None), None
-                    response, mask = ops.pad_rows(response, m2)
+            response, mask, row_index = ops.chunkable_rows(response, mask, row_index)
             table = posterior if posterior is not None else self._mean_posterior(response, mask, row_index, item_feat)
         else:
             table = self.ability_encoder.expert_table(item_feat if self.conditional_posterior else None)
@@ -545,14 +539,12 @@ class VIBO_1PL(nn.Module):
         ll = ctx.ll
         if self.n_norm_flows > 0:
             assert item_feat_k is not None and item_logabsdetjac is not None
-            log_q_d = _normal_logpdf(item_feat, item_feat_mu, item_feat_logvar).sum() - item_logabsdetjac.sum()
-            log_p_d = _std_normal_logpdf(item_feat_k).sum()
+            log_p_d, log_q_d = _item_log_terms(item_feat, item_feat_mu, item_feat_logvar, item_feat_k, item_logabsdetjac)
             return -(ll + log_p_d - reg - log_q_d)
         if use_kl_divergence:
             kl_d = (-0.5 * (1.0 + item_feat_logvar - item_feat_mu.pow(2) - item_feat_logvar.exp())).sum()
             return -(ll - annealing_factor * reg - annealing_factor * kl_d)
-        log_q_d = _normal_logpdf(item_feat, item_feat_mu, item_feat_logvar).sum()
-        log_p_d = _std_normal_logpdf(item_feat).sum()
+        log_p_d, log_q_d = _item_log_terms(item_feat, item_feat_mu, item_feat_logvar, item_feat, None)
         return -(ll + log_p_d - reg - log_q_d)
 
     def _decoder_elbo(self, ctx, annealing_factor, use_kl_divergence):
@@ -622,87 +614,67 @@ class VIBO_1PL(nn.Module):
                     ctx = self._run_decoder(response, mask, eps_item=None if eps_item is None else eps_item[s],
                                             eps_ability=None if eps_ability is None else eps_ability[s])
                     log_w.append(-self._decoder_elbo(ctx, 1.0, False))
-                return torch.logsumexp(torch.stack(log_w), 0) - math.log(S)
-            mean_merge = self.ability_merge == 'mean'
-            posts = None      # mean merge: the posteriors _log_weights_multi computed before the backend answered None
+                return _log_mean_exp(torch.stack(log_w))
+            draws = None
             # (person-sharded mean merge or conditional posterior: the loop reduces its heads through the collective)
-            if self._reducer is None or not (mean_merge or self.conditional_posterior):
-                if not isinstance(response, ops.CellCodes):
-                    response = ops.prepare_response(response)
-                    if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
-                        # (a compact copy of e.g. 95-item rows: pad the minibatch so the multi-sample kernel applies; the mean
-                        #  path of _run_fused pads the same way)
-                        response, mask = ops.pad_rows(response, ops.prepare_mask(mask)[0])
-                log_w, eps_item, eps_ability, posts = self._log_weights_multi(response, mask, S, eps_item, eps_ability)
+            if self._reducer is None or not (self.ability_merge == 'mean' or self.conditional_posterior):
+                response, mask = ops.chunkable_rows(response, mask)
+                draws = self._draw_samples(response, mask, S, eps_item, eps_ability)
+            if draws is not None:
+                log_w = _multi_log_weights(self.spec, response, mask, draws)
                 if log_w is not None:
-                    return torch.logsumexp(log_w, 0) - math.log(S)
+                    return _log_mean_exp(log_w)
                 # not covered (fewer than 4 items, ...): the loop below replays the noise already drawn and, for mean merge,
                 # takes the posteriors already computed from it
+                eps_item, eps_ability = draws.eps_item, draws.eps_ability
             log_w = []
             for s in range(S):
                 ctx = self._run_fused(response, mask, reg_mode=_lib.REG_SAMPLED,
                                       eps_item=None if eps_item is None else eps_item[s],
                                       eps_ability=None if eps_ability is None else eps_ability[s],
-                                      posterior=None if posts is None else (posts[s] if posts.dim() == 3 else posts))
-                log_q_d = _normal_logpdf(ctx.item_feat, ctx.item_mu, ctx.item_lv).sum()
-                if ctx.item_ladj is not None:
-                    log_q_d = log_q_d - ctx.item_ladj.sum()
-                log_p_d = _std_normal_logpdf(ctx.item_k).sum()
-                log_w.append(ctx.ll + log_p_d - ctx.reg - log_q_d)
-            log_w = torch.stack(log_w)
-            return torch.logsumexp(log_w, 0) - math.log(S)
+                                      posterior=None if draws is None else draws.posterior(s))
+                log_pd, log_qd = _item_log_terms(ctx.item_feat, ctx.item_mu, ctx.item_lv, ctx.item_k, ctx.item_ladj)
+                log_w.append(ctx.ll + log_pd - ctx.reg - log_qd)
+            return _log_mean_exp(torch.stack(log_w))
 
-    def _log_weights_multi(self, response, mask, S, eps_item, eps_ability):
-        """log w_s for s < S through the multi-sample forward kernel, or None if the configuration is not covered.
+    def _draw_samples(self, response, mask, S, eps_item, eps_ability):
+        """The S samples of log_marginal as the multi-sample forward kernel takes them (_Draws), or None -- nothing drawn, nothing
+        stacked -- for an int64 mask and where the native backend's workspace query already declines the call.
         --ability-merge mean: the posterior goes to the kernel as given -- _mean_posterior once for all samples, or (conditional
         posterior: it depends on the item sample) once per sample, stacked to [S, B, 2A].  Product of experts x conditional
         posterior: the encoder's table of every item sample (expert_table of the sample in front of the item flows, as _run_fused),
         stacked to [S, 2, I, 2A]; the kernel forms the posteriors.  Memory: the stacked noise is S B A floats
         and the per-sample posteriors S B 2A (1M persons, A = 8, S = 16: 0.5 + 1 GB): a caller with a whole resident split and many
-        samples passes it in minibatches.
-        -> (log_w or None, eps_item, eps_ability, posteriors or None): after None the caller's loop replays the last three."""
-        rows, mask_in = response, mask
-        response, mask2, code = ops.prepare_rows(response, mask)
-        if code == _lib.MASK_I64:
-            return None, eps_item, eps_ability, None
-        B = response.shape[0]
+        samples passes it in minibatches."""
+        rows, mask2, code = ops.prepare_rows(response, mask)
+        B = rows.shape[0]
+        if code == _lib.MASK_I64 or ops.multi_forward_declined(self.spec, rows, mask2, code, S, B):
+            return None
         mean_merge = self.ability_merge == 'mean'
-        if ops.multi_forward_declined(self.spec, response, mask2, code, S, B):
-            return None, eps_item, eps_ability, None      # (nothing drawn, nothing stacked: the loop runs as it always did)
         item_mu, item_lv = self.item_encoder()
-        items, log_qd, log_pd, eps_ab, drawn_items, posts, tables = [], [], [], [], [], [], []
+        drawn_items, items, eps_ab, log_pd, log_qd, tables = [], [], [], [], [], []
         for s in range(S):                      # draw order of the reference's loop: item eps, then ability eps
             e_i = self._randn(item_mu.shape, item_mu, self._item_gen) if eps_item is None else eps_item[s]
             drawn_items.append(e_i)
             item_feat = e_i * torch.exp(0.5 * item_lv) + item_mu
-            lq = _normal_logpdf(item_feat, item_mu, item_lv).sum()
-            item_k = item_feat
-            if self.n_norm_flows > 0:
-                item_k, item_ladj = self.item_norm_flows(item_feat)
-                lq = lq - item_ladj.sum()
-            if mean_merge and self.conditional_posterior:      # (from the item sample in front of the item flows, as _run_fused)
-                posts.append(self._mean_posterior(rows, mask_in, None, item_feat))
-            elif self.conditional_posterior:
-                tables.append(self.ability_encoder.expert_table(item_feat))
+            item_k, item_ladj = self.item_norm_flows(item_feat) if self.n_norm_flows > 0 else (item_feat, None)
+            lp, lq = _item_log_terms(item_feat, item_mu, item_lv, item_k, item_ladj)
+            if self.conditional_posterior:      # (from the item sample in front of the item flows, as _run_fused)
+                tables.append(self._mean_posterior(response, mask, None, item_feat) if mean_merge
+                              else self.ability_encoder.expert_table(item_feat))
             items.append(item_k)
+            log_pd.append(lp)
             log_qd.append(lq)
-            log_pd.append(_std_normal_logpdf(item_k).sum())
             eps_ab.append(self._randn((B, self.ability_dim), item_mu, self._ability_gen)
                           if eps_ability is None else eps_ability[s])
-        if not mean_merge:
-            table = torch.stack(tables) if self.conditional_posterior else self.ability_encoder.expert_table(None)
-        elif self.conditional_posterior:
-            table = torch.stack(posts)
-            posts = None          # (one copy)
+        if self.conditional_posterior:
+            table = torch.stack(tables)
         else:
-            table = self._mean_posterior(rows, mask_in, None, None)
-        flow_packed = self.ability_norm_flows.packed() if self.n_norm_flows > 0 else None
-        eps_ab = torch.stack(eps_ab)
-        sc = ops._BACKEND['multi'](self.spec, response, mask2, code, None, table.contiguous(),
-                                   torch.stack(items).contiguous(), eps_ab, flow_packed, _lib.REG_SAMPLED, B)
-        if sc is None:
-            return None, (torch.stack(drawn_items) if eps_item is None else eps_item), eps_ab, (table if mean_merge else None)
-        return sc[:, _lib.S_LL] - sc[:, _lib.S_REG] + torch.stack(log_pd) - torch.stack(log_qd), eps_item, eps_ability, None
+            table = self._mean_posterior(response, mask, None, None) if mean_merge else self.ability_encoder.expert_table(None)
+        return _Draws(eps_item=drawn_items if eps_item is None else eps_item, items=torch.stack(items).contiguous(),
+                      eps_ability=torch.stack(eps_ab), log_pd=torch.stack(log_pd), log_qd=torch.stack(log_qd),
+                      table=table.contiguous(), given=mean_merge,
+                      flow_packed=self.ability_norm_flows.packed() if self.n_norm_flows > 0 else None)
 
     # ---- fast path for training loops (no tuple round trip) -------------------
     def elbo_step(self, response, mask, annealing_factor=1.0, row_index=None):
@@ -769,13 +741,7 @@ class VI_1PL(nn.Module):
         B = amu.shape[0]
         if eps_ability is None:
             eps_ability = torch.randn(B, self.ability_dim, dtype=amu.dtype, device=amu.device)
-        if not isinstance(response, ops.CellCodes):
-            response = ops.prepare_response(response)
-            if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
-                m2 = ops.prepare_mask(mask)[0]           # compact ragged rows: this mode has no fallback kernel
-                if row_index is not None:
-                    response, m2, row_index = response[row_index], (m2[row_index] if m2 is not None else None), None
-                response, mask = ops.pad_rows(response, m2)
+        response, mask, row_index = ops.chunkable_rows(response, mask, row_index)
         table = torch.cat([amu, alv], dim=1)
         heads = fused_elbo(self.spec, table, item_feat, None, response, mask, eps_ability, reg_mode=reg_mode,
                            row_index=row_index)
@@ -822,8 +788,7 @@ class VI_1PL(nn.Module):
         if use_kl_divergence:
             kl_d = (-0.5 * (1.0 + item_feat_logvar - item_feat_mu.pow(2) - item_feat_logvar.exp())).sum()
             return -(ctx.ll - annealing_factor * reg - annealing_factor * kl_d)
-        log_q_d = _normal_logpdf(item_feat, item_feat_mu, item_feat_logvar).sum()
-        log_p_d = _std_normal_logpdf(item_feat).sum()
+        log_p_d, log_q_d = _item_log_terms(item_feat, item_feat_mu, item_feat_logvar, item_feat, None)
         return -(ctx.ll + log_p_d - reg - log_q_d)
 
     def log_marginal(self, index, response, mask, num_samples=100):
@@ -831,19 +796,21 @@ class VI_1PL(nn.Module):
         forward call and cannot run -- this is the same estimator with the index passed)."""
         with torch.no_grad():
             S = int(num_samples)
-            log_w, eps = self._log_weights_multi(index, response, mask, S)
+            response, mask = ops.chunkable_rows(response, mask)      # (as _run pads compact ragged rows)
+            draws = self._draw_samples(index, S)
+            log_w = _multi_log_weights(self.spec, response, mask, draws)
             if log_w is None:      # not covered by the multi-sample kernel: one forward per sample on the noise already drawn
                 log_w = []
                 for s in range(S):
-                    outs = self.forward(index, response, mask, eps_item=eps[0][s], eps_ability=eps[1][s])
+                    outs = self.forward(index, response, mask, eps_item=draws.eps_item[s], eps_ability=draws.eps_ability[s])
                     log_w.append(-self.elbo(*outs, annealing_factor=1, use_kl_divergence=False))
                 log_w = torch.stack(log_w)
-            return torch.logsumexp(log_w, 0) - math.log(S)
+            return _log_mean_exp(log_w)
 
-    def _log_weights_multi(self, index, response, mask, S):
-        """log w_s for s < S in one pass over the responses (vibo_elbo_multi_forward_given: the looked-up (mu | logvar) rows are
-        the posterior of every sample), or None and the noise drawn where the backend does not cover the call.  The noise comes
-        from the default generator in _run's order: item randn_like, then randn(B, A), per sample."""
+    def _draw_samples(self, index, S):
+        """The S samples of log_marginal for the multi-sample forward (vibo_elbo_multi_forward_given: the looked-up (mu | logvar)
+        rows are the posterior of every sample).  The noise comes from the default generator in _run's order: item randn_like, then
+        randn(B, A), per sample."""
         item_mu, item_lv = self.item_mu_lookup.weight, self.item_logvar_lookup.weight
         amu, alv = self._posterior_rows(index)
         B = amu.shape[0]
@@ -854,18 +821,9 @@ class VI_1PL(nn.Module):
             eps_ab.append(torch.randn(B, self.ability_dim, dtype=amu.dtype, device=amu.device))
         eps_item, eps_ab = torch.stack(eps_item), torch.stack(eps_ab)
         items = eps_item * std + item_mu                                              # [S, I, D]
-        log_qd = _normal_logpdf(items, item_mu, item_lv).sum((1, 2))
-        log_pd = _std_normal_logpdf(items).sum((1, 2))
-        if not isinstance(response, ops.CellCodes):
-            response = ops.prepare_response(response)
-            if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
-                response, mask = ops.pad_rows(response, ops.prepare_mask(mask)[0])      # (as _run pads compact ragged rows)
-        response, mask2, code = ops.prepare_rows(response, mask)
-        sc = ops._BACKEND['multi'](self.spec, response, mask2, code, None, torch.cat([amu, alv], dim=1).contiguous(),
-                                   items.contiguous(), eps_ab, None, _lib.REG_SAMPLED, B)
-        if sc is None:
-            return None, (eps_item, eps_ab)
-        return sc[:, _lib.S_LL] - sc[:, _lib.S_REG] + log_pd - log_qd, None
+        return _Draws(eps_item=eps_item, items=items.contiguous(), eps_ability=eps_ab,
+                      log_pd=_std_normal_logpdf(items).sum((1, 2)), log_qd=_normal_logpdf(items, item_mu, item_lv).sum((1, 2)),
+                      table=torch.cat([amu, alv], dim=1).contiguous(), flow_packed=None, given=True)
 
 
 class VI_2PL(VI_1PL):
@@ -924,13 +882,7 @@ class MLE_1PL(nn.Module):
         """mean_{B x I}(mask * BCE(response_mu, response)) (mle.py:193-196) without materialising response_mu."""
         ability, item = self.encode(index)
         B = ability.shape[0]
-        if not isinstance(response, ops.CellCodes):
-            response = ops.prepare_response(response)
-            if response.shape[1] % 4 != 0 and response.stride(0) < (response.shape[1] + 3) // 4 * 4:
-                m2 = ops.prepare_mask(mask)[0]
-                if row_index is not None:
-                    response, m2, row_index = response[row_index], (m2[row_index] if m2 is not None else None), None
-                response, mask = ops.pad_rows(response, m2)
+        response, mask, row_index = ops.chunkable_rows(response, mask, row_index)
         table = torch.cat([ability, torch.zeros_like(ability)], dim=1)          # (mu | logvar = 0), eps = 0: theta = mu
         heads = fused_elbo(self.spec, table, item, None, response, mask, torch.zeros_like(ability), reg_mode=_lib.REG_KL,
                            row_index=row_index)
@@ -951,3 +903,51 @@ def _normal_logpdf(x, mu, logvar):
 
 def _std_normal_logpdf(x):
     return -0.5 * LOG_2PI - 0.5 * x * x
+
+
+def _item_log_terms(item_feat, item_mu, item_lv, item_k, item_ladj):
+    """The item side of an importance weight ll + log_pd - reg - log_qd: (log p(d) at the item sample behind the item flows,
+    log q(d) of the sample in front of them minus the flows' log-determinant).  Without flows item_k is item_feat, item_ladj None."""
+    log_qd = _normal_logpdf(item_feat, item_mu, item_lv).sum()
+    if item_ladj is not None:
+        log_qd = log_qd - item_ladj.sum()
+    return _std_normal_logpdf(item_k).sum(), log_qd
+
+
+def _log_mean_exp(log_w):
+    """log of the mean of the S weights exp(log_w[s])."""
+    return torch.logsumexp(log_w, 0) - math.log(log_w.shape[0])
+
+
+@dataclasses.dataclass
+class _Draws:
+    """What log_marginal drew for its S samples, stacked as the multi-sample forward takes it.  eps_item (the caller's [S, I, D]
+    or the S tensors drawn), items [S, I, D] behind the item flows, eps_ability [S, B, A], log_pd / log_qd [S]
+    (_item_log_terms), flow_packed (the ability flows, or None) and `table` as the backend reads it: the expert table [2, 2A] or,
+    conditional posterior, one per sample [S, 2, I, 2A]; given=True: the posterior (mu | logvar) [B, 2A] or one per sample
+    [S, B, 2A]."""
+    eps_item: object
+    items: torch.Tensor
+    eps_ability: torch.Tensor
+    log_pd: torch.Tensor
+    log_qd: torch.Tensor
+    table: torch.Tensor
+    flow_packed: object
+    given: bool
+
+    def posterior(self, s):
+        """The given posterior [B, 2A] of sample s for a forward of that sample alone; None where the kernel forms it itself."""
+        if not self.given:
+            return None
+        return self.table[s] if self.table.dim() == 3 else self.table
+
+
+def _multi_log_weights(spec, response, mask, draws):
+    """log w_s [S] of the samples `draws` in one pass over the rows (ops._BACKEND['multi']), or None where the backend does not
+    cover the call: the caller then runs one forward per sample on the same draws."""
+    response, mask, code = ops.prepare_rows(response, mask)
+    sc = ops._BACKEND['multi'](spec, response, mask, code, None, draws.table, draws.items, draws.eps_ability, draws.flow_packed,
+                               _lib.REG_SAMPLED, draws.eps_ability.shape[1])
+    if sc is None:
+        return None
+    return sc[:, _lib.S_LL] - sc[:, _lib.S_REG] + draws.log_pd - draws.log_qd
