@@ -8,7 +8,12 @@ singles leg is then one GIVEN forward launch (want_grad = 0) per sample.
 ([S, 2, I, 2A]); the singles leg is one conditional forward launch per sample.
 --log-marginal: the module instead of the kernel legs -- VIBO_*PL(...).log_marginal of this checkout's package on the same rows
 (with --minibatch N: summed over minibatches of N persons, as the reference's evaluation pass), torch.manual_seed(7) in front of
-every call; prints `log_marginal <ms median> <min> <max> <value>`.  Run from two checkouts for a parent / new comparison."""
+every call; prints `log_marginal <ms median> <min> <max> <value>`.  Run from two checkouts for a parent / new comparison.
+--generative-model link | deep | residual: the MLP-decoder model instead (with --log-marginal; with --predictive:
+vibo.posterior_predictive's mean over --samples draws in minibatches of --minibatch, prints `posterior_predictive <ms ...> <sum>`).
+These decoder legs warm up on the first and the last minibatch only (every shape of the timed pass); the IRT legs on a whole pass.
+--decoder-kernel deep | link | residual: the kernel legs of the decoder -- vibo_decoder_multi_forward on --samples stacked samples
+against one vibo_decoder_fwd_bwd forward launch per sample."""
 import argparse
 import os
 import sys
@@ -34,6 +39,9 @@ ap.add_argument('--per-sample', action='store_true', help='with --given: one pos
 ap.add_argument('--cond', action='store_true', help='product of experts x conditional posterior: one encoder table per sample')
 ap.add_argument('--log-marginal', action='store_true', help='time model.log_marginal instead of the kernel legs')
 ap.add_argument('--minibatch', type=int, default=0, help='with --log-marginal: persons per call (0: all)')
+ap.add_argument('--generative-model', default='irt', choices=['irt', 'link', 'deep', 'residual'])
+ap.add_argument('--predictive', action='store_true', help='time vibo.posterior_predictive (mean over the draws) instead')
+ap.add_argument('--decoder-kernel', default=None, choices=['link', 'deep', 'residual'], help='decoder kernel legs: stacked vs one launch per sample')
 ap.add_argument('--reps', type=int, default=3)
 a = ap.parse_args()
 d = torch.device('cuda:0')
@@ -43,30 +51,74 @@ spec = ElboSpec(irt_model=a.irt, ability_dim=A, given=a.given, conditional=a.con
 resp = (torch.rand(P, I, device=d, generator=g) < 0.5).float()
 mask = torch.rand(P, I, device=d, generator=g) >= 0.1
 
-if a.log_marginal:
-    from vibo_amd.torch_core import models
+if a.log_marginal or a.predictive:
+    import types
+    from vibo_amd.torch_core import models, vibo
     torch.manual_seed(3)
     model = {1: models.VIBO_1PL, 2: models.VIBO_2PL, 3: models.VIBO_3PL}[a.irt](
-        A, I, ability_merge='mean' if a.given else 'product', conditional_posterior=a.cond or a.per_sample).to(d)
+        A, I, ability_merge='mean' if a.given else 'product', conditional_posterior=a.cond or a.per_sample,
+        **({} if a.generative_model == 'irt' else {'generative_model': a.generative_model})).to(d)
     rows = ops.pack_cell_codes(resp, mask) if a.codes else resp
     step = a.minibatch or P
+    starts = list(range(0, P, step))
 
-    def one_pass():
+    def log_marginal_pass(starts):
         torch.manual_seed(7)
         total = 0.0
-        for p0 in range(0, P, step):
+        for p0 in starts:
             r = rows.rows(torch.arange(p0, min(P, p0 + step), device=d)) if a.codes else rows[p0:p0 + step]
             total += float(model.log_marginal(r, None if a.codes else mask[p0:p0 + step], num_samples=S))      # (float() synchronises)
         return total
 
-    value = one_pass()
+    class Rows:      # the slice of vibo.py's dataset that posterior_predictive reads
+        def __init__(self, starts):
+            self.response, self.mask, self.starts = resp.unsqueeze(2), mask.unsqueeze(2), starts
+
+        def batches(self, batch_size, shuffle=False):
+            return [torch.arange(p0, min(P, p0 + step), device=d) for p0 in self.starts]
+
+    def predictive_pass(starts):
+        torch.manual_seed(7)
+        out = vibo.posterior_predictive(model, Rows(starts), types.SimpleNamespace(num_posterior_samples=S), step, False)
+        return float(out['response'].double().sum())          # (the result is on the host: the pass has synchronised)
+
+    one_pass = predictive_pass if a.predictive else log_marginal_pass
+    # warm-up: a whole pass; the decoder legs' loop side takes tens of seconds per pass, so they warm the first and the last minibatch
+    # only (every shape of the timed pass)
+    one_pass(starts if a.generative_model == 'irt' and not a.predictive else sorted({starts[0], starts[-1]}))
     times = []
     for _ in range(a.reps):
         t0 = time.perf_counter()
-        value = one_pass()
+        value = one_pass(starts)
         times.append((time.perf_counter() - t0) * 1e3)
     times.sort()
-    print(f'log_marginal {times[len(times) // 2]:.3f} {times[0]:.3f} {times[-1]:.3f} {value!r}')
+    print(f'{"posterior_predictive" if a.predictive else "log_marginal"} {times[len(times) // 2]:.3f} {times[0]:.3f} {times[-1]:.3f} {value!r}')
+    sys.exit(0)
+
+if a.decoder_kernel:
+    from vibo_amd import decoder as D
+    kind, Hd = a.decoder_kernel, D.HIDDEN
+    rn = lambda *shape, sc=1.0: torch.randn(*shape, device=d, generator=g) * sc
+    m8 = ops.prepare_mask(mask)[0]
+    U = None if kind == 'link' else rn(S, I, Hd, sc=0.7)
+    V, L = rn(S, P, Hd, sc=0.7), (None if kind == 'deep' else rn(S, P, I, sc=1.5))
+    w1 = rn(Hd, sc=0.5) if kind == 'link' else None
+    W2, b2, w3, b3 = rn(Hd, Hd, sc=0.18), rn(Hd, sc=0.1), rn(Hd, sc=0.25), rn(1, sc=0.1)
+    resid = 1.0 if kind == 'residual' else 0.0
+    at = lambda t, s: None if t is None else t[s]
+    legs = (('stacked launch', lambda: D._launch_multi(resp, m8, U, V, L, None, w1, W2, b2, w3, b3, resid)['ll_part'].sum(1)),
+            ('one launch per sample', lambda: torch.stack([D._launch(resp, m8, at(U, s), V[s], at(L, s), None, w1, W2, b2, w3, b3, resid,
+                                                                     False)['ll_part'].sum() for s in range(S)])))
+    for name, f in legs:
+        value = f()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            f()
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / a.reps
+        print(f'decoder {kind} P={P} I={I} S={S} {name:24s}: {dt * 1e3:8.3f} ms = {dt * 1e3 / S:6.3f} ms per sample, '
+              f'{P * I * S / dt / 1e12:.3f} T sample-terms/s, ll[0]={float(value[0])!r}')
     sys.exit(0)
 
 table = torch.randn(2, 2 * A, device=d, generator=g) * 0.5

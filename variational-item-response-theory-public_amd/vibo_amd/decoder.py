@@ -6,6 +6,8 @@ layer's input is a concatenation / a scalar, so it splits exactly into a per-ite
 V [B, 64] and (link) a rank-one term w1 * logit; those halves -- a few small dense layers over I or B rows -- are
 ordinary PyTorch modules here, and `decoder_log_lik` is the O(B I 64^2) rest: forward, masked Bernoulli log-likelihood
 and the whole backward in one launch, returned to autograd as gradients of (U, V, logit, guess, w1, W2, b2, w3, b3).
+Forward only, for S stacked samples in one launch (log_marginal, posterior_predictive): `decoder_multi_log_lik` /
+`decoder_multi_prob_sum` on csrc/vibo_decoder_multi.hip (vibo_decoder_multi_forward).
 """
 import ctypes
 
@@ -52,6 +54,40 @@ def _launch(response, mask, U, V, L, guess, w1, W2, b2, w3, b3, resid, want_grad
 
 
 ops._BACKEND.setdefault('decoder', _launch)      # (tests without a GPU swap in oracle/cpu_backend.py's stand-in)
+
+
+def _launch_multi(response, mask, U, V, L, guess, w1, W2, b2, w3, b3, resid, prob_sum=None, prob_accumulate=False, person_chunks=None):
+    """vibo_decoder_multi_forward: the forward of `_launch` for S stacked samples in one launch -- U [S, I, 64] or None,
+    V [S, B, 64], L [S, B, I] or None, guess [S, I] or None, the rest shared.  -> {'ll_part': [S, n_wave]} (sum over dim 1 per sample;
+    row s holds the bits of `_launch`'s ll_part for sample s alone at the same person_chunks); prob_sum [B, I]: the samples'
+    P(response = 1) are summed into it in sample order (prob_accumulate: onto what it holds).
+    None -- "not covered", the caller then makes one `_launch` per sample -- for tensors that are not on the device: this entry
+    stays in place under the CPU stand-in of the tests, which covers the single launch only."""
+    if any(t.device.type != 'cuda' for t in (response, V, W2, b2, w3, b3)):
+        return None
+    lib = _lib.load()
+    S, B = V.shape[0], V.shape[1]
+    I = response.shape[1]
+    dev = response.device
+    if person_chunks is None:      # (prob_sum: one workgroup owns a cell for all samples, so the samples add no parallelism)
+        person_chunks = lib.vibo_decoder_person_chunks(B, I) if prob_sum is not None else lib.vibo_decoder_multi_person_chunks(B, I, S)
+    n_wave = 4 * ((I + 63) // 64) * person_chunks
+    d = _lib.ViboDecoderDesc(B, I, HIDDEN, 0, person_chunks, float(resid), response.stride(0), mask.stride(0) if mask is not None else 0)
+    out = {'ll_part': torch.empty(S, n_wave, dtype=torch.float32, device=dev)}
+    p = ops._ptr
+    ops._call('vibo_decoder_multi_forward', ctypes.byref(d), S, p(response), p(mask), p(U), p(V), p(L), p(guess), p(w1), p(W2), p(b2),
+              p(w3), p(b3), p(out['ll_part']), p(prob_sum), int(bool(prob_accumulate)), ops._stream(dev))
+    return out
+
+
+ops._BACKEND.setdefault('decoder_multi', _launch_multi)
+
+
+def multi_declined(rows):
+    """True where the multi-sample launch will not take a call on `rows` (a tensor or CellCodes), asked before anything is drawn or
+    stacked (as ops.multi_forward_declined): no backend entry, or the native entry with rows that are not on the device."""
+    backend = ops._BACKEND.get('decoder_multi')
+    return backend is None or (backend is _launch_multi and rows.device.type != 'cuda')
 
 
 def _prep(t):
@@ -163,6 +199,106 @@ def decoder_probs(B, I, *, U, V, W2, b2, w3, b3, logit=None, w1=None, guess=None
     return outs[0] if len(outs) == 1 else torch.cat(outs, 0)
 
 
+MULTI_STACK_BYTES = 1 << 30      # samples per multi-sample call: their stacked per-person inputs (V, the logits) stay under this
+
+
+def multi_sample_group(B, I, S, has_logit):
+    """Samples per decoder_multi call: as many as keep V [s, B, 64] and (link / residual) the logits [s, B, I] under MULTI_STACK_BYTES."""
+    per_sample = 4 * B * (HIDDEN + (I if has_logit else 0))
+    return max(1, min(S, MULTI_STACK_BYTES // per_sample))
+
+
+def _multi_chunks(response, mask, U, V, logit, guess, w1, W2, b2, w3, b3):
+    """The prepared arguments of ops._BACKEND['decoder_multi'], person chunk by person chunk (PERSON_CHUNK, as the single call)."""
+    U, V, W2, b2, w3, w1 = _pad_hidden(U, V, W2, b2, w3, w1)
+    Up, Vp, Lp, gp, w1p, W2p, b2p, w3p, b3p = (_prep(t) for t in (U, V, logit, guess, w1, W2, b2, w3, b3))
+    B = Vp.shape[1]
+    for s in range(0, B, PERSON_CHUNK):
+        e = min(B, s + PERSON_CHUNK)
+        whole = s == 0 and e == B
+        yield s, e, (response if (response is None or whole) else response[s:e], mask if (mask is None or whole) else mask[s:e], Up,
+                     Vp if whole else Vp[:, s:e].contiguous(), Lp if (Lp is None or whole) else Lp[:, s:e].contiguous(),
+                     gp, w1p, W2p, b2p, w3p, b3p)
+
+
+@torch.no_grad()
+def decoder_multi_log_lik(response, mask, *, U, V, W2, b2, w3, b3, logit=None, w1=None, guess=None, resid=0.0):
+    """decoder_log_lik of S stacked samples in one launch per person chunk: U [S, I, H] or None, V [S, B, H], logit [S, B, I] or
+    None, guess [S, I] or None; the weights and the rows are shared.  -> [S] log-likelihood sums; forward only (log_marginal).
+    None where ops._BACKEND['decoder_multi'] does not cover the call: the caller then evaluates sample by sample."""
+    backend = ops._BACKEND.get('decoder_multi')
+    if backend is None:
+        return None
+    response, mask = _rows(response, mask)
+    ll = None
+    for s, e, args in _multi_chunks(response, mask, U, V, logit, guess, w1, W2, b2, w3, b3):
+        out = backend(*args, resid)
+        if out is None:
+            return None
+        part = out['ll_part'].sum(1)
+        ll = part if ll is None else ll + part
+    return ll
+
+
+@torch.no_grad()
+def decoder_multi_prob_sum(B, I, *, U, V, W2, b2, w3, b3, logit=None, w1=None, guess=None, resid=0.0, out=None):
+    """Sum over the S stacked samples of decoder_probs [B, I], added cell by cell in sample order inside one launch per person chunk
+    (the bits of accumulating S decoder_probs calls); `out`: a running sum of earlier calls to continue.  None where the backend does
+    not cover the call."""
+    backend = ops._BACKEND.get('decoder_multi')
+    if backend is None:
+        return None
+    acc = out if out is not None else torch.empty(B, I, dtype=torch.float32, device=V.device)
+    for s, e, args in _multi_chunks(None, None, U, V, logit, guess, w1, W2, b2, w3, b3):
+        dummy = torch.zeros(e - s, I, device=V.device)
+        if backend(dummy, *args[1:], resid, prob_sum=acc[s:e], prob_accumulate=out is not None) is None:
+            return None
+    return acc
+
+
+def irt_logit_multi(irt_model, abilities, items):
+    """irt_logit of stacked samples: abilities [S, B, A], items [S, I, D] -> logits [S, B, I] (and the 3PL guess [S, I])."""
+    A = abilities.shape[2]
+    if irt_model == 1:
+        return abilities.sum(2, keepdim=True) + items.transpose(1, 2), None
+    logit = torch.bmm(abilities, -items[:, :, :A].transpose(1, 2)) + items[:, :, A].unsqueeze(1)
+    guess = torch.sigmoid(items[:, :, A + 1]) if irt_model == 3 else None
+    return logit, guess
+
+
+class _MultiSample:
+    """log_marginal's and posterior_predictive's S samples through the multi-sample launch, in groups of multi_sample_group samples."""
+
+    def _groups(self, abilities, items):
+        S, B, I = abilities.shape[0], abilities.shape[1], items.shape[1]
+        n = multi_sample_group(B, I, S, isinstance(self, LinkedIRT) or self.RESIDUAL)
+        for s in range(0, S, n):
+            yield self._args_multi(abilities[s:s + n], items[s:s + n])
+
+    def multi_log_lik(self, response, mask, abilities, items):
+        """[S] log-likelihood sums of the samples (abilities [S, B, A], items [S, I, D]), or None (not covered: evaluate one by one)."""
+        if multi_declined(abilities):
+            return None
+        parts = []
+        for args in self._groups(abilities, items):
+            ll = decoder_multi_log_lik(response, mask, **args)
+            if ll is None:
+                return None
+            parts.append(ll)
+        return parts[0] if len(parts) == 1 else torch.cat(parts)
+
+    def multi_prob_sum(self, abilities, items):
+        """sum over the samples of forward(abilities[s], items[s]) [B, I], in sample order, or None (not covered)."""
+        if multi_declined(abilities):
+            return None
+        acc = None
+        for args in self._groups(abilities, items):
+            acc = decoder_multi_prob_sum(abilities.shape[1], items.shape[1], out=acc, **args)
+            if acc is None:
+                return None
+        return acc
+
+
 def irt_logit(irt_model, ability, item_feat):
     """irt_model_*pl(..., return_logit=True) (models.py:729-766): [B, I] logits (and the 3PL guess probability [I])."""
     A = ability.shape[1]
@@ -186,7 +322,7 @@ def _xavier(m):
         nn.init.constant_(m.bias.data, 0)
 
 
-class LinkedIRT(nn.Module):
+class LinkedIRT(_MultiSample, nn.Module):
     """models.py:769-813: response_mu = link(irt logit), link = 1 -> H -> H -> 1 -> sigmoid (3PL: guess mixture)."""
 
     def __init__(self, irt_model=1, hidden_dim=HIDDEN):
@@ -204,6 +340,14 @@ class LinkedIRT(nn.Module):
         return dict(U=None, V=V, W2=lk[2].weight, b2=lk[2].bias, w3=lk[4].weight.reshape(-1), b3=lk[4].bias,
                     logit=logit, w1=lk[0].weight.reshape(-1), guess=guess, resid=0.0)
 
+    def _args_multi(self, abilities, items):
+        """_args of stacked samples: abilities [S, B, A], items [S, I, D]."""
+        logit, guess = irt_logit_multi(self.irt_model, abilities, items)
+        lk = self.link
+        V = lk[0].bias.reshape(1, 1, -1).expand(abilities.shape[0], abilities.shape[1], -1)
+        return dict(U=None, V=V, W2=lk[2].weight, b2=lk[2].bias, w3=lk[4].weight.reshape(-1), b3=lk[4].bias,
+                    logit=logit, w1=lk[0].weight.reshape(-1), guess=guess, resid=0.0)
+
     def log_lik(self, response, mask, ability, item_feat):
         return decoder_log_lik(response, mask, **self._args(ability, item_feat))
 
@@ -211,7 +355,7 @@ class LinkedIRT(nn.Module):
         return decoder_probs(ability.shape[0], item_feat.shape[0], **self._args(ability, item_feat)).unsqueeze(2)
 
 
-class DeepIRT(nn.Module):
+class DeepIRT(_MultiSample, nn.Module):
     """models.py:816-877: sigmoid(mlp_concat([mlp_item_feat(item), mlp_ability(ability)]))."""
     RESIDUAL = False
 
@@ -235,6 +379,17 @@ class DeepIRT(nn.Module):
         a = dict(U=U, V=V, W2=mc[2].weight, b2=mc[2].bias, w3=mc[4].weight.reshape(-1), b3=mc[4].bias)
         if self.RESIDUAL:
             logit, guess = irt_logit(self.irt_model, ability, item_feat)
+            a.update(logit=logit, guess=guess, resid=1.0)
+        return a
+
+    def _args_multi(self, abilities, items):
+        """_args of stacked samples: abilities [S, B, A], items [S, I, D] (the small MLPs act on the last dimension)."""
+        mc, H = self.mlp_concat, self.hidden_dim
+        U = self.mlp_item_feat(items) @ mc[0].weight[:, :H].t()
+        V = self.mlp_ability(abilities) @ mc[0].weight[:, H:].t() + mc[0].bias
+        a = dict(U=U, V=V, W2=mc[2].weight, b2=mc[2].bias, w3=mc[4].weight.reshape(-1), b3=mc[4].bias)
+        if self.RESIDUAL:
+            logit, guess = irt_logit_multi(self.irt_model, abilities, items)
             a.update(logit=logit, guess=guess, resid=1.0)
         return a
 

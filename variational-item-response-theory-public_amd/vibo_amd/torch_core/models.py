@@ -24,7 +24,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import _lib, ops
-from ..decoder import DeepIRT, LinkedIRT, ResidualIRT
+from ..decoder import DeepIRT, LinkedIRT, ResidualIRT, multi_declined as decoder_multi_declined
 from ..ops import ElboSpec, decode_probs, encode_posterior, fused_elbo, item_feat_dim
 
 LOG_2PI = math.log(2.0 * math.pi)
@@ -603,12 +603,20 @@ class VIBO_1PL(nn.Module):
         (vibo_elbo_multi_forward); --ability-merge mean, whose posterior reaches the kernel as given
         (vibo_elbo_multi_forward_given: one [B, 2A] posterior for all samples, or with --conditional-posterior one per sample);
         product of experts x conditional posterior, whose per-sample encoder tables go in stacked (vibo_elbo_multi_forward_cond:
-        the experts' sums of up to 64 / 2A samples per contraction pass over the cell codes).  Otherwise -- a person-sharded
+        the experts' sums of up to 64 / 2A samples per contraction pass over the cell codes); the MLP-decoder models
+        (--generative-model link | deep | residual: vibo_decoder_multi_forward, _decoder_multi_log_weights; person-sharded ones keep
+        the loop).  Otherwise -- a person-sharded
         mean-merge or conditional model (its heads go through the collective), a backend that answers None -- one forward launch
         per sample."""
         with torch.no_grad():
             S = int(num_samples)
             if self.generative_model != 'irt':
+                if self._reducer is None and not decoder_multi_declined(response):
+                    # all S samples through one decoder launch (asked before anything is drawn or stacked); where the backend still
+                    # answers None the loop below replays the noise
+                    log_w, eps_item, eps_ability = self._decoder_multi_log_weights(response, mask, S, eps_item, eps_ability)
+                    if log_w is not None:
+                        return _log_mean_exp(log_w)
                 log_w = []
                 for s in range(S):
                     ctx = self._run_decoder(response, mask, eps_item=None if eps_item is None else eps_item[s],
@@ -636,6 +644,57 @@ class VIBO_1PL(nn.Module):
                 log_pd, log_qd = _item_log_terms(ctx.item_feat, ctx.item_mu, ctx.item_lv, ctx.item_k, ctx.item_ladj)
                 log_w.append(ctx.ll + log_pd - ctx.reg - log_qd)
             return _log_mean_exp(torch.stack(log_w))
+
+    def _decoder_multi_log_weights(self, response, mask, S, eps_item, eps_ability):
+        """log_marginal of an MLP-decoder model (not person-sharded) with its S samples stacked: -> (log w [S], eps_item [S, I, D],
+        eps_ability [S, B, A]); log w is None where the multi-sample decoder launch does not cover the call -- the noise, drawn in
+        the loop's order (item then ability, per sample), is then the loop's to replay.  The posterior is computed once where it
+        does not depend on the sample (from the row counts, counted once) and once per item sample where it does (conditional
+        posterior, through the loop's own calls); flows act on the stacked rows; one ops._BACKEND['decoder_multi'] call gives the
+        S log-likelihoods; the remaining terms are _decoder_elbo(ctx, 1.0, False)'s, per sample."""
+        item_mu, item_lv = self.item_encoder()
+        B, A = response.shape[0], self.ability_dim
+        if eps_item is None or eps_ability is None:
+            drawn_i, drawn_a = [], []
+            for s in range(S):
+                drawn_i.append(self._randn(item_mu.shape, item_mu, self._item_gen) if eps_item is None else eps_item[s])
+                drawn_a.append(self._randn((B, A), item_mu, self._ability_gen) if eps_ability is None else eps_ability[s])
+            eps_item, eps_ability = torch.stack(drawn_i), torch.stack(drawn_a)
+        else:
+            eps_item, eps_ability = (t[:S] if torch.is_tensor(t) else torch.stack(list(t[:S])) for t in (eps_item, eps_ability))
+        item_feat = eps_item * torch.exp(0.5 * item_lv) + item_mu                       # [S, I, D]
+        if self.conditional_posterior:      # depends on the item sample (in front of the item flows, as _run_decoder)
+            if self.ability_merge == 'mean':
+                per = [torch.chunk(self._mean_posterior(response, mask, None, item_feat[s], None, reduce_in_backward=False), 2, dim=1)
+                       for s in range(S)]
+            else:
+                per = [self._conditional_posterior_poe(response, mask, None, item_feat[s]) for s in range(S)]
+            amu, alv = torch.stack([p[0] for p in per]), torch.stack([p[1] for p in per])
+        else:
+            counts = ops.row_counts(response, mask, None)
+            if self.ability_merge == 'mean':
+                amu, alv = torch.chunk(self._mean_posterior(response, mask, None, None, counts, reduce_in_backward=False), 2, dim=1)
+            else:
+                amu, alv = self._posterior_from_counts(counts)
+            amu, alv = amu.unsqueeze(0), alv.unsqueeze(0)
+        ability = eps_ability * torch.exp(0.5 * alv) + amu                              # [S, B, A]
+        if self.n_norm_flows > 0:           # FlowStack is row-wise: the samples' rows go through stacked
+            ability_k, ability_ladj = self.ability_norm_flows(ability.reshape(S * B, A))
+            item_k, item_ladj = self.item_norm_flows(item_feat.reshape(S * item_feat.shape[1], -1))
+            ability_k, item_k = ability_k.reshape(ability.shape), item_k.reshape(item_feat.shape)
+            ladj = ability_ladj.reshape(S, B).sum(1), item_ladj.reshape(S, -1).sum(1)
+        else:
+            ability_k, item_k, ladj = ability, item_feat, None
+        ll = self.decoder.multi_log_lik(response, mask, ability_k, item_k)
+        if ll is None:
+            return None, eps_item, eps_ability
+        per_sample = lambda t: t.flatten(1).sum(1)
+        log_q_u = per_sample(_normal_logpdf(ability, amu, alv))
+        log_q_d = per_sample(_normal_logpdf(item_feat, item_mu, item_lv))
+        if ladj is not None:
+            log_q_u, log_q_d = log_q_u - ladj[0], log_q_d - ladj[1]
+        log_p = ll + per_sample(_std_normal_logpdf(ability_k)) + per_sample(_std_normal_logpdf(item_k))
+        return log_p - (log_q_u + log_q_d), eps_item, eps_ability
 
     def _draw_samples(self, response, mask, S, eps_item, eps_ability):
         """The S samples of log_marginal as the multi-sample forward kernel takes them (_Draws), or None -- nothing drawn, nothing

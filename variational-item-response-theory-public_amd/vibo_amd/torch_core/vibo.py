@@ -400,10 +400,14 @@ def posterior_predictive(model, data, args, batch_size, keep_samples):
                 per = [model.decode(a_s[s], i_s[s]).squeeze(2).cpu() for s in range(S)]
                 stacks.append(torch.stack(per))
                 means.append(stacks[-1].mean(0))
-            elif getattr(model, 'generative_model', 'irt') != 'irt':      # per-term MLP decoders: one decoder launch per draw, mean kept on the device
-                acc = model.decode(a_s[0], i_s[0]).squeeze(2)
-                for s in range(1, S):
-                    acc += model.decode(a_s[s], i_s[s]).squeeze(2)
+            elif getattr(model, 'generative_model', 'irt') != 'irt':
+                # per-term MLP decoders: the S draws summed inside one launch (vibo_decoder_multi_forward's prob_sum, in draw order);
+                # where that is not covered, one decoder launch per draw with the sum kept on the device
+                acc = model.decoder.multi_prob_sum(a_s, i_s)
+                if acc is None:
+                    acc = model.decode(a_s[0], i_s[0]).squeeze(2)
+                    for s in range(1, S):
+                        acc += model.decode(a_s[s], i_s[s]).squeeze(2)
                 means.append((acc / S).cpu())
             else:        # one kernel: mean over the S draws, no [S,B,I] intermediate (vibo_decode_mean)
                 means.append(ops.decode_probs_mean(model.spec, a_s, i_s).cpu())
