@@ -350,8 +350,13 @@ int vibo_train_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, c
  *       eps == NULL: the kernel draws eps[b][a] = entry b * A + a of vibo_fill_normal's stream ability_stream_id of `seed`
  *                    at counter step_count[1] -- the values vibo_fill_normal(eps, B * A, seed, step_count + 1,
  *                    ability_stream_id) would leave in memory, bit for bit (row b = minibatch position, row_index or not);
- *       ability_mu == ability_logvar == NULL: the posterior's mean / log-variance are not written (`ability` still is).
- *     The same NULLs are accepted by vibo_elbo_fwd_bwd_step (ability_mu / ability_logvar) there; elsewhere they return -5.
+ *       ability_mu == ability_logvar == NULL: the posterior's mean / log-variance are not written;
+ *       ability == NULL: nor is the sample (32 MB per 1M x 8 call that nothing on the device reads).  It can be rebuilt later:
+ *                    vibo_fill_normal at the step's counter, then vibo_elbo_fwd_bwd with that eps, the same rows and the table
+ *                    the step ran on returns it bit for bit (vibo_train_epilogue_fused keeps that table, see below).
+ *                    Not for fp32 rows gathered through row_index at fewer than 897 items (under 8 waves per workgroup: that
+ *                    kernel variant measured slower with the choice than with the store): -5 there, pass the buffer.
+ *     The same NULLs are accepted by vibo_elbo_fwd_bwd_step there; elsewhere, and at every other entry point, they return -5.
  *     A step that draws its own noise needs no eps_ability fill from the epilogue before it: pass eps_ability = NULL,
  *     n_eps_ability = 0 to vibo_train_epilogue_fused (no noise blocks) and skip the fill in front of vibo_train_prime.
  * vibo_train_epilogue_fused = [finalize] + vibo_train_epilogue for THIS step + vibo_train_prologue_noise for the NEXT one.
@@ -364,6 +369,10 @@ int vibo_train_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, c
  *     vibo_train_prologue_noise would draw), item_feat / the next half of kl_parts / table / saved_h are recomputed --
  *     the same statements in the same order as vibo_train_prologue: the two forms of the step agree bit for bit.
  *     kl_parts: [2][ceil(I*D/64)] floats, double-buffered by the parity of step_count[0].  step_count[1] += 1.
+ *     table: [2][2][2A] floats HERE.  [0] is the expert table as everywhere else ([2][2A]: read by the step's ELBO launch, replaced by
+ *     the next step's); [1] receives the table THIS step ran on before [0] is replaced, and nothing else writes it.  Together
+ *     with step_count[1] - 1 (the counter the step's noise was drawn at) it is what rebuilds the step's ability sample until
+ *     the next epilogue runs.  The sample does not depend on the item sample, which is not kept.
  * vibo_train_prime = the head of the FIRST folded step (and of the first one after the parameters were changed from
  *     outside): vibo_train_prologue without the tick, writing the kl_parts half the coming step reads.  The caller fills
  *     eps_item / eps_ability with vibo_fill_normal(step_count + 1) before it.

@@ -352,13 +352,12 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     const int num_cu = device_cus();
     int rc = check_desc(d);
     if (rc) return rc;
-    if ((!a.response && d->mask_dtype != VIBO_MASK_CODES) || !a.table || !a.item || !a.out_scalars || !a.ability)
+    if ((!a.response && d->mask_dtype != VIBO_MASK_CODES) || !a.table || !a.item || !a.out_scalars)
         return fail(-5, "null required pointer");
-    // (null eps / ability_mu / ability_logvar: the folded step on the matrix kernel only, checked once the plan is known)
-    const bool own_post = a.eps && a.ability_mu && a.ability_logvar;
+    // (null eps / ability_mu / ability_logvar / ability: the folded step on the matrix kernel only, checked once the plan is known)
+    const bool own_post = a.eps && a.ability_mu && a.ability_logvar && a.ability;
     if (!own_post && !a.step_count) return fail(-5, "null required pointer");
-    if ((a.ability_mu == nullptr) != (a.ability_logvar == nullptr)) return fail(-5, "ability_mu / ability_logvar: both or neither");
-    if ((rc = require_rows(d, a.response, a.mask)) != 0) return rc;
+    if ((a.ability_mu == nullptr) != (a.ability_logvar == nullptr)) return fail(-5, "ability_mu / ability_logvar: both or neither");    if ((rc = require_rows(d, a.response, a.mask)) != 0) return rc;
     if (d->want_grad && (!a.grad_table || !a.grad_item)) return fail(-5, "want_grad needs grad_table and grad_item");
     if (d->n_flows > 0 && (!a.flow || !a.ability_k || !a.ability_ladj)) return fail(-5, "flows need flow, ability_k, ability_ladj");
     if (d->n_flows > 0 && d->want_grad && !a.grad_flow) return fail(-5, "want_grad with flows needs grad_flow");
@@ -378,8 +377,11 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
         return fail(-8, "vibo_elbo_fwd_bwd_step: single-launch row-split calls of the plain model only (unconditional posterior, no "
                         "flows, KL regulariser, gradients, 4..1024 items, aligned rows): use vibo_train_prologue + vibo_elbo_fwd_bwd");
     if (!own_post && !step_draws_noise(d, pl))
-        return fail(-5, "null eps / ability_mu / ability_logvar: only where the folded step runs the matrix kernel "
+        return fail(-5, "null eps / ability_mu / ability_logvar / ability: only where the folded step runs the matrix kernel "
                         "(vibo_train_step_draws_noise)");
+    // (msplit_kernel's kSampleOptional: the <fp32 rows gathered, fewer than 8 waves> instantiations store the sample unconditionally)
+    if (!a.ability && a.row_index && d->mask_dtype != VIBO_MASK_CODES && (d->num_item + 127) / 128 < 8)
+        return fail(-5, "null ability: not for fp32 rows gathered through row_index at fewer than 897 items");
     if (path == Path::General) return run_general(d, pl, a, num_cu);
 
     ElboParams p = elbo_params(d, pl, a, vec);

@@ -948,7 +948,11 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 __builtin_nontemporal_store(amu, p.ability_mu + o);
                 __builtin_nontemporal_store(alv, p.ability_logvar + o);
             }
-            __builtin_nontemporal_store(th0, p.ability + o);
+            // (... nor a sample where it draws its own noise: 32 MB per 1M x 8 launch, rebuilt on demand from the same table and
+            //  draws.  Gathered fp32 rows at fewer than 8 waves always store: with the branch that instantiation ran 1.5-4 % slower,
+            //  profiles/r12_lazy_sample.txt; the host refuses the NULL there)
+            constexpr bool kSampleOptional = kDraw && (NW8 || RM != 1);
+            if (!kSampleOptional || p.ability) __builtin_nontemporal_store(th0, p.ability + o);
             if constexpr (FLOWS) {
                 p.ability_k[o] = thv;
                 if (ed == 0) {

@@ -138,7 +138,7 @@ struct EpiParams {
     int nblk;
     PartialLayout lay;
     float* item_feat;         // out: the next step's item sample
-    float* table;             // out: the next step's expert table
+    float* table;             // [2][2][O]: in = the expert table this step ran on, kept in the second half; out = the next step's
     uint32_t seed_lo, seed_hi;
     float* eps_ab;            // out: the next step's ability noise [n_ab]
     long long n_ab;

@@ -90,6 +90,7 @@ __global__ __launch_bounds__(kEpiThreads) void train_epilogue_kernel(int H, int 
 //     step_count[0] = what the next step's prologue would read from step_count[1]) and forms the next item sample and KL
 //     term (kl_parts is double-buffered by step parity: this step's half is still being read by block 0); block 0, after
 //     Adam, runs the 2-row MLP forward on the NEW parameters (table, saved_h); the blocks past the item blocks fill eps_ab.
+//   * the table this step ran on stays behind the new one (e.table + 2 O): 16-64 floats, see block 0.
 constexpr int kEpiOut = 64, kEpiSlices = kEpiThreads / kEpiOut;
 constexpr int kEpiStageHidden = 64;
 constexpr int kEpiStageFloats = 3 * kEpiStageHidden + (kEpiStageHidden + 2 * VIBO_MAX_ABILITY_DIM_WIDE) * (kEpiStageHidden + 1) + 2 * VIBO_MAX_ABILITY_DIM_WIDE;
@@ -127,6 +128,10 @@ __global__ __launch_bounds__(kEpiThreads) void train_epilogue_fused_kernel(const
         const MlpOffsets ow = staged ? mlp_offsets(H, e.O, H + 1) : og;
         float pv[kEpiU], mv[kEpiU], vv[kEpiU];
         epi_mlp_prefetch(og.total, e.P, e.M, e.V, pv, mv, vv, tid);
+        // the expert table THIS step ran on is kept behind the next one's (thread t writes the new table[t] below, after this read):
+        // with it, the rows and the step's noise counter a caller can rebuild the step's ability sample, which the ELBO kernel
+        // no longer stores where it draws its own noise
+        if (tid < n_table) e.table[n_table + tid] = e.table[tid];
         const float* scp = e.flat_in;
         const float* gtp = e.flat_in + VIBO_NUM_SCALARS;
         if (e.partial) {

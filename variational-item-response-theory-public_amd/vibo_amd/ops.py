@@ -12,8 +12,8 @@ import contextlib
 import ctypes
 import math
 import weakref
-from dataclasses import dataclass
-from typing import Optional
+from dataclasses import dataclass, field
+from typing import Callable, Optional
 
 import torch
 
@@ -63,10 +63,13 @@ class RawElbo:
     table_shape: tuple
     ability_mu: Optional[torch.Tensor]      # (None: the folded train step that draws its own noise)
     ability_logvar: Optional[torch.Tensor]
-    ability: torch.Tensor
+    ability: Optional[torch.Tensor] = field(repr=False, compare=False)      # (a property, below: where the call stored no sample, reading it asks `ability_source`)
     ability_k: Optional[torch.Tensor]
     ability_ladj: Optional[torch.Tensor]
     workspace: Optional[torch.Tensor] = None      # folded train step: the partial records vibo_train_epilogue_fused sums
+    # The folded train step that draws its own noise stores no sample (ability None): its trainer hangs the rebuild here, a
+    # callable -> [B, A] tensor that raises once the step's table and noise counter are gone (trainer._StepSample)
+    ability_source: Optional[Callable[[], torch.Tensor]] = field(default=None, repr=False, compare=False)
 
     @property
     def scalars(self):
@@ -83,6 +86,16 @@ class RawElbo:
     def grad_flow(self, s):
         o = _lib.NUM_SCALARS + 2 * self.n_table + self.n_item + s * self.n_flow
         return self.flat[o:o + self.n_flow]
+
+
+def _stored_or_rebuilt_ability(self):
+    if self._ability is None and self.ability_source is not None:
+        return self.ability_source()
+    return self._ability
+
+
+# (the dataclass field stays, so RawElbo(ability=...) is what it was; the stored tensor lives in `_ability`)
+RawElbo.ability = property(_stored_or_rebuilt_ability, lambda self, value: setattr(self, '_ability', value))
 
 
 def _ptr(t):
@@ -470,11 +483,13 @@ def _resident_row_counts(spec, response, mask, mask_code, row_index, num_person,
 def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, eps, flow, reg_mode,
                      want_grad, num_person, train_step=None):
     """Single call into vibo_elbo_fwd_bwd on the current stream.
-    train_step = (step_count tensor, skip_finalize[, (seed, stream) | None]): vibo_elbo_fwd_bwd_step instead -- the same call that
+    train_step = (step_count tensor, skip_finalize[, (seed, stream) | None[, no_sample]]): vibo_elbo_fwd_bwd_step instead -- the same call that
     also ticks Adam's step counter (the folded train step, trainer.FusedTrainer); with skip_finalize the partial records stay in
     RawElbo.workspace for vibo_train_epilogue_fused and `flat` is filled by that call.  With (seed, stream) (where
     vibo_train_step_draws_noise says so; eps None) the kernel draws the ability noise of Philox stream `stream` at counter
-    step_count[1] itself and writes no posterior mean / log-variance: RawElbo.ability_mu / ability_logvar are None."""
+    step_count[1] itself and writes no posterior mean / log-variance: RawElbo.ability_mu / ability_logvar are None.  With no_sample
+    it writes no sample either (ability = NULL): no [B, A] buffer is allocated and the stored `ability` is None -- the caller sets
+    RawElbo.ability_source, which rebuilds it when read (trainer._StepSample)."""
     lib = _lib.load()
     _require_device(response, mask, table, item, eps)
     dev = response.device
@@ -485,7 +500,9 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     n_table, n_item, n_flow = math.prod(table_shape), I * D, spec.n_flows * (2 * A + 1)
     flat = torch.empty(_lib.NUM_SCALARS + 2 * n_table + n_item + 2 * n_flow, dtype=torch.float32, device=dev)
     own_noise = train_step is not None and len(train_step) > 2 and train_step[2] is not None
-    post = torch.empty(1 if own_noise else 3, B, A, dtype=torch.float32, device=dev)
+    no_sample = own_noise and len(train_step) > 3 and bool(train_step[3])
+    # posterior mean | log-variance | sample: the drawing step writes the sample alone, or nothing
+    post = None if no_sample else torch.empty(1 if own_noise else 3, B, A, dtype=torch.float32, device=dev)
     ability_k = torch.empty(B, A, dtype=torch.float32, device=dev) if spec.n_flows else None
     ladj = torch.empty(B, dtype=torch.float32, device=dev) if spec.n_flows else None
     d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, want_grad)
@@ -502,7 +519,7 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     if own_noise:
         name = 'vibo_elbo_fwd_bwd_step_noise'
         args = (_ptr(train_step[0]), 1 if train_step[1] else 0, *rows, _ptr(table), _ptr(item), None, ctypes.c_uint64(train_step[2][0]),
-                ctypes.c_uint32(train_step[2][1]), vp(fbase), None, None, _ptr(post[0]), *grads, *tail)
+                ctypes.c_uint32(train_step[2][1]), vp(fbase), None, None, None if no_sample else _ptr(post[0]), *grads, *tail)
     elif train_step is not None:
         name = 'vibo_elbo_fwd_bwd_step'
         args = (_ptr(train_step[0]), 1 if train_step[1] else 0, *rows, _ptr(table), _ptr(item), _ptr(eps), vp(fbase), _ptr(post[0]),
@@ -515,7 +532,8 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
                 vp(fbase + 4 * (o_item + n_item)) if n_flow else vp(0), *tail)
     _call(name, ctypes.byref(d), *args)
     raw = RawElbo(flat=flat, n_table=n_table, n_item=n_item, n_flow=n_flow, table_shape=table_shape,
-                  ability_mu=None if own_noise else post[0], ability_logvar=None if own_noise else post[1], ability=post[-1],
+                  ability_mu=None if own_noise else post[0], ability_logvar=None if own_noise else post[1],
+                  ability=None if no_sample else post[-1],
                   ability_k=ability_k, ability_ladj=ladj)
     if train_step is not None and train_step[1]:
         raw.workspace = ws          # (kept alive until the epilogue has summed the partial records)

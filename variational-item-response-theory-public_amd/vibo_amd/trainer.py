@@ -7,11 +7,14 @@ reference loop (vibo.py:243-268) as TWO kernel launches instead of ~80.
 What runs (the folded step, `fold=True` with rng='native', the default of the CLI and the benchmark):
     vibo_elbo_fwd_bwd_step     the fused ELBO forward + backward over the rows (ticks Adam's step counter); on the matrix
                                row-split kernel it draws the ability noise itself (vibo_elbo_fwd_bwd_step_noise) and leaves
-                               the posterior's mean / log-variance unwritten: `trainer.last.ability_mu` / `.ability_logvar`
-                               are None there, `trainer.last.ability` (the sample) and `.flat` are what they always were
+                               the posterior's mean / log-variance and the sample unwritten: `trainer.last.ability_mu` /
+                               `.ability_logvar` are None there, `.flat` is what it always was, and `trainer.last.ability` is
+                               rebuilt when read (_StepSample: two extra launches, the same values bit for bit; valid until the
+                               next update(), raises afterwards and under capture) -- nothing is materialised otherwise
     [person-sharded: finalize inside that call, then ONE all-reduce of the flat buffer]
     vibo_train_epilogue_fused  finalize (one GPU), loss, encoder-MLP / item backward, Adam -- and the NEXT step's head: Philox
                                noise, item sample, item KL, the 2-row encoder table from the parameters just updated
+                               (the table this step ran on is kept behind it: `trainer.table_prev`)
 The step is software-pipelined across its own iterations: when the ELBO kernel starts, everything it reads is in memory.  The
 first step's head comes from vibo_fill_normal x 2 + vibo_train_prime ("priming"), repeated whenever the parameters were
 changed from outside between two steps (load_state_dict, optimizers, `.copy_`: detected through the tensors' version
@@ -247,6 +250,48 @@ class _FusedStep:
         return self._update(*self._pending)
 
 
+class _StepSample:
+    """`trainer.last.ability` of a folded step that drew its own noise: the kernel stored no sample, this rebuilds it when asked
+    -- vibo_fill_normal at the step's noise counter, then vibo_elbo_fwd_bwd (the same kernel, given noise) on the step's rows with
+    the expert table the step ran on; its `ability` is the step's, bit for bit (tests/test_gpu_step_noise.py, test_gpu_noise.py:
+    a given-noise call returns the drawing call's sample; the sample does not depend on the item sample, so today's serves).
+    The table is in `trainer.table` until the step's update() has run and in `trainer.table_prev` from then until the next
+    update(); the counter is step_count[1], less one once the update has ticked it.  Afterwards -- and while the stream is
+    capturing -- the call raises.  An eager step's sample is cached; a step captured into a hipGraph is rebuilt on every read, from
+    what the last replay left (read it before an eager step or another graph moves the trainer on: replays are not seen here)."""
+
+    def __init__(self, trainer, rows, B, ab_stream):
+        self.trainer, self.rows, self.B, self.ab_stream = trainer, rows, B, ab_stream
+        self.flags = ops.DESC_FLAGS           # (the rebuild has to run the kernel the step ran)
+        self.captured = rows[0].is_cuda and torch.cuda.is_current_stream_capturing()
+        self.sample = None
+
+    def __call__(self):
+        if self.sample is not None:
+            return self.sample
+        tr = self.trainer
+        if tr._head_of is self:
+            table, ticked = tr.table, 0
+        elif tr._kept_of is self:
+            table, ticked = tr.table_prev, 1
+        else:
+            raise RuntimeError('FusedTrainer: this step stored no ability sample (it drew its own noise), and a later step has replaced '
+                               'the expert table it would be rebuilt from: read `last.ability` before the next update()')
+        response, mask, code, row_index = self.rows
+        if response.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('FusedTrainer: `last.ability` of a step that drew its own noise is rebuilt by two extra launches, which '
+                               'do not belong in a captured step: read it after the capture')
+        counter = tr._steps[1:2] - 1 if ticked else tr._steps[1:2]
+        eps = torch.empty(self.B, tr.model.ability_dim, device=tr.table.device)
+        ops._call('vibo_fill_normal', ops._ptr(eps), eps.numel(), tr.seed, ops._ptr(counter), self.ab_stream, ops._stream(eps.device))
+        with ops.desc_flags(self.flags):
+            sample = ops._BACKEND['elbo'](tr.model.spec, response, mask, code, row_index, table, tr.item_feat, eps, None, _lib.REG_KL,
+                                          True, self.B).ability
+        if not self.captured:
+            self.sample, self.rows = sample, None
+        return sample
+
+
 class FusedTrainer(_FusedStep):
     def __new__(cls, model=None, *args, **kwargs):
         # one entry point: the class the coverage table names is built and returned (not an instance of this one: no second __init__)
@@ -270,7 +315,11 @@ class FusedTrainer(_FusedStep):
         self.mlp_flat, self.mlp_m, self.mlp_v = self._flatten(plist)      # W0 | b0 | W1 | b1 | W2 | b2
         self._watched = plist + [self.mlp_flat, self.item_mu, self.item_lv]
         dev, n_item = self.item_mu.device, self.item_mu.numel()
-        self.table = torch.empty(2, 2 * model.ability_dim, device=dev)
+        # the expert table, and behind it in the same allocation the one the last folded step ran on (vibo_train_epilogue_fused
+        # keeps it there before it writes the next): what a step that stored no sample is rebuilt from (_StepSample)
+        self.table, self.table_prev = torch.empty(2, 2, 2 * model.ability_dim, device=dev).unbind(0)
+        self._head_of = None                  # the open folded step's _StepSample: `table` is still the table it ran on
+        self._kept_of = None                  # the last finished folded step's: `table_prev` is, and step_count[1] - 1 its noise counter
         self.saved_h = torch.empty(4 * self.hidden, device=dev)
         self.kl_parts = torch.empty(2 * ((n_item + 63) // 64), device=dev)      # (two halves: the folded step double-buffers them)
         self.fused_noise = bool(fused_noise)      # rng='native': draw the noise inside the prologue launch (2 launches fewer)
@@ -285,6 +334,7 @@ class FusedTrainer(_FusedStep):
         # ---- the four-launch form ----
         eps_item, eps_ab, native = self._choose_noise(B, response.device, eps_item, eps_ability)
         self._primed_for = None               # (these draws move on without refilling the folded step's buffers)
+        self._head_of = None                  # (... and the prologue replaces the table of a folded step left open)
         prologue = (ctypes.byref(d), self.hidden, p(self.mlp_flat), p(self.item_mu), p(self.item_lv), p(eps_item), p(self.item_feat),
                     p(self.table), p(self.saved_h), p(self.kl_parts), p(self._steps))
         if native and self.fused_noise:       # noise drawn inside the prologue launch
@@ -352,8 +402,12 @@ class FusedTrainer(_FusedStep):
         if self._draw_mode and not draws:
             ops._call('vibo_fill_normal', p(eps_ab), need, self.seed, noise_step, ab_stream, stream)
         fused_finalize = bool(step_bits & 2) and model._reducer is None
+        # A drawing step stores no sample: `raw.ability` rebuilds it on demand, from the rows this call was handed.  (The library's one
+        # exception, include/vibo_hip.h: fp32 rows gathered through row_index at fewer than 897 items keep the store.)
+        lazy = draws and not (row_index is not None and code != _lib.MASK_CODES and response.shape[1] <= 896)
         raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, None if draws else eps_ab, None,
-                                   _lib.REG_KL, True, B, train_step=(self._steps, fused_finalize, (self.seed, ab_stream) if draws else None))
+                                   _lib.REG_KL, True, B, train_step=(self._steps, fused_finalize, (self.seed, ab_stream) if draws else None, lazy))
+        raw.ability_source = self._head_of = _StepSample(self, (response, mask, code, row_index), B, ab_stream) if lazy else None
         self._pending = (d, eps_item, raw, ab_stream)
         self._folded_open = True
         self.last = raw
@@ -362,6 +416,7 @@ class FusedTrainer(_FusedStep):
     def _update(self, d, eps_item, raw, folded_stream):
         p = ops._ptr
         stream = ops._stream(raw.flat.device)
+        self._kept_of, self._head_of = raw.ability_source if folded_stream is not None else None, None
         if folded_stream is not None:
             self._folded_open = False
             ops._call('vibo_train_epilogue_fused', ctypes.byref(d), self.hidden, p(raw.workspace), p(raw.flat), p(self.saved_h),
