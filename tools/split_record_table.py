@@ -5,6 +5,9 @@
 
     VIBO_TOL_RECORD=record.jsonl python -m pytest tests/test_gpu_narrow_cells.py -q -m gpu
     python tools/split_record_table.py record.jsonl narrow_cells > profiles/narrow_cells_record.txt
+
+    VIBO_TOL_RECORD=record.jsonl python -m pytest tests/test_gpu_fallback_cells.py -q -m gpu
+    python tools/split_record_table.py record.jsonl fallback_cells > profiles/fallback_cells_record.txt
 """
 import collections
 import json
@@ -59,7 +62,33 @@ def narrow_cells(recs):
         print()
 
 
-KINDS = {'split_worst_case': split_worst_case, 'narrow_cells': narrow_cells}
+def fallback_cells(recs):
+    parts = ('edges', 'encode', 'trips', 'dense')
+    worst, trips = collections.defaultdict(float), {}
+    for r in recs:
+        worst[(r['part'], r['kernel'], r['observable'])] = max(worst[(r['part'], r['kernel'], r['observable'])], r['ratio'])
+        if r['part'] not in ('edges', 'encode'):
+            trips[r['case']] = r['trips']
+    kernels = ('tiled', 'wave-per-row', 'wave-per-person')
+    obs = sorted({k[2] for k in worst})
+    print(f'Worst error / a-priori bound per part, kernel and observable ({len(recs)} records of tests/test_gpu_fallback_cells.py on one MI355X;')
+    print('bounds: oracle/fallback_model.py).  edges: one trip, every waves / chunk / LDS boundary; trips: every workgroup or wave takes')
+    print('two trips or more through its persistent loop, one observer per item, at the first trip, a later one and the ragged end;')
+    print('dense: 30 % missing, summed bounds with the counted chain; encode: encode_kernel through ops.encode_posterior on the edge rows,')
+    print('against its own bound and against the ELBO launch within the summed bounds.  S_NOBS is exact or the ratio is infinite.')
+    print()
+    for part in parts:
+        print(f'{part:22s} ' + ' '.join(f'{k:>16s}' for k in kernels))
+        for o in obs:
+            if any((part, k, o) in worst for k in kernels):
+                print(f'  {o:22s} ' + ' '.join(f'{worst[(part, k, o)]:16.3f}' if (part, k, o) in worst else f'{"-":>16s}' for k in kernels))
+        print()
+    print('Trips per workgroup (tiled) or wave of the multi-trip launches, (fewest, most), from the geometry functions:')
+    for cid in sorted(trips):
+        print(f'  {cid:70s} {tuple(trips[cid])}')
+
+
+KINDS = {'split_worst_case': split_worst_case, 'narrow_cells': narrow_cells, 'fallback_cells': fallback_cells}
 
 
 def main(path, kind='split_worst_case'):

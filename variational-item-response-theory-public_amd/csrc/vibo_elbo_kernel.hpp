@@ -38,6 +38,7 @@ typedef float float4v __attribute__((ext_vector_type(4)));
 
 struct PersonDim {
     float lam, inv_lam, amu, sig, eps, n0, n1;
+    float theta0;      // the sample amu + sig * eps
 };
 
 // ---------------------------------------------------------------------------
@@ -180,6 +181,7 @@ __device__ __forceinline__ PersonDim person_dim(const ElboParams& p, const float
     d.amu = s * d.inv_lam;
     d.sig = fast_rsq(lam);
     d.eps = eps;
+    d.theta0 = fmaf(d.sig, eps, d.amu);
     return d;
 }
 
@@ -268,7 +270,7 @@ __global__ __launch_bounds__(NW * 64, 4) void elbo_kernel(const ElboParams p) {
                 float th = 0.f;
                 if (a < Ar && valid) {
                     const PersonDim d = person_dim<A>(p, ctab, cnt, epsv[k], a);
-                    th = d.amu + d.sig * d.eps;
+                    th = d.theta0;
                 }
                 share[a * PS + lane] = th;
             }
@@ -468,7 +470,11 @@ __global__ __launch_bounds__(NW * 64, 4) void elbo_kernel(const ElboParams p) {
             if (a < Ar && valid) {
                 const PersonDim d = person_dim<A>(p, ctab, cnt, eps_cur[k], a);
                 const float alv = -kLn2 * fast_log2(d.lam);
-                const float theta0 = d.amu + d.sig * d.eps;
+                // the sample the tile's cells ran on, from the share itself.  A sample recomputed here came out a rounding of the mean
+                // away from the one the logits and d LL / d a used (measured: visible where mean and noise cancel).  Supposed cause, not
+                // read from the ISA: person_dim is inlined here and in make_share, and the compiler is free to contract
+                // `n0 * tau0 + n1 * tau1` and `amu + sig * eps` differently at the two sites
+                const float theta0 = share[a * PS + lane];
                 p.ability_mu[grow * Ar + a] = d.amu;
                 p.ability_logvar[grow * Ar + a] = alv;
                 p.ability[grow * Ar + a] = theta0;
