@@ -50,6 +50,8 @@ enum { VIBO_MASK_U8 = 0,         /* torch.bool / uint8, 1 byte per cell (dataset
                                     (fp32 responses with -1 for missing + a separate mask, datasets.py:928-940).
                                     Row-split paths only: 4..32767 items, code rows 4-byte aligned with a stride that
                                     is a multiple of 4 (cells past num_item are ignored).  Anything else returns -8.  */
+/* (One more row format -- fp32 responses whose sign bit is the mask, no mask stream -- is declared with its two exports in
+   vibo_hip_sign_rows.h beside this header.) */
 enum { VIBO_REG_KL = 0,          /* elbo(use_kl_divergence=True): analytic KL (models.py:427-430) */
        VIBO_REG_SAMPLED = 1 };   /* use_kl_divergence=False / flows: log q - log p at the sample
                                     (models.py:406-424, 432-441)                             */

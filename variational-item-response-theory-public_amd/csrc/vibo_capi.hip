@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include "../../include/vibo_hip.h"
+#include "../../include/vibo_hip_sign_rows.h"
 #include "vibo_cond.hpp"
 #include "vibo_general.hpp"
 #include "vibo_helpers.hpp"
@@ -44,6 +45,7 @@ static hipError_t launch_split(const ElboParams& p, Engine engine, int AT, bool 
             if (p.row_index) return launch_elbo_msplit_fg(p, irt, grad, nw, grid, s);
             return launch_elbo_msplit_fa(p, irt, grad, nw, grid, s);
         }
+        if (p.mask_dtype == VIBO_MASK_SIGN) return launch_elbo_msplit_s(p, irt, grad, nw, grid, s);
         if (codes) return launch_elbo_msplit_c(p, irt, grad, nw, grid, s);
         if (p.row_index) return launch_elbo_msplit_g(p, irt, grad, nw, grid, s);
         return launch_elbo_msplit_a(p, irt, grad, nw, grid, s);
@@ -350,8 +352,11 @@ static int run_finalize(const vibo_desc* d, const Plan& pl, Path path, const Elb
 
 static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     const int num_cu = device_cus();
-    int rc = check_desc(d);
+    int rc = check_desc(d, true);
     if (rc) return rc;
+    const bool sign_rows = d->mask_dtype == VIBO_MASK_SIGN;
+    if (sign_rows && (a.row_index || a.row_counts))
+        return fail(-8, "VIBO_MASK_SIGN rows: rows in order only (row_index must be NULL), without caller-supplied row counts");
     if ((!a.response && d->mask_dtype != VIBO_MASK_CODES) || !a.table || !a.item || !a.out_scalars)
         return fail(-5, "null required pointer");
     // (null eps / ability_mu / ability_logvar / ability: the folded step on the matrix kernel only, checked once the plan is known)
@@ -371,6 +376,8 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     const Path path = resolve_path(pl, d, vec);
     const bool row_split = path == Path::Panels || path == Path::Split;
     if (d->mask_dtype == VIBO_MASK_CODES && !row_split) return codes_unsupported();
+    if (sign_rows && !(path == Path::Split && pl.engine == Engine::Matrix))
+        return fail(-8, "VIBO_MASK_SIGN rows: the response rows must be 16-byte aligned with a stride that is a multiple of 4");
     if (pl.given() && path != Path::Panels)
         return fail(-8, "VIBO_POSTERIOR_GIVEN: rows must be aligned for 4-cell chunks (see vibo_amd.ops.pad_rows)");
     if ((a.step_count || a.skip_finalize) && !(step_plan_ok(d, pl) && path == Path::Split))
@@ -421,7 +428,7 @@ int vibo_plan_cond_passes(const vibo_desc* d) {
 // whose launch later falls back because the caller's rows are not aligned for 16-byte loads (Panels / flows -> the wave-per-person
 // kernel, Split / Row -> the tiled kernel).
 int vibo_plan_kernel(const vibo_desc* d) {
-    int rc = check_desc(d);
+    int rc = check_desc(d, true);
     if (rc) return rc;
     Plan pl;
     rc = make_plan(d, device_cus(), &pl);
@@ -452,7 +459,7 @@ int vibo_insitu_timer_reset(uint64_t* block, void* stream) {
 }
 
 size_t vibo_workspace_bytes(const vibo_desc* d) {
-    if (check_desc(d) != 0) return 0;
+    if (check_desc(d, true) != 0) return 0;
     Plan pl;
     if (make_plan(d, device_cus(), &pl) < 0) return 0;
     const size_t enc = encode_scratch_bytes(d);
@@ -474,6 +481,8 @@ int vibo_elbo_fwd_bwd_counts(const vibo_desc* d, const float* response, const vo
                              float* out_scalars, float* ability_mu, float* ability_logvar, float* ability,
                              float* ability_k, float* ability_ladj, float* grad_table, float* grad_item,
                              float* grad_flow, void* workspace, size_t workspace_bytes, void* stream) {
+    const int rc = check_desc(d);               // (refuses VIBO_MASK_SIGN rows)
+    if (rc) return rc;
     if (!row_counts) return fail(-5, "null row_counts");
     ElboArgs a{response, mask, row_index, table, item, eps, flow, out_scalars, ability_mu, ability_logvar, ability,
                ability_k, ability_ladj, grad_table, grad_item, grad_flow, workspace, workspace_bytes, (hipStream_t)stream};
@@ -481,7 +490,31 @@ int vibo_elbo_fwd_bwd_counts(const vibo_desc* d, const float* response, const vo
     return elbo_fwd_bwd_impl(d, a);
 }
 
-int vibo_train_step_supported(const vibo_desc* d) {
+// (VIBO_MASK_SIGN rows: the two step queries answer for the same descriptor with VIBO_MASK_U8 -- the plan does not look at the code)
+static vibo_desc sign_rows_as_u8(const vibo_desc* d) {
+    vibo_desc u = *d;
+    if (u.mask_dtype == VIBO_MASK_SIGN) u.mask_dtype = VIBO_MASK_U8;
+    return u;
+}
+
+int vibo_sign_rows_supported(const vibo_desc* d) {
+    return (d && d->mask_dtype == VIBO_MASK_SIGN && check_desc(d, true) == 0) ? 1 : 0;
+}
+
+int vibo_rows_sign_is_mask(const vibo_desc* d, const float* response, const void* mask, int32_t* differs, void* stream) {
+    const int rc = check_desc(d);
+    if (rc) return rc;
+    if (d->mask_dtype != VIBO_MASK_U8) return fail(-8, "vibo_rows_sign_is_mask: fp32 rows with a VIBO_MASK_U8 mask");
+    if (!response || !mask || !differs) return fail(-5, "null required pointer");
+    const hipError_t e = launch_sign_is_mask(d, response, mask, rows_vec_ok(d, response, mask), differs, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "rows_sign_is_mask launch");
+    return 0;
+}
+
+int vibo_train_step_supported(const vibo_desc* d_in) {
+    if (!d_in) return 0;
+    const vibo_desc du = sign_rows_as_u8(d_in);
+    const vibo_desc* d = &du;
     if (check_desc(d) != 0) return 0;
     Plan pl;
     if (make_plan(d, device_cus(), &pl) < 0) return 0;
@@ -493,7 +526,10 @@ int vibo_train_step_supported(const vibo_desc* d) {
     return 1 | ((pl.split_nblk < 1024 && n_out > 64) ? 2 : 0);
 }
 
-int vibo_train_step_draws_noise(const vibo_desc* d) {
+int vibo_train_step_draws_noise(const vibo_desc* d_in) {
+    if (!d_in) return 0;
+    const vibo_desc du = sign_rows_as_u8(d_in);
+    const vibo_desc* d = &du;
     if (check_desc(d) != 0) return 0;
     Plan pl;
     if (make_plan(d, device_cus(), &pl) < 0) return 0;

@@ -211,6 +211,49 @@ __global__ __launch_bounds__(256) void pack_codes4_kernel(const float* __restric
 }
 
 // ---------------------------------------------------------------------------
+// vibo_rows_sign_is_mask: is every mask byte 0 or 1, and (mask byte == 1) == (sign bit of the response clear), in every cell of
+// the rows?  (A byte above 1 "differs": the matrix kernel's pack takes the mask bytes as 0 / 1, so only for those do the two
+// formats form the same code words.)  One streaming pass; a thread that meets a cell where it does not hold stores 1 (every
+// writer the same value: a plain store)
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void sign_is_mask4_kernel(const float* __restrict__ response, const uint8_t* __restrict__ mask,
+                                                            long long resp_stride, long long mask_stride, long long B, int I,
+                                                            int32_t* __restrict__ differs) {
+    const int n4 = (I + 3) >> 2;
+    const long long n = B * n4;
+    bool bad = false;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const long long row = e / n4;
+        const int c = (int)(e - row * n4);
+        const float4 x = reinterpret_cast<const float4*>(response + row * resp_stride)[c];
+        const uint32_t m = reinterpret_cast<const uint32_t*>(mask + row * mask_stride)[c];
+        const uint32_t x0 = __builtin_bit_cast(uint32_t, x.x), x1 = __builtin_bit_cast(uint32_t, x.y);
+        const uint32_t x2 = __builtin_bit_cast(uint32_t, x.z), x3 = __builtin_bit_cast(uint32_t, x.w);
+        const uint32_t top = __builtin_amdgcn_perm(x1, x0, 0x0c0c0703u) | __builtin_amdgcn_perm(x3, x2, 0x07030c0cu);
+        // bit 0 of a byte: mask bit against [sign clear]; bits 1..7: a mask byte above 1
+        uint32_t diff = ((m ^ ~(top >> 7)) & 0x01010101u) | (m & 0xFEFEFEFEu);
+        if ((I & 3) && c == (I >> 2)) diff &= (1u << (8 * (I & 3))) - 1u;      // (the row padding is not looked at)
+        bad = bad || diff != 0u;
+    }
+    if (bad) *differs = 1;
+}
+// (rows that cannot be read in aligned 4-cell chunks: one cell per thread)
+__global__ __launch_bounds__(256) void sign_is_mask_kernel(const float* __restrict__ response, const uint8_t* __restrict__ mask,
+                                                           long long resp_stride, long long mask_stride, long long B, int I,
+                                                           int32_t* __restrict__ differs) {
+    const long long n = B * I;
+    bool bad = false;
+    for (long long e = (long long)blockIdx.x * 256 + threadIdx.x; e < n; e += (long long)gridDim.x * 256) {
+        const long long row = e / I;
+        const int i = (int)(e - row * I);
+        const bool sign_clear = (__builtin_bit_cast(uint32_t, response[row * resp_stride + i]) >> 31) == 0u;
+        const uint8_t mb = mask[row * mask_stride + i];
+        bad = bad || mb > 1 || (mb == 1) != sign_clear;
+    }
+    if (bad) *differs = 1;
+}
+
+// ---------------------------------------------------------------------------
 // finalize: fixed-order sum of the per-block partial records (fp64 accumulate)
 // ---------------------------------------------------------------------------
 // 1024 threads = OUT outputs x (1024 / OUT) slices of the block list; OUT = 64 normally, 16 when there are many small
@@ -564,6 +607,18 @@ hipError_t launch_pack_codes(const vibo_desc* d, const float* response, const vo
     if (grid > 65536) grid = 65536;
     hipLaunchKernelGGL(pack_codes_kernel, dim3((unsigned)grid), dim3(256), 0, s, response, mask, codes, (long long)d->response_row_stride,
                        (long long)d->mask_row_stride, codes_row_stride, (long long)d->num_person, d->num_item, d->mask_dtype);
+    return hipGetLastError();
+}
+
+hipError_t launch_sign_is_mask(const vibo_desc* d, const float* response, const void* mask, bool chunks, int32_t* differs, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(differs, 0, sizeof(int32_t), s);
+    if (e != hipSuccess) return e;
+    const long long n = (long long)d->num_person * (chunks ? (d->num_item + 3) / 4 : d->num_item);
+    long long grid = (n + 255) / 256;
+    if (grid > 65536) grid = 65536;
+    hipLaunchKernelGGL(chunks ? sign_is_mask4_kernel : sign_is_mask_kernel, dim3((unsigned)grid), dim3(256), 0, s, response,
+                       static_cast<const uint8_t*>(mask), (long long)d->response_row_stride, (long long)d->mask_row_stride,
+                       (long long)d->num_person, d->num_item, differs);
     return hipGetLastError();
 }
 

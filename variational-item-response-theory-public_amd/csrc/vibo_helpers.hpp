@@ -29,6 +29,8 @@ hipError_t launch_given_post(const float* post, const float* coef, int panels, f
 
 // fp32 rows + mask -> 1-byte cell codes; chunks: 4 cells per thread (aligned rows, codes_row_stride % 4 == 0).
 // row_index (chunks only): the code rows are the minibatch's, in its order
+// vibo_rows_sign_is_mask (chunks: aligned rows, 4 cells per thread)
+hipError_t launch_sign_is_mask(const vibo_desc* d, const float* response, const void* mask, bool chunks, int32_t* differs, hipStream_t s);
 hipError_t launch_pack_codes(const vibo_desc* d, const float* response, const void* mask, uint8_t* codes, long long codes_row_stride,
                              bool chunks, hipStream_t s, const int64_t* row_index = nullptr);
 

@@ -39,6 +39,7 @@ hipError_t launch_elbo_split_c8(const ElboParams& p, int irt, bool grad, int nq,
 // in 4 cells; nw = ceil(I / 128) waves per workgroup; fp32 rows in order / through row_index / 1-byte cell codes
 hipError_t launch_elbo_msplit_a(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s);
 hipError_t launch_elbo_msplit_g(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s);
+hipError_t launch_elbo_msplit_s(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s);      // (VIBO_MASK_SIGN rows)
 hipError_t launch_elbo_msplit_c(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s);
 // ... the same with planar flows on the ability sample
 hipError_t launch_elbo_msplit_fa(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s);

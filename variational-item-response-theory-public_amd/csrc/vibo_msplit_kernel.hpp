@@ -133,7 +133,9 @@ __device__ __forceinline__ half8 cat8(const half2v a, const half2v b, const half
 }
 
 // IRT: 1/2/3PL.  GRAD: also gradients.  RM (row mode): 0 = fp32 responses + mask bytes, rows in order; 1 = the same
-// through p.row_index; 2 = 1-byte cell codes (VIBO_MASK_CODES, through p.mask), with or without p.row_index.
+// through p.row_index; 2 = 1-byte cell codes (VIBO_MASK_CODES, through p.mask), with or without p.row_index; 3 = fp32 responses in
+// order whose sign bit IS the mask (VIBO_MASK_SIGN: no mask stream -- 4 B per cell, two load instructions per quarter instead of
+// four; XM 0 without flows only).
 // FLOWS: planar flows on the ability sample (flows.py:21-66, models.py:342-348) in the (person, dim) lanes.
 // NW8: the workgroup has exactly 8 waves (897..1024 items, the benchmark's width): slot ownership and the sums over the
 // waves' LDS records are compile-time.  XM: which hooks the launch uses (0: none -- those branches do not exist in the code;
@@ -162,6 +164,9 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // order, no spills -- measured 2 % slower with the same pins, so they keep the hoisted addresses.)
     constexpr bool kPinFlowAddr = FLOWS && (IRT == 3 || XM != 0 || RM == 1);
     constexpr bool CODES = RM == 2;
+    constexpr bool SIGN = RM == 3;
+    constexpr bool kMayGather = RM == 1 || RM == 2;       // (the instantiation can meet p.row_index)
+    static_assert(!SIGN || (XM == 0 && !FLOWS), "sign-as-mask rows: the plain model's instantiations only");
     constexpr int R = kMsRows;
     constexpr float kLoS = kLogitLo * kLog2e, kHiS = kLogitHi * kLog2e;
     // fp8 (e4m3) look-up tables of the pack.  fp32 rows: selector {missing, wrong, -, right}; cell codes: {wrong, right, missing}.
@@ -221,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // waited a memory round trip for them at the top of the loop (gathered rows: +22 % on fp32 rows, +60 % on cell codes).
     int ridx[8], ridx_n[8];
     auto fetch_idx = [&](const int bt, int (&dst)[8]) __attribute__((always_inline)) {
-        if constexpr (RM != 0) {
+        if constexpr (kMayGather) {
             if (!p.row_index) return;
             const int row0 = bt * R;
 #pragma unroll
@@ -242,6 +247,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // resource has no records (its loads return zeros) and the cells are switched on when they are packed (`fillw`).
     // Gathered rows compute their addresses at the load.  Chunks past the row's end read its last chunk; both cases are
     // masked when the cells are packed.
+    // Sign rows (RM 3) load the responses alone: `m` / `m2` are never written or read there (no registers, no load slots), and
+    // the pack takes the observed word from the responses' sign bits.
     // (Round 6 measured the lane's two chunks ADJACENT -- 2 i16 and 2 i16 + 1, the two mask words one 8-byte load: 24 load
     //  instructions per batch instead of 32, 8 instead of 16 on cell codes.  Cell codes 670 -> 657 us per 1M x 1k, but fp32 rows
     //  942-957 -> 972 us: every 16-byte response load then covers 512 bytes of a row at half density.  Not adopted.)
@@ -266,22 +273,26 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             const unsigned bc = (rows > 0 && p.codes_out) ? (unsigned)(rows - 1) * cstride + 4u * n4 : 0u;
             rs.c = __builtin_amdgcn_make_buffer_rsrc(p.codes_out + (size_t)bt * R * p.codes_stride, (short)0, (int)bc, 0x00020000);
         }
-        rs.m = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(static_cast<const uint8_t*>(p.mask) + (size_t)bt * R * p.mask_stride + item0),
-                                                 (short)0, (int)bm, 0x00020000);
+        if constexpr (!SIGN)
+            rs.m = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(static_cast<const uint8_t*>(p.mask) + (size_t)bt * R * p.mask_stride + item0),
+                                                     (short)0, (int)bm, 0x00020000);
         if constexpr (!CODES) rs.r = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.response + (size_t)bt * R * p.resp_stride + item0),
                                                                        (short)0, (int)br, 0x00020000);
         else rs.r = rs.m;
+        if constexpr (SIGN) rs.m = rs.r;              // (no mask resource: nothing is loaded through it)
         if constexpr (!(XFUSE && GRAD)) rs.c = rs.m;
         return rs;
     };
     // quarter (h, j) = person 4 h + j of the lane (row 4 g + j + 16 h of the batch), both chunks: 2 x 16 B + 2 x 4 B
     auto load_quarter = [&](const int bt, const RowSrc& rs, const int h, const int j, float4 (&x)[CODES ? 1 : 8], uint32_t (&m)[8]) __attribute__((always_inline)) {
-        bool linear = RM == 0;
+        bool linear = RM == 0 || SIGN;
         if constexpr (RM == 2) linear = p.row_index == nullptr;
         if (linear) {
-            const int mso = (j + 16 * h) * (int)mstride;
-            m[2 * j] = __builtin_amdgcn_raw_buffer_load_b32(rs.m, mvo0, mso, 0);
-            m[2 * j + 1] = __builtin_amdgcn_raw_buffer_load_b32(rs.m, mvo1, mso, 0);
+            if constexpr (!SIGN) {
+                const int mso = (j + 16 * h) * (int)mstride;
+                m[2 * j] = __builtin_amdgcn_raw_buffer_load_b32(rs.m, mvo0, mso, 0);
+                m[2 * j + 1] = __builtin_amdgcn_raw_buffer_load_b32(rs.m, mvo1, mso, 0);
+            }
             if constexpr (!CODES) {
                 const int so = (j + 16 * h) * (int)rstride4;
                 x[2 * j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(rs.r, rvo0, so, 0));
@@ -674,7 +685,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     const uint32_t tm1 = (32 * q + 16 + i16) >= n4 ? 0u : ((I & 3) && (32 * q + 16 + i16) == (I >> 2)) ? tm_tail : 0xFFFFFFFFu;
     // Rows past the matrix' end (last batch only): in-order rows with a mask read zeros there (the resource's record
     // limit) and need nothing; gathered rows, rows without a mask and cell codes (0 = an answer) are masked per lane -- in
-    // a variant of the pack of its own, so that the common case carries no selects.
+    // a variant of the pack of its own, so that the common case carries no selects.  (Sign-as-mask rows: a zero there is an OBSERVED
+    // wrong answer, as without a mask.)
     bool need_in = RM != 0 || !have_mask;
     if constexpr (RM == 2) need_in = true;
     // pk[j]: 8-bit fields nobs | nobs of M-tile 1 | n1 | n1 of M-tile 1 of persons j and 4 + j (each <= 8 per lane)
@@ -737,6 +749,9 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 }
             }
             xacc[4 * h + j] = acc;
+        } else if constexpr (SIGN) {
+            cw0[4 * h + j] = pack_codes4_sign_lut(x[2 * j], k0 & 0x01010101u, kLutFp32, nobs, n1);
+            cw1[4 * h + j] = pack_codes4_sign_lut(x[2 * j + 1], k1 & 0x01010101u, kLutFp32, nobs, n1);
         } else {
             cw0[4 * h + j] = pack_codes4_lut(x[2 * j], (m[2 * j] | fillw) & k0, kLutFp32, nobs, n1);
             cw1[4 * h + j] = pack_codes4_lut(x[2 * j + 1], (m[2 * j + 1] | fillw) & k1, kLutFp32, nobs, n1);
@@ -1470,7 +1485,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         if (late) {
             // (a batch of slack: the rows are asked for once the long workgroups' first batches -- rem_wg x the bytes of a batch at
             //  ~5 TB/s, + 1 us of latency -- are through, 6 us at most; ticks of 10 ns)
-            const long long batch_bytes = (long long)R * n4 * (CODES ? 4 : 20);
+            const long long batch_bytes = (long long)R * n4 * (CODES ? 4 : SIGN ? 16 : 20);
             long long wait_ticks = (long long)rem_wg * batch_bytes / 50000 + 100;
             wait_ticks = wait_ticks > 600 ? 600 : wait_ticks;
             while ((long long)(realtime_ticks() - t_wave_start) < wait_ticks) __builtin_amdgcn_s_sleep(8);
@@ -1511,7 +1526,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         sat3 = false;                                 // (3PL: see the tile)
 #pragma unroll
         for (int k = 0; k < 4; ++k) pk[k] = 0;
-        if constexpr (RM != 0) {
+        if constexpr (kMayGather) {
             if (p.row_index) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) ridx[k] = ridx_n[k];      // (requested an iteration ago)
@@ -1560,7 +1575,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         }
         f32x4 da0, da1, db0, db1;
         logits(bopA, da0, da1);
-        if constexpr (RM == 0 && IRT != 3) {
+        if constexpr ((RM == 0 || SIGN) && IRT != 3) {
             // fp32 rows in order, 1PL / 2PL (round 6): the next batch's M-tile 0 quarter j is packed, and its M-tile 1 quarter j requested into the
             // registers that frees, IN FRONT OF tile (0, j) -- four load instructions per tile instead of a burst of sixteen behind
             // tile (0, 3).  The CU's address path takes a load instruction per ~16 cycles: when the eight waves' bursts meet there,
@@ -1572,6 +1587,11 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             // 1.105, forward only 0.970 -> 0.927, wide rows 1.654 -> 1.635.  Also measured: the M-tile 0 requests
             // spread over tiles (1, j) as well -- loads in flight across the loop's back edge -- +-0 against this (885 vs 884,
             // 809 vs 803); the slower wave group (4-7) issuing its M-tile 0 burst behind the first barrier: 863 vs 858, 810 vs 805.
+            // Sign-as-mask rows (RM 3, two load instructions per quarter instead of four) measured both forms as well, whole train step
+            // at 1M x 1k, ability_dim 8, alternated on one box, three runs each: this one 0.7586-0.7636 ms (median 0.7596), the burst
+            // behind tile (0, 3) 0.7602-0.7669 (0.7632); on a second, slower box, five runs each: 0.7723-0.7913 (0.7796) against
+            // 0.7753-0.7966 (0.7890): no difference beyond the spread (profiles/sign_rows_record.txt, section 6), so the mode keeps the
+            // form of the rows it otherwise shares everything with.
             auto side = [&](const int j) __attribute__((always_inline)) {
                 pack_one(nxt, 0, j, cwB0, cwB1, pk, x, m, sn);
                 __builtin_amdgcn_sched_barrier(0);
@@ -1613,7 +1633,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         asm volatile("" : "+v"(epn));                 // (eps is in: nothing is pending at the back edge)
         if constexpr (EXTRA && kPrs) asm volatile("" : "+v"(prs0), "+v"(prs1), "+v"(prs2));
         if constexpr (XCOND && kPrs) asm volatile("" : "+v"(prc));
-        if constexpr (RM != 0) {                      // (nor the row numbers: they were requested before this batch's rows)
+        if constexpr (kMayGather) {                   // (nor the row numbers: they were requested before this batch's rows)
 #pragma unroll
             for (int k = 0; k < 8; ++k) asm volatile("" : "+v"(ridx_n[k]));
         }

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 
+#include "../../include/vibo_hip_sign_rows.h"
 #include "vibo_cond.hpp"
 
 namespace vibo {
@@ -21,7 +22,7 @@ int fail(int code, const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
-int check_desc(const vibo_desc* d) {
+int check_desc(const vibo_desc* d, bool sign_rows) {
     if (!d) return fail(-1, "null descriptor");
     if (d->abi_version != VIBO_ABI_VERSION) return fail(-2, "abi_version %d != %d", d->abi_version, VIBO_ABI_VERSION);
     if (d->num_person < 1) return fail(-3, "num_person must be >= 1");
@@ -37,7 +38,9 @@ int check_desc(const vibo_desc* d) {
         d->posterior != VIBO_POSTERIOR_GIVEN)
         return fail(-3, "bad posterior");
     if (d->missing_mode != VIBO_MISSING_PRIOR && d->missing_mode != VIBO_MISSING_DROP) return fail(-3, "bad missing_mode");
-    if (d->mask_dtype < 0 || d->mask_dtype > VIBO_MASK_CODES) return fail(-3, "bad mask_dtype");
+    if (d->mask_dtype < 0 || d->mask_dtype > VIBO_MASK_SIGN) return fail(-3, "bad mask_dtype");
+    if (d->mask_dtype == VIBO_MASK_SIGN && !sign_rows)
+        return fail(-8, "VIBO_MASK_SIGN rows (the response's sign bit is the mask): taken by vibo_elbo_fwd_bwd and its _step forms only");
     if (d->reg_mode != VIBO_REG_KL && d->reg_mode != VIBO_REG_SAMPLED) return fail(-3, "bad reg_mode");
     if (d->n_flows < 0 || d->n_flows > VIBO_MAX_FLOWS) return fail(-3, "n_flows outside 0..%d", VIBO_MAX_FLOWS);
     if (d->n_flows > 0 && d->reg_mode != VIBO_REG_SAMPLED) return fail(-3, "flows need reg_mode SAMPLED");
@@ -45,7 +48,18 @@ int check_desc(const vibo_desc* d) {
                      VIBO_FLAG_COND_THREE_PASS)) return fail(-3, "unknown flags");
     if ((d->flags & VIBO_FLAG_KERNEL_VALU) && (d->flags & VIBO_FLAG_KERNEL_MATRIX)) return fail(-3, "flags pin two kernels");
     if ((d->flags & VIBO_FLAG_COND_VALU) && (d->flags & VIBO_FLAG_COND_MATRIX)) return fail(-3, "flags pin two forms of the conditional passes");
+    if (d->mask_dtype == VIBO_MASK_SIGN && !sign_rows_ok(d))
+        return fail(-8, "VIBO_MASK_SIGN rows (the response's sign bit is the mask): only calls the planner sends to the single-launch "
+                        "matrix row-split kernel (unconditional posterior, no flows, 4..1024 items, chunkable rows, enough persons or "
+                        "VIBO_FLAG_KERNEL_MATRIX)");
     return 0;
+}
+
+bool sign_rows_ok(const vibo_desc* d) {
+    if (d->posterior != VIBO_POSTERIOR_UNCONDITIONAL || d->n_flows != 0) return false;
+    Plan pl;
+    // (path and engine do not depend on the compute-unit count)
+    return make_plan(d, 256, &pl) == 0 && pl.path == Path::Split && pl.engine == Engine::Matrix;
 }
 
 int codes_unsupported() {
@@ -55,7 +69,8 @@ int codes_unsupported() {
 
 int require_rows(const vibo_desc* d, const float* response, const void* mask) {
     if (!response && d->mask_dtype != VIBO_MASK_CODES) return fail(-5, "null required pointer");
-    if ((d->mask_dtype == VIBO_MASK_NONE) != (mask == nullptr)) return fail(-5, "mask pointer / mask_dtype mismatch");
+    const bool no_mask = d->mask_dtype == VIBO_MASK_NONE || d->mask_dtype == VIBO_MASK_SIGN;
+    if (no_mask != (mask == nullptr)) return fail(-5, "mask pointer / mask_dtype mismatch");
     return 0;
 }
 

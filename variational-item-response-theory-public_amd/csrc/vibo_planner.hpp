@@ -14,7 +14,12 @@ namespace vibo {
 int fail(int code, const char* fmt, ...);
 const char* last_error();
 
-int check_desc(const vibo_desc* d);
+// sign_rows: the entry point takes VIBO_MASK_SIGN rows (include/vibo_hip_sign_rows.h) where sign_rows_ok says so; every other one
+// refuses them here (-8)
+int check_desc(const vibo_desc* d, bool sign_rows = false);
+// VIBO_MASK_SIGN: the shapes the format is implemented for -- what the planner sends to the single-launch matrix row-split kernel
+// (unconditional posterior, no flows, 4..1024 items, chunkable rows)
+bool sign_rows_ok(const vibo_desc* d);
 int codes_unsupported();
 // the pointer checks the entry points that read person rows share (after check_desc)
 int require_rows(const vibo_desc* d, const float* response, const void* mask);

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/vibo_hip.h"
+#include "../../include/vibo_hip_sign_rows.h"
 #include "vibo_device.hpp"
 #include "vibo_finalize.hpp"
 #include "vibo_philox.hpp"
@@ -272,6 +273,11 @@ extern "C" int vibo_fill_normal(float* out, int64_t n, uint64_t seed, const int3
 static bool plain_ok(const vibo_desc* d, int hidden_dim) {
     return d && hidden_dim >= 1 && hidden_dim <= kMaxHidden && d->posterior == VIBO_POSTERIOR_UNCONDITIONAL && d->n_flows == 0;
 }
+// (-8: VIBO_MASK_SIGN is a row format of the ELBO call alone; these calls take the trainer's own descriptor)
+static int plain_check(const vibo_desc* d, int hidden_dim) {
+    if (d && d->mask_dtype == VIBO_MASK_SIGN) return -8;
+    return plain_ok(d, hidden_dim) ? 0 : -6;
+}
 // train_prologue_kernel: block 0, the item blocks and (gen) the ability-noise blocks behind them
 static int launch_prologue(const vibo_desc* d, int hidden_dim, const float* mlp_params, const float* item_mu, const float* item_logvar,
                            const float* eps_item, float* item_feat, float* table, float* saved_h, float* kl_parts, int32_t* step_count,
@@ -289,7 +295,7 @@ static int launch_prologue(const vibo_desc* d, int hidden_dim, const float* mlp_
 extern "C" int vibo_train_prologue(const vibo_desc* d, int hidden_dim, const float* mlp_params, const float* item_mu,
                                    const float* item_logvar, const float* eps_item, float* item_feat, float* table,
                                    float* saved_h, float* kl_parts, int32_t* step_count, void* stream) {
-    if (!plain_ok(d, hidden_dim)) return -6;
+    if (const int rc = plain_check(d, hidden_dim)) return rc;
     return launch_prologue(d, hidden_dim, mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts, step_count, 1, 0, 0,
                            nullptr, nullptr, 0u, stream);
 }
@@ -297,7 +303,7 @@ extern "C" int vibo_train_prologue(const vibo_desc* d, int hidden_dim, const flo
 extern "C" int vibo_train_prime(const vibo_desc* d, int hidden_dim, const float* mlp_params, const float* item_mu,
                                 const float* item_logvar, const float* eps_item, float* item_feat, float* table,
                                 float* saved_h, float* kl_parts, int32_t* step_count, void* stream) {
-    if (!plain_ok(d, hidden_dim)) return -6;
+    if (const int rc = plain_check(d, hidden_dim)) return rc;
     if (!mlp_params || !item_mu || !item_logvar || !eps_item || !item_feat || !table || !saved_h || !kl_parts || !step_count) return -5;
     return launch_prologue(d, hidden_dim, mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts, step_count, 0, 0, 0,
                            nullptr, nullptr, 0u, stream);
@@ -307,7 +313,7 @@ extern "C" int vibo_train_prologue_noise(const vibo_desc* d, int hidden_dim, con
                                          const float* item_logvar, float* eps_item, float* item_feat, float* table,
                                          float* saved_h, float* kl_parts, int32_t* step_count, uint64_t seed, float* eps_ability,
                                          uint32_t ability_stream_id, void* stream) {
-    if (!plain_ok(d, hidden_dim)) return -6;
+    if (const int rc = plain_check(d, hidden_dim)) return rc;
     if (!eps_item || !eps_ability || !step_count) return -5;
     return launch_prologue(d, hidden_dim, mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts, step_count, 1, 1, seed,
                            eps_item, eps_ability, ability_stream_id, stream);
@@ -318,7 +324,7 @@ extern "C" int vibo_train_epilogue(const vibo_desc* d, int hidden_dim, const flo
                                    const int32_t* step_count, float* mlp_params, float* mlp_m, float* mlp_v,
                                    float* item_mu, float* item_logvar, float* item_m, float* item_v, float* loss_out,
                                    void* stream) {
-    if (!plain_ok(d, hidden_dim)) return -6;
+    if (const int rc = plain_check(d, hidden_dim)) return rc;
     const int n = d->num_item * item_feat_dim(d->irt_model, d->ability_dim);
     const int parts = kl_part_count(n);                      // the prologue's item-KL partial sums (one per 64 entries)
     hipLaunchKernelGGL(train_epilogue_kernel, dim3(1 + (n + kEpiThreads - 1) / kEpiThreads), dim3(kEpiThreads), 0, (hipStream_t)stream,

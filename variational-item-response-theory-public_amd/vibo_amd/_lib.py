@@ -1,7 +1,7 @@
 """ctypes binding of libvibo_hip.so.  The C ABI is declared in include/vibo_hip.h and read from there: every export's
 restype / argtypes come from its prototype (parse_prototypes); the constants and the two structs mirror the header by hand
 (tests/test_capi_symbols.py compares them).  Exports declared in a header of their own beside it (EXTRA_HEADERS:
-vibo_hip_decoder_multi.h) are bound the same way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself, EXTRA_SYMBOLS is theirs.
+vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h) are bound the same way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself, EXTRA_SYMBOLS and SIGN_ROWS_SYMBOLS are theirs.
 
 The product path has no CPU or eager-PyTorch fallback: if the HIP library is
 missing or a call fails, this module raises.
@@ -18,6 +18,7 @@ IRT_1PL, IRT_2PL, IRT_3PL = 1, 2, 3
 POSTERIOR_UNCONDITIONAL, POSTERIOR_CONDITIONAL, POSTERIOR_GIVEN = 0, 1, 2
 MISSING_PRIOR, MISSING_DROP = 0, 1
 MASK_U8, MASK_I64, MASK_NONE, MASK_CODES = 0, 1, 2, 3
+MASK_SIGN = 4                 # include/vibo_hip_sign_rows.h: no mask, the response's sign bit says "missing"
 REG_KL, REG_SAMPLED = 0, 1
 FLAG_KERNEL_VALU, FLAG_KERNEL_MATRIX, FLAG_NO_EMIT_CODES, FLAG_COND_VALU, FLAG_COND_MATRIX, FLAG_COND_THREE_PASS = 1, 2, 4, 8, 16, 32
 KERNEL_NAMES = {1: 'matrix row-split (msplit_kernel)', 2: 'VALU row-split (split_kernel)', 3: 'wave-per-row', 4: 'tiled',
@@ -102,16 +103,21 @@ def parse_prototypes(header):
     return protos
 
 
-EXTRA_HEADERS = ('vibo_hip_decoder_multi.h',)
+EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h')
 
 with open(HEADER_PATH) as _header:
     PROTOTYPES = parse_prototypes(_header.read())
 EXPORTED_SYMBOLS = tuple(name for name, _, _ in PROTOTYPES)
 EXTRA_PROTOTYPES = []
+_HEADER_SYMBOLS = {}
 for _name in EXTRA_HEADERS:
     with open(os.path.join(os.path.dirname(HEADER_PATH), _name)) as _header:
-        EXTRA_PROTOTYPES += parse_prototypes(_header.read())
-EXTRA_SYMBOLS = tuple(name for name, _, _ in EXTRA_PROTOTYPES)
+        _protos = parse_prototypes(_header.read())
+    EXTRA_PROTOTYPES += _protos
+    _HEADER_SYMBOLS[_name] = tuple(name for name, _, _ in _protos)
+# (one list per header: EXTRA_SYMBOLS is vibo_hip_decoder_multi.h's, as its tests pin it)
+EXTRA_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_decoder_multi.h']
+SIGN_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sign_rows.h']
 
 _lib = None
 

@@ -416,13 +416,14 @@ class ResidentMatrix:
     ONE record per response tensor: a response that alternates between two masks is counted again at every switch.
     The record lives ON the response tensor (`_vibo_row_counts`): the counts are freed with the data they describe and never
     before -- a captured hipGraph that holds the data's address holds the counts' too."""
-    __slots__ = ('response', 'has_mask', 'mask', 'counts', 'stream', 'event', 'in_graph')
+    __slots__ = ('response', 'has_mask', 'mask', 'counts', 'stream', 'event', 'in_graph', 'sign_is_mask')
     __reduce__ = _not_saved
 
     def __init__(self, response, mask):
         self.response, self.has_mask = _Seen(response), mask is not None
         self.mask = _Seen(_caller_mask(mask)) if self.has_mask else None
         self.counts = self.stream = self.event = None
+        self.sign_is_mask = None              # does the responses' sign bit say what the mask says?  None: not verified yet (_sign_rows)
         self.in_graph = False                 # the count was recorded into a hipGraph: run when that graph replays
 
     def is_(self, response, mask):
@@ -480,6 +481,58 @@ def _resident_row_counts(spec, response, mask, mask_code, row_index, num_person,
                           num_person, for_elbo=True, capturing=torch.cuda.is_current_stream_capturing, stream=stream)
 
 
+SIGN_ROWS = True           # (tests / A-B runs switch it off)
+
+
+def _sign_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode, want_grad, train_step, *, capturing):
+    """The one decision about the row format of an ELBO launch -> (mask, mask_code) it goes out with: the caller's, or
+    (None, MASK_SIGN) -- the matrix kernel then reads no mask bytes (4 instead of 5 B per cell) and takes a cell as missing where its
+    response's sign bit is set, which is how the reference stores its data (-1 at missing cells, every mask built from that).
+    Whether that holds for THESE tensors is verified, never assumed: the fact hangs on the matrix' ResidentMatrix record, so an
+    in-place edit of either tensor throws it away with the rest.
+    Eligibility first (nothing is looked up or verified without it): fp32 responses with a u8 mask, the whole matrix in order,
+    rows the matrix kernel's 16-byte loads can take (base 16-byte aligned, stride a multiple of 4: a MASK_U8 call on other rows
+    falls back to the tiled kernel, a MASK_SIGN call is refused), and a shape the library takes the format for
+    (vibo_sign_rows_supported).  Then: the first sighting of a pair records it, the second
+    verifies (one streaming pass and one .item(); never while the stream is capturing) and still carries the mask, from the third on
+    MASK_SIGN goes out; a "no" is kept as well.
+    While capturing, the two regimes of _lookup_counts: a plain launch whose input is the whole matrix keeps the mask
+    (a replay after `response.copy_(new)` has to read what is there then); the trainers' folded step (train_step given) uses the
+    verified fact -- the resident-matrix contract row_counts() has there.  capturing(): asked only where the answer matters."""
+    keep = (mask, mask_code)
+    if (not SIGN_ROWS or mask is None or mask_code != _lib.MASK_U8 or response is None or response.dtype != torch.float32
+            or row_index is not None or num_person != response.shape[0]
+            or response.data_ptr() % 16 != 0 or response.stride(0) % 4 != 0):
+        return keep
+    if not _BACKEND['sign_supported'](_rows_desc(spec, num_person, response, None, _lib.MASK_SIGN, reg_mode, want_grad)):
+        return keep
+    rec = getattr(response, '_vibo_row_counts', None)
+    if rec is None or not rec.is_(response, mask):
+        response._vibo_row_counts = ResidentMatrix(response, mask)
+        return keep
+    if rec.sign_is_mask is None:
+        if capturing():
+            return keep
+        rec.sign_is_mask = bool(_BACKEND['sign_verify'](response, mask))
+        return keep                  # (the verifying launch itself still carries the mask)
+    if not rec.sign_is_mask or (train_step is None and capturing()):
+        return keep
+    return None, _lib.MASK_SIGN
+
+
+def _hip_sign_rows_supported(d):
+    return _lib.load().vibo_sign_rows_supported(ctypes.byref(d)) == 1
+
+
+def _hip_sign_is_mask(response, mask):
+    """vibo_rows_sign_is_mask on the current stream, waited for: True where every cell's mask byte and sign bit agree."""
+    _require_device(response, mask)
+    differs = torch.empty(1, dtype=torch.int32, device=response.device)
+    d = _rows_desc(ElboSpec(irt_model=1, ability_dim=1), response.shape[0], response, mask, _lib.MASK_U8, _lib.REG_KL, False)
+    _call('vibo_rows_sign_is_mask', ctypes.byref(d), _ptr(response), _ptr(mask), _ptr(differs), _stream(response.device))
+    return int(differs.item()) == 0
+
+
 def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, eps, flow, reg_mode,
                      want_grad, num_person, train_step=None):
     """Single call into vibo_elbo_fwd_bwd on the current stream.
@@ -505,6 +558,8 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     post = None if no_sample else torch.empty(1 if own_noise else 3, B, A, dtype=torch.float32, device=dev)
     ability_k = torch.empty(B, A, dtype=torch.float32, device=dev) if spec.n_flows else None
     ladj = torch.empty(B, dtype=torch.float32, device=dev) if spec.n_flows else None
+    mask, mask_code = _sign_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step,
+                                 capturing=torch.cuda.is_current_stream_capturing)
     d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, want_grad)
     ws_bytes = lib.vibo_workspace_bytes(ctypes.byref(d))
     if ws_bytes == 0:
@@ -803,7 +858,8 @@ def _hip_cond_mean_sum(feature, response, mask, row_index):
 # oracle to exercise the host logic without a GPU (never done by product code).
 _BACKEND = {'elbo': _hip_launch_elbo, 'encode': _hip_encode, 'decode': _hip_decode, 'multi': _hip_multi_forward,
             'decode_mean': _hip_decode_mean, 'counts': _hip_row_counts, 'mean_fwd': _hip_mean_encoder_fwd,
-            'mean_bwd': _hip_mean_encoder_bwd, 'flow_stack': _hip_flow_stack, 'cond_mean_sum': _hip_cond_mean_sum}
+            'mean_bwd': _hip_mean_encoder_bwd, 'flow_stack': _hip_flow_stack, 'cond_mean_sum': _hip_cond_mean_sum,
+            'sign_supported': _hip_sign_rows_supported, 'sign_verify': _hip_sign_is_mask}
 
 
 class FusedELBO(torch.autograd.Function):
