@@ -356,8 +356,8 @@ int vibo_train_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, c
  *       ability == NULL: nor is the sample (32 MB per 1M x 8 call that nothing on the device reads).  It can be rebuilt later:
  *                    vibo_fill_normal at the step's counter, then vibo_elbo_fwd_bwd with that eps, the same rows and the table
  *                    the step ran on returns it bit for bit (vibo_train_epilogue_fused keeps that table, see below).
- *                    Not for fp32 rows gathered through row_index at fewer than 897 items (under 8 waves per workgroup: that
- *                    kernel variant measured slower with the choice than with the store): -5 there, pass the buffer.
+ *                    Only where vibo_train_step_sample_optional(d, row_index != NULL) is 1 -- every drawing step but fp32 rows gathered
+ *                    at fewer than 897 items (under 8 waves per workgroup: slower with the choice than with the store) --, else -5.
  *     The same NULLs are accepted by vibo_elbo_fwd_bwd_step there; elsewhere, and at every other entry point, they return -5.
  *     A step that draws its own noise needs no eps_ability fill from the epilogue before it: pass eps_ability = NULL,
  *     n_eps_ability = 0 to vibo_train_epilogue_fused (no noise blocks) and skip the fill in front of vibo_train_prime.
@@ -385,6 +385,7 @@ int vibo_elbo_fwd_bwd_step(const vibo_desc* d, int32_t* step_count, int skip_fin
                            float* ability_mu, float* ability_logvar, float* ability, float* grad_table, float* grad_item,
                            void* workspace, size_t workspace_bytes, void* stream);
 int vibo_train_step_draws_noise(const vibo_desc* d);
+int vibo_train_step_sample_optional(const vibo_desc* d, int rows_gathered);
 int vibo_elbo_fwd_bwd_step_noise(const vibo_desc* d, int32_t* step_count, int skip_finalize, const float* response, const void* mask,
                                  const int64_t* row_index, const float* table, const float* item, const float* eps, uint64_t seed,
                                  uint32_t ability_stream_id, float* out_scalars, float* ability_mu, float* ability_logvar, float* ability,

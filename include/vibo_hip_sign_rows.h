@@ -21,8 +21,8 @@ extern "C" {
  * Taken only where it is implemented -- a call the planner sends to the single-launch matrix row-split kernel: unconditional
  * posterior, no flows, 4..1024 items, rows chunkable as for VIBO_MASK_U8 (response stride only), row_index == NULL -- by
  *     vibo_elbo_fwd_bwd, vibo_elbo_fwd_bwd_step, vibo_elbo_fwd_bwd_step_noise (also drawing its own noise),
- *     vibo_workspace_bytes, vibo_plan_kernel, vibo_train_step_supported, vibo_train_step_draws_noise
- * (the last two answer what they answer for the same descriptor with VIBO_MASK_U8).  Every other export, and every other shape,
+ *     vibo_workspace_bytes, vibo_plan_kernel, vibo_train_step_supported / _draws_noise / _sample_optional
+ * (the three step queries answer what they answer for the same descriptor with VIBO_MASK_U8).  Every other export, and every other shape,
  * refuses the descriptor before anything is launched: -8 (size queries: 0; vibo_dtrain_scratch_offset: -1) with
  * vibo_last_error_string naming the format where the export sets it.
  */

@@ -8,7 +8,7 @@ import ctypes
 import pytest
 import torch
 
-from gpu_common import assert_same_parameters, dev, simulated, twin_trainers
+from gpu_common import assert_same_parameters, coin_flip_rows, dev, simulated, twin_trainers
 from vibo_amd import _lib, ops
 from vibo_amd.torch_core.models import VIBO_2PL
 
@@ -81,6 +81,38 @@ def test_rebuilt_sample_of_a_gathered_minibatch(I):
             with pytest.raises(_lib.ViboLibraryError, match='null ability'):
                 raw(m1.spec, *ops.prepare_rows(resp, mask), rows, t1.table, t1.item_feat, None, None, _lib.REG_KL, True, 64,
                     train_step=(t1._steps.clone(), False, (SEED, 1), True))
+
+
+@pytest.mark.parametrize('rows', ['in order', 'gathered', 'codes'])
+@pytest.mark.parametrize('I', [896, 900])
+def test_null_sample_is_taken_exactly_where_the_query_says(I, rows, monkeypatch):
+    """vibo_train_step_sample_optional against the call it speaks for, on both sides of the 8-wave line (896 items: 7 waves of 128, 900:
+    8) for each way the rows reach the matrix kernel.  Where it answers 1, vibo_elbo_fwd_bwd_step_noise takes ability = NULL and its
+    `flat` equals, bit for bit, that of the same call (seed, step counter) with the sample stored; where it answers 0 the call
+    returns -5 before anything is launched."""
+    monkeypatch.setattr(ops, 'SIGN_ROWS', False)
+    B, A = 64, 1
+    spec, r, mk, table, item, g = coin_flip_rows(B + 37 if rows == 'gathered' else B, I, A, 7)
+    index = torch.randperm(B + 37, device=r.device, generator=g)[:B] if rows == 'gathered' else None
+    r, m8, code = ops.prepare_rows(ops.pack_cell_codes(r, mk) if rows == 'codes' else r, None if rows == 'codes' else mk)
+
+    def launch(no_sample):
+        steps = torch.tensor([0, 11], dtype=torch.int32, device=dev())
+        return ops._hip_launch_elbo(spec, r, m8, code, index, table, item, None, None, _lib.REG_KL, True, B,
+                                    train_step=ops.TrainStepCall(steps, False, (SEED, 1), no_sample=no_sample))
+
+    with ops.desc_flags(_lib.FLAG_KERNEL_MATRIX):
+        desc = ops._rows_desc(spec, B, r, m8, code, _lib.REG_KL, True)
+        optional = _lib.load().vibo_train_step_sample_optional(ctypes.byref(desc), int(index is not None))
+        assert optional == (0 if rows == 'gathered' and I == 896 else 1)
+        if not optional:
+            with pytest.raises(_lib.ViboLibraryError, match=r'rc=-5\).*null ability'):
+                launch(True)
+            return
+        lazy, stored = launch(True), launch(False)
+    torch.cuda.synchronize()
+    assert lazy.ability is None and stored.ability is not None
+    assert torch.equal(lazy.flat.view(torch.int32), stored.flat.view(torch.int32))
 
 
 def test_the_kernel_is_handed_no_sample_buffer_and_none_is_allocated(monkeypatch):

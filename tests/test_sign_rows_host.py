@@ -12,7 +12,7 @@ from conftest import ROOT
 from vibo_amd import _lib, ops
 
 SIGN_ENTRY_POINTS = {'vibo_elbo_fwd_bwd', 'vibo_elbo_fwd_bwd_step', 'vibo_elbo_fwd_bwd_step_noise', 'vibo_workspace_bytes',
-                     'vibo_plan_kernel', 'vibo_train_step_supported', 'vibo_train_step_draws_noise'}
+                     'vibo_plan_kernel', 'vibo_train_step_supported', 'vibo_train_step_draws_noise', 'vibo_train_step_sample_optional'}
 
 
 def desc(B=1_000_000, I=1000, A=8, irt=2, mask=_lib.MASK_SIGN, posterior=_lib.POSTERIOR_UNCONDITIONAL, n_flows=0, flags=0, grad=1,
@@ -49,6 +49,7 @@ def test_supported_query_and_plan(case):
     u8 = desc(**{**GRID[case], 'mask': _lib.MASK_U8})
     for fn in (lib.vibo_train_step_supported, lib.vibo_train_step_draws_noise):
         assert fn(ctypes.byref(d)) == fn(ctypes.byref(u8)), fn
+    assert lib.vibo_train_step_sample_optional(ctypes.byref(d), 0) == lib.vibo_train_step_sample_optional(ctypes.byref(u8), 0)
     assert lib.vibo_workspace_bytes(ctypes.byref(d)) in (0, lib.vibo_workspace_bytes(ctypes.byref(u8)))
 
 
@@ -106,9 +107,9 @@ def test_new_header_is_bound_and_the_main_header_keeps_its_lists():
     assert lib.vibo_sign_rows_supported.argtypes == [dp] and lib.vibo_rows_sign_is_mask.argtypes == [dp, vp, vp, vp, vp]
     new = open(os.path.join(ROOT, 'include', 'vibo_hip_sign_rows.h')).read()
     assert re.search(r'#define\s+VIBO_MASK_SIGN\s+4\b', new)
-    # vibo_hip.h itself: the lists tests/test_capi_symbols.py computes from it, unchanged (58 prototypes, no new constant)
+    # vibo_hip.h itself: the lists tests/test_capi_symbols.py computes from it, 58 prototypes + vibo_train_step_sample_optional, no new constant
     src = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', 'vibo_hip.h')).read(), flags=re.S)
-    assert len(re.findall(r'\b(vibo_[a-z_0-9]+)\s*\(', src)) == 58 == len(_lib.EXPORTED_SYMBOLS)
+    assert len(re.findall(r'\b(vibo_[a-z_0-9]+)\s*\(', src)) == 59 == len(_lib.EXPORTED_SYMBOLS)
     assert not set(_lib.SIGN_ROWS_SYMBOLS) & set(_lib.EXPORTED_SYMBOLS)
     header = dict(re.findall(r'\bVIBO_([A-Z0-9_]+)\s*=\s*(\d+)', src) + re.findall(r'#define\s+VIBO_([A-Z0-9_]+)\s+(\d+)', src))
     assert 'MASK_SIGN' not in header and len(header) == 33 + 2 + 3 + 6 + 1      # mirrored + the two dim limits + DECODER_ + KERNEL_ + S_RESERVED

@@ -1,5 +1,6 @@
 """Every public answer of the planner (csrc/vibo_planner.hip) over a fixed sweep of descriptors, one line each: vibo_plan_kernel,
-vibo_plan_cond_passes, vibo_workspace_bytes, vibo_train_step_supported, vibo_train_step_draws_noise and vibo_multi_workspace_bytes
+vibo_plan_cond_passes, vibo_workspace_bytes, vibo_train_step_supported, vibo_train_step_draws_noise, vibo_train_step_sample_optional
+(rows in order / gathered; for a library from before that query: the rule it replaced, evaluated here) and vibo_multi_workspace_bytes
 (1, 3 and 16 samples), plus the error string where vibo_plan_kernel refuses.  No launch, no GPU needed (without one the planner
 assumes 256 compute units).  Two builds of the library plan alike exactly when their outputs are byte-identical:
 
@@ -8,7 +9,7 @@ assumes 256 compute units).  Two builds of the library plan alike exactly when t
 
 The sweep is the full factorial of num_item x ability_dim x posterior x mask_dtype x flags over every constant the planner compares
 against, times `per_cell` seeded draws (without replacement) from persons x irt_model x row strides x want_grad x flows /
-regulariser x missing_mode: 42 240 cells x 24 = 1 013 760 distinct descriptors by default."""
+regulariser x missing_mode: 52 800 cells x 24 = 1 267 200 distinct descriptors by default."""
 import argparse
 import ctypes
 import hashlib
@@ -23,7 +24,7 @@ from vibo_amd import _lib  # noqa: E402
 ITEMS = (3, 4, 5, 64, 65, 128, 129, 144, 192, 255, 256, 304, 320, 512, 640, 896, 1000, 1023, 1024, 1025, 32767, 32768)
 ABILITY_DIMS = (1, 2, 3, 4, 5, 8, 9, 16)
 POSTERIORS = (_lib.POSTERIOR_UNCONDITIONAL, _lib.POSTERIOR_CONDITIONAL, _lib.POSTERIOR_GIVEN)
-MASKS = (_lib.MASK_U8, _lib.MASK_I64, _lib.MASK_NONE, _lib.MASK_CODES)
+MASKS = (_lib.MASK_U8, _lib.MASK_I64, _lib.MASK_NONE, _lib.MASK_CODES, _lib.MASK_SIGN)
 _SINGLE = (_lib.FLAG_KERNEL_VALU, _lib.FLAG_KERNEL_MATRIX, _lib.FLAG_NO_EMIT_CODES, _lib.FLAG_COND_VALU, _lib.FLAG_COND_MATRIX,
            _lib.FLAG_COND_THREE_PASS)
 _REFUSED = (_lib.FLAG_KERNEL_VALU | _lib.FLAG_KERNEL_MATRIX, _lib.FLAG_COND_VALU | _lib.FLAG_COND_MATRIX)
@@ -57,14 +58,18 @@ def answers(lib, d):
     p = ctypes.byref(d)
     kernel = lib.vibo_plan_kernel(p)
     err = lib.vibo_last_error_string().decode() if kernel < 0 else ''
-    return (kernel, lib.vibo_plan_cond_passes(p), lib.vibo_workspace_bytes(p), lib.vibo_train_step_supported(p),
-            lib.vibo_train_step_draws_noise(p), lib.vibo_multi_workspace_bytes(p, 1), lib.vibo_multi_workspace_bytes(p, 3),
-            lib.vibo_multi_workspace_bytes(p, 16), err)
+    noise = lib.vibo_train_step_draws_noise(p)
+    if hasattr(lib, 'vibo_train_step_sample_optional'):
+        lazy = [lib.vibo_train_step_sample_optional(p, gathered) for gathered in (0, 1)]
+    else:      # a library from before the query: the rule of vibo_elbo_fwd_bwd_step_noise that it replaced
+        lazy = [noise, int(noise and not (d.mask_dtype != _lib.MASK_CODES and (d.num_item + 127) // 128 < 8))]
+    return (kernel, lib.vibo_plan_cond_passes(p), lib.vibo_workspace_bytes(p), lib.vibo_train_step_supported(p), noise, *lazy,
+            lib.vibo_multi_workspace_bytes(p, 1), lib.vibo_multi_workspace_bytes(p, 3), lib.vibo_multi_workspace_bytes(p, 16), err)
 
 
 def line(d, a):
     return ('B=%d I=%d A=%d irt=%d post=%d miss=%d mask=%d reg=%d flows=%d grad=%d stride=%d flags=%d -> '
-            'kernel=%d cond=%d ws=%d step=%d noise=%d multi=%d/%d/%d %s\n'
+            'kernel=%d cond=%d ws=%d step=%d noise=%d lazy=%d/%d multi=%d/%d/%d %s\n'
             % ((d.num_person, d.num_item, d.ability_dim, d.irt_model, d.posterior, d.missing_mode, d.mask_dtype, d.reg_mode, d.n_flows,
                 d.want_grad, d.response_row_stride, d.flags) + a))
 
@@ -75,7 +80,10 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--digest', action='store_true', help='print only the descriptor count and the SHA-256 of the output')
     args = ap.parse_args()
-    lib = _lib.load()
+    lib = ctypes.CDLL(_lib.LIB_PATH)        # (_lib.load() wants every export of the header: an older library lacks the newest)
+    for name, restype, argtypes in _lib.PROTOTYPES:
+        if hasattr(lib, name):
+            getattr(lib, name).restype, getattr(lib, name).argtypes = restype, argtypes
     sha, n = hashlib.sha256(), 0
     for d in descriptors(args.per_cell, args.seed):
         text = line(d, answers(lib, d))

@@ -32,36 +32,26 @@ static int device_cus() {
             hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
 }
 
+// descriptor check + plan of the exports that launch nothing: 0, or the refusal's code (error string set)
+static int plan_for(const vibo_desc* d, Plan* pl, bool sign_rows = false) {
+    const int rc = check_desc(d, sign_rows);
+    return rc ? rc : make_plan(d, device_cus(), pl);
+}
 
-// Which instantiation of the row-split kernels a launch runs: all of that choice is here.  p.cond_table set: the matrix kernel with the
-// conditional posterior's first pass folded in.
-static hipError_t launch_split(const ElboParams& p, Engine engine, int AT, bool codes, int irt, bool grad, int grid, hipStream_t s) {
-    if (engine == Engine::Narrow) return launch_elbo_narrow(p, codes, irt, grad, grid, s);
-    if (engine == Engine::Matrix) {
-        const int nw = (p.I + 127) / 128;
-        if (p.cond_table) return p.row_index ? launch_elbo_msplit_xg(p, irt, grad, nw, grid, s) : launch_elbo_msplit_xa(p, irt, grad, nw, grid, s);
-        if (p.n_flows > 0) {
-            if (codes) return launch_elbo_msplit_fc(p, irt, grad, nw, grid, s);
-            if (p.row_index) return launch_elbo_msplit_fg(p, irt, grad, nw, grid, s);
-            return launch_elbo_msplit_fa(p, irt, grad, nw, grid, s);
-        }
-        if (p.mask_dtype == VIBO_MASK_SIGN) return launch_elbo_msplit_s(p, irt, grad, nw, grid, s);
-        if (codes) return launch_elbo_msplit_c(p, irt, grad, nw, grid, s);
-        if (p.row_index) return launch_elbo_msplit_g(p, irt, grad, nw, grid, s);
-        return launch_elbo_msplit_a(p, irt, grad, nw, grid, s);
-    }
-    const int nq = (p.I + 255) / 256;
-    if (codes)
-        return AT <= 2   ? launch_elbo_split_c2(p, irt, grad, nq, grid, s)
-               : AT == 4 ? launch_elbo_split_c4(p, irt, grad, nq, grid, s)
-                         : launch_elbo_split_c8(p, irt, grad, nq, grid, s);
-    if (p.row_index)
-        return AT <= 2   ? launch_elbo_split_g2(p, irt, grad, nq, grid, s)
-               : AT == 4 ? launch_elbo_split_g4(p, irt, grad, nq, grid, s)
-                         : launch_elbo_split_g8(p, irt, grad, nq, grid, s);
-    return AT <= 2   ? launch_elbo_split_a2(p, irt, grad, nq, grid, s)
-           : AT == 4 ? launch_elbo_split_a4(p, irt, grad, nq, grid, s)
-                     : launch_elbo_split_a8(p, irt, grad, nq, grid, s);
+// One row-split launch: split_variant (vibo_planner.hip) names the instantiation or refuses; the variant alone picks the unit.
+static hipError_t launch_split(const vibo_desc* d, const Plan& pl, const ElboParams& p, int grid, hipStream_t s) {
+    static SplitLauncher* const valu[3][3] = {{launch_elbo_split_a2, launch_elbo_split_a4, launch_elbo_split_a8},
+                                              {launch_elbo_split_g2, launch_elbo_split_g4, launch_elbo_split_g8},
+                                              {launch_elbo_split_c2, launch_elbo_split_c4, launch_elbo_split_c8}};
+    static SplitLauncher* const matrix[3][4] = {{launch_elbo_msplit_a, launch_elbo_msplit_g, launch_elbo_msplit_c, launch_elbo_msplit_s},
+                                                {launch_elbo_msplit_fa, launch_elbo_msplit_fg, launch_elbo_msplit_fc, nullptr},
+                                                {launch_elbo_msplit_xa, launch_elbo_msplit_xg, nullptr, nullptr}};      // plain | flows | fused
+    SplitVariant v;
+    if (!split_variant(d, pl, p, &v)) return hipErrorInvalidValue;      // (also: none of the table's empty cells)
+    SplitLauncher* const unit = v.engine == Engine::Narrow ? launch_elbo_narrow
+                                : v.engine == Engine::Valu ? valu[v.rm][v.at == 2 ? 0 : v.at == 4 ? 1 : 2]
+                                                           : matrix[v.xm == kHooksCondFused ? 2 : v.flows ? 1 : 0][v.rm];
+    return unit(p, v, grid, s);
 }
 
 // the pointers of one ELBO call (vibo_elbo_fwd_bwd and its variants)
@@ -236,16 +226,15 @@ static hipError_t first_pass(const vibo_desc* d, const Plan& pl, const ElboArgs&
 }
 
 // Panels: the row-split launches
-static hipError_t launch_panels(const vibo_desc* d, const Plan& pl, ElboParams& p, float* coef, bool codes, hipStream_t s) {
+static hipError_t launch_panels(const vibo_desc* d, const Plan& pl, ElboParams& p, float* coef, hipStream_t s) {
     const int I = d->num_item, A = d->ability_dim;
-    const bool grad = d->want_grad != 0;
     float* partial = p.partial;
     if (pl.tail == Tail::None) coef = nullptr;      // (no pass reads the per-person backward coefficients)
     if (pl.engine == Engine::Matrix && pl.panels > 1) {
         // the matrix kernel takes all panels in one launch: workgroup = (panel, slot), see ElboParams::panel_count
         p.item0 = 0; p.I = 1024; p.primary = 1; p.panel_count = pl.panels;
         p.post_coef = coef;
-        return launch_split(p, Engine::Matrix, pl.AT, codes, d->irt_model, grad, pl.panels * pl.split_nblk, s);
+        return launch_split(d, pl, p, pl.panels * pl.split_nblk, s);
     }
     hipError_t e = hipSuccess;
     for (int pn = 0; pn < pl.panels && e == hipSuccess; ++pn) {
@@ -254,7 +243,7 @@ static hipError_t launch_panels(const vibo_desc* d, const Plan& pl, ElboParams& 
         p.primary = pn == 0 ? 1 : 0;
         p.partial = partial + (size_t)pn * pl.split_nblk * pl.lay.stride;
         p.post_coef = coef ? coef + (size_t)pn * d->num_person * 4 * A : nullptr;
-        e = launch_split(p, pl.engine, pl.AT, codes, d->irt_model, grad, pl.split_nblk, s);
+        e = launch_split(d, pl, p, pl.split_nblk, s);
     }
     p.partial = partial;
     return e;
@@ -306,16 +295,12 @@ static hipError_t run_panels(const vibo_desc* d, const Plan& pl, const ElboArgs&
 
     hipError_t e = first_pass(d, pl, a, num_cu, cp, b, p);
     if (e != hipSuccess) return e;
-    bool codes = d->mask_dtype == VIBO_MASK_CODES;
     if (b.code_rows) {
         read_emitted_codes(cp, b.code_rows, pl.codes_stride);
         // (CondFused: the matrix kernel reads the fp32 rows; the gradient pass the codes it leaves behind)
-        if (pl.first != FirstPass::CondFused) {
-            read_emitted_codes(p, b.code_rows, pl.codes_stride);
-            codes = true;
-        }
+        if (pl.first != FirstPass::CondFused) read_emitted_codes(p, b.code_rows, pl.codes_stride);
     }
-    e = launch_panels(d, pl, p, b.coef, codes, a.stream);
+    e = launch_panels(d, pl, p, b.coef, a.stream);
     if (e != hipSuccess) return e;
     return gradient_tail(d, pl, a, cp, b, tail);
 }
@@ -323,7 +308,7 @@ static hipError_t run_panels(const vibo_desc* d, const Plan& pl, const ElboArgs&
 // Split / Row / Tiled: one launch
 static hipError_t run_single(const vibo_desc* d, const Plan& pl, Path path, const ElboParams& p, hipStream_t s) {
     const bool grad = d->want_grad != 0;
-    if (path == Path::Split) return launch_split(p, pl.engine, pl.AT, d->mask_dtype == VIBO_MASK_CODES, d->irt_model, grad, pl.split_nblk, s);
+    if (path == Path::Split) return launch_split(d, pl, p, pl.split_nblk, s);
     if (path == Path::Row) return launch_elbo_rows(p, d->irt_model, grad, pl.row_nblk, s);
     switch (pl.AT) {
         case 1: return launch_elbo_a1(p, d->irt_model, grad, pl.geom, s);
@@ -380,14 +365,14 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
         return fail(-8, "VIBO_MASK_SIGN rows: the response rows must be 16-byte aligned with a stride that is a multiple of 4");
     if (pl.given() && path != Path::Panels)
         return fail(-8, "VIBO_POSTERIOR_GIVEN: rows must be aligned for 4-cell chunks (see vibo_amd.ops.pad_rows)");
-    if ((a.step_count || a.skip_finalize) && !(step_plan_ok(d, pl) && path == Path::Split))
+    const StepContract step = step_contract(d, pl, a.row_index != nullptr);
+    if ((a.step_count || a.skip_finalize) && !(step.ok && path == Path::Split))
         return fail(-8, "vibo_elbo_fwd_bwd_step: single-launch row-split calls of the plain model only (unconditional posterior, no "
                         "flows, KL regulariser, gradients, 4..1024 items, aligned rows): use vibo_train_prologue + vibo_elbo_fwd_bwd");
-    if (!own_post && !step_draws_noise(d, pl))
+    if (!own_post && !step.draws_noise)
         return fail(-5, "null eps / ability_mu / ability_logvar / ability: only where the folded step runs the matrix kernel "
                         "(vibo_train_step_draws_noise)");
-    // (msplit_kernel's kSampleOptional: the <fp32 rows gathered, fewer than 8 waves> instantiations store the sample unconditionally)
-    if (!a.ability && a.row_index && d->mask_dtype != VIBO_MASK_CODES && (d->num_item + 127) / 128 < 8)
+    if (!a.ability && !step.sample_optional)      // (ms_sample_optional, vibo_variant.hpp)
         return fail(-5, "null ability: not for fp32 rows gathered through row_index at fewer than 897 items");
     if (path == Path::General) return run_general(d, pl, a, num_cu);
 
@@ -416,24 +401,18 @@ int vibo_version(void) { return VIBO_ABI_VERSION; }
 const char* vibo_last_error_string(void) { return last_error(); }
 
 int vibo_plan_cond_passes(const vibo_desc* d) {
-    int rc = check_desc(d);
-    if (rc) return rc;
     Plan pl;
-    rc = make_plan(d, device_cus(), &pl);
-    if (rc < 0) return rc;
-    return plan_cond_pass_bits(pl);
+    const int rc = plan_for(d, &pl);
+    return rc ? rc : plan_cond_pass_bits(pl);
 }
 
 // The kernel the plan names: resolve_path for aligned rows.  The answer depends on the descriptor alone, so it is the same for a call
 // whose launch later falls back because the caller's rows are not aligned for 16-byte loads (Panels / flows -> the wave-per-person
 // kernel, Split / Row -> the tiled kernel).
 int vibo_plan_kernel(const vibo_desc* d) {
-    int rc = check_desc(d, true);
-    if (rc) return rc;
     Plan pl;
-    rc = make_plan(d, device_cus(), &pl);
-    if (rc < 0) return rc;
-    return plan_kernel_code(pl);
+    const int rc = plan_for(d, &pl, true);
+    return rc ? rc : plan_kernel_code(pl);
 }
 
 int vibo_selftest_lane_swaps(const float* in, float* out, void* stream) {
@@ -459,9 +438,8 @@ int vibo_insitu_timer_reset(uint64_t* block, void* stream) {
 }
 
 size_t vibo_workspace_bytes(const vibo_desc* d) {
-    if (check_desc(d, true) != 0) return 0;
     Plan pl;
-    if (make_plan(d, device_cus(), &pl) < 0) return 0;
+    if (plan_for(d, &pl, true) != 0) return 0;
     const size_t enc = encode_scratch_bytes(d);
     return pl.total_bytes > enc ? pl.total_bytes : enc;
 }
@@ -490,13 +468,6 @@ int vibo_elbo_fwd_bwd_counts(const vibo_desc* d, const float* response, const vo
     return elbo_fwd_bwd_impl(d, a);
 }
 
-// (VIBO_MASK_SIGN rows: the two step queries answer for the same descriptor with VIBO_MASK_U8 -- the plan does not look at the code)
-static vibo_desc sign_rows_as_u8(const vibo_desc* d) {
-    vibo_desc u = *d;
-    if (u.mask_dtype == VIBO_MASK_SIGN) u.mask_dtype = VIBO_MASK_U8;
-    return u;
-}
-
 int vibo_sign_rows_supported(const vibo_desc* d) {
     return (d && d->mask_dtype == VIBO_MASK_SIGN && check_desc(d, true) == 0) ? 1 : 0;
 }
@@ -511,30 +482,21 @@ int vibo_rows_sign_is_mask(const vibo_desc* d, const float* response, const void
     return 0;
 }
 
-int vibo_train_step_supported(const vibo_desc* d_in) {
-    if (!d_in) return 0;
-    const vibo_desc du = sign_rows_as_u8(d_in);
-    const vibo_desc* d = &du;
-    if (check_desc(d) != 0) return 0;
+// The folded step's contract as the step queries ask it: none for a refused descriptor.  (VIBO_MASK_SIGN rows answer as the same rows
+// under a u8 mask: row modes 0 and 3 agree on every rule of the contract.)
+static StepContract step_query(const vibo_desc* d, bool rows_gathered) {
+    vibo_desc u = d ? *d : vibo_desc{};      // (null: refused by the descriptor check like any zeroed descriptor)
+    if (u.mask_dtype == VIBO_MASK_SIGN) u.mask_dtype = VIBO_MASK_U8;
     Plan pl;
-    if (make_plan(d, device_cus(), &pl) < 0) return 0;
-    if (!step_plan_ok(d, pl)) return 0;
-    // bit 1: vibo_train_epilogue_fused can also take over the finalize -- where it sums the partial records in the same order as the
-    // stand-alone finalize would (16 slices; elbo_fwd_bwd_impl picks the 64-slice finalize_kernel<16> for fewer than 65 outputs
-    // or 1024+ records: there the four-launch form and the folded one would differ in the last bits)
-    const int n_out = 8 + 8 * d->ability_dim + d->num_item * pl.D;
-    return 1 | ((pl.split_nblk < 1024 && n_out > 64) ? 2 : 0);
+    return plan_for(&u, &pl) == 0 ? step_contract(&u, pl, rows_gathered) : StepContract{};
 }
 
-int vibo_train_step_draws_noise(const vibo_desc* d_in) {
-    if (!d_in) return 0;
-    const vibo_desc du = sign_rows_as_u8(d_in);
-    const vibo_desc* d = &du;
-    if (check_desc(d) != 0) return 0;
-    Plan pl;
-    if (make_plan(d, device_cus(), &pl) < 0) return 0;
-    return step_draws_noise(d, pl) ? 1 : 0;
+int vibo_train_step_supported(const vibo_desc* d) {
+    const StepContract c = step_query(d, false);
+    return c.ok ? 1 | (c.fused_finalize ? 2 : 0) : 0;
 }
+int vibo_train_step_draws_noise(const vibo_desc* d) { return step_query(d, false).draws_noise ? 1 : 0; }
+int vibo_train_step_sample_optional(const vibo_desc* d, int rows_gathered) { return step_query(d, rows_gathered != 0).sample_optional ? 1 : 0; }
 
 int vibo_elbo_fwd_bwd_step_noise(const vibo_desc* d, int32_t* step_count, int skip_finalize, const float* response, const void* mask,
                                  const int64_t* row_index, const float* table, const float* item, const float* eps, uint64_t seed,
@@ -582,12 +544,13 @@ int vibo_train_epilogue_fused(const vibo_desc* d, int hidden_dim, const void* wo
         // the partial records vibo_elbo_fwd_bwd_step(skip_finalize) left behind: same descriptor -> same plan
         Plan pl;
         if (make_plan(d, device_cus(), &pl) < 0) return fail(-8, "no plan for this descriptor");
-        if (!step_plan_ok(d, pl)) return fail(-8, "vibo_train_epilogue_fused: the descriptor is not a vibo_elbo_fwd_bwd_step call");
+        if (!step_contract(d, pl, false).ok) return fail(-8, "vibo_train_epilogue_fused: the descriptor is not a vibo_elbo_fwd_bwd_step call");
         if ((uintptr_t)workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
         e.partial = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + pl.off_partial);
         e.nblk = pl.split_nblk;
         e.lay = pl.lay;
-        if (e.nblk >= 1024) return fail(-8, "vibo_train_epilogue_fused: %d partial records (finalize order of many small records): "
+        // (the record count alone: whatever the outputs, the stand-alone finalize would sum this many in groups of 16)
+        if (finalize_group(e.nblk, 1 << 30) != 64) return fail(-8, "vibo_train_epilogue_fused: %d partial records (finalize order of many small records): "
                                             "call vibo_elbo_fwd_bwd_step without skip_finalize", e.nblk);
     }
     e.seed_lo = (uint32_t)seed; e.seed_hi = (uint32_t)(seed >> 32);

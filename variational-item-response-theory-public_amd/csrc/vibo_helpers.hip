@@ -626,7 +626,7 @@ hipError_t launch_finalize(FinalizeParams& f, hipStream_t s) {
     const int n_out = 8 + (f.want_grad ? 8 * f.A + 2 * f.n_flows * (2 * f.A + 1) + f.I * f.D : 0);
     // (the conditional posterior's table-gradient finalize rides in the same launch: workgroups past n_fin)
     const int n_tail = f.tail.kind ? f.tail.gx * f.tail.gy : 0;
-    if (f.bpp >= 1024 || n_out <= 64) {    // many small records, or the 8 scalars of a forward-only call: more slices per output
+    if (finalize_group(f.bpp, n_out) == 16) {    // (vibo_variant.hpp)
         f.n_fin = (n_out + 15) / 16;
         hipLaunchKernelGGL(finalize_kernel<16>, dim3(f.n_fin + n_tail), dim3(1024), 0, s, f);
     } else {

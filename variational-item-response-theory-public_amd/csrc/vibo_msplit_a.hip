@@ -2,8 +2,8 @@
 #include "vibo_msplit_kernel.hpp"
 #include "vibo_launch.hpp"
 namespace vibo {
-hipError_t launch_elbo_msplit_a(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s) {
-    return launch_msplit_rm<0, false>(p, irt, grad, nw, grid, s);
+hipError_t launch_elbo_msplit_a(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    return launch_msplit_rm<kRowsInOrder, false>(p, v, grid, s);
 }
 }  // namespace vibo
 #ifdef VIBO_MS_TIMING

@@ -2,8 +2,8 @@
 #include "vibo_msplit_kernel.hpp"
 #include "vibo_launch.hpp"
 namespace vibo {
-hipError_t launch_elbo_msplit_fc(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s) {
-    return launch_msplit_rm<2, true>(p, irt, grad, nw, grid, s);
+hipError_t launch_elbo_msplit_fc(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    return launch_msplit_rm<kRowsCodes, true>(p, v, grid, s);
 }
 }  // namespace vibo
 #ifdef VIBO_MS_TIMING

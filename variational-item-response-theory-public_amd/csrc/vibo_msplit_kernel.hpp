@@ -33,6 +33,7 @@
 #include "vibo_device.hpp"
 #include "vibo_params.hpp"
 #include "vibo_philox.hpp"
+#include "vibo_variant.hpp"
 
 #ifdef VIBO_MS_TIMING
 // development build (make TIMING=1): shader-clock time per phase of the batch loop, summed per wave
@@ -132,25 +133,20 @@ __device__ __forceinline__ half8 cat8(const half2v a, const half2v b, const half
     return half8{a[0], a[1], b[0], b[1], c[0], c[1], d[0], d[1]};
 }
 
-// IRT: 1/2/3PL.  GRAD: also gradients.  RM (row mode): 0 = fp32 responses + mask bytes, rows in order; 1 = the same
-// through p.row_index; 2 = 1-byte cell codes (VIBO_MASK_CODES, through p.mask), with or without p.row_index; 3 = fp32 responses in
-// order whose sign bit IS the mask (VIBO_MASK_SIGN: no mask stream -- 4 B per cell, two load instructions per quarter instead of
-// four; XM 0 without flows only).
+// IRT: 1/2/3PL.  GRAD: also gradients.  RM: RowMode (vibo_variant.hpp; cell codes come through p.mask; sign rows have no mask stream --
+// 4 B per cell, two load instructions per quarter instead of four; XM 0 without flows only).
 // FLOWS: planar flows on the ability sample (flows.py:21-66, models.py:342-348) in the (person, dim) lanes.
 // NW8: the workgroup has exactly 8 waves (897..1024 items, the benchmark's width): slot ownership and the sums over the
-// waves' LDS records are compile-time.  XM: which hooks the launch uses (0: none -- those branches do not exist in the code;
-// 1: panel / conditional: p.row_cnt, p.pre_stats, p.post_coef, p.primary == 0, p.panel_count; 2: p.given_post / p.given_grad;
-// 3: conditional posterior with the experts' sums formed HERE (one panel, ability_dim 1, fp32 rows): p.cond_table, p.codes_out, p.post_coef).
+// waves' LDS records are compile-time.  XM: HookMode (vibo_variant.hpp), which hooks the launch uses (0: those branches do not exist
+// in the code; 3: the experts' sums of the conditional posterior are formed HERE: one panel, ability_dim 1, fp32 rows).
 // blockDim.x = 64 nw, dynamic LDS = msplit_lds_bytes(nw, FLOWS).
 // The kernel runs at 2 waves per SIMD, where a wave issues at most one instruction per ~5 cycles whatever its type: every
 // scalar instruction, branch and spill reload in the batch loop costs as much as a vector instruction (round 3: the loop
 // lost ~500 of its ~2 300 executed instructions per wave and batch this way).
 template <int IRT, bool GRAD, int RM, bool FLOWS, bool NW8, int XM>
 __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
-    // XM (hook mode): 0 = none; 1 = the panel / conditional hooks (p.row_cnt, p.pre_stats, p.post_coef, p.primary, p.panel_count);
-    // 2 = the caller-supplied posterior read / written by the slot lanes themselves (p.given_post, p.given_grad; one panel).
-    // Two modes instead of one EXTRA flag (round 4): each carries the other's pointers, branches and -- the given mode's expf /
-    // logvar loads -- spilled registers no longer.
+    // Hook modes 1 and 2 instead of one EXTRA flag (round 4): each carries the other's pointers, branches and -- the given mode's
+    // expf / logvar loads -- spilled registers no longer.
     // 3 (round 6) = the conditional posterior q(theta | responses, items) (models.py:664-710) of ONE panel at ability_dim 1 with its
     // first pass folded in: the lanes that pack a row's cells also gather the experts their codes select (tau, mu tau of the item's
     // wrong / right row of p.cond_table, kept in LDS) and the 16 lanes of a row group add them up; the slot lanes take lam and s from
@@ -165,7 +161,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     constexpr bool kPinFlowAddr = FLOWS && (IRT == 3 || XM != 0 || RM == 1);
     constexpr bool CODES = RM == 2;
     constexpr bool SIGN = RM == 3;
-    constexpr bool kMayGather = RM == 1 || RM == 2;       // (the instantiation can meet p.row_index)
+    constexpr bool kMayGather = ms_may_gather(RM);        // (the instantiation can meet p.row_index)
     static_assert(!SIGN || (XM == 0 && !FLOWS), "sign-as-mask rows: the plain model's instantiations only");
     constexpr int R = kMsRows;
     constexpr float kLoS = kLogitLo * kLog2e, kHiS = kLogitHi * kLog2e;
@@ -336,7 +332,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             s0 = q; s1 = 4; step = nw;
         }
     };
-    constexpr bool kDraw = XM == 0 && !FLOWS && GRAD;
+    constexpr bool kDraw = ms_draws_noise(XM, FLOWS, GRAD);
     const bool draw = kDraw && p.eps == nullptr;      // (wave-uniform) the kernel draws the noise: see draw_eps
     float epn = 0.f;                                  // eps of this wave's slot of the next batch (4 or more waves), loaded a batch ahead
     auto fetch_eps = [&](const int bt, const int par) __attribute__((always_inline)) {
@@ -966,7 +962,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             // (... nor a sample where it draws its own noise: 32 MB per 1M x 8 launch, rebuilt on demand from the same table and
             //  draws.  Gathered fp32 rows at fewer than 8 waves always store: with the branch that instantiation ran 1.5-4 % slower,
             //  profiles/r12_lazy_sample.txt; the host refuses the NULL there)
-            constexpr bool kSampleOptional = kDraw && (NW8 || RM != 1);
+            constexpr bool kSampleOptional = ms_sample_optional(XM, FLOWS, GRAD, RM, NW8);
             if (!kSampleOptional || p.ability) __builtin_nontemporal_store(th0, p.ability + o);
             if constexpr (FLOWS) {
                 p.ability_k[o] = thv;
@@ -1787,63 +1783,37 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
 
 template <int IRT, bool GRAD, int RM, bool FLOWS, bool NW8, int XM>
 static hipError_t launch_msplit_inst(const ElboParams& p, int nw, int grid, hipStream_t s) {
+    constexpr bool kFuse = XM == kHooksCondFused;
     // more than 64 KB of dynamic LDS has to be opted into (once per kernel; gfx950 has 160 KB per CU)
     static bool lds_opt_in = false;
     if (!lds_opt_in) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)msplit_lds_bytes(8, FLOWS, IRT == 3) + kMsNoiseBytes);
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)msplit_lds_bytes(8, FLOWS, IRT == 3, kFuse) + (kFuse ? 0 : kMsNoiseBytes));
         if (e != hipSuccess) return e;
         lds_opt_in = true;
     }
-    // (p.eps null: the kernel draws the noise -- XM 0 without flows, with gradients only; 1 KB more LDS)
-    if (!p.eps && !(XM == 0 && !FLOWS && GRAD && p.step_tick)) return hipErrorInvalidValue;
-    const size_t lds = msplit_lds_bytes(nw, FLOWS, IRT == 3) + (p.eps ? 0 : kMsNoiseBytes);
+    // (p.eps null -- split_variant: only where the instantiation draws the noise -- takes 1 KB more LDS)
+    const size_t lds = msplit_lds_bytes(nw, FLOWS, IRT == 3, kFuse) + (p.eps ? 0 : kMsNoiseBytes);
     hipLaunchKernelGGL((msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>), dim3(grid), dim3(64 * nw), lds, s, p);
     return hipGetLastError();
 }
-// XM == 3 (p.cond_table): its own translation units (vibo_msplit_xa / xg.hip)
-template <int IRT, bool GRAD, int RM, bool NW8>
-static hipError_t launch_msplit_fused_inst(const ElboParams& p, int nw, int grid, hipStream_t s) {
-    static bool lds_opt_in = false;
-    if (!lds_opt_in) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&msplit_kernel<IRT, GRAD, RM, false, NW8, 3>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)msplit_lds_bytes(8, false, IRT == 3, true));
-        if (e != hipSuccess) return e;
-        lds_opt_in = true;
-    }
-    hipLaunchKernelGGL((msplit_kernel<IRT, GRAD, RM, false, NW8, 3>), dim3(grid), dim3(64 * nw), msplit_lds_bytes(nw, false, IRT == 3, true), s, p);
-    return hipGetLastError();
+// the unit's instantiations of one hook mode: IRT x GRAD x NW8
+template <int RM, bool FLOWS, int XM>
+static hipError_t launch_msplit_xm(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+#define VIBO_MS(IRT_, GRAD_) (v.nw8 ? launch_msplit_inst<IRT_, GRAD_, RM, FLOWS, true, XM>(p, v.waves, grid, s) \
+                                    : launch_msplit_inst<IRT_, GRAD_, RM, FLOWS, false, XM>(p, v.waves, grid, s))
+    if (v.irt == 1) return v.grad ? VIBO_MS(1, true) : VIBO_MS(1, false);
+    if (v.irt == 2) return v.grad ? VIBO_MS(2, true) : VIBO_MS(2, false);
+    return v.grad ? VIBO_MS(3, true) : VIBO_MS(3, false);
+#undef VIBO_MS
 }
-template <int RM>
-static hipError_t launch_msplit_fused(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s) {
-    if (!p.cond_table || p.A != 1 || p.n_flows != 0 || p.row_cnt || p.pre_stats || p.given_post || p.given_grad || !p.primary || p.panel_count > 1 ||
-        (grad && !p.post_coef)) return hipErrorInvalidValue;
-#define VIBO_MSF(IRT_, GRAD_) (nw == 8 ? launch_msplit_fused_inst<IRT_, GRAD_, RM, true>(p, nw, grid, s) : launch_msplit_fused_inst<IRT_, GRAD_, RM, false>(p, nw, grid, s))
-    if (irt == 1) return grad ? VIBO_MSF(1, true) : VIBO_MSF(1, false);
-    if (irt == 2) return grad ? VIBO_MSF(2, true) : VIBO_MSF(2, false);
-    return grad ? VIBO_MSF(3, true) : VIBO_MSF(3, false);
-#undef VIBO_MSF
-}
-template <int IRT, bool GRAD, int RM, bool FLOWS>
-static hipError_t launch_msplit_one(const ElboParams& p, int nw, int grid, hipStream_t s) {
-    // XM: the hook mode (see the kernel): 2 = the slot lanes read / write a caller-supplied posterior, 1 = panel / conditional hooks;
-    // NW8: exactly 8 waves per workgroup
-    const int xm = (p.given_post || p.given_grad) ? 2
-                   : (p.row_cnt || p.pre_stats || p.post_coef || !p.primary || p.panel_count > 1) ? 1 : 0;
-    if (p.cond_table) return hipErrorInvalidValue;      // (XM == 3: launch_msplit_fused)
-    if (xm == 2 && (!p.given_post || p.row_cnt || p.pre_stats || p.post_coef || !p.primary || p.panel_count > 1)) return hipErrorInvalidValue;
-    if (nw == 8) return xm == 2 ? launch_msplit_inst<IRT, GRAD, RM, FLOWS, true, 2>(p, nw, grid, s)
-                      : xm == 1 ? launch_msplit_inst<IRT, GRAD, RM, FLOWS, true, 1>(p, nw, grid, s)
-                                : launch_msplit_inst<IRT, GRAD, RM, FLOWS, true, 0>(p, nw, grid, s);
-    return xm == 2 ? launch_msplit_inst<IRT, GRAD, RM, FLOWS, false, 2>(p, nw, grid, s)
-         : xm == 1 ? launch_msplit_inst<IRT, GRAD, RM, FLOWS, false, 1>(p, nw, grid, s)
-                   : launch_msplit_inst<IRT, GRAD, RM, FLOWS, false, 0>(p, nw, grid, s);
-}
+// hook modes 0..2 (3 has its own translation units: vibo_msplit_xa / xg.hip)
 template <int RM, bool FLOWS>
-static hipError_t launch_msplit_rm(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s) {
-    if (irt == 1) return grad ? launch_msplit_one<1, true, RM, FLOWS>(p, nw, grid, s) : launch_msplit_one<1, false, RM, FLOWS>(p, nw, grid, s);
-    if (irt == 2) return grad ? launch_msplit_one<2, true, RM, FLOWS>(p, nw, grid, s) : launch_msplit_one<2, false, RM, FLOWS>(p, nw, grid, s);
-    return grad ? launch_msplit_one<3, true, RM, FLOWS>(p, nw, grid, s) : launch_msplit_one<3, false, RM, FLOWS>(p, nw, grid, s);
+static hipError_t launch_msplit_rm(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    return v.xm == kHooksGiven   ? launch_msplit_xm<RM, FLOWS, kHooksGiven>(p, v, grid, s)
+           : v.xm == kHooksPanel ? launch_msplit_xm<RM, FLOWS, kHooksPanel>(p, v, grid, s)
+                                 : launch_msplit_xm<RM, FLOWS, kHooksNone>(p, v, grid, s);
 }
 
 }  // namespace vibo

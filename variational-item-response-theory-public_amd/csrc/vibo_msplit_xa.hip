@@ -2,8 +2,8 @@
 #include "vibo_msplit_kernel.hpp"
 #include "vibo_launch.hpp"
 namespace vibo {
-hipError_t launch_elbo_msplit_xa(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s) {
-    return launch_msplit_fused<0>(p, irt, grad, nw, grid, s);
+hipError_t launch_elbo_msplit_xa(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    return launch_msplit_xm<kRowsInOrder, false, kHooksCondFused>(p, v, grid, s);
 }
 }  // namespace vibo
 #ifdef VIBO_MS_TIMING

@@ -2,7 +2,7 @@
 #include "vibo_msplit_kernel.hpp"
 #include "vibo_launch.hpp"
 namespace vibo {
-hipError_t launch_elbo_msplit_xg(const ElboParams& p, int irt, bool grad, int nw, int grid, hipStream_t s) {
-    return launch_msplit_fused<1>(p, irt, grad, nw, grid, s);
+hipError_t launch_elbo_msplit_xg(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    return launch_msplit_xm<kRowsGathered, false, kHooksCondFused>(p, v, grid, s);
 }
 }  // namespace vibo

@@ -420,26 +420,21 @@ static hipError_t launch_narrow_il(const ElboParams& p, int grid, hipStream_t s)
     return hipGetLastError();
 }
 template <int AT, int RM>
-static hipError_t launch_narrow_irt(const ElboParams& p, int irt, bool grad, int grid, hipStream_t s) {
-    if (irt == 1) return grad ? launch_narrow_il<AT, 1, true, RM>(p, grid, s) : launch_narrow_il<AT, 1, false, RM>(p, grid, s);
-    if (irt == 2) return grad ? launch_narrow_il<AT, 2, true, RM>(p, grid, s) : launch_narrow_il<AT, 2, false, RM>(p, grid, s);
-    return grad ? launch_narrow_il<AT, 3, true, RM>(p, grid, s) : launch_narrow_il<AT, 3, false, RM>(p, grid, s);
+static hipError_t launch_narrow_irt(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    if (v.irt == 1) return v.grad ? launch_narrow_il<AT, 1, true, RM>(p, grid, s) : launch_narrow_il<AT, 1, false, RM>(p, grid, s);
+    if (v.irt == 2) return v.grad ? launch_narrow_il<AT, 2, true, RM>(p, grid, s) : launch_narrow_il<AT, 2, false, RM>(p, grid, s);
+    return v.grad ? launch_narrow_il<AT, 3, true, RM>(p, grid, s) : launch_narrow_il<AT, 3, false, RM>(p, grid, s);
 }
 template <int RM>
-static hipError_t launch_narrow_at(const ElboParams& p, int irt, bool grad, int grid, hipStream_t s) {
-    if (p.A <= 1) return launch_narrow_irt<1, RM>(p, irt, grad, grid, s);
-    if (p.A <= 2) return launch_narrow_irt<2, RM>(p, irt, grad, grid, s);
-    return launch_narrow_irt<4, RM>(p, irt, grad, grid, s);
+static hipError_t launch_narrow_at(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    if (v.at == 1) return launch_narrow_irt<1, RM>(p, v, grid, s);
+    if (v.at == 2) return launch_narrow_irt<2, RM>(p, v, grid, s);
+    return launch_narrow_irt<4, RM>(p, v, grid, s);
 }
-// rows: fp32 in order / fp32 through p.row_index / cell codes (codes = true: through p.mask, with or without p.row_index)
-hipError_t launch_elbo_narrow(const ElboParams& p, bool codes, int irt, bool grad, int grid, hipStream_t s) {
-    if (p.I < 4 || p.I > 128 || p.A > 4 || p.n_flows > 0) return hipErrorInvalidValue;
-    // the plain model on 1-byte masks / cell codes only: no hooks (conditional / given posterior, panels), no int64 mask
-    if (p.row_cnt || p.pre_stats || p.post_coef || p.given_post || p.given_grad || p.panel_count > 1 || !p.primary) return hipErrorInvalidValue;
-    if (!codes && p.mask_dtype == VIBO_MASK_I64) return hipErrorInvalidValue;
-    if (codes) return launch_narrow_at<2>(p, irt, grad, grid, s);
-    if (p.row_index) return launch_narrow_at<1>(p, irt, grad, grid, s);
-    return launch_narrow_at<0>(p, irt, grad, grid, s);
+hipError_t launch_elbo_narrow(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    if (v.rm == kRowsCodes) return launch_narrow_at<kRowsCodes>(p, v, grid, s);
+    if (v.rm == kRowsGathered) return launch_narrow_at<kRowsGathered>(p, v, grid, s);
+    return launch_narrow_at<kRowsInOrder>(p, v, grid, s);
 }
 
 }  // namespace vibo

@@ -159,11 +159,47 @@ int plan_cond_pass_bits(const Plan& pl) {
     return (pl.first == FirstPass::CondMatrix ? 1 : 0) | (pl.tail == Tail::CondMatrix ? 2 : 0) | (pl.first == FirstPass::CondFused ? 4 : 0);
 }
 
-bool step_plan_ok(const vibo_desc* d, const Plan& pl) {
-    return d->posterior == VIBO_POSTERIOR_UNCONDITIONAL && d->n_flows == 0 && d->reg_mode == VIBO_REG_KL && d->want_grad &&
-           pl.path == Path::Split;
+// the variant's fields that the descriptor and the plan fix, for a launch over `items` items whose rows reach the kernel as mask_dtype
+static SplitVariant variant_of(const vibo_desc* d, const Plan& pl, int items, int mask_dtype, bool gathered) {
+    SplitVariant v{};
+    v.engine = pl.engine; v.irt = d->irt_model; v.grad = d->want_grad != 0; v.flows = d->n_flows > 0;
+    v.rm = mask_dtype == VIBO_MASK_CODES ? kRowsCodes : mask_dtype == VIBO_MASK_SIGN ? kRowsSign : gathered ? kRowsGathered : kRowsInOrder;
+    v.xm = pl.path != Path::Panels ? kHooksNone
+           : pl.first == FirstPass::CondFused ? kHooksCondFused : pl.first == FirstPass::GivenDirect ? kHooksGiven : kHooksPanel;
+    v.at = pl.engine == Engine::Matrix ? 8 : pl.engine == Engine::Narrow ? (d->ability_dim <= 2 ? d->ability_dim : 4) : pl.AT <= 2 ? 2 : pl.AT == 4 ? 4 : 8;
+    v.waves = pl.engine == Engine::Matrix ? (items + 127) / 128 : pl.engine == Engine::Narrow ? 4 : (items + 255) / 256;
+    v.nw8 = pl.engine == Engine::Matrix && v.waves == 8;
+    return v;
 }
-bool step_draws_noise(const vibo_desc* d, const Plan& pl) { return step_plan_ok(d, pl) && pl.engine == Engine::Matrix; }
+
+bool split_variant(const vibo_desc* d, const Plan& pl, const ElboParams& p, SplitVariant* out) {
+    const SplitVariant v = *out = variant_of(d, pl, p.I, p.mask_dtype, p.row_index != nullptr);
+    // the hook fields first_pass / launch_panels left in p against the mode the plan names (fused: one panel, ability_dim 1, fp32 rows)
+    const bool panel = p.row_cnt || p.pre_stats || !p.primary || p.panel_count > 1, given = p.given_post || p.given_grad;
+    const bool hooks_ok = v.xm == kHooksNone    ? !(panel || p.post_coef || given || p.cond_table)
+                          : v.xm == kHooksPanel ? !(given || p.cond_table)
+                          : v.xm == kHooksGiven ? p.given_post && !(panel || p.post_coef || p.cond_table)
+                                                : p.cond_table && !(panel || given) && (p.post_coef || !v.grad) && p.A == 1 && !v.flows &&
+                                                      v.rm <= kRowsGathered && v.engine == Engine::Matrix;
+    // sign-as-mask rows: the matrix kernel's plain instantiations, rows in order without a mask
+    const bool sign_ok = v.rm != kRowsSign || (v.engine == Engine::Matrix && v.xm == kHooksNone && !v.flows && !p.row_index && !p.mask && p.response);
+    // the narrow-row kernel: the plain model on 1-byte masks / cell codes
+    const bool narrow_ok = v.engine != Engine::Narrow || (p.I >= 4 && p.I <= 128 && p.A <= 4 && !v.flows && v.xm == kHooksNone &&
+                                                          (v.rm == kRowsCodes || p.mask_dtype != VIBO_MASK_I64));
+    // eps may be null only where the instantiation draws the noise itself, and only in the folded step
+    return hooks_ok && sign_ok && narrow_ok && (p.eps || (ms_draws_noise(v) && p.step_tick));
+}
+
+StepContract step_contract(const vibo_desc* d, const Plan& pl, bool rows_gathered) {
+    StepContract c{};
+    c.ok = d->posterior == VIBO_POSTERIOR_UNCONDITIONAL && d->n_flows == 0 && d->reg_mode == VIBO_REG_KL && d->want_grad && pl.path == Path::Split;
+    if (!c.ok) return c;
+    const SplitVariant v = variant_of(d, pl, d->num_item, d->mask_dtype, rows_gathered);
+    // (vibo_train_epilogue_fused sums in groups of 64: where the stand-alone finalize picks 16, the step's two forms would differ in the last bits)
+    c.fused_finalize = finalize_group(pl.split_nblk, 8 + 8 * d->ability_dim + d->num_item * pl.D) == 64;
+    c.draws_noise = ms_draws_noise(v); c.sample_optional = ms_sample_optional(v);
+    return c;
+}
 
 // ---------------------------------------------------------------------------
 // stage 2: engine choice -- the measured thresholds

@@ -43,11 +43,7 @@ enum class Path {
     Row,          // wave-per-row register kernel (int64 masks)
     Tiled         // tiled kernel
 };
-enum class Engine {   // which row-split kernel (Panels / Split)
-    Valu,         // vibo_split_kernel.hpp
-    Matrix,       // vibo_msplit_kernel.hpp: split_nq = waves of 128 items per workgroup, batches of 32 rows
-    Narrow        // vibo_narrow.hip: <= 128 items, a row per 16 lanes; split_nblk = its grid
-};
+// (Engine -- which row-split kernel a Panels / Split call runs; Plan::split_nblk is the narrow-row kernel's grid too: vibo_variant.hpp)
 enum class FirstPass {   // Panels: what supplies the whole-row statistics
     None,
     RowCount,     // unconditional posterior: packed counts of the whole row
@@ -100,10 +96,14 @@ int make_plan(const vibo_desc* d, int num_cu, Plan* pl, bool allow_msplit = true
 Path resolve_path(const Plan& pl, const vibo_desc* d, bool vec);
 int plan_kernel_code(const Plan& pl);        // VIBO_KERNEL_* of resolve_path(vec = true)
 int plan_cond_pass_bits(const Plan& pl);     // vibo_plan_cond_passes
-// the folded train step (vibo_elbo_fwd_bwd_step + vibo_train_epilogue_fused) covers single-launch row-split calls of the plain model
-bool step_plan_ok(const vibo_desc* d, const Plan& pl);
-// ... and where that step runs the matrix kernel, it may draw its own ability noise and skip the posterior's mean / log-variance
-bool step_draws_noise(const vibo_desc* d, const Plan& pl);
+// Which instantiation a row-split launch of this plan runs, every field derived once: from the descriptor and the plan, and from `p` what
+// only the launch knows (its items, rows gathered / become cell codes).  false: there is none, or p's hook fields contradict the one named.
+bool split_variant(const vibo_desc* d, const Plan& pl, const ElboParams& p, SplitVariant* v);
+// The folded train step (vibo_elbo_fwd_bwd_step + vibo_train_epilogue_fused) covers single-launch row-split calls of the plain model.
+// ok: the descriptor can take it (vibo_train_step_supported bit 0); fused_finalize: vibo_train_epilogue_fused sums in the stand-alone finalize's
+// order (bit 1); draws_noise: the step's kernel may draw its ability noise and skip the posterior's mean / log-variance; sample_optional: and the sample
+struct StepContract { bool ok, fused_finalize, draws_noise, sample_optional; };
+StepContract step_contract(const vibo_desc* d, const Plan& pl, bool rows_gathered);
 // plan of a multi-sample forward: the single-launch plan with want_grad = 0, restricted to the row-split paths.
 // given_call: vibo_elbo_multi_forward_given (VIBO_POSTERIOR_GIVEN descriptors only; the plain call refuses those)
 int multi_plan(const vibo_desc* d, int num_cu, vibo_desc* d0, Plan* pl, size_t* prep_bytes, bool given_call = false);

@@ -28,6 +28,7 @@
 #include "../../include/vibo_hip.h"
 #include "vibo_device.hpp"
 #include "vibo_params.hpp"
+#include "vibo_variant.hpp"
 
 namespace vibo {
 
@@ -708,24 +709,23 @@ __global__ __launch_bounds__(256, (RM == 2 && (AT <= 2 || (AT == 4 && IRT <= 2))
 }
 
 template <int AT, int IRT, bool GRAD, int RM>
-static hipError_t launch_split_flows(const ElboParams& p, int nq, int grid, hipStream_t s) {
-    const bool flows = p.n_flows > 0;
-    const size_t lds = split_lds_bytes(nq, flows);
-    if (nq == 4) {
-        if (flows) hipLaunchKernelGGL((split_kernel<AT, IRT, GRAD, true, 4, RM>), dim3(grid), dim3(256), 0, s, p);
+static hipError_t launch_split_flows(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    const size_t lds = split_lds_bytes(v.waves, v.flows);
+    if (v.waves == 4) {
+        if (v.flows) hipLaunchKernelGGL((split_kernel<AT, IRT, GRAD, true, 4, RM>), dim3(grid), dim3(256), 0, s, p);
         else hipLaunchKernelGGL((split_kernel<AT, IRT, GRAD, false, 4, RM>), dim3(grid), dim3(256), 0, s, p);
     } else {
-        if (flows) hipLaunchKernelGGL((split_kernel<AT, IRT, GRAD, true, 0, RM>), dim3(grid), dim3(64 * nq), lds, s, p);
-        else hipLaunchKernelGGL((split_kernel<AT, IRT, GRAD, false, 0, RM>), dim3(grid), dim3(64 * nq), lds, s, p);
+        if (v.flows) hipLaunchKernelGGL((split_kernel<AT, IRT, GRAD, true, 0, RM>), dim3(grid), dim3(64 * v.waves), lds, s, p);
+        else hipLaunchKernelGGL((split_kernel<AT, IRT, GRAD, false, 0, RM>), dim3(grid), dim3(64 * v.waves), lds, s, p);
     }
     return hipGetLastError();
 }
 
 template <int AT, int RM = 0>
-static hipError_t launch_split_at(const ElboParams& p, int irt, bool grad, int nq, int grid, hipStream_t s) {
-    if (irt == 1) return grad ? launch_split_flows<AT, 1, true, RM>(p, nq, grid, s) : launch_split_flows<AT, 1, false, RM>(p, nq, grid, s);
-    if (irt == 2) return grad ? launch_split_flows<AT, 2, true, RM>(p, nq, grid, s) : launch_split_flows<AT, 2, false, RM>(p, nq, grid, s);
-    return grad ? launch_split_flows<AT, 3, true, RM>(p, nq, grid, s) : launch_split_flows<AT, 3, false, RM>(p, nq, grid, s);
+static hipError_t launch_split_at(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s) {
+    if (v.irt == 1) return v.grad ? launch_split_flows<AT, 1, true, RM>(p, v, grid, s) : launch_split_flows<AT, 1, false, RM>(p, v, grid, s);
+    if (v.irt == 2) return v.grad ? launch_split_flows<AT, 2, true, RM>(p, v, grid, s) : launch_split_flows<AT, 2, false, RM>(p, v, grid, s);
+    return v.grad ? launch_split_flows<AT, 3, true, RM>(p, v, grid, s) : launch_split_flows<AT, 3, false, RM>(p, v, grid, s);
 }
 
 }  // namespace vibo

@@ -1,0 +1,49 @@
+// vibo_variant.hpp -- which instantiation of the row-split ELBO kernels a launch runs, and the rules that follow from that choice: ONE
+// definition for the kernels' own constants (vibo_msplit_kernel.hpp, vibo_helpers.hip), the host dispatch (split_variant, launch_split) and
+// the folded step's contract (step_contract).  Plain constexpr functions and PODs for host and device code: no HIP runtime calls.
+#pragma once
+
+namespace vibo {
+
+// which row-split kernel (Panels / Split): vibo_split_kernel.hpp | vibo_msplit_kernel.hpp | vibo_narrow.hip (<= 128 items, a row per 16 lanes)
+enum class Engine { Valu, Matrix, Narrow };
+// the kernels' template parameter RM: how the rows reach the kernel
+enum RowMode : int {
+    kRowsInOrder = 0,    // fp32 responses + mask bytes (or no mask), rows in order
+    kRowsGathered = 1,   // the same through row_index
+    kRowsCodes = 2,      // 1-byte cell codes (VIBO_MASK_CODES), with or without row_index
+    kRowsSign = 3        // fp32 responses in order whose sign bit is the mask (VIBO_MASK_SIGN): matrix kernel, no hooks, no flows
+};
+// the matrix kernel's template parameter XM: which hooks the launch uses (the VALU kernel reads the same fields at run time)
+enum HookMode : int {
+    kHooksNone = 0,
+    kHooksPanel = 1,     // panel / conditional: row_cnt, pre_stats, post_coef, primary == 0, panel_count
+    kHooksGiven = 2,     // caller-supplied posterior read / written by the slot lanes: given_post, given_grad (one panel)
+    kHooksCondFused = 3  // conditional posterior with the experts' sums formed in the kernel: cond_table, codes_out, post_coef
+};
+struct SplitVariant {
+    Engine engine;
+    int at;              // template ability width: 2 / 4 / 8 (Valu), 8 (Matrix), 1 / 2 / 4 (Narrow)
+    int irt;             // 1 / 2 / 3 PL
+    bool grad, flows;
+    int rm, xm;          // RowMode, HookMode
+    int waves;           // per workgroup: nw = ceil(items / 128) (Matrix), nq = ceil(items / 256) (Valu), 4 (Narrow)
+    bool nw8;            // Matrix: exactly 8 waves
+};
+constexpr bool ms_may_gather(int rm) { return rm == kRowsGathered || rm == kRowsCodes; }      // the instantiation can meet row_index
+// the matrix kernel draws the ability noise itself where the launch passes no eps (the folded train step)
+constexpr bool ms_draws_noise(int xm, bool flows, bool grad) { return xm == kHooksNone && !flows && grad; }
+// ... and such a launch may pass no `ability` either: the <fp32 rows gathered, fewer than 8 waves> instantiations store the sample
+// unconditionally (they measured slower with the choice than with the store)
+constexpr bool ms_sample_optional(int xm, bool flows, bool grad, int rm, bool nw8) {
+    return ms_draws_noise(xm, flows, grad) && (nw8 || rm != kRowsGathered);
+}
+constexpr bool ms_draws_noise(const SplitVariant& v) { return v.engine == Engine::Matrix && ms_draws_noise(v.xm, v.flows, v.grad); }
+constexpr bool ms_sample_optional(const SplitVariant& v) {
+    return v.engine == Engine::Matrix && ms_sample_optional(v.xm, v.flows, v.grad, v.rm, v.nw8);
+}
+// outputs per workgroup of the finalize (finalize_kernel's template parameter) over n_out outputs and bpp partial records per panel:
+// many small records, or the few outputs of a forward-only call, get more slices per output
+constexpr int finalize_group(int bpp, int n_out) { return (bpp >= 1024 || n_out <= 64) ? 16 : 64; }
+
+}  // namespace vibo

@@ -13,7 +13,7 @@ import ctypes
 import math
 import weakref
 from dataclasses import dataclass, field
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -533,16 +533,19 @@ def _hip_sign_is_mask(response, mask):
     return int(differs.item()) == 0
 
 
+class TrainStepCall(NamedTuple):
+    """The folded train step's ELBO launch (trainer.FusedTrainer): vibo_elbo_fwd_bwd_step, the call that also ticks Adam's step counter."""
+    step_count: torch.Tensor          # the trainer's int32[2] counters
+    skip_finalize: bool               # the partial records stay in RawElbo.workspace and vibo_train_epilogue_fused fills `flat`
+    # (seed, stream) where vibo_train_step_draws_noise says so (eps None): the kernel draws Philox stream `stream` at counter step_count[1] itself
+    noise: Optional[tuple] = None     # ... and writes no posterior mean / log-variance (RawElbo.ability_mu / ability_logvar: None)
+    # with noise, where vibo_train_step_sample_optional says so: ability = NULL, no [B, A] buffer; the caller sets RawElbo.ability_source
+    no_sample: bool = False           # ... which rebuilds `ability` when read (trainer._StepSample)
+
+
 def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, eps, flow, reg_mode,
                      want_grad, num_person, train_step=None):
-    """Single call into vibo_elbo_fwd_bwd on the current stream.
-    train_step = (step_count tensor, skip_finalize[, (seed, stream) | None[, no_sample]]): vibo_elbo_fwd_bwd_step instead -- the same call that
-    also ticks Adam's step counter (the folded train step, trainer.FusedTrainer); with skip_finalize the partial records stay in
-    RawElbo.workspace for vibo_train_epilogue_fused and `flat` is filled by that call.  With (seed, stream) (where
-    vibo_train_step_draws_noise says so; eps None) the kernel draws the ability noise of Philox stream `stream` at counter
-    step_count[1] itself and writes no posterior mean / log-variance: RawElbo.ability_mu / ability_logvar are None.  With no_sample
-    it writes no sample either (ability = NULL): no [B, A] buffer is allocated and the stored `ability` is None -- the caller sets
-    RawElbo.ability_source, which rebuilds it when read (trainer._StepSample)."""
+    """Single call into vibo_elbo_fwd_bwd on the current stream, or (train_step: a TrainStepCall) into vibo_elbo_fwd_bwd_step."""
     lib = _lib.load()
     _require_device(response, mask, table, item, eps)
     dev = response.device
@@ -552,8 +555,9 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     table_shape = tuple(table.shape) if table is not None else tuple(spec.table_shape(I))
     n_table, n_item, n_flow = math.prod(table_shape), I * D, spec.n_flows * (2 * A + 1)
     flat = torch.empty(_lib.NUM_SCALARS + 2 * n_table + n_item + 2 * n_flow, dtype=torch.float32, device=dev)
-    own_noise = train_step is not None and len(train_step) > 2 and train_step[2] is not None
-    no_sample = own_noise and len(train_step) > 3 and bool(train_step[3])
+    train_step = None if train_step is None else TrainStepCall(*train_step)      # (a plain tuple of the same fields is taken too)
+    own_noise = train_step is not None and train_step.noise is not None
+    no_sample = own_noise and bool(train_step.no_sample)
     # posterior mean | log-variance | sample: the drawing step writes the sample alone, or nothing
     post = None if no_sample else torch.empty(1 if own_noise else 3, B, A, dtype=torch.float32, device=dev)
     ability_k = torch.empty(B, A, dtype=torch.float32, device=dev) if spec.n_flows else None
@@ -573,12 +577,13 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     tail = (_ptr(ws), ctypes.c_size_t(ws_bytes), vp(stream.cuda_stream))
     if own_noise:
         name = 'vibo_elbo_fwd_bwd_step_noise'
-        args = (_ptr(train_step[0]), 1 if train_step[1] else 0, *rows, _ptr(table), _ptr(item), None, ctypes.c_uint64(train_step[2][0]),
-                ctypes.c_uint32(train_step[2][1]), vp(fbase), None, None, None if no_sample else _ptr(post[0]), *grads, *tail)
+        args = (_ptr(train_step.step_count), 1 if train_step.skip_finalize else 0, *rows, _ptr(table), _ptr(item), None,
+                ctypes.c_uint64(train_step.noise[0]), ctypes.c_uint32(train_step.noise[1]), vp(fbase), None, None,
+                None if no_sample else _ptr(post[0]), *grads, *tail)
     elif train_step is not None:
         name = 'vibo_elbo_fwd_bwd_step'
-        args = (_ptr(train_step[0]), 1 if train_step[1] else 0, *rows, _ptr(table), _ptr(item), _ptr(eps), vp(fbase), _ptr(post[0]),
-                _ptr(post[1]), _ptr(post[2]), *grads, *tail)
+        args = (_ptr(train_step.step_count), 1 if train_step.skip_finalize else 0, *rows, _ptr(table), _ptr(item), _ptr(eps), vp(fbase),
+                _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), *grads, *tail)
     else:
         counts = _resident_row_counts(spec, response, mask, mask_code, row_index, B, stream)
         name = 'vibo_elbo_fwd_bwd' if counts is None else 'vibo_elbo_fwd_bwd_counts'
@@ -590,7 +595,7 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
                   ability_mu=None if own_noise else post[0], ability_logvar=None if own_noise else post[1],
                   ability=None if no_sample else post[-1],
                   ability_k=ability_k, ability_ladj=ladj)
-    if train_step is not None and train_step[1]:
+    if train_step is not None and train_step.skip_finalize:
         raw.workspace = ws          # (kept alive until the epilogue has summed the partial records)
     return raw
 

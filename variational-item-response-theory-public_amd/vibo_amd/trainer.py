@@ -402,11 +402,11 @@ class FusedTrainer(_FusedStep):
         if self._draw_mode and not draws:
             ops._call('vibo_fill_normal', p(eps_ab), need, self.seed, noise_step, ab_stream, stream)
         fused_finalize = bool(step_bits & 2) and model._reducer is None
-        # A drawing step stores no sample: `raw.ability` rebuilds it on demand, from the rows this call was handed.  (The library's one
-        # exception, include/vibo_hip.h: fp32 rows gathered through row_index at fewer than 897 items keep the store.)
-        lazy = draws and not (row_index is not None and code != _lib.MASK_CODES and response.shape[1] <= 896)
+        # A drawing step stores no sample where the library lets it: `raw.ability` rebuilds it on demand, from the rows this call was handed
+        lazy = bool(lib.vibo_train_step_sample_optional(ctypes.byref(d), int(row_index is not None)))
+        step = ops.TrainStepCall(self._steps, fused_finalize, (self.seed, ab_stream) if draws else None, no_sample=lazy)
         raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, self.table, self.item_feat, None if draws else eps_ab, None,
-                                   _lib.REG_KL, True, B, train_step=(self._steps, fused_finalize, (self.seed, ab_stream) if draws else None, lazy))
+                                   _lib.REG_KL, True, B, train_step=step)
         raw.ability_source = self._head_of = _StepSample(self, (response, mask, code, row_index), B, ab_stream) if lazy else None
         self._pending = (d, eps_item, raw, ab_stream)
         self._folded_open = True
