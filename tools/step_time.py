@@ -4,7 +4,14 @@
    python tools/step_time.py [--irt 3] [--items 1000] [--ability-dim 1] [--batch 16] [--cond] [--flows 4] [--merge product]
 With --generative-model link | deep | residual: the module step (eager) against FusedDecoderTrainer's native step, eager and
 replayed from a hipGraph, A/B interleaved on one box in --blocks blocks of --steps steps; medians and ranges per leg:
-   python tools/step_time.py --generative-model deep --irt 2 --items 100 --batch 16 --persons 20000 --blocks 5"""
+   python tools/step_time.py --generative-model deep --irt 2 --items 100 --batch 16 --persons 20000 --blocks 5
+With --method vi | mle: the un-amortized methods -- the module step as vi.py / mle.py run it (autograd + torch.optim.Adam on the
+dense embeddings) against FusedVITrainer / FusedMLETrainer, eager and replayed, the same interleaved blocks (rows as 1-byte cell
+codes, the CLIs' default on the GPU):
+   python tools/step_time.py --method vi --irt 2 --persons 1000000 --items 1000 --batch 16 --ability-dim 8 --blocks 5 --steps 50
+With --table-update: the person-table update alone (vibo_person_table_adam, HIP events around the call) at --persons x --ability-dim
+entries per table, as a fraction of 24 B per entry at the 6.29 TB/s copy ceiling:
+   python tools/step_time.py --method vi --table-update --persons 1000000 --ability-dim 8"""
 import argparse
 import os
 import sys
@@ -30,6 +37,8 @@ ap.add_argument('--generative-model', default='irt', choices=['irt', 'link', 'de
 ap.add_argument('--hidden-dim', type=int, default=64)
 ap.add_argument('--blocks', type=int, default=5, help='MLP decoders: interleaved timing blocks per leg')
 ap.add_argument('--steps', type=int, default=200, help='MLP decoders: steps per block')
+ap.add_argument('--method', default='vibo', choices=['vibo', 'vi', 'mle'], help='vi | mle: the un-amortized methods (per-person tables)')
+ap.add_argument('--table-update', action='store_true', help='--method vi | mle: time vibo_person_table_adam alone')
 a = ap.parse_args()
 d = torch.device('cuda:0')
 g = torch.Generator(device=d).manual_seed(0)
@@ -41,8 +50,9 @@ class Data:
 
 
 data = Data()
-data.response = (torch.rand(P, I, device=d, generator=g) < 0.5).float()
-data.mask = torch.rand(P, I, device=d, generator=g) >= 0.1
+if not a.table_update:
+    data.response = (torch.rand(P, I, device=d, generator=g) < 0.5).float()
+    data.mask = torch.rand(P, I, device=d, generator=g) >= 0.1
 data.device = d
 cls = {1: M.VIBO_1PL, 2: M.VIBO_2PL, 3: M.VIBO_3PL}[a.irt]
 
@@ -83,6 +93,12 @@ def decoder_legs():
             rbuf.copy_(rows[k % 8]); gr.replay()
             return loss_g
         legs['native graph'] = replay
+    time_legs(legs, f'{a.generative_model} irt={a.irt} I={I} A={A} B={B} H={a.hidden_dim}')
+
+
+def time_legs(legs, label):
+    """A/B interleaved: --blocks blocks of --steps steps per leg; medians and ranges."""
+    import statistics
     for fn in legs.values():
         for k in range(4):
             fn(k)
@@ -96,10 +112,96 @@ def decoder_legs():
                 loss = fn(k)
             torch.cuda.synchronize()
             times[name].append((time.perf_counter() - t0) / a.steps * 1e6)
-            print(f'  block {blk} {name:13s}: {times[name][-1]:10.1f} us/step  loss {float(loss):.1f}')
+            print(f'  block {blk} {name:13s}: {times[name][-1]:10.1f} us/step  loss {float(loss):.4f}', flush=True)
     for name, t in times.items():
-        print(f'{a.generative_model} irt={a.irt} I={I} A={A} B={B} H={a.hidden_dim} {name:13s}: median {statistics.median(t):10.1f} us/step  '
-              f'range {min(t):.1f} .. {max(t):.1f}  ({a.blocks} blocks x {a.steps} steps)')
+        print(f'{label} {name:13s}: median {statistics.median(t):10.1f} us/step  '
+              f'range {min(t):.1f} .. {max(t):.1f}  ({a.blocks} blocks x {a.steps} steps)', flush=True)
+
+
+def person_table_legs():
+    """vi.py / mle.py's own train step (module + autograd + torch.optim.Adam over the dense embeddings) vs the native step, eager and
+    replayed.  Person = row of the resident split, minibatches are row-index vectors."""
+    from vibo_amd import ops
+    from vibo_amd.torch_core.vi import ResidentVI
+    from vibo_amd.trainer import FusedTrainer
+    mcls = {'vi': {1: M.VI_1PL, 2: M.VI_2PL, 3: M.VI_3PL}, 'mle': {1: M.MLE_1PL, 2: M.MLE_2PL, 3: M.MLE_3PL}}[a.method][a.irt]
+    response, mask = ops.pack_cell_codes(data.response, data.mask), None
+    del data.response, data.mask
+    rows = [torch.randperm(P, device=d)[:B].contiguous() for _ in range(8)]
+    rbuf = torch.zeros(B, dtype=torch.int64, device=d)
+
+    def build():
+        torch.manual_seed(0)
+        return mcls(A, P, I).to(d)
+    m_mod = build()
+    opt = torch.optim.Adam(m_mod.parameters(), lr=5e-3)                   # (as vi.py / mle.py build it)
+    face = ResidentVI(m_mod) if a.method == 'vi' else None
+
+    def module_step(k):
+        opt.zero_grad(set_to_none=True)
+        if face is not None:
+            loss = face.elbo_step(response, mask, annealing_factor=1.0, row_index=rows[k % 8])
+        else:
+            loss = m_mod.nll_step(rows[k % 8], response, mask, row_index=rows[k % 8])
+        loss.backward()
+        opt.step()
+        return loss.detach()
+    tr_e = FusedTrainer(build(), lr=5e-3, rng='native', seed=3)
+    tr_g = FusedTrainer(build(), lr=5e-3, rng='native', seed=3)
+    for k in range(4):
+        rbuf.copy_(rows[k]); tr_g.step(response, mask, row_index=rbuf)
+    torch.cuda.synchronize()
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(gr):
+        loss_g = tr_g.step(response, mask, row_index=rbuf)
+
+    def replay(k):
+        rbuf.copy_(rows[k % 8]); gr.replay()
+        return loss_g
+    legs = {'module eager': module_step, 'native eager': lambda k: tr_e.step(response, mask, row_index=rows[k % 8]), 'native graph': replay}
+    time_legs(legs, f'{a.method} irt={a.irt} P={P} I={I} A={A} B={B}')
+
+
+def table_update_time():
+    """vibo_person_table_adam alone, HIP events around each call (claims + update + reset: the export's three launches)."""
+    import ctypes
+    import statistics
+    from vibo_amd import _lib, ops
+    T = 2 if a.method == 'vi' else 1
+    n = P * A
+    stride = (n + 3) // 4 * 4
+    tabs = [torch.randn(P, A, device=d) for _ in range(T)]
+    m, v = torch.zeros(T, stride, device=d), torch.zeros(T, stride, device=d)
+    slot = torch.full((P,), -1, dtype=torch.int32, device=d)
+    bad = torch.zeros(1, dtype=torch.int32, device=d)
+    idx = torch.randperm(P, device=d)[:B].contiguous()
+    grows = torch.randn(2, B, 2 * A, device=d)
+    steps = torch.tensor([1, 0], dtype=torch.int32, device=d)
+    scal = torch.tensor([1.0, 5e-3], device=d)
+    dsc = ops._make_desc(ops.ElboSpec(irt_model=a.irt, ability_dim=A, given=True), B, I, _lib.MASK_U8, _lib.REG_KL, True, I, I)
+    p = ops._ptr
+
+    def call():
+        ops._call('vibo_person_table_adam', ctypes.byref(dsc), _lib.PTRAIN_VI if T == 2 else _lib.PTRAIN_MLE, P, p(idx), p(grows), p(scal[0:1]),
+                  p(scal[1:2]), p(steps), p(tabs[0]), p(tabs[1]) if T > 1 else None, p(m), p(v), stride, p(slot), p(bad), ops._stream(d))
+    for _ in range(5):
+        call()
+    torch.cuda.synchronize()
+    us = []
+    for _ in range(a.steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); call(); e1.record()
+        e1.synchronize()
+        us.append(e0.elapsed_time(e1) * 1e3)
+    floor = T * n * 24 / 6.29e12 * 1e6
+    med = statistics.median(us)
+    print(f'table update {a.method} P={P} A={A} ({T} x {n} entries, B={B}): median {med:.1f} us  range {min(us):.1f} .. {max(us):.1f} '
+          f'({a.steps} calls); 24 B/entry at 6.29 TB/s = {floor:.1f} us -> {floor / med:.2f} of the copy ceiling', flush=True)
+
+
+if a.method != 'vibo':
+    table_update_time() if a.table_update else person_table_legs()
+    sys.exit(0)
 
 
 if a.generative_model != 'irt':

@@ -1,7 +1,8 @@
 """ctypes binding of libvibo_hip.so.  The C ABI is declared in include/vibo_hip.h and read from there: every export's
 restype / argtypes come from its prototype (parse_prototypes); the constants and the two structs mirror the header by hand
 (tests/test_capi_symbols.py compares them).  Exports declared in a header of their own beside it (EXTRA_HEADERS:
-vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h) are bound the same way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself, EXTRA_SYMBOLS and SIGN_ROWS_SYMBOLS are theirs.
+vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h) are bound the same way; EXPORTED_SYMBOLS stays the list of
+vibo_hip.h itself, EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS and PERSON_TABLE_SYMBOLS are theirs.
 
 The product path has no CPU or eager-PyTorch fallback: if the HIP library is
 missing or a call fails, this module raises.
@@ -103,7 +104,7 @@ def parse_prototypes(header):
     return protos
 
 
-EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h')
+EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h', 'vibo_hip_person_tables.h')
 
 with open(HEADER_PATH) as _header:
     PROTOTYPES = parse_prototypes(_header.read())
@@ -118,6 +119,9 @@ for _name in EXTRA_HEADERS:
 # (one list per header: EXTRA_SYMBOLS is vibo_hip_decoder_multi.h's, as its tests pin it)
 EXTRA_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_decoder_multi.h']
 SIGN_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sign_rows.h']
+PERSON_TABLE_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_person_tables.h']      # the VI / MLE train step (trainer.FusedVITrainer / FusedMLETrainer)
+PTRAIN_VI, PTRAIN_MLE = 0, 1                                            # VIBO_PTRAIN_*
+PTRAIN_MAX_BLOCKS = 2048                                                # VIBO_PTRAIN_MAX_BLOCKS: the table update's grid cap
 
 _lib = None
 

@@ -49,15 +49,29 @@ def build_parser():
     p.add_argument('--cuda', action='store_true', default=False)
     p.add_argument('--row-format', choices=['auto', 'f32', 'codes'], default='auto',
                    help="device-resident rows: fp32 responses + mask bytes, or one byte per cell (see the VIBO CLI)")
+    p.add_argument('--native-step', action='store_true', default=False,
+                   help='train with the native step (trainer.FusedMLETrainer: prologue / fused ELBO / epilogue kernels with dense Adam over '
+                        'the per-person table, no autograd, no torch.optim; replayed from a hipGraph unless --no-graph): needs --cuda; '
+                        'without the flag the model trains through the module + torch.optim.Adam as before')
+    p.add_argument('--no-graph', action='store_true', default=False,
+                   help='with --native-step: launch every train step eagerly instead of replaying a hipGraph')
+    p.add_argument('--rng', choices=['torch', 'native'], default='torch',
+                   help='accepted for symmetry with the VI CLI: maximum likelihood draws no noise')
     return p
 
 
-def epoch_loss(model, optimizer, data, batch_size, train, index_of=lambda rows: rows):
-    """One pass over a resident split; minibatch loss weighted by its size (AverageMeter semantics, mle.py:200,224)."""
+def epoch_loss(model, optimizer, data, batch_size, train, index_of=lambda rows: rows, trainer=None, graphed=None):
+    """One pass over a resident split; minibatch loss weighted by its size (AverageMeter semantics, mle.py:200,224).
+    Training with trainer= (a FusedMLETrainer) or graphed= (vibo.GraphedTrainStep around it) runs the native step instead of
+    the module + optimizer, as vibo.train_epoch does."""
     model.train(train)
     wsum, count = torch.zeros((), device=data.device), 0
     for rows in data.batches(batch_size, shuffle=train):
-        if train:
+        if train and graphed is not None:
+            loss = graphed(rows, 1.0)
+        elif train and trainer is not None:
+            loss = trainer.step(data.response, data.mask, row_index=rows, index=index_of(rows))
+        elif train:
             optimizer.zero_grad(set_to_none=True)
             loss = model.nll_step(index_of(rows), data.response, data.mask, row_index=rows)
             loss.backward()
@@ -74,6 +88,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.artificial_missing_perc:
         args.no_infer_dict = False                                           # mle.py:78-79
+    if args.native_step and not args.cuda:
+        raise SystemExit('--native-step needs --cuda (the native train step has no CPU path: drop the flag)')
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     if config.IS_REAL_WORLD[args.dataset]:                                   # mle.py:84-98
@@ -107,12 +123,18 @@ def main(argv=None):
         print(f'Found MAX_ITERS={args.max_iters}, setting EPOCHS={args.epochs}')
     model = {'1pl': MLE_1PL, '2pl': MLE_2PL, '3pl': MLE_3PL}[args.irt_model](args.ability_dim, num_person, num_item).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
+    trainer = graphed = None
+    if args.native_step:                      # opt-in: the whole step natively, person = row of the resident split
+        from ..trainer import FusedTrainer
+        trainer = FusedTrainer(model, lr=args.lr, rng=args.rng, seed=args.seed)
+        if not args.no_graph:
+            graphed = _cli.GraphedTrainStep(trainer, train, args.batch_size)
 
     best_loss = np.inf
     train_losses, test_losses, train_times = np.zeros(args.epochs), np.zeros(args.epochs), np.zeros(args.epochs)
     for epoch in range(args.epochs):
         t0 = time.time()
-        train_losses[epoch] = epoch_loss(model, optimizer, train, args.batch_size, True)
+        train_losses[epoch] = epoch_loss(model, optimizer, train, args.batch_size, True, trainer=trainer, graphed=graphed)
         if args.cuda:
             torch.cuda.synchronize()
         train_times[epoch] = t0 - time.time()                                # negative, like the reference (mle.py:268)

@@ -58,6 +58,15 @@ def build_parser():
                    help="device-resident rows: fp32 responses + mask bytes, or one byte per cell (see the VIBO CLI)")
     p.add_argument('--store-predictive-samples', action='store_true', default=False,
                    help='keep all S posterior-predictive samples [S,P,I,1] like the reference (default: their mean)')
+    p.add_argument('--native-step', action='store_true', default=False,
+                   help='train with the native step (trainer.FusedVITrainer: prologue / fused ELBO / epilogue kernels with dense Adam over '
+                        'the per-person tables, no autograd, no torch.optim; replayed from a hipGraph unless --no-graph): needs --cuda; '
+                        'without the flag the model trains through the module + torch.optim.Adam as before')
+    p.add_argument('--no-graph', action='store_true', default=False,
+                   help='with --native-step: launch every train step eagerly instead of replaying a hipGraph')
+    p.add_argument('--rng', choices=['torch', 'native'], default='torch',
+                   help="reparameterisation noise of the native step: torch.randn (the stream torch.manual_seed(--seed) governs) or "
+                        "the library's Philox generator drawn inside the prologue kernel")
     return p
 
 
@@ -102,6 +111,8 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.artificial_missing_perc > 0:
         args.no_predictive = False                                           # vi.py:80-81
+    if args.native_step and not args.cuda:
+        raise SystemExit('--native-step needs --cuda (the native train step has no CPU path: drop the flag)')
     torch.manual_seed(args.seed)
     np.random.seed(args.seed)
     args.out_dir = os.path.join(args.out_dir, 'vi_{}_{}_{}person_{}item_{}maskperc_{}ability'.format(
@@ -130,12 +141,18 @@ def main(argv=None):
     model = {'1pl': VI_1PL, '2pl': VI_2PL, '3pl': VI_3PL}[args.irt_model](args.ability_dim, num_person, num_item).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=args.lr)
     face = ResidentVI(model)
+    trainer = graphed = None
+    if args.native_step:                      # opt-in: the whole step natively, person = row of the resident split
+        from ..trainer import FusedTrainer
+        trainer = FusedTrainer(model, lr=args.lr, rng=args.rng, seed=args.seed)
+        if not args.no_graph:
+            graphed = _cli.GraphedTrainStep(trainer, train, args.batch_size)
 
     best_loss = np.inf
     train_losses, train_times = np.zeros(args.epochs), np.zeros(args.epochs)
     for epoch in range(args.epochs):
         t0 = time.time()
-        train_loss = _cli.train_epoch(face, optimizer, train, args, epoch, args.batch_size)
+        train_loss = _cli.train_epoch(face, optimizer, train, args, epoch, args.batch_size, trainer=trainer, graphed=graphed)
         if args.cuda:
             torch.cuda.synchronize()
         train_losses[epoch] = train_loss

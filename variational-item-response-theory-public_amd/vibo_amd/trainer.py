@@ -35,8 +35,9 @@ populated.
 One entry point: `FusedTrainer(model, ...)` returns the class that runs the model's step natively -- fused_trainer_for() is the
 table: FusedTrainer itself (plain), FusedCondFlowTrainer (vibo_ctrain_*: --conditional-posterior / --n-norm-flows), FusedMeanTrainer
 (vibo_mtrain_*: --ability-merge mean), FusedDecoderTrainer (vibo_dtrain_*[_cond]: --generative-model link | deep | residual; the
-conditional posterior asked for with `conditional=True`) -- or says why none does: those train through the module + torch.optim.
-All four share _FusedStep: the state, the noise, and step() = forward_backward() -> reduce_shards() -> update().
+conditional posterior asked for with `conditional=True`), FusedVITrainer / FusedMLETrainer (vibo_ptrain_*: the un-amortized VI_*PL /
+MLE_*PL models, dense Adam over their per-person tables) -- or says why none does: those train through the module + torch.optim.
+All share _FusedStep: the state, the noise, and step() = forward_backward() -> reduce_shards() -> update().
 """
 import ctypes
 
@@ -51,7 +52,17 @@ def fused_trainer_for(model, hidden_dim=None, conditional=False):
     """THE coverage table -> (the trainer class that runs the model's whole train step natively, None), or (None, why none does:
     the constructors' NotImplementedError).  hidden_dim: the encoder's width when the caller knows it (else read from the model);
     conditional: FusedDecoderTrainer was asked for the conditional posterior (conditional=True).  Reads the model's
-    generative_model, ability_merge, conditional_posterior, n_norm_flows, ability_dim, num_item and _reducer, nothing else."""
+    generative_model, ability_merge, conditional_posterior, n_norm_flows, ability_dim, num_item and _reducer, nothing else -- but for
+    the two un-amortized models (no encoder: a caller-supplied posterior, `spec.given`, and per-person nn.Embedding tables), which
+    are known by their embeddings: VI_*PL -> FusedVITrainer, MLE_*PL -> FusedMLETrainer."""
+    if getattr(getattr(model, 'spec', None), 'given', False) and not hasattr(model, 'ability_encoder'):
+        vi = all(hasattr(model, name) for name in ('ability_mu_lookup', 'ability_logvar_lookup', 'item_mu_lookup', 'item_logvar_lookup'))
+        if vi or (hasattr(model, 'ability') and hasattr(model, 'item_feat')):
+            cls = FusedVITrainer if vi else FusedMLETrainer
+            if model.ability_dim > _lib.MAX_ABILITY_DIM_FAST:
+                return None, (f'{cls.__name__}: ability_dim <= {_lib.MAX_ABILITY_DIM_FAST} (the caller-supplied posterior runs on the '
+                              f'row-split kernels); {_MODULE_PATH}')
+            return cls, None
     kind, merge, A = getattr(model, 'generative_model', 'irt'), model.ability_merge, model.ability_dim
     cond, flows = bool(model.conditional_posterior), model.n_norm_flows > 0
 
@@ -93,7 +104,8 @@ def fused_trainer_for(model, hidden_dim=None, conditional=False):
 
 
 def fused_trainer_covers(model, hidden_dim=None):
-    """True when FusedTrainer, FusedCondFlowTrainer or FusedMeanTrainer runs the model's whole train step natively (the IRT decoder)."""
+    """True when FusedTrainer, FusedCondFlowTrainer, FusedMeanTrainer, FusedVITrainer or FusedMLETrainer runs the model's whole train
+    step natively (the IRT decoder)."""
     return fused_trainer_for(model, hidden_dim)[0] not in (None, FusedDecoderTrainer)
 
 
@@ -103,7 +115,7 @@ def fused_decoder_trainer_covers(model, hidden_dim=None, conditional=False):
 
 
 class _FusedStep:
-    """What the four trainers share: the state every step reads, the noise, and the step protocol."""
+    """What the trainers share: the state every step reads, the noise, and the step protocol."""
 
     def __init__(self, model, lr, rng, seed, fold=False, conditional=False, keep_item_noise=True):
         covering, why = fused_trainer_for(model, conditional=conditional)
@@ -118,28 +130,34 @@ class _FusedStep:
         self._folded_open = False             # a folded forward_backward() whose update() has not run yet
         self._pending = None                  # what forward_backward() leaves for update(): the arguments of the class's _update()
         self.last = None                      # RawElbo of the last step (posterior outputs, scalars)
-        enc = model.ability_encoder
-        self.hidden = (enc.mlp1 if model.ability_merge == 'mean' else enc.mlp)[0].weight.shape[0]
+        enc = getattr(model, 'ability_encoder', None)      # (None: the un-amortized models have no encoder)
+        self.hidden = 0 if enc is None else (enc.mlp1 if model.ability_merge == 'mean' else enc.mlp)[0].weight.shape[0]
         # the item tensors and their moments, Adam's counters and scalars, the item sample, the loss
-        self.item_mu = model.item_encoder.mu_lookup.weight
-        self.item_lv = model.item_encoder.logvar_lookup.weight
-        assert self.item_mu.is_contiguous() and self.item_lv.is_contiguous()
+        # (item_lv None: the item table is not variational -- MLE -- and is its own "sample"; its moments are one table's)
+        self.item_mu, self.item_lv = self._item_tensors(model)
+        variational = self.item_lv is not None
+        assert self.item_mu.is_contiguous() and (not variational or self.item_lv.is_contiguous())
         dev, n_item = self.item_mu.device, self.item_mu.numel()
-        self.item_m = torch.zeros(2 * n_item, device=dev)
-        self.item_v = torch.zeros(2 * n_item, device=dev)
+        self.item_m = torch.zeros((2 if variational else 1) * n_item, device=dev)
+        self.item_v = torch.zeros((2 if variational else 1) * n_item, device=dev)
         self._steps = torch.zeros(2, dtype=torch.int32, device=dev)      # [Adam step t, completed steps (noise counter)]
         self.lr = torch.tensor(float(lr), device=dev)
         self.beta = torch.tensor(1.0, device=dev)
         self._beta_host = 1.0
-        self.item_feat = torch.empty_like(self.item_mu)
+        self.item_feat = torch.empty_like(self.item_mu) if variational else self.item_mu
         self.loss = torch.zeros((), device=dev)
         # Reparameterisation noise: 'torch' = torch.randn on the model's generators (the reference's stream for a given seed),
         # 'native' = Philox4x32-10 keyed by `seed` (vibo_fill_normal's streams, ~5x faster on [1M, 8]).
         # (person-sharded: item noise is the same on every rank, ability noise uses stream 1 + rank)
         self.rng, self.seed = rng, int(seed)
         self.fused_noise = True               # rng='native': the noise is drawn inside the prologue launch
-        self._eps_item = torch.empty_like(self.item_mu) if keep_item_noise else None
+        self._eps_item = torch.empty_like(self.item_mu) if keep_item_noise and variational else None
         self._eps_ab = {}
+
+    @staticmethod
+    def _item_tensors(model):
+        """Where the model keeps its item tensors -> (mean, log-variance)."""
+        return model.item_encoder.mu_lookup.weight, model.item_encoder.logvar_lookup.weight
 
     @staticmethod
     def _flatten(plist):
@@ -728,3 +746,176 @@ class FusedDecoderTrainer(_FusedStep):
                   p(self.beta), p(self.lr), p(self._steps), p(self.par_flat), p(self.par_m), p(self.par_v),
                   p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.loss), ops._stream(scratch.device))
         return self.loss
+
+
+class _PersonTableStep(_FusedStep):
+    """The fused train step of the two un-amortized methods, whose person side is nn.Embedding tables with one row per person
+    (include/vibo_hip_person_tables.h): vibo_ptrain_prologue (Adam's tick, the minibatch's rows gathered into the [B, 2A] posterior
+    the ELBO call reads, the inverse map person -> minibatch position; VI: item sample, item KL, optionally the Philox noise) ->
+    vibo_elbo_fwd_bwd in VIBO_POSTERIOR_GIVEN mode -> vibo_ptrain_epilogue (loss, item backward + Adam, and Adam over EVERY row of the
+    person tables with the minibatch's gradients scattered in: torch.optim.Adam on a dense embedding, not a lazy variant -- rows
+    outside the minibatch decay their moments and move on momentum).  No PyTorch autograd node, no torch.optim: with rng='native'
+    the step is those three calls and replays from a hipGraph.  The parameters are updated in place in the Embedding weights
+    (state_dict unchanged); the tables' moments are `person_m` / `person_v` [tables, P, A].
+
+        step(response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None, index=None)
+
+    index [B] int64 on the trainer's device: the person of every minibatch position; default `row_index` (person = row of the resident
+    split), else arange(B).  A person named twice gets the sum of its positions' gradients (embedding backward); an index outside
+    the tables is never dereferenced: its position runs on the posterior (0 | 0), its gradient is dropped and `bad_index_count`
+    counts it.  Rows: fp32 + bool / uint8 mask, CellCodes, a `row_index` gather from a resident matrix."""
+    MODE = None
+
+    def __init__(self, model, lr=5e-3, rng='torch', seed=0, fused_noise=True, fold=True, max_batch=None):
+        # (fused_noise / fold / max_batch: FusedTrainer's keywords; this step is prologue / ELBO call / epilogue either way)
+        super().__init__(model, lr, rng, seed)
+        self.tables = self._person_tables(model)
+        P, A = self.tables[0].shape
+        dev = self.item_mu.device
+        assert all(t.shape == (P, A) and t.is_contiguous() and t.dtype == torch.float32 and t.device == dev for t in self.tables)
+        self.num_person = P
+        # each table's moments start 16 bytes aligned (the update's vector path): the stride between them is P A rounded up to 4
+        n, self._moment_stride = P * A, (P * A + 3) // 4 * 4
+        self.person_m, self.person_v = (torch.zeros(len(self.tables), self._moment_stride, device=dev)[:, :n].view(-1, P, A)
+                                        for _ in range(2))
+        self.slot = torch.full((P,), -1, dtype=torch.int32, device=dev)      # person -> owning minibatch position; all -1 between steps
+        self._bad = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.kl_parts = torch.empty((self.item_mu.numel() + 63) // 64, device=dev) if self.item_lv is not None else None
+        # per batch size, never freed or replaced (a captured hipGraph keeps the pointers): the posterior table, the default index
+        self._post, self._arange = {}, {}
+
+    @property
+    def bad_index_count(self):
+        """Minibatch positions so far whose index was outside the tables (sticky; one device read)."""
+        return int(self._bad)
+
+    def invalidate(self):
+        """_FusedStep.invalidate, and the inverse map is all -1 again (the way out after a step that died between its two halves)."""
+        super().invalidate()
+        self.slot.fill_(-1)
+
+    reprime = invalidate
+
+    @torch.no_grad()
+    def step(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None, index=None):
+        """One train step; returns the loss (device scalar).  = forward_backward(); update()."""
+        self._forward_backward(response, mask, beta, row_index, eps_item, eps_ability, index)
+        return self._finish()
+
+    @torch.no_grad()
+    def forward_backward(self, response, mask, beta=None, row_index=None, eps_item=None, eps_ability=None, index=None):
+        return self._forward_backward(response, mask, beta, row_index, eps_item, eps_ability, index)
+
+    def reduce_shards(self):
+        """Nothing to reduce: the person tables are not sharded."""
+
+    def _index(self, index, row_index, B, dev):
+        """The step's person index, checked on the host before anything is launched."""
+        name = type(self).__name__
+        if index is None:
+            index = row_index
+        if index is None:
+            if B > self.num_person:
+                raise ValueError(f'{name}: {B} rows for tables of {self.num_person} persons: pass `index`')
+            index = self._arange.get(B)
+            if index is None:
+                index = self._arange[B] = torch.arange(B, dtype=torch.int64, device=dev)
+            return index
+        if index.device != dev:
+            raise ValueError(f'{name}: `index` is on {index.device}, the tables are on {dev}')
+        if index.dtype != torch.int64:
+            raise TypeError(f'{name}: `index` must be int64 (got {index.dtype})')
+        if index.numel() != B:
+            raise ValueError(f'{name}: `index` names {index.numel()} persons for a minibatch of {B}')
+        return index.reshape(-1) if index.is_contiguous() else index.reshape(-1).contiguous()
+
+    def _forward_backward(self, response, mask, beta, row_index, eps_item, eps_ability, index=None):
+        name, p = type(self).__name__, ops._ptr
+        if mask is not None and mask.dtype == torch.int64:
+            raise NotImplementedError(f'{name} reads bool / uint8 masks; use the module step + torch.optim.Adam for int64 masks')
+        dev = self.item_mu.device
+        B = int(row_index.numel()) if row_index is not None else len(response)
+        index = self._index(index, row_index, B, dev)
+        if self._pending is not None:         # a forward_backward() whose update() never ran left its claims in the map
+            self.slot.fill_(-1)
+        # (rows the kernels cannot read in chunks of 4 cells -- a width that is no multiple of 4, not padded -- are copied, as the module path does)
+        response, mask, row_index = ops.chunkable_rows(response, mask, row_index)
+        response, mask, code, B, I, stream, d, ab_stream = self._begin(response, mask, beta, row_index, _lib.REG_KL)
+        A = self.model.ability_dim
+        post = self._post.get(B)
+        if post is None:
+            post = self._post[B] = torch.empty(B, 2 * A, device=dev)
+        eps_item, eps_ab, native = self._noise(B, dev, eps_item, eps_ability)
+        lv = self.item_lv
+        ops._call('vibo_ptrain_prologue', ctypes.byref(d), self.MODE, self.num_person, p(self.tables[0]),
+                  p(self.tables[1]) if len(self.tables) > 1 else None, p(index), p(post), p(self.slot), p(self._bad),
+                  p(self.item_mu) if lv is not None else None, p(lv), p(eps_item), self.seed, 1 if native else 0,
+                  p(eps_ab) if native else None, ab_stream, p(self.item_feat) if lv is not None else None, p(self.kl_parts),
+                  p(self._steps), stream)
+        if eps_ab is None:                    # rng='torch': the reference's order, item noise then ability noise
+            eps_ab = torch.randn(B, A, dtype=torch.float32, device=dev)
+        raw = ops._BACKEND['elbo'](self.model.spec, response, mask, code, row_index, post, self.item_feat, eps_ab, None, _lib.REG_KL,
+                                   True, B)
+        self._pending = (d, eps_item, raw, index)
+        self.last = raw
+        return raw
+
+    def _update(self, d, eps_item, raw, index):
+        self._pending = None
+        p = ops._ptr
+        ops._call('vibo_ptrain_epilogue', ctypes.byref(d), self.MODE, self.num_person, p(raw.flat), p(index), p(self.kl_parts),
+                  p(eps_item), p(self.beta), p(self.lr), p(self._steps), p(self.tables[0]),
+                  p(self.tables[1]) if len(self.tables) > 1 else None, p(self.person_m), p(self.person_v), self._moment_stride,
+                  p(self.slot), p(self.item_mu), p(self.item_lv), p(self.item_m), p(self.item_v), p(self.loss),
+                  ops._stream(raw.flat.device))
+        return self.loss
+
+
+class FusedVITrainer(_PersonTableStep):
+    """_PersonTableStep for VI_1PL / 2PL / 3PL (vi.py's loop, models.py:100-172): tables ability_mu_lookup / ability_logvar_lookup,
+    variational items in item_mu_lookup / item_logvar_lookup.  rng='torch' draws torch.randn_like(item std), then
+    torch.randn(B, A), from the default generator -- VI_1PL._run's order, so the same torch.manual_seed gives the module step's
+    draws; rng='native' draws both inside the prologue; given eps_item / eps_ability replay recorded noise.
+    (`FusedTrainer(vi_model, ...)` returns this class.)"""
+    MODE = _lib.PTRAIN_VI
+
+    @staticmethod
+    def _item_tensors(model):
+        return model.item_mu_lookup.weight, model.item_logvar_lookup.weight
+
+    @staticmethod
+    def _person_tables(model):
+        return [model.ability_mu_lookup.weight, model.ability_logvar_lookup.weight]
+
+    def _noise(self, B, dev, eps_item, eps_ability):
+        """-> (eps_item, eps_ab, native): the caller's; this trainer's buffers for the prologue to fill; or the item draw from
+        torch's default generator, eps_ab None (drawn behind the prologue)."""
+        if eps_item is not None or eps_ability is not None:
+            if eps_item is None or eps_ability is None:
+                raise ValueError('pass both eps_item and eps_ability, or neither')
+            return eps_item.contiguous().float(), eps_ability.contiguous().float(), False
+        if self.rng == 'native':
+            return self._eps_item, self._ab_buffer(B, dev), True
+        return torch.randn_like(self.item_lv), None, False
+
+
+class FusedMLETrainer(_PersonTableStep):
+    """_PersonTableStep for MLE_1PL / 2PL / 3PL (mle.py's loop, models.py:22-97; MLE_1PL.nll_step's loss, the mean over all
+    B x num_item cells of mask x BCE): one table, `ability`; the item table `item_feat` is a plain parameter.  No noise: the ELBO
+    call runs on (ability | logvar 0) with a persistent zero eps, so the sample is the point estimate; beta, rng and given noise
+    are accepted and not used.  (`FusedTrainer(mle_model, ...)` returns this class.)"""
+    MODE = _lib.PTRAIN_MLE
+
+    @staticmethod
+    def _item_tensors(model):
+        return model.item_feat.weight, None
+
+    @staticmethod
+    def _person_tables(model):
+        return [model.ability.weight]
+
+    def _noise(self, B, dev, eps_item, eps_ability):
+        zero = self._eps_ab.get(B)
+        if zero is None:
+            zero = self._eps_ab[B] = torch.zeros(B, self.model.ability_dim, device=dev)
+        return None, zero, False
