@@ -25,6 +25,7 @@ ap.add_argument('--missing', type=float, default=0.1)
 ap.add_argument('--gather', action='store_true', help='rows through a random row_index permutation (shuffled minibatch)')
 ap.add_argument('--given', action='store_true', help='caller-supplied per-person posterior (VIBO_POSTERIOR_GIVEN, the --ability-merge mean path)')
 ap.add_argument('--codes', action='store_true', help='rows as 1-byte cell codes (VIBO_MASK_CODES, Format P) instead of fp32 + mask')
+ap.add_argument('--tiles', action='store_true', help='the launches go out on the matrix\' tile image from the third on (ops.TILE_ROWS_PLAIN_LAUNCHES; 16 384 persons or more); tools/ms_timing.py then reads the timing buffer of the tile-rows unit')
 ap.add_argument('--kernel', choices=['auto', 'matrix', 'valu'], default='auto', help='pin a row-split kernel (vibo_desc.flags)')
 ap.add_argument('--cond-valu', action='store_true', help='conditional posterior: the VALU passes (VIBO_FLAG_COND_VALU) instead of the matrix-pipe ones')
 ap.add_argument('--cond-three-pass', action='store_true', help='conditional posterior at ability_dim 1: the separate first pass (VIBO_FLAG_COND_THREE_PASS) instead of the one folded into the matrix kernel')
@@ -48,6 +49,8 @@ if a.init_like:
     item = torch.randn(I, D, device=d, generator=g) + torch.exp(0.5 * torch.randn(I, D, device=d, generator=g)) * torch.randn(I, D, device=d, generator=g)
 eps = torch.randn(P, A, device=d, generator=g)
 m, code = ops.prepare_mask(mask)
+if a.tiles:
+    ops.TILE_ROWS_PLAIN_LAUNCHES = True      # (these are plain launches: let them use the image)
 if a.codes:
     resp, m, code = ops.prepare_rows(ops.pack_cell_codes(resp, mask), None)
     del mask

@@ -7,6 +7,7 @@
 
 #include "../../include/vibo_hip.h"
 #include "../../include/vibo_hip_sign_rows.h"
+#include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_cond.hpp"
 #include "vibo_general.hpp"
 #include "vibo_helpers.hpp"
@@ -43,9 +44,9 @@ static hipError_t launch_split(const vibo_desc* d, const Plan& pl, const ElboPar
     static SplitLauncher* const valu[3][3] = {{launch_elbo_split_a2, launch_elbo_split_a4, launch_elbo_split_a8},
                                               {launch_elbo_split_g2, launch_elbo_split_g4, launch_elbo_split_g8},
                                               {launch_elbo_split_c2, launch_elbo_split_c4, launch_elbo_split_c8}};
-    static SplitLauncher* const matrix[3][4] = {{launch_elbo_msplit_a, launch_elbo_msplit_g, launch_elbo_msplit_c, launch_elbo_msplit_s},
-                                                {launch_elbo_msplit_fa, launch_elbo_msplit_fg, launch_elbo_msplit_fc, nullptr},
-                                                {launch_elbo_msplit_xa, launch_elbo_msplit_xg, nullptr, nullptr}};      // plain | flows | fused
+    static SplitLauncher* const matrix[3][5] = {{launch_elbo_msplit_a, launch_elbo_msplit_g, launch_elbo_msplit_c, launch_elbo_msplit_s, launch_elbo_msplit_t},
+                                                {launch_elbo_msplit_fa, launch_elbo_msplit_fg, launch_elbo_msplit_fc, nullptr, nullptr},
+                                                {launch_elbo_msplit_xa, launch_elbo_msplit_xg, nullptr, nullptr, nullptr}};      // plain | flows | fused
     SplitVariant v;
     if (!split_variant(d, pl, p, &v)) return hipErrorInvalidValue;      // (also: none of the table's empty cells)
     SplitLauncher* const unit = v.engine == Engine::Narrow ? launch_elbo_narrow
@@ -339,9 +340,11 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     const int num_cu = device_cus();
     int rc = check_desc(d, true);
     if (rc) return rc;
-    const bool sign_rows = d->mask_dtype == VIBO_MASK_SIGN;
+    const bool tile_rows = d->mask_dtype == VIBO_MASK_TILES;
+    const bool sign_rows = d->mask_dtype == VIBO_MASK_SIGN || tile_rows;      // (the row formats of this call alone)
     if (sign_rows && (a.row_index || a.row_counts))
-        return fail(-8, "VIBO_MASK_SIGN rows: rows in order only (row_index must be NULL), without caller-supplied row counts");
+        return fail(-8, "%s rows: rows in order only (row_index must be NULL), without caller-supplied row counts",
+                    tile_rows ? "VIBO_MASK_TILES" : "VIBO_MASK_SIGN");
     if ((!a.response && d->mask_dtype != VIBO_MASK_CODES) || !a.table || !a.item || !a.out_scalars)
         return fail(-5, "null required pointer");
     // (null eps / ability_mu / ability_logvar / ability: the folded step on the matrix kernel only, checked once the plan is known)
@@ -362,7 +365,8 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     const bool row_split = path == Path::Panels || path == Path::Split;
     if (d->mask_dtype == VIBO_MASK_CODES && !row_split) return codes_unsupported();
     if (sign_rows && !(path == Path::Split && pl.engine == Engine::Matrix))
-        return fail(-8, "VIBO_MASK_SIGN rows: the response rows must be 16-byte aligned with a stride that is a multiple of 4");
+        return tile_rows ? fail(-8, "VIBO_MASK_TILES rows: the tile image must be 16-byte aligned")
+                         : fail(-8, "VIBO_MASK_SIGN rows: the response rows must be 16-byte aligned with a stride that is a multiple of 4");
     if (pl.given() && path != Path::Panels)
         return fail(-8, "VIBO_POSTERIOR_GIVEN: rows must be aligned for 4-cell chunks (see vibo_amd.ops.pad_rows)");
     const StepContract step = step_contract(d, pl, a.row_index != nullptr);
@@ -482,11 +486,43 @@ int vibo_rows_sign_is_mask(const vibo_desc* d, const float* response, const void
     return 0;
 }
 
+int vibo_tile_rows_supported(const vibo_desc* d) {
+    return (d && d->mask_dtype == VIBO_MASK_TILES && check_desc(d, true) == 0) ? 1 : 0;
+}
+
+size_t vibo_tile_rows_bytes(const vibo_desc* d) {
+    if (!vibo_tile_rows_supported(d)) return 0;
+    return (size_t)(((long long)d->num_person + 31) / 32) * (size_t)((d->num_item + 127) / 128) * kTileWaveBytes;
+}
+
+int vibo_tile_rows_build(const vibo_desc* src, const void* response, const void* mask, void* image, size_t image_bytes, void* stream) {
+    if (!src) return fail(-1, "null descriptor");
+    const int fmt = src->mask_dtype;
+    vibo_desc t = *src;                      // the launches that will read the image
+    t.mask_dtype = VIBO_MASK_TILES;
+    const int rc = check_desc(&t, true);
+    if (rc) return rc;
+    if (fmt != VIBO_MASK_U8 && fmt != VIBO_MASK_NONE && fmt != VIBO_MASK_SIGN && fmt != VIBO_MASK_CODES)
+        return fail(-8, "vibo_tile_rows_build: source rows as fp32 with VIBO_MASK_U8 / VIBO_MASK_NONE / VIBO_MASK_SIGN, or VIBO_MASK_CODES");
+    if (!image || (fmt != VIBO_MASK_CODES && !response)) return fail(-5, "null required pointer");
+    if ((fmt == VIBO_MASK_U8 || fmt == VIBO_MASK_CODES) != (mask != nullptr)) return fail(-5, "mask pointer / mask_dtype mismatch");
+    if (image_bytes < vibo_tile_rows_bytes(&t)) return fail(-7, "tile image too small: %zu < %zu", image_bytes, vibo_tile_rows_bytes(&t));
+    if ((uintptr_t)image & 15) return fail(-7, "the tile image must be 16-byte aligned");
+    const float* resp = fmt == VIBO_MASK_CODES ? nullptr : static_cast<const float*>(response);
+    const hipError_t e = launch_tile_rows_build(src, resp, mask, rows_vec_ok(src, resp, mask), image, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "tile_rows_build launch");
+    return 0;
+}
+
 // The folded step's contract as the step queries ask it: none for a refused descriptor.  (VIBO_MASK_SIGN rows answer as the same rows
 // under a u8 mask: row modes 0 and 3 agree on every rule of the contract.)
 static StepContract step_query(const vibo_desc* d, bool rows_gathered) {
     vibo_desc u = d ? *d : vibo_desc{};      // (null: refused by the descriptor check like any zeroed descriptor)
     if (u.mask_dtype == VIBO_MASK_SIGN) u.mask_dtype = VIBO_MASK_U8;
+    if (u.mask_dtype == VIBO_MASK_TILES) {      // (a tile image: the same matrix as padded rows under a u8 mask)
+        u.mask_dtype = VIBO_MASK_U8;
+        u.response_row_stride = u.mask_row_stride = (u.num_item + 3) & ~3;
+    }
     Plan pl;
     return plan_for(&u, &pl) == 0 ? step_contract(&u, pl, rows_gathered) : StepContract{};
 }

@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/vibo_hip.h"
-#include "../../include/vibo_hip_sign_rows.h"
+#include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
 #include "vibo_philox.hpp"
 #include "vibo_train_hook.hpp"
@@ -692,7 +692,7 @@ using namespace vibo;
 static int ct_check(const vibo_desc* d, int hidden_dim, CtLayout* L) {
     if (!d || d->abi_version != VIBO_ABI_VERSION) return -2;
     if (d->posterior == VIBO_POSTERIOR_GIVEN) return -6;
-    if (d->mask_dtype == VIBO_MASK_SIGN) return -8;      // (VIBO_MASK_SIGN: a row format of the ELBO call alone)
+    if (VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return -8;      // (VIBO_MASK_SIGN / _TILES: row formats of the ELBO call alone)
     if (hidden_dim < 1 || hidden_dim > 64) return -6;                 // (one 64-wide tile of the matrix-pipe MLP kernels; narrower: zero-padded)
     if (d->num_item < 1 || d->ability_dim < 1 || d->ability_dim > VIBO_MAX_ABILITY_DIM || d->n_flows < 0 || d->n_flows > VIBO_MAX_FLOWS) return -3;
     *L = ct_layout(d->num_item, d->ability_dim, d->irt_model, d->posterior == VIBO_POSTERIOR_CONDITIONAL ? 1 : 0, d->n_flows, hidden_dim);

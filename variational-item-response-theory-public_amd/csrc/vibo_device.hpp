@@ -172,6 +172,9 @@ __device__ __forceinline__ uint32_t pack_cell_codes4(const uint32_t w, const uin
 // accumulators: no `m * 0xFF` -- hipcc turns the shift-and-subtract form above back into a quarter-rate v_mul_lo_u32.
 //   fp32 rows: selector byte = 2 [correct] + [observed] in {0..3} -> {0, code(wrong), 0, code(right)}
 // `lut`: bytes {missing, wrong, -, right} as fp8 (e4m3) values, e.g. 0xB8003800 = {0, +1, 0, -1}
+// (the tables the matrix kernel and the tile-image builder pass: every model carries -w in the codes -- the exponent is -w x logit)
+constexpr uint32_t kPackLutFp32 = 0xB8003800u;      // {missing, wrong, -, right}
+constexpr uint32_t kPackLutCode = 0x0000B838u;      // {wrong, right, missing}
 __device__ __forceinline__ uint32_t pack_codes4_lut(const float4 x, const uint32_t m, const uint32_t lut, int& nobs, int& n1) {
     const uint32_t x0 = __builtin_bit_cast(uint32_t, x.x), x1 = __builtin_bit_cast(uint32_t, x.y);
     const uint32_t x2 = __builtin_bit_cast(uint32_t, x.z), x3 = __builtin_bit_cast(uint32_t, x.w);

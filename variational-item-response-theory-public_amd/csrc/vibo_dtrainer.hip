@@ -42,7 +42,7 @@
 #include <stdint.h>
 #include <string.h>
 #include "../../include/vibo_hip.h"
-#include "../../include/vibo_hip_sign_rows.h"
+#include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
 #include "vibo_finalize.hpp"
 #include "vibo_philox.hpp"
@@ -856,7 +856,7 @@ __global__ __launch_bounds__(kEpiThreads) void dt_epilogue_cond_kernel(const DEp
 enum { kPostUncond = 0, kPostCond = 1, kPostEither = 2 };
 static int dt_check(const vibo_desc* d, const int kind, const int H, const int post = kPostUncond) {
     if (!d || d->abi_version != VIBO_ABI_VERSION) return -2;
-    if (d->mask_dtype == VIBO_MASK_SIGN) return -8;      // (VIBO_MASK_SIGN: a row format of the ELBO call alone)
+    if (VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return -8;      // (VIBO_MASK_SIGN / _TILES: row formats of the ELBO call alone)
     if (d->ability_dim < 1 || d->ability_dim > VIBO_MAX_ABILITY_DIM_WIDE || d->num_item < 1 || d->num_person < 1) return -3;
     if (d->irt_model < VIBO_IRT_1PL || d->irt_model > VIBO_IRT_3PL) return -3;
     if (kind != VIBO_DECODER_LINK && kind != VIBO_DECODER_DEEP && kind != VIBO_DECODER_RESIDUAL) return -3;
@@ -874,7 +874,7 @@ using namespace vibo;
 
 extern "C" int64_t vibo_dtrain_param_floats(const vibo_desc* d, int decoder, int hidden_dim) {
     if (!d || hidden_dim < 1 || d->ability_dim < 1 || d->irt_model < VIBO_IRT_1PL || d->irt_model > VIBO_IRT_3PL) return 0;
-    if (d->mask_dtype == VIBO_MASK_SIGN) return 0;      // (VIBO_MASK_SIGN: a row format of the ELBO call alone)
+    if (VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return 0;      // (VIBO_MASK_SIGN / _TILES: row formats of the ELBO call alone)
     if (decoder != VIBO_DECODER_LINK && decoder != VIBO_DECODER_DEEP && decoder != VIBO_DECODER_RESIDUAL) return 0;
     const int D = item_feat_dim(d->irt_model, d->ability_dim);
     return dparams(decoder, hidden_dim, d->ability_dim, D, d->posterior == VIBO_POSTERIOR_CONDITIONAL ? 1 + D : 1).total;

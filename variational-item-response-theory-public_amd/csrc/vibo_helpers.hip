@@ -2,10 +2,12 @@
 // caller-supplied posterior's hooks, partial finalize, forward-only encode, decode) and their launch wrappers (vibo_helpers.hpp).
 #include "vibo_helpers.hpp"
 
+#include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_cond_finalize.hpp"
 #include "vibo_device.hpp"
 #include "vibo_finalize.hpp"
 #include "vibo_planner.hpp"
+#include "vibo_variant.hpp"
 
 namespace vibo {
 
@@ -251,6 +253,80 @@ __global__ __launch_bounds__(256) void sign_is_mask_kernel(const float* __restri
         bad = bad || mb > 1 || (mb == 1) != sign_clear;
     }
     if (bad) *differs = 1;
+}
+
+// ---------------------------------------------------------------------------
+// vibo_tile_rows_build: the image of a matrix as the matrix row-split kernel's tile rows read it (include/vibo_hip_tile_rows.h: THE
+// layout).  A wave forms one wave block -- 32 rows x 128 items -- as a wave of that kernel would: lane (g, i16) packs the cells of
+// persons 16 h + 4 g + j at chunks 32 q + 16 u + i16 with the kernel's own pack of the source format and its keep words (cells past
+// the row's end, rows past the matrix' end: dropped), the 16 lanes of a row group add their counts.  Rows of any alignment: `vec`
+// says that 4-cell chunks can be read whole (rows_vec_ok), else cell by cell.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void tile_rows_build_kernel(const float* __restrict__ response, const uint8_t* __restrict__ mask,
+                                                              long long resp_stride, long long mask_stride, long long B, int I,
+                                                              int mask_dtype, bool vec, uint32_t* __restrict__ image, long long n_wave_blocks,
+                                                              int W) {
+    __shared__ int row_cnt[4][32];
+    const int wv = threadIdx.x >> 6, lane = threadIdx.x & 63, i16 = lane & 15, g = lane >> 4;
+    const int n4 = (I + 3) >> 2;
+    const uint32_t tm_tail = (I & 3) ? ((1u << (8 * (I & 3))) - 1u) : 0xFFFFFFFFu;
+    for (long long wb0 = (long long)blockIdx.x * 4; wb0 < n_wave_blocks; wb0 += (long long)gridDim.x * 4) {      // (block-uniform)
+        const long long wb = wb0 + wv;
+        const bool live = wb < n_wave_blocks;
+        const long long bt = wb / W;
+        const int q = (int)(wb - bt * W);
+        uint32_t cw[2][8];
+        int own = 0;
+#pragma unroll
+        for (int h = 0; h < 2; ++h)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const long long row = 32 * bt + 16 * h + 4 * g + j;
+                int nobs = 0, n1 = 0;
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const int c = 32 * q + 16 * u + i16;
+                    const uint32_t keep = (!live || row >= B || c >= n4) ? 0u : ((I & 3) && c == (I >> 2)) ? tm_tail : 0xFFFFFFFFu;
+                    float4 x = float4{0.f, 0.f, 0.f, 0.f};
+                    uint32_t w = 0u;
+                    if (keep) {
+                        if (vec) {
+                            if (mask_dtype != VIBO_MASK_CODES) x = reinterpret_cast<const float4*>(response + row * resp_stride)[c];
+                            if (mask) w = reinterpret_cast<const uint32_t*>(mask + row * mask_stride)[c];
+                        } else {
+                            float xs[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                            for (int k = 0; k < 4; ++k) {
+                                if (4 * c + k < I) {
+                                    if (mask_dtype != VIBO_MASK_CODES) xs[k] = response[row * resp_stride + 4 * c + k];
+                                    if (mask) w |= (uint32_t)mask[row * mask_stride + 4 * c + k] << (8 * k);
+                                }
+                            }
+                            x = float4{xs[0], xs[1], xs[2], xs[3]};
+                        }
+                    }
+                    cw[u][4 * h + j] = mask_dtype == VIBO_MASK_CODES  ? pack_cell_codes4_lut(w, keep, kPackLutCode, nobs, n1)
+                                       : mask_dtype == VIBO_MASK_SIGN ? pack_codes4_sign_lut(x, keep & 0x01010101u, kPackLutFp32, nobs, n1)
+                                       : mask_dtype == VIBO_MASK_U8   ? pack_codes4_lut(x, w & keep, kPackLutFp32, nobs, n1)
+                                                                      : pack_codes4_lut(x, 0x01010101u & keep, kPackLutFp32, nobs, n1);
+                }
+                own += nobs;
+                int t = nobs | (n1 << 16);                     // (<= 8 each per lane: 128 over the row group)
+                t += __shfl_xor(t, 1, 16); t += __shfl_xor(t, 2, 16); t += __shfl_xor(t, 4, 16); t += __shfl_xor(t, 8, 16);
+                if (i16 == 0) row_cnt[wv][16 * h + 4 * g + j] = t;
+            }
+        __syncthreads();
+        if (live) {
+            uint32_t* blk = image + wb * (kTileWaveBytes / 4);
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+#pragma unroll
+                for (int u = 0; u < 2; ++u)
+                    reinterpret_cast<uint4*>(blk + 256 * (2 * h + u))[lane] = uint4{cw[u][4 * h], cw[u][4 * h + 1], cw[u][4 * h + 2], cw[u][4 * h + 3]};
+            blk[kTileWordBytes / 4 + lane] = ((uint32_t)row_cnt[wv][lane & 31] & 0x00ffffffu) | ((uint32_t)own << 24);
+        }
+        __syncthreads();
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -619,6 +695,17 @@ hipError_t launch_sign_is_mask(const vibo_desc* d, const float* response, const 
     hipLaunchKernelGGL(chunks ? sign_is_mask4_kernel : sign_is_mask_kernel, dim3((unsigned)grid), dim3(256), 0, s, response,
                        static_cast<const uint8_t*>(mask), (long long)d->response_row_stride, (long long)d->mask_row_stride,
                        (long long)d->num_person, d->num_item, differs);
+    return hipGetLastError();
+}
+
+hipError_t launch_tile_rows_build(const vibo_desc* src, const float* response, const void* mask, bool vec, void* image, hipStream_t s) {
+    const int W = (src->num_item + 127) / 128;
+    const long long n_wave_blocks = ((long long)src->num_person + 31) / 32 * W;
+    long long grid = (n_wave_blocks + 3) / 4;
+    if (grid > (1 << 20)) grid = 1 << 20;
+    hipLaunchKernelGGL(tile_rows_build_kernel, dim3((unsigned)grid), dim3(256), 0, s, response, static_cast<const uint8_t*>(mask),
+                       (long long)src->response_row_stride, (long long)src->mask_row_stride, (long long)src->num_person, src->num_item,
+                       src->mask_dtype, vec, static_cast<uint32_t*>(image), n_wave_blocks, W);
     return hipGetLastError();
 }
 

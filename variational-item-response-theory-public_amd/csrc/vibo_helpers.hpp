@@ -31,6 +31,8 @@ hipError_t launch_given_post(const float* post, const float* coef, int panels, f
 // row_index (chunks only): the code rows are the minibatch's, in its order
 // vibo_rows_sign_is_mask (chunks: aligned rows, 4 cells per thread)
 hipError_t launch_sign_is_mask(const vibo_desc* d, const float* response, const void* mask, bool chunks, int32_t* differs, hipStream_t s);
+// vibo_tile_rows_build (src: the source rows' descriptor; vec: its rows can be read in aligned 4-cell chunks)
+hipError_t launch_tile_rows_build(const vibo_desc* src, const float* response, const void* mask, bool vec, void* image, hipStream_t s);
 hipError_t launch_pack_codes(const vibo_desc* d, const float* response, const void* mask, uint8_t* codes, long long codes_row_stride,
                              bool chunks, hipStream_t s, const int64_t* row_index = nullptr);
 

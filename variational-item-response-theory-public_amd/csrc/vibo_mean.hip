@@ -16,7 +16,7 @@
 #include <stdint.h>
 
 #include "../../include/vibo_hip.h"
-#include "../../include/vibo_hip_sign_rows.h"
+#include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
 
 namespace vibo {
@@ -162,7 +162,7 @@ static int mean_check(const vibo_desc* d, int hidden) {
     if (!d || d->abi_version != VIBO_ABI_VERSION) return -2;
     if (d->num_person < 1 || d->ability_dim < 1 || d->ability_dim > VIBO_MAX_ABILITY_DIM) return -3;
     if (hidden < 1 || hidden > kMeanMaxHidden) return -6;
-    if (d->mask_dtype == VIBO_MASK_SIGN) return -8;      // (VIBO_MASK_SIGN: a row format of the ELBO call alone)
+    if (VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return -8;      // (VIBO_MASK_SIGN / _TILES: row formats of the ELBO call alone)
     return 0;
 }
 
@@ -171,7 +171,7 @@ static int mean_check(const vibo_desc* d, int hidden) {
 using namespace vibo;
 
 extern "C" int vibo_mean_encoder_partials(const vibo_desc* d) {
-    if (!d || d->num_person < 1 || d->mask_dtype == VIBO_MASK_SIGN) return 0;
+    if (!d || d->num_person < 1 || VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return 0;
     int dev = 0, n = 0;
     const int cus = (hipGetDevice(&dev) == hipSuccess &&
                      hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;

@@ -161,14 +161,19 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     constexpr bool kPinFlowAddr = FLOWS && (IRT == 3 || XM != 0 || RM == 1);
     constexpr bool CODES = RM == 2;
     constexpr bool SIGN = RM == 3;
+    // Tile rows (RM 4, VIBO_MASK_TILES): p.response is the matrix' image (include/vibo_hip_tile_rows.h) -- a batch's code words and
+    // counts are LOADED in the layout the tiles consume: five load instructions per wave and batch, no x[] / m[], no pack, no pk[],
+    // no count reduction.
+    constexpr bool TILES = RM == kRowsTiles;
     constexpr bool kMayGather = ms_may_gather(RM);        // (the instantiation can meet p.row_index)
     static_assert(!SIGN || (XM == 0 && !FLOWS), "sign-as-mask rows: the plain model's instantiations only");
+    static_assert(!TILES || (XM == 0 && !FLOWS), "tile rows: the plain model's instantiations only");
     constexpr int R = kMsRows;
     constexpr float kLoS = kLogitLo * kLog2e, kHiS = kLogitHi * kLog2e;
     // fp8 (e4m3) look-up tables of the pack.  fp32 rows: selector {missing, wrong, -, right}; cell codes: {wrong, right, missing}.
     // Every model carries -w (the exponent is -w x logit: one VOP2 multiply).
-    constexpr uint32_t kLutFp32 = 0xB8003800u;
-    constexpr uint32_t kLutCode = 0x0000B838u;
+    constexpr uint32_t kLutFp32 = kPackLutFp32;
+    constexpr uint32_t kLutCode = kPackLutCode;
     extern __shared__ __attribute__((aligned(16))) unsigned char ms_smem[];
     MsCommonLds& cl = *reinterpret_cast<MsCommonLds*>(ms_smem);
     MsWaveLds* wls = reinterpret_cast<MsWaveLds*>(ms_smem + sizeof(MsCommonLds));
@@ -221,6 +226,9 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // ahead (ridx_n, a whole iteration before their use) -- fetched right in front of the row loads they feed, every batch
     // waited a memory round trip for them at the top of the loop (gathered rows: +22 % on fp32 rows, +60 % on cell codes).
     int ridx[8], ridx_n[8];
+    // code words of the batch in the tiles (A) and of the next one (B): [u-step][4 h + j] = person 16 h + 4 g + j of the batch
+    uint32_t cwA0[8], cwA1[8], cwB0[8], cwB1[8];
+    uint32_t tcnt = 0;                              // tile rows: the lane's counts dword of the batch on its way in
     auto fetch_idx = [&](const int bt, int (&dst)[8]) __attribute__((always_inline)) {
         if constexpr (kMayGather) {
             if (!p.row_index) return;
@@ -265,6 +273,15 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         const unsigned br = rows > 0 ? (unsigned)(rows - 1) * rstride4 + 16u * n4 : 0u;
         const unsigned bm = (rows > 0 && have_mask) ? (unsigned)(rows - 1) * mstride + 4u * n4 : 0u;
         RowSrc rs;
+        if constexpr (TILES) {
+            // the batch's block of the image: nw wave blocks; a batch past the end has no records (its loads return zeros)
+            const bool in = bt < n_batches;
+            rs.r = __builtin_amdgcn_make_buffer_rsrc(const_cast<char*>(reinterpret_cast<const char*>(p.response)) +
+                                                         (size_t)(in ? bt : 0) * nw * kTileWaveBytes,
+                                                     (short)0, in ? nw * kTileWaveBytes : 0, 0x00020000);
+            rs.m = rs.c = rs.r;
+            return rs;
+        }
         if constexpr (XFUSE && GRAD) {
             const unsigned bc = (rows > 0 && p.codes_out) ? (unsigned)(rows - 1) * cstride + 4u * n4 : 0u;
             rs.c = __builtin_amdgcn_make_buffer_rsrc(p.codes_out + (size_t)bt * R * p.codes_stride, (short)0, (int)bc, 0x00020000);
@@ -316,6 +333,19 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 m[2 * j + 1] = hm ? w1 : 0u;
             }
         }
+    };
+    // Tile rows: M-tile h of the wave's block = runs 2 h and 2 h + 1 of its code words, 16 bytes per lane each (1 KB per instruction,
+    // whole cache lines); the counts dword behind them.  Offsets: the lane's in the vector register, the wave's and the run's scalar.
+    const unsigned tvo = 16u * (unsigned)lane, tvc = 4u * (unsigned)lane;
+    const int tso = q * kTileWaveBytes;
+    auto load_tiles = [&](const RowSrc& rs, const int h, uint32_t (&cw0)[8], uint32_t (&cw1)[8]) __attribute__((always_inline)) {
+        const uint4 w0 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs.r, tvo, tso + 2048 * h, 0));
+        const uint4 w1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs.r, tvo, tso + 2048 * h + 1024, 0));
+        cw0[4 * h] = w0.x; cw0[4 * h + 1] = w0.y; cw0[4 * h + 2] = w0.z; cw0[4 * h + 3] = w0.w;
+        cw1[4 * h] = w1.x; cw1[4 * h + 1] = w1.y; cw1[4 * h + 2] = w1.z; cw1[4 * h + 3] = w1.w;
+    };
+    auto load_tile_counts = [&](const RowSrc& rs) __attribute__((always_inline)) {
+        return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs.r, tvc, tso + kTileWordBytes, 0);
     };
     // the single-panel statistics of the conditional / given posterior travel a batch ahead with eps (prs0..2) in every row mode
     // (round 3: cell codes only; on fp32 rows the slot lanes read them in the sync phase -- a memory round trip between the
@@ -412,6 +442,16 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     int bt = wg;
     const RowSrc src_first = row_src(bt);
     auto first_rows = [&]() __attribute__((always_inline)) {      // the first batch's rows (both M-tiles) and noise; (two call sites)
+        if constexpr (TILES) {
+            if (bt < n_batches) {
+                load_tiles(src_first, 0, cwA0, cwA1);
+                load_tiles(src_first, 1, cwA0, cwA1);
+                tcnt = load_tile_counts(src_first);
+                fetch_eps(bt, 0);
+                draw_eps(bt);
+            }
+            return;
+        }
         if (bt < n_batches) {
             fetch_idx(bt, ridx);
 #pragma unroll
@@ -831,6 +871,13 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         if (i16 < 8) wl.cnt[4 * g + (i16 & 3) + 16 * (i16 >> 2)] = (f & 0xff) | (((f >> 16) & 0xff) << 16);
     };
 
+    // tile rows: the same two results from the image's counts dword -- row (lane & 31)'s packed count of the wave's items, and the
+    // lane's own observed cells in bits 24-31
+    auto put_tile_counts = [&](const uint32_t cw, const bool real) {
+        if (real) unobs += 64 - (int)(cw >> 24);
+        if (lane < 32) wl.cnt[lane] = (int)(cw & 0x00ffffffu);
+    };
+
     // ---- (person, dim) lanes.  Slot s = 64 of the batch's 256 (person, dim) pairs; with 8 waves the slots of even batches
     //      belong to waves 0-3 and those of odd batches to waves 4-7, else to wave s mod nw.
     // product of experts + reparameterised sample of one slot (models.py:596-629)
@@ -1203,11 +1250,13 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         //  built and measured: 952 -> 1 112 us per 1M x 1k call, the eight extra LDS round trips and scalar compares per batch
         //  cost far more than the balance wins.)
         // (s_setprio takes an immediate: set one value, skip the other for half of the waves -- one short forward branch)
-        if constexpr (CODES) {
+        if constexpr (CODES || TILES) {
             // Cell-code rows (round 6): priority FALLS with the wave's own progress through the batch (4 levels) -- a wave that has
             // run ahead of its SIMD partner sits at a lower level than the partner: a restoring force without communication (the
             // alternation below has none: a wave one tile ahead sits in a tile of the same priority and wins the tie by age).
-            // At equal progress the two staircases are offset by one tile, so the lead still alternates.  Same-box A/B, 1M x 1k:
+            // At equal progress the two staircases are offset by one tile, so the lead still alternates.  (Tile rows take it too: their
+            // tiles carry no row loads either -- whole step at 1M x 1k, libraries alternated on one box, three runs each: 0.5925-0.5939 ms
+            // against 0.5963-0.5981 under the alternation, profiles/tile_rows_record.txt section 3.)  Same-box A/B, 1M x 1k:
             // cell codes 671 -> 645 us (-3.9 %); fp32 rows 817 -> 832 (ability_dim 1), ~930 -> 965 (8): they keep the alternation
             // (their tiles carry the next batch's row loads).  Three more staircases were measured on fp32 rows -- restarting per
             // u-step 840 / 984 us, the offset given to the older waves 823 / 957, two levels 822 / 954, against 818 / 960 for the
@@ -1473,7 +1522,6 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     };
 
     // ================= prologue: first batch =================
-    uint32_t cwA0[8], cwA1[8], cwB0[8], cwB1[8];
     int pk[4];
     if (bt < n_batches) {
 #pragma unroll
@@ -1481,17 +1529,18 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         if (late) {
             // (a batch of slack: the rows are asked for once the long workgroups' first batches -- rem_wg x the bytes of a batch at
             //  ~5 TB/s, + 1 us of latency -- are through, 6 us at most; ticks of 10 ns)
-            const long long batch_bytes = (long long)R * n4 * (CODES ? 4 : SIGN ? 16 : 20);
+            const long long batch_bytes = TILES ? (long long)nw * kTileWaveBytes : (long long)R * n4 * (CODES ? 4 : SIGN ? 16 : 20);
             long long wait_ticks = (long long)rem_wg * batch_bytes / 50000 + 100;
             wait_ticks = wait_ticks > 600 ? 600 : wait_ticks;
             while ((long long)(realtime_ticks() - t_wave_start) < wait_ticks) __builtin_amdgcn_s_sleep(8);
             first_rows();
         }
-        pack_half(bt, 0, cwA0, cwA1, pk, x, m, src_first);
+        if constexpr (!TILES) pack_half(bt, 0, cwA0, cwA1, pk, x, m, src_first);
         MS_P(22, t_entry)
-        pack_half(bt, 1, cwA0, cwA1, pk, x2, m2, src_first);
+        if constexpr (!TILES) pack_half(bt, 1, cwA0, cwA1, pk, x2, m2, src_first);
         MS_P(23, t_entry)
-        put_counts(pk, true);
+        if constexpr (TILES) put_tile_counts(tcnt, true);      // (the words are where the tiles read them)
+        else put_counts(pk, true);
         put_stats();
         asm volatile("" : "+v"(epn));                 // (in before the loop: no wait on it behind the loop's own loads)
         if constexpr (EXTRA && kPrs) asm volatile("" : "+v"(prs0), "+v"(prs1), "+v"(prs2));
@@ -1549,7 +1598,19 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         // put_counts / put_gtheta / the cell-word moves of the previous iteration's tail, one batch
         // further ahead -- 843.9 vs 838.7 us at 1M x 1000 A=8, 797 vs 796 at A=1: nothing; the same
         // with the falling tile priority of the cell-code rows on top -- 858 / 806 us: slower.)
-        burst_a();
+        // Tile rows: the batch's five requests in one place -- their registers (cwB, tcnt) are free from here to the end of the
+        // iteration, where the words become the next batch's and the counts go to LDS.  (Measured as well, same record: M-tile 1's
+        // two requests behind the barriers, in front of tile (0, 0) -- 0.608-0.611 ms under the alternation, 0.5909-0.5926 against
+        // 0.5925-0.5939 under the staircase: nothing beyond the spread.)
+        auto burst_tiles = [&]() {
+            __builtin_amdgcn_sched_barrier(0);
+            load_tiles(sn, 0, cwB0, cwB1);
+            load_tiles(sn, 1, cwB0, cwB1);
+            tcnt = load_tile_counts(sn);
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        if constexpr (TILES) burst_tiles();
+        else burst_a();
         MS_T(4)
         __syncthreads();                              // counts of bt and d LL/d theta shares of bt - G are out
         MS_T(5)
@@ -1606,6 +1667,15 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             fetch_eps(nxt, par ^ 1);                  // (complete by the second pack: free to carry across the back edge)
             draw_eps(nxt);
             MS_T(1)
+        } else if constexpr (TILES) {
+            tile(IC0{}, IC0{}, da0, da1, db0, db1, cwA0, bopB, bopA);
+            tile(IC0{}, IC1{}, db0, db1, da0, da1, cwA0, bopA, bopB);
+            tile(IC0{}, IC2{}, da0, da1, db0, db1, cwA0, bopB, bopA);
+            tile(IC0{}, IC3{}, db0, db1, da0, da1, cwA0, bopA, bopB);
+            MS_T(0)
+            fetch_eps(nxt, par ^ 1);
+            draw_eps(nxt);
+            MS_T(1)
         } else {
             tile(IC0{}, IC0{}, da0, da1, db0, db1, cwA0, bopB, bopA);
             tile(IC0{}, IC1{}, db0, db1, da0, da1, cwA0, bopA, bopB);
@@ -1625,7 +1695,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         //  tile's last priority (0) against its partner's tiles: tools/ms_timing.py showed 7.2 k cycles there against the partner's
         //  4.3 k, and the partner waiting.  1M x 1k: 1.625 -> 1.600 ms.  The falling-priority staircase of the cell-code rows on top: +-0.)
         if constexpr (XFUSE) __builtin_amdgcn_s_setprio(2);
-        pack_half(nxt, 1, cwB0, cwB1, pk, x, m, sn);
+        if constexpr (!TILES) pack_half(nxt, 1, cwB0, cwB1, pk, x, m, sn);
         asm volatile("" : "+v"(epn));                 // (eps is in: nothing is pending at the back edge)
         if constexpr (EXTRA && kPrs) asm volatile("" : "+v"(prs0), "+v"(prs1), "+v"(prs2));
         if constexpr (XCOND && kPrs) asm volatile("" : "+v"(prc));
@@ -1634,7 +1704,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             for (int k = 0; k < 8; ++k) asm volatile("" : "+v"(ridx_n[k]));
         }
         MS_T(3)
-        put_counts(pk, nxt < n_batches);
+        if constexpr (TILES) put_tile_counts(tcnt, nxt < n_batches);      // (waits for the five loads: none crosses the back edge)
+        else put_counts(pk, nxt < n_batches);
         MS_T(10)
         put_stats();
         MS_T(11)

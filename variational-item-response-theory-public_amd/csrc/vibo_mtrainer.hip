@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/vibo_hip.h"
-#include "../../include/vibo_hip_sign_rows.h"
+#include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
 #include "vibo_finalize.hpp"
 #include "vibo_philox.hpp"
@@ -184,7 +184,7 @@ static int mt_check(const vibo_desc* d, int H) {
     if (!d || d->abi_version != VIBO_ABI_VERSION) return -2;
     if (d->ability_dim < 1 || d->ability_dim > VIBO_MAX_ABILITY_DIM || d->num_item < 1 || d->num_person < 1) return -3;
     if (H < 1 || H > kMtMaxHidden) return -6;
-    if (d->mask_dtype == VIBO_MASK_SIGN) return -8;      // (VIBO_MASK_SIGN: a row format of the ELBO call alone)
+    if (VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return -8;      // (VIBO_MASK_SIGN / _TILES: row formats of the ELBO call alone)
     if (d->posterior != VIBO_POSTERIOR_GIVEN || d->n_flows != 0 || d->reg_mode != VIBO_REG_KL) return -6;
     return 0;
 }
@@ -194,7 +194,7 @@ static int mt_check(const vibo_desc* d, int H) {
 using namespace vibo;
 
 extern "C" int64_t vibo_mtrain_param_floats(const vibo_desc* d, int hidden_dim) {
-    if (!d || hidden_dim < 1 || d->mask_dtype == VIBO_MASK_SIGN) return 0;
+    if (!d || hidden_dim < 1 || VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return 0;
     return moff(hidden_dim, 2 * d->ability_dim).total;
 }
 

@@ -7,6 +7,7 @@
 #include <string.h>
 
 #include "../../include/vibo_hip_sign_rows.h"
+#include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_cond.hpp"
 
 namespace vibo {
@@ -38,9 +39,11 @@ int check_desc(const vibo_desc* d, bool sign_rows) {
         d->posterior != VIBO_POSTERIOR_GIVEN)
         return fail(-3, "bad posterior");
     if (d->missing_mode != VIBO_MISSING_PRIOR && d->missing_mode != VIBO_MISSING_DROP) return fail(-3, "bad missing_mode");
-    if (d->mask_dtype < 0 || d->mask_dtype > VIBO_MASK_SIGN) return fail(-3, "bad mask_dtype");
+    if (d->mask_dtype < 0 || d->mask_dtype > VIBO_MASK_TILES || d->mask_dtype == 5) return fail(-3, "bad mask_dtype");
     if (d->mask_dtype == VIBO_MASK_SIGN && !sign_rows)
         return fail(-8, "VIBO_MASK_SIGN rows (the response's sign bit is the mask): taken by vibo_elbo_fwd_bwd and its _step forms only");
+    if (d->mask_dtype == VIBO_MASK_TILES && !sign_rows)
+        return fail(-8, "VIBO_MASK_TILES rows (the matrix' prepacked tile image): taken by vibo_elbo_fwd_bwd and its _step forms only");
     if (d->reg_mode != VIBO_REG_KL && d->reg_mode != VIBO_REG_SAMPLED) return fail(-3, "bad reg_mode");
     if (d->n_flows < 0 || d->n_flows > VIBO_MAX_FLOWS) return fail(-3, "n_flows outside 0..%d", VIBO_MAX_FLOWS);
     if (d->n_flows > 0 && d->reg_mode != VIBO_REG_SAMPLED) return fail(-3, "flows need reg_mode SAMPLED");
@@ -51,6 +54,10 @@ int check_desc(const vibo_desc* d, bool sign_rows) {
     if (d->mask_dtype == VIBO_MASK_SIGN && !sign_rows_ok(d))
         return fail(-8, "VIBO_MASK_SIGN rows (the response's sign bit is the mask): only calls the planner sends to the single-launch "
                         "matrix row-split kernel (unconditional posterior, no flows, 4..1024 items, chunkable rows, enough persons or "
+                        "VIBO_FLAG_KERNEL_MATRIX)");
+    if (d->mask_dtype == VIBO_MASK_TILES && !sign_rows_ok(d))
+        return fail(-8, "VIBO_MASK_TILES rows (the matrix' prepacked tile image): only calls the planner sends to the single-launch "
+                        "matrix row-split kernel (unconditional posterior, no flows, 4..1024 items, enough persons or "
                         "VIBO_FLAG_KERNEL_MATRIX)");
     return 0;
 }
@@ -69,7 +76,7 @@ int codes_unsupported() {
 
 int require_rows(const vibo_desc* d, const float* response, const void* mask) {
     if (!response && d->mask_dtype != VIBO_MASK_CODES) return fail(-5, "null required pointer");
-    const bool no_mask = d->mask_dtype == VIBO_MASK_NONE || d->mask_dtype == VIBO_MASK_SIGN;
+    const bool no_mask = d->mask_dtype == VIBO_MASK_NONE || d->mask_dtype == VIBO_MASK_SIGN || d->mask_dtype == VIBO_MASK_TILES;
     if (no_mask != (mask == nullptr)) return fail(-5, "mask pointer / mask_dtype mismatch");
     return 0;
 }
@@ -81,7 +88,7 @@ int require_rows(const vibo_desc* d, const float* response, const void* mask) {
 // the row's end are read but masked out in the kernels)
 bool rows_chunkable(const vibo_desc* d) {
     const int I = d->num_item;
-    if (I % 4 == 0) return true;
+    if (I % 4 == 0 || d->mask_dtype == VIBO_MASK_TILES) return true;      // (a tile image has no rows: its strides are not read)
     const long long i4 = (I + 3) & ~3;
     if (d->mask_dtype != VIBO_MASK_CODES && d->response_row_stride < i4) return false;
     if ((d->mask_dtype == VIBO_MASK_U8 || d->mask_dtype == VIBO_MASK_CODES) && d->mask_row_stride < i4) return false;
@@ -90,6 +97,7 @@ bool rows_chunkable(const vibo_desc* d) {
 
 bool rows_vec_ok(const vibo_desc* d, const float* response, const void* mask) {
     bool vec = rows_chunkable(d);
+    if (d->mask_dtype == VIBO_MASK_TILES) return ((uintptr_t)response & 15) == 0;
     if (d->mask_dtype != VIBO_MASK_CODES) vec = vec && (d->response_row_stride % 4 == 0) && (((uintptr_t)response & 15) == 0);
     if (d->mask_dtype == VIBO_MASK_U8 || d->mask_dtype == VIBO_MASK_CODES)
         vec = vec && (d->mask_row_stride % 4 == 0) && (((uintptr_t)mask & 3) == 0);
@@ -163,7 +171,8 @@ int plan_cond_pass_bits(const Plan& pl) {
 static SplitVariant variant_of(const vibo_desc* d, const Plan& pl, int items, int mask_dtype, bool gathered) {
     SplitVariant v{};
     v.engine = pl.engine; v.irt = d->irt_model; v.grad = d->want_grad != 0; v.flows = d->n_flows > 0;
-    v.rm = mask_dtype == VIBO_MASK_CODES ? kRowsCodes : mask_dtype == VIBO_MASK_SIGN ? kRowsSign : gathered ? kRowsGathered : kRowsInOrder;
+    v.rm = mask_dtype == VIBO_MASK_CODES ? kRowsCodes : mask_dtype == VIBO_MASK_SIGN ? kRowsSign : mask_dtype == VIBO_MASK_TILES ? kRowsTiles
+           : gathered ? kRowsGathered : kRowsInOrder;
     v.xm = pl.path != Path::Panels ? kHooksNone
            : pl.first == FirstPass::CondFused ? kHooksCondFused : pl.first == FirstPass::GivenDirect ? kHooksGiven : kHooksPanel;
     v.at = pl.engine == Engine::Matrix ? 8 : pl.engine == Engine::Narrow ? (d->ability_dim <= 2 ? d->ability_dim : 4) : pl.AT <= 2 ? 2 : pl.AT == 4 ? 4 : 8;
@@ -181,8 +190,8 @@ bool split_variant(const vibo_desc* d, const Plan& pl, const ElboParams& p, Spli
                           : v.xm == kHooksGiven ? p.given_post && !(panel || p.post_coef || p.cond_table)
                                                 : p.cond_table && !(panel || given) && (p.post_coef || !v.grad) && p.A == 1 && !v.flows &&
                                                       v.rm <= kRowsGathered && v.engine == Engine::Matrix;
-    // sign-as-mask rows: the matrix kernel's plain instantiations, rows in order without a mask
-    const bool sign_ok = v.rm != kRowsSign || (v.engine == Engine::Matrix && v.xm == kHooksNone && !v.flows && !p.row_index && !p.mask && p.response);
+    // sign-as-mask rows and tile images: the matrix kernel's plain instantiations, rows in order without a mask
+    const bool sign_ok = (v.rm != kRowsSign && v.rm != kRowsTiles) || (v.engine == Engine::Matrix && v.xm == kHooksNone && !v.flows && !p.row_index && !p.mask && p.response);
     // the narrow-row kernel: the plain model on 1-byte masks / cell codes
     const bool narrow_ok = v.engine != Engine::Narrow || (p.I >= 4 && p.I <= 128 && p.A <= 4 && !v.flows && v.xm == kHooksNone &&
                                                           (v.rm == kRowsCodes || p.mask_dtype != VIBO_MASK_I64));

@@ -14,7 +14,8 @@ namespace vibo {
 int fail(int code, const char* fmt, ...);
 const char* last_error();
 
-// sign_rows: the entry point takes VIBO_MASK_SIGN rows (include/vibo_hip_sign_rows.h) where sign_rows_ok says so; every other one
+// sign_rows: the entry point takes VIBO_MASK_SIGN rows (include/vibo_hip_sign_rows.h) and VIBO_MASK_TILES images
+// (include/vibo_hip_tile_rows.h) where sign_rows_ok says so; every other one
 // refuses them here (-8)
 int check_desc(const vibo_desc* d, bool sign_rows = false);
 // VIBO_MASK_SIGN: the shapes the format is implemented for -- what the planner sends to the single-launch matrix row-split kernel

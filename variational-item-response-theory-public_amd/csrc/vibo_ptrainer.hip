@@ -18,7 +18,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/vibo_hip.h"
-#include "../../include/vibo_hip_sign_rows.h"
+#include "../../include/vibo_hip_tile_rows.h"
 #include "../../include/vibo_hip_person_tables.h"
 #include "vibo_device.hpp"
 #include "vibo_params.hpp"
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kPtThreads) void pt_epilogue_kernel(const PtEpilogu
 static int pt_check(const vibo_desc* d, int mode, int64_t table_rows) {
     if (!d || d->abi_version != VIBO_ABI_VERSION) return -2;
     if (d->ability_dim < 1 || d->ability_dim > VIBO_MAX_ABILITY_DIM || d->num_item < 1 || d->num_person < 1) return -3;
-    if (d->mask_dtype == VIBO_MASK_SIGN) return -8;      // (VIBO_MASK_SIGN: a row format of the ELBO call alone)
+    if (VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return -8;      // (VIBO_MASK_SIGN / _TILES: row formats of the ELBO call alone)
     if (d->posterior != VIBO_POSTERIOR_GIVEN || d->n_flows != 0 || d->reg_mode != VIBO_REG_KL) return -6;
     if (mode != VIBO_PTRAIN_VI && mode != VIBO_PTRAIN_MLE) return -6;
     if (table_rows < 1 || table_rows > ((int64_t)1 << 40)) return -3;

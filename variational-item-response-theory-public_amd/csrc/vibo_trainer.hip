@@ -4,7 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/vibo_hip.h"
-#include "../../include/vibo_hip_sign_rows.h"
+#include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
 #include "vibo_finalize.hpp"
 #include "vibo_philox.hpp"
@@ -273,9 +273,9 @@ extern "C" int vibo_fill_normal(float* out, int64_t n, uint64_t seed, const int3
 static bool plain_ok(const vibo_desc* d, int hidden_dim) {
     return d && hidden_dim >= 1 && hidden_dim <= kMaxHidden && d->posterior == VIBO_POSTERIOR_UNCONDITIONAL && d->n_flows == 0;
 }
-// (-8: VIBO_MASK_SIGN is a row format of the ELBO call alone; these calls take the trainer's own descriptor)
+// (-8: VIBO_MASK_SIGN and VIBO_MASK_TILES are row formats of the ELBO call alone; these calls take the trainer's own descriptor)
 static int plain_check(const vibo_desc* d, int hidden_dim) {
-    if (d && d->mask_dtype == VIBO_MASK_SIGN) return -8;
+    if (d && VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return -8;
     return plain_ok(d, hidden_dim) ? 0 : -6;
 }
 // train_prologue_kernel: block 0, the item blocks and (gen) the ability-noise blocks behind them

@@ -12,8 +12,11 @@ enum RowMode : int {
     kRowsInOrder = 0,    // fp32 responses + mask bytes (or no mask), rows in order
     kRowsGathered = 1,   // the same through row_index
     kRowsCodes = 2,      // 1-byte cell codes (VIBO_MASK_CODES), with or without row_index
-    kRowsSign = 3        // fp32 responses in order whose sign bit is the mask (VIBO_MASK_SIGN): matrix kernel, no hooks, no flows
+    kRowsSign = 3,       // fp32 responses in order whose sign bit is the mask (VIBO_MASK_SIGN): matrix kernel, no hooks, no flows
+    kRowsTiles = 4       // the matrix' prepacked code words and counts (VIBO_MASK_TILES, include/vibo_hip_tile_rows.h): the same launches
 };
+// VIBO_MASK_TILES: bytes of one wave's block of the image (16 code words and one counts dword per lane), and of its code words
+constexpr int kTileWaveBytes = 4352, kTileWordBytes = 4096;
 // the matrix kernel's template parameter XM: which hooks the launch uses (the VALU kernel reads the same fields at run time)
 enum HookMode : int {
     kHooksNone = 0,

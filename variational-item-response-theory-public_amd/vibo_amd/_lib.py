@@ -1,8 +1,8 @@
 """ctypes binding of libvibo_hip.so.  The C ABI is declared in include/vibo_hip.h and read from there: every export's
 restype / argtypes come from its prototype (parse_prototypes); the constants and the two structs mirror the header by hand
 (tests/test_capi_symbols.py compares them).  Exports declared in a header of their own beside it (EXTRA_HEADERS:
-vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h) are bound the same way; EXPORTED_SYMBOLS stays the list of
-vibo_hip.h itself, EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS and PERSON_TABLE_SYMBOLS are theirs.
+vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h, vibo_hip_tile_rows.h) are bound the same way; EXPORTED_SYMBOLS
+stays the list of vibo_hip.h itself, EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS, PERSON_TABLE_SYMBOLS and TILE_ROWS_SYMBOLS are theirs.
 
 The product path has no CPU or eager-PyTorch fallback: if the HIP library is
 missing or a call fails, this module raises.
@@ -20,6 +20,8 @@ POSTERIOR_UNCONDITIONAL, POSTERIOR_CONDITIONAL, POSTERIOR_GIVEN = 0, 1, 2
 MISSING_PRIOR, MISSING_DROP = 0, 1
 MASK_U8, MASK_I64, MASK_NONE, MASK_CODES = 0, 1, 2, 3
 MASK_SIGN = 4                 # include/vibo_hip_sign_rows.h: no mask, the response's sign bit says "missing"
+MASK_TILES = 6                # include/vibo_hip_tile_rows.h: `response` is the matrix' prepacked tile image, no mask
+TILE_WAVE_BLOCK_BYTES = 4352  # ... one wave's 128 items x 32 rows: 16 code words and a counts dword per lane
 REG_KL, REG_SAMPLED = 0, 1
 FLAG_KERNEL_VALU, FLAG_KERNEL_MATRIX, FLAG_NO_EMIT_CODES, FLAG_COND_VALU, FLAG_COND_MATRIX, FLAG_COND_THREE_PASS = 1, 2, 4, 8, 16, 32
 KERNEL_NAMES = {1: 'matrix row-split (msplit_kernel)', 2: 'VALU row-split (split_kernel)', 3: 'wave-per-row', 4: 'tiled',
@@ -104,7 +106,7 @@ def parse_prototypes(header):
     return protos
 
 
-EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h', 'vibo_hip_person_tables.h')
+EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h', 'vibo_hip_person_tables.h', 'vibo_hip_tile_rows.h')
 
 with open(HEADER_PATH) as _header:
     PROTOTYPES = parse_prototypes(_header.read())
@@ -120,6 +122,7 @@ for _name in EXTRA_HEADERS:
 EXTRA_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_decoder_multi.h']
 SIGN_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sign_rows.h']
 PERSON_TABLE_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_person_tables.h']      # the VI / MLE train step (trainer.FusedVITrainer / FusedMLETrainer)
+TILE_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_tile_rows.h']
 PTRAIN_VI, PTRAIN_MLE = 0, 1                                            # VIBO_PTRAIN_*
 PTRAIN_MAX_BLOCKS = 2048                                                # VIBO_PTRAIN_MAX_BLOCKS: the table update's grid cap
 

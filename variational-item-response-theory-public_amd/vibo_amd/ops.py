@@ -416,7 +416,7 @@ class ResidentMatrix:
     ONE record per response tensor: a response that alternates between two masks is counted again at every switch.
     The record lives ON the response tensor (`_vibo_row_counts`): the counts are freed with the data they describe and never
     before -- a captured hipGraph that holds the data's address holds the counts' too."""
-    __slots__ = ('response', 'has_mask', 'mask', 'counts', 'stream', 'event', 'in_graph', 'sign_is_mask')
+    __slots__ = ('response', 'has_mask', 'mask', 'counts', 'stream', 'event', 'in_graph', 'sign_is_mask', 'tiles')
     __reduce__ = _not_saved
 
     def __init__(self, response, mask):
@@ -425,6 +425,7 @@ class ResidentMatrix:
         self.counts = self.stream = self.event = None
         self.sign_is_mask = None              # does the responses' sign bit say what the mask says?  None: not verified yet (_sign_rows)
         self.in_graph = False                 # the count was recorded into a hipGraph: run when that graph replays
+        self.tiles = None                     # the matrix' tile image (_tile_rows): None not decided yet, False none, else the uint8 tensor
 
     def is_(self, response, mask):
         """THE predicate: the same response, unmodified; a mask given then and now, or neither time (whatever became of the
@@ -533,6 +534,110 @@ def _hip_sign_is_mask(response, mask):
     return int(differs.item()) == 0
 
 
+TILE_ROWS = True                   # (tests / A-B runs switch it off)
+# From this many persons on, every workgroup of an 8-wave launch on 256 compute units runs the matrix kernel's batch loop at least once
+# (2 x 32 x 256 rows): below it the launch is that kernel's one-shot prologue and end code, and the loop the image shortens does not run.
+TILE_ROWS_MIN_PERSONS = 16384
+# Plain launches (fused_elbo, evaluation: no train_step) too?  Off: they keep the caller's rows, captured or not, and run as they ran
+# before the format existed -- an eager plain launch and the same launch replayed from a hipGraph stay one kernel (the in-situ
+# timer's test holds them within 25 % of each other; under capture a plain launch must read the caller's rows in any case, see
+# _tile_rows).  On: an eager plain launch counts as a sighting and uses the image like the trainers' step.
+TILE_ROWS_PLAIN_LAUNCHES = False
+
+
+def _tile_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode, want_grad, train_step, *, capturing):
+    """The one decision about a resident matrix' tile image (include/vibo_hip_tile_rows.h) -> the image this ELBO launch goes out on
+    (a uint8 tensor: the launch is (image, None, MASK_TILES)), False (the launch keeps the caller's rows as they are: the matrix is
+    on its way to an image, or a plain launch is being captured), or None (no image for this call: _sign_rows decides as ever).
+    The matrix kernel then loads a batch's code words and counts instead of forming them from 4-5 bytes per cell: about 1.06 bytes
+    per cell, no pack.  What the words are depends on the data alone, so the image hangs on the matrix' ResidentMatrix record: freed
+    with the response, thrown away with the record by an in-place edit of response or mask.  It costs one more byte per cell of
+    device memory while the matrix lives.
+    Eligibility first (nothing is looked up or built without it): the trainers' folded step (train_step given; any launch with
+    TILE_ROWS_PLAIN_LAUNCHES on), the whole matrix in order -- fp32 responses with a u8 mask or without one, or CellCodes --, in
+    rows the matrix kernel itself can load (_matrix_kernel_rows: the launch on the image then has the bits of the launch on the
+    rows), at least TILE_ROWS_MIN_PERSONS persons, a shape the library takes the format for
+    (vibo_tile_rows_supported).  Then: the first sighting records, the second builds (one streaming pass, waited for; never while
+    the stream is capturing; only if the image takes at most half of the free device memory -- an allocation that fails all the
+    same counts as a "no") and still goes out on the caller's rows, from the third on the image goes out.  A "no" is kept: such a
+    matrix is _sign_rows' from then on.  A matrix with an image is never sign-verified: the fact would save nothing.
+    While capturing, the two regimes of _lookup_counts / _sign_rows: a plain launch whose input is the whole matrix keeps the
+    caller's rows (a replay after `response.copy_(new)` has to read what is there then); the trainers' folded step (train_step
+    given) uses the image -- the resident-matrix contract "counted once".  capturing(): asked only where the answer matters."""
+    if (not TILE_ROWS or (train_step is None and not TILE_ROWS_PLAIN_LAUNCHES)
+            or response is None or row_index is not None or num_person != response.shape[0]
+            or num_person < TILE_ROWS_MIN_PERSONS or mask_code not in (_lib.MASK_U8, _lib.MASK_NONE, _lib.MASK_CODES)):
+        return None
+    if mask_code != _lib.MASK_CODES and (response.dtype != torch.float32 or (mask is None) != (mask_code == _lib.MASK_NONE)):
+        return None
+    if not _matrix_kernel_rows(response, mask, mask_code):
+        return None
+    d = _tile_desc(spec, num_person, response.shape[1], reg_mode, want_grad)
+    if not _BACKEND['tile_supported'](d):
+        return None
+    known_mask = None if mask_code == _lib.MASK_CODES else mask        # (CellCodes rows are known by the codes alone)
+    rec = getattr(response, '_vibo_row_counts', None)
+    if rec is None or not rec.is_(response, known_mask):
+        response._vibo_row_counts = ResidentMatrix(response, known_mask)
+        return False
+    if rec.tiles is None:
+        if capturing():
+            return False
+        rec.tiles = False                                              # (a "no" until the image stands)
+        need = _BACKEND['tile_bytes'](d)
+        if 0 < need <= _BACKEND['tile_free'](response.device) // 2:
+            try:
+                rec.tiles = _BACKEND['tile_build'](spec, response, mask, mask_code, num_person, reg_mode, want_grad, need)
+            except torch.cuda.OutOfMemoryError:
+                pass
+        return False if rec.tiles is not False else None               # (the building launch itself still reads the caller's rows)
+    if rec.tiles is False:
+        return None
+    if train_step is None and capturing():
+        return False
+    return rec.tiles
+
+
+def _matrix_kernel_rows(response, mask, mask_code):
+    """Can the matrix kernel's chunk loads take these rows as they are -- bases aligned (16 bytes fp32, 4 bytes masks / codes), strides
+    multiples of 4 that pad every row to whole chunks?  (A call on other rows falls back to the tiled kernel, whose last bits are
+    its own: an image would change the results of such a matrix.)"""
+    i4 = (response.shape[1] + 3) & ~3
+    for t, align in ((None if mask_code == _lib.MASK_CODES else response, 16), (mask, 4)):
+        if t is not None and (t.data_ptr() % align != 0 or t.stride(0) % 4 != 0 or t.stride(0) < i4):
+            return False
+    return True
+
+
+def _tile_desc(spec, num_person, num_item, reg_mode, want_grad):
+    """The descriptor of a launch on the tile image of a num_person x num_item matrix (the row strides are not read)."""
+    i4 = (num_item + 3) & ~3
+    return _make_desc(spec, num_person, num_item, _lib.MASK_TILES, reg_mode, want_grad, i4, i4)
+
+
+def _hip_tile_rows_supported(d):
+    return _lib.load().vibo_tile_rows_supported(ctypes.byref(d)) == 1
+
+
+def _hip_tile_rows_bytes(d):
+    return int(_lib.load().vibo_tile_rows_bytes(ctypes.byref(d)))
+
+
+def _hip_free_bytes(device):
+    return int(torch.cuda.mem_get_info(device)[0])
+
+
+def _hip_tile_rows_build(spec, response, mask, mask_code, num_person, reg_mode, want_grad, nbytes):
+    """vibo_tile_rows_build on the current stream, waited for (any stream may read the image afterwards)."""
+    _require_device(response, mask)
+    image = torch.empty(nbytes, dtype=torch.uint8, device=response.device)
+    src = _rows_desc(spec, num_person, response, mask, mask_code, reg_mode, want_grad)
+    _call('vibo_tile_rows_build', ctypes.byref(src), _ptr(response), _ptr(mask), _ptr(image), ctypes.c_size_t(nbytes),
+          _stream(response.device))
+    torch.cuda.current_stream(response.device).synchronize()
+    return image
+
+
 class TrainStepCall(NamedTuple):
     """The folded train step's ELBO launch (trainer.FusedTrainer): vibo_elbo_fwd_bwd_step, the call that also ticks Adam's step counter."""
     step_count: torch.Tensor          # the trainer's int32[2] counters
@@ -562,9 +667,16 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     post = None if no_sample else torch.empty(1 if own_noise else 3, B, A, dtype=torch.float32, device=dev)
     ability_k = torch.empty(B, A, dtype=torch.float32, device=dev) if spec.n_flows else None
     ladj = torch.empty(B, dtype=torch.float32, device=dev) if spec.n_flows else None
-    mask, mask_code = _sign_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step,
-                                 capturing=torch.cuda.is_current_stream_capturing)
-    d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, want_grad)
+    image = _tile_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step,
+                       capturing=torch.cuda.is_current_stream_capturing)
+    if image is None:
+        mask, mask_code = _sign_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step,
+                                     capturing=torch.cuda.is_current_stream_capturing)
+    if image is None or image is False:
+        d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, want_grad)
+    else:
+        response, mask, mask_code = image, None, _lib.MASK_TILES
+        d = _tile_desc(spec, B, I, reg_mode, want_grad)
     ws_bytes = lib.vibo_workspace_bytes(ctypes.byref(d))
     if ws_bytes == 0:
         _lib.check(-1, 'vibo_workspace_bytes')
@@ -585,7 +697,7 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
         args = (_ptr(train_step.step_count), 1 if train_step.skip_finalize else 0, *rows, _ptr(table), _ptr(item), _ptr(eps), vp(fbase),
                 _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), *grads, *tail)
     else:
-        counts = _resident_row_counts(spec, response, mask, mask_code, row_index, B, stream)
+        counts = None if mask_code == _lib.MASK_TILES else _resident_row_counts(spec, response, mask, mask_code, row_index, B, stream)
         name = 'vibo_elbo_fwd_bwd' if counts is None else 'vibo_elbo_fwd_bwd_counts'
         args = (*rows, *(() if counts is None else (_ptr(counts),)), _ptr(table), _ptr(item), _ptr(eps), _ptr(flow), vp(fbase),
                 _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), _ptr(ability_k), _ptr(ladj), *grads,
@@ -864,7 +976,9 @@ def _hip_cond_mean_sum(feature, response, mask, row_index):
 _BACKEND = {'elbo': _hip_launch_elbo, 'encode': _hip_encode, 'decode': _hip_decode, 'multi': _hip_multi_forward,
             'decode_mean': _hip_decode_mean, 'counts': _hip_row_counts, 'mean_fwd': _hip_mean_encoder_fwd,
             'mean_bwd': _hip_mean_encoder_bwd, 'flow_stack': _hip_flow_stack, 'cond_mean_sum': _hip_cond_mean_sum,
-            'sign_supported': _hip_sign_rows_supported, 'sign_verify': _hip_sign_is_mask}
+            'sign_supported': _hip_sign_rows_supported, 'sign_verify': _hip_sign_is_mask,
+            'tile_supported': _hip_tile_rows_supported, 'tile_bytes': _hip_tile_rows_bytes, 'tile_free': _hip_free_bytes,
+            'tile_build': _hip_tile_rows_build}
 
 
 class FusedELBO(torch.autograd.Function):
