@@ -7,7 +7,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OBJ=$ROOT/variational-item-response-theory-public_amd/csrc/build/$1.o
 TMP=$(mktemp -d)
 cd $TMP
-/opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section .hip_fatbin=fat.bin $OBJ
+/opt/rocm/lib/llvm/bin/llvm-objcopy --dump-section .hip_fatbin=fat.bin $OBJ /dev/null
 /opt/rocm/lib/llvm/bin/clang-offload-bundler --type=o --targets=hipv4-amdgcn-amd-amdhsa--gfx950 --input=fat.bin --output=dev.co --unbundle
 /opt/rocm/lib/llvm/bin/llvm-readelf --notes dev.co | python3 -c "
 import sys, re

@@ -21,6 +21,10 @@ raw = np.frombuffer(buf, dtype=np.int64).reshape(1024, 8, SLOTS)[:256]
 t = raw[:, :, :12].astype(np.float64)
 nb = (P + 31) // 32 / (256 // max(1, (I + 1023) // 1024) if I > 1024 else 256)
 names = ['tiles u0', 'pack0', 'tiles u1', 'pack1', 'counts+gth', 'barrier A', 'forward', 'barrier B', 'read ops', 'backward', 'put_counts', 'put_stats']
+if '--tiles' in sys.argv and 896 < I <= 1024:
+    # the one-barrier loop (tile rows, 8 waves): one barrier phase; the per-person phases only in the iterations in which the wave owns
+    # the other parity's slots (every second one), still divided by all batches here
+    names = ['tiles u0', 'noise ahead', 'tiles u1', '-', 'requests+gth', 'barrier X', 'forward(+1)', '-', 'read ops', 'backward(-1)', 'put_counts', '-']
 print('rc', rc, 'batches per workgroup %.1f' % nb)
 print('phase           ' + ''.join(f' wave{w:1d}  ' for w in range(8)) + '   (cycles per batch, mean over workgroups)')
 for k, nm in enumerate(names):

@@ -24,7 +24,8 @@
 // [128 q, 128 q + 128) as two "u-steps" of 64 items.  Per u-step and lane: 8 persons x one float4 (+ 4 mask bytes),
 // a wave-load instruction reads 4 rows x 256 contiguous bytes.  Loads run one u-step ahead of the math; the next
 // batch's cells are packed to fp8 codes (16 registers) as they arrive.  Two workgroup barriers per batch: counts +
-// d LL/d theta shares out, (person, dim) lanes do backward(batch) and forward(batch + 1), theta operands back.
+// d LL/d theta shares out, (person, dim) lanes do backward(batch) and forward(batch + 1), theta operands back.  (Tile rows at 8
+// waves: ONE barrier per batch, the (person, dim) lanes' work under the SIMD partner's tiles -- see the batch loop.)
 // Outputs use the per-workgroup partial record of the other kernels (fixed order, bitwise reproducible).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -96,6 +97,15 @@ constexpr int kMsGuessFloats = 2 * 4 * 16;
 constexpr int kMsFuseFloats = 2 * 4 * 16 * 4 + 2 * kMsRows;
 // the folded train step's own ability noise (p.eps null): one batch's 32 rows x A entries, behind everything else
 constexpr int kMsNoiseBytes = kMsRows * 8 * (int)sizeof(float);
+// One-barrier loop (ms_one_barrier, vibo_variant.hpp; 8 waves): everything a forward that runs a batch AHEAD of the tiles reads or
+// writes, twice -- by batch parity -- in one block where the noise block otherwise sits (with or without the caller's noise).  The
+// single-buffered members of the records above (thA, thT, cnt) are not used by these instantiations.
+struct alignas(16) MsPipeLds {
+    _Float16 thA[2][2][kMsRows][8];   // [batch parity] as MsCommonLds::thA
+    _Float16 thT[2][16][kMsRows];     // [batch parity] as MsCommonLds::thT
+    int cnt[2][8][kMsRows];           // [batch parity][wave] as MsWaveLds::cnt, written two batches ahead
+    float nz[2][kMsRows * 8];         // [batch parity] the drawn noise, two batches ahead
+};
 inline size_t msplit_lds_bytes(int nw, bool flows = false, bool guess = false, bool fuse = false) {
     return sizeof(MsCommonLds) + (size_t)nw * sizeof(MsWaveLds) + (flows ? sizeof(MsFlowLds) : 0) +
            (guess ? (size_t)nw * kMsGuessFloats * sizeof(float) : 0) + (fuse ? (size_t)nw * kMsFuseFloats * sizeof(float) : 0);
@@ -166,6 +176,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // no count reduction.
     constexpr bool TILES = RM == kRowsTiles;
     constexpr bool kMayGather = ms_may_gather(RM);        // (the instantiation can meet p.row_index)
+    // One barrier per batch (tile rows, 8 waves): see the batch loop.  Every other instantiation keeps the two-barrier loop.
+    constexpr bool OB = ms_one_barrier(RM, XM, FLOWS, NW8);
     static_assert(!SIGN || (XM == 0 && !FLOWS), "sign-as-mask rows: the plain model's instantiations only");
     static_assert(!TILES || (XM == 0 && !FLOWS), "tile rows: the plain model's instantiations only");
     constexpr int R = kMsRows;
@@ -229,6 +241,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // code words of the batch in the tiles (A) and of the next one (B): [u-step][4 h + j] = person 16 h + 4 g + j of the batch
     uint32_t cwA0[8], cwA1[8], cwB0[8], cwB1[8];
     uint32_t tcnt = 0;                              // tile rows: the lane's counts dword of the batch on its way in
+    uint32_t tcnt2 = 0;                             // one-barrier loop, prologue only: that of the workgroup's second batch
     auto fetch_idx = [&](const int bt, int (&dst)[8]) __attribute__((always_inline)) {
         if constexpr (kMayGather) {
             if (!p.row_index) return;
@@ -407,22 +420,28 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                                                (IRT == 3 ? (size_t)nw * kMsGuessFloats * sizeof(float) : 0));
     const uint32_t nz_step = draw ? (uint32_t)__builtin_amdgcn_readfirstlane(p.step_tick[1]) : 0u;     // completed steps
     int nz_wave = 0;
-    auto draw_eps = [&](const int bt) __attribute__((always_inline)) {
+    // (one-barrier loop: the parity-indexed block takes the noise block's place; `par` = parity of batch bt, unused otherwise)
+    MsPipeLds& pl = *reinterpret_cast<MsPipeLds*>(nz);
+    auto draw_eps = [&](const int bt, const int par = 0) __attribute__((always_inline)) {
         if constexpr (kDraw) {
             if (draw) {
-                if (q == nz_wave && bt < n_batches && lane < 8 * A)
-                    reinterpret_cast<float4*>(nz)[lane] =
-                        philox_normal4((long long)bt * (8 * A) + lane, nz_step, p.noise_stream, p.noise_seed_lo, p.noise_seed_hi);
+                if (q == nz_wave && bt < n_batches && lane < 8 * A) {
+                    const float4 v = philox_normal4((long long)bt * (8 * A) + lane, nz_step, p.noise_stream, p.noise_seed_lo, p.noise_seed_hi);
+                    if constexpr (OB) reinterpret_cast<float4*>(pl.nz[par])[lane] = v;
+                    else reinterpret_cast<float4*>(nz)[lane] = v;
+                }
                 nz_wave = nz_wave + 1 == nw ? 0 : nz_wave + 1;
             }
         }
     };
     // eps of slot s of batch bt: drawn (LDS) or loaded (e0)
-    auto slot_eps = [&](const int bt, const int s, const float e0) __attribute__((always_inline)) {
+    auto slot_eps = [&](const int bt, const int par, const int s, const float e0) __attribute__((always_inline)) {
         if constexpr (kDraw) {
             if (draw) {
                 const int r = (64 * s + lane) >> 3;
-                const float v = nz[r * A + ed];
+                float v;
+                if constexpr (OB) v = pl.nz[par][r * A + ed];
+                else v = nz[r * A + ed];
                 return (ed < A && bt * R + r < p.B) ? v : 0.f;
             }
         }
@@ -449,6 +468,11 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 tcnt = load_tile_counts(src_first);
                 fetch_eps(bt, 0);
                 draw_eps(bt);
+                if constexpr (OB) {       // counts and noise run two batches ahead there: the second batch's as well
+                    tcnt2 = load_tile_counts(row_src(bt + G));
+                    fetch_eps(bt + G, 1);
+                    draw_eps(bt + G, 1);
+                }
             }
             return;
         }
@@ -873,9 +897,14 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
 
     // tile rows: the same two results from the image's counts dword -- row (lane & 31)'s packed count of the wave's items, and the
     // lane's own observed cells in bits 24-31
-    auto put_tile_counts = [&](const uint32_t cw, const bool real) {
+    // (one-barrier loop: into the record of the batch's parity `par`)
+    auto put_tile_counts = [&](const uint32_t cw, const bool real, const int par = 0) {
         if (real) unobs += 64 - (int)(cw >> 24);
-        if (lane < 32) wl.cnt[lane] = (int)(cw & 0x00ffffffu);
+        if constexpr (OB) {
+            if (lane < 32) pl.cnt[par][q][lane] = (int)(cw & 0x00ffffffu);
+        } else {
+            if (lane < 32) wl.cnt[lane] = (int)(cw & 0x00ffffffu);
+        }
     };
 
     // ---- (person, dim) lanes.  Slot s = 64 of the batch's 256 (person, dim) pairs; with 8 waves the slots of even batches
@@ -909,7 +938,10 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             if (p.row_cnt) { cnt = prc; have_cnt = true; }
         }
         if (!have_cnt) {
-            if constexpr (NW8) {
+            if constexpr (OB) {
+#pragma unroll
+                for (int w = 0; w < 8; ++w) cnt += pl.cnt[par][w][pp];
+            } else if constexpr (NW8) {
                 int ppo = pp;
                 if constexpr (kPinFlowAddr) asm volatile("" : "+v"(ppo));     // (see backward_slot)
 #pragma unroll
@@ -1033,10 +1065,17 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         _Float16 hi, lo;
         split16(ths, hi, lo);
         const int slot = 8 * ((pp & 15) >> 2) + 4 * (pp >> 4) + (pp & 3);
-        cl.thA[0][pp][ed] = hi;
-        cl.thA[1][pp][ed] = lo;
-        cl.thT[ed][slot] = hi;
-        cl.thT[8 + ed][slot] = lo;
+        if constexpr (OB) {
+            pl.thA[par][0][pp][ed] = hi;
+            pl.thA[par][1][pp][ed] = lo;
+            pl.thT[par][ed][slot] = hi;
+            pl.thT[par][8 + ed][slot] = lo;
+        } else {
+            cl.thA[0][pp][ed] = hi;
+            cl.thA[1][pp][ed] = lo;
+            cl.thT[ed][slot] = hi;
+            cl.thT[8 + ed][slot] = lo;
+        }
     };
     // backward of one slot through the sample and the product of experts; the 8 table-gradient sums of the wave's lanes
     // go to the wave's LDS record (fixed order: bitwise reproducible)
@@ -1183,12 +1222,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                         const int row = bt * R + ((64 * s + lane) >> 3);
                         eps_c = (ed < A && row < p.B) ? p.eps[(long long)row * A + ed] : 0.f;
                     }
-                    forward_slot(std::integral_constant<bool, EXTRA>{}, bt, par, s, slot_eps(bt, s, eps_c));
+                    forward_slot(std::integral_constant<bool, EXTRA>{}, bt, par, s, slot_eps(bt, par, s, eps_c));
                 }
                 return;
             }
         }
-        if (s0 < s1) forward_slot(std::false_type{}, bt, par, s0, slot_eps(bt, s0, epn));
+        if (s0 < s1) forward_slot(std::false_type{}, bt, par, s0, slot_eps(bt, par, s0, epn));
     };
     auto person_backward = [&](const int bt, const int par) {
         int s0, s1, step;
@@ -1511,14 +1550,17 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         }
         acc_gt[0] = acc_gt[1] = zero4;
     };
-    auto read_theta_ops = [&]() {
+    auto read_theta_ops = [&](const int par = 0) {
         const half8 ones = half8{one_b, one_b, one_b, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-            const half8 v = *reinterpret_cast<const half8*>(&cl.thA[g >> 1][16 * mt + i16][0]);
+            half8 v;
+            if constexpr (OB) v = *reinterpret_cast<const half8*>(&pl.thA[par][g >> 1][16 * mt + i16][0]);
+            else v = *reinterpret_cast<const half8*>(&cl.thA[g >> 1][16 * mt + i16][0]);
             A1[mt] = (g == 3) ? ones : v;
         }
-        B2 = *reinterpret_cast<const half8*>(&cl.thT[i16][8 * g]);
+        if constexpr (OB) B2 = *reinterpret_cast<const half8*>(&pl.thT[par][i16][8 * g]);
+        else B2 = *reinterpret_cast<const half8*>(&cl.thT[i16][8 * g]);
     };
 
     // ================= prologue: first batch =================
@@ -1542,6 +1584,13 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         if constexpr (TILES) put_tile_counts(tcnt, true);      // (the words are where the tiles read them)
         else put_counts(pk, true);
         put_stats();
+        if constexpr (OB) {
+            // one-barrier loop: the second batch's counts too, and theta of the first batch -- iteration 0's barrier publishes it
+            put_tile_counts(tcnt2, bt + G < n_batches, 1);
+            __syncthreads();                          // (workgroup-uniform branch) counts and noise of both batches are out
+            person_forward(bt, 0);
+            fetch_eps(bt + 2 * G, 0);                 // (a forward's owners ask for the noise of their next batch right behind it)
+        }
         asm volatile("" : "+v"(epn));                 // (in before the loop: no wait on it behind the loop's own loads)
         if constexpr (EXTRA && kPrs) asm volatile("" : "+v"(prs0), "+v"(prs1), "+v"(prs2));
         if constexpr (XCOND && kPrs) asm volatile("" : "+v"(prc));
@@ -1566,6 +1615,84 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // Nothing loaded is in flight across the loop's back edge: hipcc otherwise parks such registers in a second set and
     // copies them at the back edge behind an s_waitcnt vmcnt(0), which serialises the prefetch.  The sched_barriers keep
     // the loads behind the pack that frees their registers.
+    //
+    // One-barrier loop (OB: tile rows, 8 waves).  theta(bt) needs the expert table, the batch's counts and its noise -- on tile rows all
+    // three exist before the loop -- and nothing in the loop reads what backward(bt) leaves.  So iteration bt has ONE barrier, X(bt), which
+    // publishes theta(bt) (written in iteration bt - 1) and the d LL/d theta shares of bt - 1 (written at its end); every wave reads its
+    // operands and goes into its tiles.  The four waves that own the slots of the OTHER parity (one per SIMD, the "busy" group) also run
+    // backward(bt - 1), right behind the barrier, and forward(bt + 1), behind their second tile -- latency chains of ~320 instructions
+    // that cost wall time, not issue slots -- under their SIMD partners' tiles; in the next iteration the groups swap.  Counts and noise
+    // run two batches ahead, the code words one.
+    // Placement and priority (whole step at 1M x 1k, ability_dim 8, libraries alternated on one box, three runs each, ms; the two-barrier
+    // loop 0.5945-0.5975 throughout; profiles/one_barrier_record.txt, section 2): both chains behind the barrier at the priority the
+    // last tile left (0) 0.6011-0.6026 -- the partner's tiles starve the chain, and the busy wave then finishes its tiles alone; the same
+    // at priority 3 0.5803-0.5812; both chains behind the wave's LAST tile 0.653-0.657; the staircase's offset given to the busy wave
+    // instead of to waves 4-7 0.5965-0.5999 (priority 0) / 0.5876-0.5895 (priority 3), to its partner 0.5917-0.5942.  At priority 3,
+    // backward behind the barrier and forward behind tile (0, 1) 0.5700-0.5727 -- this form; behind tile (0, 3) 0.5761-0.5779, behind
+    // (1, 1) 0.5878-0.5907; backward behind (0, 0) and forward behind (0, 2) 0.5843-0.5870, behind (0, 1) and (1, 0) 0.5833-0.5854.
+    // Hazards, each closed by a barrier or a buffer per parity (MsPipeLds), with par = parity of bt:
+    //   thA / thT [par ^ 1]  written by forward(bt + 1) behind X(bt); last read (theta(bt - 1)) into registers behind X(bt - 1)
+    //   gth [par]            written at the end of iteration bt; read by backward(bt) behind X(bt + 1); next write behind X(bt + 2)
+    //   st [par ^ 1]         read by backward(bt - 1), then written by forward(bt + 1): same wave, same lane, program order
+    //   tacc [par ^ 1]       one owner lane per address (backward k < 8, forward k >= 8), the batches in their old order: same bits
+    //   cnt [par]            counts of bt + 2, written at the end of iteration bt; read by forward(bt + 2) behind X(bt + 1); the last
+    //                        reader of the old contents, forward(bt), ran before X(bt)
+    //   nz [par]             noise of bt + 2, drawn in iteration bt: as cnt
+    //   epn                  the caller's noise: a register of the slot's owner, asked for right behind the forward that used it,
+    //                        two batches ahead, and waited for at the end of the iteration
+    // A batch past the end has no buffer records (its loads return zeros) and no forward.
+    if constexpr (OB) {
+        for (; bt < n_batches; bt += G, par ^= 1) {
+            const int nxt = bt + G;
+            sat3 = false;                             // (3PL: see the tile)
+            const RowSrc sn = row_src(nxt), sc = row_src(nxt + G);
+            __builtin_amdgcn_sched_barrier(0);
+            load_tiles(sn, 0, cwB0, cwB1);
+            load_tiles(sn, 1, cwB0, cwB1);
+            tcnt = load_tile_counts(sc);
+            __builtin_amdgcn_sched_barrier(0);
+            MS_T(4)
+            __syncthreads();                          // X(bt): theta(bt) and the d LL/d theta shares of bt - G are out
+            MS_T(5)
+            read_theta_ops(par);
+            MS_T(8)
+            const bool busy = (q >> 2) != par;        // (wave-uniform) the owners of the other parity's slots
+            if constexpr (GRAD) {
+                if (busy) {
+                    __builtin_amdgcn_s_setprio(3);    // (the chains at the top priority; every tile sets its own)
+                    if (bt >= G + wg) person_backward(bt - G, par ^ 1);
+                    MS_T(9)
+                }
+            }
+            f32x4 da0, da1, db0, db1;
+            logits(bopA, da0, da1);
+            tile(IC0{}, IC0{}, da0, da1, db0, db1, cwA0, bopB, bopA);
+            tile(IC0{}, IC1{}, db0, db1, da0, da1, cwA0, bopA, bopB);
+            if (busy) {
+                MS_T(0)
+                __builtin_amdgcn_s_setprio(3);
+                if (nxt < n_batches) person_forward(nxt, par ^ 1);
+                fetch_eps(nxt + 2 * G, par ^ 1);      // (its noise is used up: the owners ask for that of their next batch)
+                MS_T(6)
+            }
+            tile(IC0{}, IC2{}, da0, da1, db0, db1, cwA0, bopB, bopA);
+            tile(IC0{}, IC3{}, db0, db1, da0, da1, cwA0, bopA, bopB);
+            MS_T(0)
+            draw_eps(nxt + G, par);
+            MS_T(1)
+            tile(IC1{}, IC0{}, da0, da1, db0, db1, cwA1, bopB, bopA);
+            tile(IC1{}, IC1{}, db0, db1, da0, da1, cwA1, bopA, bopB);
+            tile(IC1{}, IC2{}, da0, da1, db0, db1, cwA1, bopB, bopA);
+            tile(IC1{}, IC3{}, db0, db1, da0, da1, cwA1, bopA, bopB);
+            MS_T(2)
+            asm volatile("" : "+v"(epn));             // (eps is in: nothing is pending at the back edge)
+            put_tile_counts(tcnt, nxt + G < n_batches, par);      // (waits for the five loads: none crosses the back edge)
+            MS_T(10)
+            if constexpr (GRAD) put_gtheta(par);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) { cwA0[k] = cwB0[k]; cwA1[k] = cwB1[k]; }
+        }
+    } else      // (the two-barrier loop of every other instantiation, unchanged)
     for (; bt < n_batches; bt += G, par ^= 1) {
         const int nxt = bt + G;
         sat3 = false;                                 // (3PL: see the tile)
@@ -1854,18 +1981,19 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
 
 template <int IRT, bool GRAD, int RM, bool FLOWS, bool NW8, int XM>
 static hipError_t launch_msplit_inst(const ElboParams& p, int nw, int grid, hipStream_t s) {
-    constexpr bool kFuse = XM == kHooksCondFused;
+    constexpr bool kFuse = XM == kHooksCondFused, kOB = ms_one_barrier(RM, XM, FLOWS, NW8);
     // more than 64 KB of dynamic LDS has to be opted into (once per kernel; gfx950 has 160 KB per CU)
     static bool lds_opt_in = false;
     if (!lds_opt_in) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)msplit_lds_bytes(8, FLOWS, IRT == 3, kFuse) + (kFuse ? 0 : kMsNoiseBytes));
+                                                 (int)msplit_lds_bytes(8, FLOWS, IRT == 3, kFuse) + (kFuse ? 0 : kOB ? (int)sizeof(MsPipeLds) : kMsNoiseBytes));
         if (e != hipSuccess) return e;
         lds_opt_in = true;
     }
     // (p.eps null -- split_variant: only where the instantiation draws the noise -- takes 1 KB more LDS)
-    const size_t lds = msplit_lds_bytes(nw, FLOWS, IRT == 3, kFuse) + (p.eps ? 0 : kMsNoiseBytes);
+    // (... and the one-barrier loop's parity block takes the noise block's place, whoever supplies the noise)
+    const size_t lds = msplit_lds_bytes(nw, FLOWS, IRT == 3, kFuse) + (kOB ? sizeof(MsPipeLds) : p.eps ? 0 : kMsNoiseBytes);
     hipLaunchKernelGGL((msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>), dim3(grid), dim3(64 * nw), lds, s, p);
     return hipGetLastError();
 }

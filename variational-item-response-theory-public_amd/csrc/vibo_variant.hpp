@@ -41,6 +41,9 @@ constexpr bool ms_draws_noise(int xm, bool flows, bool grad) { return xm == kHoo
 constexpr bool ms_sample_optional(int xm, bool flows, bool grad, int rm, bool nw8) {
     return ms_draws_noise(xm, flows, grad) && (nw8 || rm != kRowsGathered);
 }
+// the matrix kernel's batch loop with ONE workgroup barrier per batch (the per-person phase of the neighbouring batches runs under the
+// SIMD partner's tiles): tile rows at exactly 8 waves -- their counts are data of the image, requested two batches ahead
+constexpr bool ms_one_barrier(int rm, int xm, bool flows, bool nw8) { return rm == kRowsTiles && xm == kHooksNone && !flows && nw8; }
 constexpr bool ms_draws_noise(const SplitVariant& v) { return v.engine == Engine::Matrix && ms_draws_noise(v.xm, v.flows, v.grad); }
 constexpr bool ms_sample_optional(const SplitVariant& v) {
     return v.engine == Engine::Matrix && ms_sample_optional(v.xm, v.flows, v.grad, v.rm, v.nw8);
