@@ -11,7 +11,12 @@ codes, the CLIs' default on the GPU):
    python tools/step_time.py --method vi --irt 2 --persons 1000000 --items 1000 --batch 16 --ability-dim 8 --blocks 5 --steps 50
 With --table-update: the person-table update alone (vibo_person_table_adam, HIP events around the call) at --persons x --ability-dim
 entries per table, as a fraction of 24 B per entry at the 6.29 TB/s copy ceiling:
-   python tools/step_time.py --method vi --table-update --persons 1000000 --ability-dim 8"""
+   python tools/step_time.py --method vi --table-update --persons 1000000 --ability-dim 8
+With --whole-matrix: the native trainer's step on the WHOLE resident matrix (no row_index: --batch is not read), replayed from a
+hipGraph, with ops.TILE_ROWS_GIVEN off (the VIBO_POSTERIOR_GIVEN launch on the rows) against on (on the matrix' tile image),
+interleaved blocks on one box; step = wall clock per replay, kernel = the GIVEN launch's own stamps (ops.InsituTimer).  For
+--merge mean (FusedMeanTrainer) and --method vi | mle (fp32 rows with a mask; --codes: 1-byte cell codes):
+   python tools/step_time.py --whole-matrix --merge mean --irt 2 --persons 1000000 --items 1000 --ability-dim 8 --blocks 5 --steps 50"""
 import argparse
 import os
 import sys
@@ -39,6 +44,8 @@ ap.add_argument('--blocks', type=int, default=5, help='MLP decoders: interleaved
 ap.add_argument('--steps', type=int, default=200, help='MLP decoders: steps per block')
 ap.add_argument('--method', default='vibo', choices=['vibo', 'vi', 'mle'], help='vi | mle: the un-amortized methods (per-person tables)')
 ap.add_argument('--table-update', action='store_true', help='--method vi | mle: time vibo_person_table_adam alone')
+ap.add_argument('--whole-matrix', action='store_true', help='--merge mean / --method vi | mle: the whole-matrix step, tile image off vs on')
+ap.add_argument('--codes', action='store_true', help='--whole-matrix: rows as 1-byte cell codes')
 a = ap.parse_args()
 d = torch.device('cuda:0')
 g = torch.Generator(device=d).manual_seed(0)
@@ -199,6 +206,79 @@ def table_update_time():
           f'({a.steps} calls); 24 B/entry at 6.29 TB/s = {floor:.1f} us -> {floor / med:.2f} of the copy ceiling', flush=True)
 
 
+def whole_matrix_legs():
+    """The whole-matrix step of the trainers whose ELBO launch reads a caller-supplied posterior, replayed from a hipGraph: the launch
+    on the rows (ops.TILE_ROWS_GIVEN off) against the launch on the matrix' tile image (on).  One trainer and one graph per leg, from
+    the same seed, on the same matrix; the legs alternate block by block."""
+    import statistics
+    from vibo_amd import ops
+    from vibo_amd.trainer import FusedTrainer
+    if a.method == 'vibo':
+        def build():
+            torch.manual_seed(0)
+            return cls(A, I, ability_merge=a.merge).to(d)
+    else:
+        mcls = {'vi': {1: M.VI_1PL, 2: M.VI_2PL, 3: M.VI_3PL}, 'mle': {1: M.MLE_1PL, 2: M.MLE_2PL, 3: M.MLE_3PL}}[a.method][a.irt]
+
+        def build():
+            torch.manual_seed(0)
+            return mcls(A, P, I).to(d)
+    response, mask = (ops.pack_cell_codes(data.response, data.mask), None) if a.codes else (data.response, data.mask)
+    legs, names = {}, []
+    real_call = ops._call
+
+    def logging_call(name, *args):
+        if name.startswith('vibo_elbo_fwd_bwd'):
+            names.append(name)
+        return real_call(name, *args)
+    ops._call = logging_call
+    for leg, on in (('rows', False), ('tile image', True)):
+        ops.TILE_ROWS_GIVEN = on
+        tr = FusedTrainer(build(), lr=5e-3, rng='native', seed=3)
+        timer = ops.InsituTimer(d)
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(3):
+                tr.step(response, mask)
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        del names[:]
+        gr = torch.cuda.CUDAGraph()
+        with timer:
+            with torch.cuda.graph(gr):
+                loss = tr.step(response, mask)
+        legs[leg] = (tr, gr, loss, timer, list(names))
+        for _ in range(5):
+            gr.replay()
+        torch.cuda.synchronize()
+    ops._call = real_call
+    label = f'{type(legs["rows"][0]).__name__} irt={a.irt} P={P} I={I} A={A} {"cell codes" if a.codes else "fp32 + mask"}'
+    for leg, (_, _, _, _, sent) in legs.items():
+        print(f'{label} {leg:10s}: captured ELBO entry point {sent}', flush=True)
+    step_us, kern_us = {leg: [] for leg in legs}, {leg: [] for leg in legs}
+    for blk in range(a.blocks):
+        for leg, (_, gr, loss, timer, _) in legs.items():
+            timer.reset()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                gr.replay()
+            torch.cuda.synchronize()
+            step_us[leg].append((time.perf_counter() - t0) / a.steps * 1e6)
+            k = timer.read()
+            kern_us[leg].append(k.get('mean_ms', 0.0) * 1e3)
+            print(f'  block {blk} {leg:10s}: step {step_us[leg][-1]:9.1f} us  kernel {kern_us[leg][-1]:9.1f} us (min {k.get("min_ms", 0.0) * 1e3:.1f}, '
+                  f'{k.get("launches", 0)} launches)  loss {float(loss):.6g}', flush=True)
+    for leg in legs:
+        s, k = step_us[leg], kern_us[leg]
+        print(f'{label} {leg:10s}: step median {statistics.median(s):9.1f} us  range {min(s):.1f} .. {max(s):.1f} | kernel median '
+              f'{statistics.median(k):9.1f} us  range {min(k):.1f} .. {max(k):.1f}  ({a.blocks} blocks x {a.steps} steps)', flush=True)
+
+
+if a.whole_matrix:
+    whole_matrix_legs()
+    sys.exit(0)
 if a.method != 'vibo':
     table_update_time() if a.table_update else person_table_legs()
     sys.exit(0)

@@ -8,6 +8,7 @@
 #include "../../include/vibo_hip.h"
 #include "../../include/vibo_hip_sign_rows.h"
 #include "../../include/vibo_hip_tile_rows.h"
+#include "../../include/vibo_hip_given_tiles.h"
 #include "vibo_cond.hpp"
 #include "vibo_general.hpp"
 #include "vibo_helpers.hpp"
@@ -49,8 +50,10 @@ static hipError_t launch_split(const vibo_desc* d, const Plan& pl, const ElboPar
                                                 {launch_elbo_msplit_xa, launch_elbo_msplit_xg, nullptr, nullptr, nullptr}};      // plain | flows | fused
     SplitVariant v;
     if (!split_variant(d, pl, p, &v)) return hipErrorInvalidValue;      // (also: none of the table's empty cells)
+    // (a tile image under the caller-supplied posterior has a unit of its own: launch_elbo_msplit_t holds hook mode 0 alone)
     SplitLauncher* const unit = v.engine == Engine::Narrow ? launch_elbo_narrow
                                 : v.engine == Engine::Valu ? valu[v.rm][v.at == 2 ? 0 : v.at == 4 ? 1 : 2]
+                                : (v.rm == kRowsTiles && v.xm == kHooksGiven) ? launch_elbo_msplit_tg
                                                            : matrix[v.xm == kHooksCondFused ? 2 : v.flows ? 1 : 0][v.rm];
     return unit(p, v, grid, s);
 }
@@ -71,6 +74,7 @@ struct ElboArgs {
     int skip_finalize = 0;
     uint64_t noise_seed = 0;                  // vibo_elbo_fwd_bwd_step_noise
     uint32_t noise_stream = 0;
+    bool given_tiles = false;                 // vibo_elbo_fwd_bwd_given_tiles: a VIBO_MASK_TILES image under VIBO_POSTERIOR_GIVEN, and nothing else
 };
 
 // the panel passes' blocks of the workspace
@@ -338,7 +342,7 @@ static int run_finalize(const vibo_desc* d, const Plan& pl, Path path, const Elb
 
 static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     const int num_cu = device_cus();
-    int rc = check_desc(d, true);
+    int rc = check_desc(d, !a.given_tiles, a.given_tiles);
     if (rc) return rc;
     const bool tile_rows = d->mask_dtype == VIBO_MASK_TILES;
     const bool sign_rows = d->mask_dtype == VIBO_MASK_SIGN || tile_rows;      // (the row formats of this call alone)
@@ -364,7 +368,8 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     const Path path = resolve_path(pl, d, vec);
     const bool row_split = path == Path::Panels || path == Path::Split;
     if (d->mask_dtype == VIBO_MASK_CODES && !row_split) return codes_unsupported();
-    if (sign_rows && !(path == Path::Split && pl.engine == Engine::Matrix))
+    const bool image_path = a.given_tiles ? path == Path::Panels && pl.first == FirstPass::GivenDirect : path == Path::Split;
+    if (sign_rows && !(image_path && pl.engine == Engine::Matrix))
         return tile_rows ? fail(-8, "VIBO_MASK_TILES rows: the tile image must be 16-byte aligned")
                          : fail(-8, "VIBO_MASK_SIGN rows: the response rows must be 16-byte aligned with a stride that is a multiple of 4");
     if (pl.given() && path != Path::Panels)
@@ -512,6 +517,36 @@ int vibo_tile_rows_build(const vibo_desc* src, const void* response, const void*
     const hipError_t e = launch_tile_rows_build(src, resp, mask, rows_vec_ok(src, resp, mask), image, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "tile_rows_build launch");
     return 0;
+}
+
+int vibo_given_tile_rows_supported(const vibo_desc* d) {
+    return (d && d->mask_dtype == VIBO_MASK_TILES && check_desc(d, false, true) == 0) ? 1 : 0;
+}
+
+size_t vibo_given_tiles_workspace_bytes(const vibo_desc* d) {
+    if (!vibo_given_tile_rows_supported(d)) return 0;
+    vibo_desc u = *d;                        // (a tile image: the same matrix as padded rows under a u8 mask)
+    u.mask_dtype = VIBO_MASK_U8;
+    u.response_row_stride = u.mask_row_stride = (u.num_item + 3) & ~3;
+    return vibo_workspace_bytes(&u);
+}
+
+int vibo_elbo_fwd_bwd_given_tiles(const vibo_desc* d, const float* response, const void* mask, const int64_t* row_index,
+                                  const float* table, const float* item, const float* eps, const float* flow,
+                                  float* out_scalars, float* ability_mu, float* ability_logvar, float* ability,
+                                  float* ability_k, float* ability_ladj, float* grad_table, float* grad_item,
+                                  float* grad_flow, void* workspace, size_t workspace_bytes, void* stream) {
+    if (!vibo_given_tile_rows_supported(d)) {
+        const int rc = check_desc(d, false, true);      // (its code and error string; a descriptor of another format: -8)
+        return rc ? rc : fail(-8, "vibo_elbo_fwd_bwd_given_tiles: a VIBO_MASK_TILES descriptor with VIBO_POSTERIOR_GIVEN only");
+    }
+    if (row_index) return fail(-8, "vibo_elbo_fwd_bwd_given_tiles: rows in order only (row_index must be NULL)");
+    if (mask || flow || ability_k || ability_ladj || grad_flow)
+        return fail(-5, "vibo_elbo_fwd_bwd_given_tiles: mask, flow, ability_k, ability_ladj and grad_flow must be NULL");
+    ElboArgs a{response, nullptr, nullptr, table, item, eps, nullptr, out_scalars, ability_mu, ability_logvar, ability,
+               nullptr, nullptr, grad_table, grad_item, nullptr, workspace, workspace_bytes, (hipStream_t)stream};
+    a.given_tiles = true;
+    return elbo_fwd_bwd_impl(d, a);
 }
 
 // The folded step's contract as the step queries ask it: none for a refused descriptor.  (VIBO_MASK_SIGN rows answer as the same rows

@@ -28,12 +28,12 @@ hipError_t launch_elbo_rows(const ElboParams& p, int irt, bool grad, int grid, h
 //   msplit_<r>, msplit_f<r>, msplit_x<r>: matrix kernel (vibo_msplit_kernel.hpp) plain / with flows / with the conditional posterior's
 //       first pass folded in (hook mode 3); at most 1024 items per launch.  narrow: vibo_narrow.hip, 4..128 items, ability_dim <= 4
 //   <r> = rows: a fp32 in order, g fp32 through row_index, c 1-byte cell codes, s fp32 in order with the sign bit as the mask,
-//       t the matrix' prepacked tile image
+//       t the matrix' prepacked tile image (msplit_tg: the same under a caller-supplied posterior, hook mode 2)
 using SplitLauncher = hipError_t(const ElboParams& p, const SplitVariant& v, int grid, hipStream_t s);
 SplitLauncher launch_elbo_split_a2, launch_elbo_split_a4, launch_elbo_split_a8, launch_elbo_split_g2, launch_elbo_split_g4,
     launch_elbo_split_g8, launch_elbo_split_c2, launch_elbo_split_c4, launch_elbo_split_c8, launch_elbo_msplit_a, launch_elbo_msplit_g,
     launch_elbo_msplit_c, launch_elbo_msplit_s, launch_elbo_msplit_t, launch_elbo_msplit_fa, launch_elbo_msplit_fg, launch_elbo_msplit_fc,
-    launch_elbo_msplit_xa, launch_elbo_msplit_xg, launch_elbo_narrow;
+    launch_elbo_msplit_xa, launch_elbo_msplit_xg, launch_elbo_msplit_tg, launch_elbo_narrow;
 
 // narrow-row kernel: waves per SIMD each instantiation is compiled for (registers: items x (parameters + gradient accumulators) + one
 // unit of rows; 3PL with gradients at 8 items per lane: 128 registers were 4-12 short -- spilled, and a spill reload waits behind the

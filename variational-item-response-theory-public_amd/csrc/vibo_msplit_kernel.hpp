@@ -179,7 +179,9 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // One barrier per batch (tile rows, 8 waves): see the batch loop.  Every other instantiation keeps the two-barrier loop.
     constexpr bool OB = ms_one_barrier(RM, XM, FLOWS, NW8);
     static_assert(!SIGN || (XM == 0 && !FLOWS), "sign-as-mask rows: the plain model's instantiations only");
-    static_assert(!TILES || (XM == 0 && !FLOWS), "tile rows: the plain model's instantiations only");
+    // (tile rows under a caller-supplied posterior, XM 2: the posterior comes from memory a batch ahead -- prs0..2, or between the
+    //  barriers at fewer than 4 waves -- and the image's counts still go to wl.cnt for backward_slot's n0 / n1; two-barrier loop)
+    static_assert(!TILES || ((XM == 0 || XM == kHooksGiven) && !FLOWS), "tile rows: the plain model's and the given posterior's instantiations only");
     constexpr int R = kMsRows;
     constexpr float kLoS = kLogitLo * kLog2e, kHiS = kLogitHi * kLog2e;
     // fp8 (e4m3) look-up tables of the pack.  fp32 rows: selector {missing, wrong, -, right}; cell codes: {wrong, right, missing}.

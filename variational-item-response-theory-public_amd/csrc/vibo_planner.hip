@@ -23,7 +23,7 @@ int fail(int code, const char* fmt, ...) {
 }
 const char* last_error() { return g_err; }
 
-int check_desc(const vibo_desc* d, bool sign_rows) {
+int check_desc(const vibo_desc* d, bool sign_rows, bool given_tiles) {
     if (!d) return fail(-1, "null descriptor");
     if (d->abi_version != VIBO_ABI_VERSION) return fail(-2, "abi_version %d != %d", d->abi_version, VIBO_ABI_VERSION);
     if (d->num_person < 1) return fail(-3, "num_person must be >= 1");
@@ -42,7 +42,7 @@ int check_desc(const vibo_desc* d, bool sign_rows) {
     if (d->mask_dtype < 0 || d->mask_dtype > VIBO_MASK_TILES || d->mask_dtype == 5) return fail(-3, "bad mask_dtype");
     if (d->mask_dtype == VIBO_MASK_SIGN && !sign_rows)
         return fail(-8, "VIBO_MASK_SIGN rows (the response's sign bit is the mask): taken by vibo_elbo_fwd_bwd and its _step forms only");
-    if (d->mask_dtype == VIBO_MASK_TILES && !sign_rows)
+    if (d->mask_dtype == VIBO_MASK_TILES && !sign_rows && !given_tiles)
         return fail(-8, "VIBO_MASK_TILES rows (the matrix' prepacked tile image): taken by vibo_elbo_fwd_bwd and its _step forms only");
     if (d->reg_mode != VIBO_REG_KL && d->reg_mode != VIBO_REG_SAMPLED) return fail(-3, "bad reg_mode");
     if (d->n_flows < 0 || d->n_flows > VIBO_MAX_FLOWS) return fail(-3, "n_flows outside 0..%d", VIBO_MAX_FLOWS);
@@ -55,6 +55,12 @@ int check_desc(const vibo_desc* d, bool sign_rows) {
         return fail(-8, "VIBO_MASK_SIGN rows (the response's sign bit is the mask): only calls the planner sends to the single-launch "
                         "matrix row-split kernel (unconditional posterior, no flows, 4..1024 items, chunkable rows, enough persons or "
                         "VIBO_FLAG_KERNEL_MATRIX)");
+    if (d->mask_dtype == VIBO_MASK_TILES && given_tiles) {      // (vibo_elbo_fwd_bwd_given_tiles: this combination and no other)
+        if (!given_tile_rows_ok(d))
+            return fail(-8, "VIBO_MASK_TILES rows under VIBO_POSTERIOR_GIVEN: only calls the planner sends to the matrix row-split kernel "
+                            "in one panel (no flows, 4..1024 items, enough persons or VIBO_FLAG_KERNEL_MATRIX)");
+        return 0;
+    }
     if (d->mask_dtype == VIBO_MASK_TILES && !sign_rows_ok(d))
         return fail(-8, "VIBO_MASK_TILES rows (the matrix' prepacked tile image): only calls the planner sends to the single-launch "
                         "matrix row-split kernel (unconditional posterior, no flows, 4..1024 items, enough persons or "
@@ -67,6 +73,13 @@ bool sign_rows_ok(const vibo_desc* d) {
     Plan pl;
     // (path and engine do not depend on the compute-unit count)
     return make_plan(d, 256, &pl) == 0 && pl.path == Path::Split && pl.engine == Engine::Matrix;
+}
+
+bool given_tile_rows_ok(const vibo_desc* d) {
+    if (d->mask_dtype != VIBO_MASK_TILES || d->posterior != VIBO_POSTERIOR_GIVEN || d->n_flows != 0 || d->num_item < 4 || d->num_item > 1024)
+        return false;
+    Plan pl;
+    return make_plan(d, 256, &pl) == 0 && pl.path == Path::Panels && pl.first == FirstPass::GivenDirect && pl.engine == Engine::Matrix;
 }
 
 int codes_unsupported() {
@@ -190,8 +203,10 @@ bool split_variant(const vibo_desc* d, const Plan& pl, const ElboParams& p, Spli
                           : v.xm == kHooksGiven ? p.given_post && !(panel || p.post_coef || p.cond_table)
                                                 : p.cond_table && !(panel || given) && (p.post_coef || !v.grad) && p.A == 1 && !v.flows &&
                                                       v.rm <= kRowsGathered && v.engine == Engine::Matrix;
-    // sign-as-mask rows and tile images: the matrix kernel's plain instantiations, rows in order without a mask
-    const bool sign_ok = (v.rm != kRowsSign && v.rm != kRowsTiles) || (v.engine == Engine::Matrix && v.xm == kHooksNone && !v.flows && !p.row_index && !p.mask && p.response);
+    // sign-as-mask rows and tile images: the matrix kernel's plain instantiations, rows in order without a mask; tile images also
+    // under the caller-supplied posterior (vibo_msplit_tg.hip)
+    const bool sign_xm = v.xm == kHooksNone || (v.rm == kRowsTiles && v.xm == kHooksGiven);
+    const bool sign_ok = (v.rm != kRowsSign && v.rm != kRowsTiles) || (v.engine == Engine::Matrix && sign_xm && !v.flows && !p.row_index && !p.mask && p.response);
     // the narrow-row kernel: the plain model on 1-byte masks / cell codes
     const bool narrow_ok = v.engine != Engine::Narrow || (p.I >= 4 && p.I <= 128 && p.A <= 4 && !v.flows && v.xm == kHooksNone &&
                                                           (v.rm == kRowsCodes || p.mask_dtype != VIBO_MASK_I64));

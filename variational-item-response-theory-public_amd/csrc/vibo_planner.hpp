@@ -16,8 +16,11 @@ const char* last_error();
 
 // sign_rows: the entry point takes VIBO_MASK_SIGN rows (include/vibo_hip_sign_rows.h) and VIBO_MASK_TILES images
 // (include/vibo_hip_tile_rows.h) where sign_rows_ok says so; every other one
-// refuses them here (-8)
-int check_desc(const vibo_desc* d, bool sign_rows = false);
+// refuses them here (-8).  given_tiles: the entry point takes VIBO_MASK_TILES images under VIBO_POSTERIOR_GIVEN
+// (include/vibo_hip_given_tiles.h) where given_tile_rows_ok says so, and no other VIBO_MASK_TILES descriptor
+int check_desc(const vibo_desc* d, bool sign_rows = false, bool given_tiles = false);
+// VIBO_MASK_TILES under VIBO_POSTERIOR_GIVEN: no flows, 4..1024 items (one panel, FirstPass::GivenDirect), the matrix kernel as the engine
+bool given_tile_rows_ok(const vibo_desc* d);
 // VIBO_MASK_SIGN: the shapes the format is implemented for -- what the planner sends to the single-launch matrix row-split kernel
 // (unconditional posterior, no flows, 4..1024 items, chunkable rows)
 bool sign_rows_ok(const vibo_desc* d);

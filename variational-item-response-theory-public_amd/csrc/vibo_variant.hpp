@@ -13,7 +13,8 @@ enum RowMode : int {
     kRowsGathered = 1,   // the same through row_index
     kRowsCodes = 2,      // 1-byte cell codes (VIBO_MASK_CODES), with or without row_index
     kRowsSign = 3,       // fp32 responses in order whose sign bit is the mask (VIBO_MASK_SIGN): matrix kernel, no hooks, no flows
-    kRowsTiles = 4       // the matrix' prepacked code words and counts (VIBO_MASK_TILES, include/vibo_hip_tile_rows.h): the same launches
+    kRowsTiles = 4       // the matrix' prepacked code words and counts (VIBO_MASK_TILES, include/vibo_hip_tile_rows.h): the same launches,
+                         // and hook mode kHooksGiven without flows (include/vibo_hip_given_tiles.h)
 };
 // VIBO_MASK_TILES: bytes of one wave's block of the image (16 code words and one counts dword per lane), and of its code words
 constexpr int kTileWaveBytes = 4352, kTileWordBytes = 4096;
@@ -42,7 +43,8 @@ constexpr bool ms_sample_optional(int xm, bool flows, bool grad, int rm, bool nw
     return ms_draws_noise(xm, flows, grad) && (nw8 || rm != kRowsGathered);
 }
 // the matrix kernel's batch loop with ONE workgroup barrier per batch (the per-person phase of the neighbouring batches runs under the
-// SIMD partner's tiles): tile rows at exactly 8 waves -- their counts are data of the image, requested two batches ahead
+// SIMD partner's tiles): tile rows at exactly 8 waves -- their counts are data of the image, requested two batches ahead.  (Tile rows
+// under a caller-supplied posterior, kHooksGiven, keep the two-barrier loop at every width.)
 constexpr bool ms_one_barrier(int rm, int xm, bool flows, bool nw8) { return rm == kRowsTiles && xm == kHooksNone && !flows && nw8; }
 constexpr bool ms_draws_noise(const SplitVariant& v) { return v.engine == Engine::Matrix && ms_draws_noise(v.xm, v.flows, v.grad); }
 constexpr bool ms_sample_optional(const SplitVariant& v) {

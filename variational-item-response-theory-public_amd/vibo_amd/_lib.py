@@ -1,8 +1,9 @@
 """ctypes binding of libvibo_hip.so.  The C ABI is declared in include/vibo_hip.h and read from there: every export's
 restype / argtypes come from its prototype (parse_prototypes); the constants and the two structs mirror the header by hand
 (tests/test_capi_symbols.py compares them).  Exports declared in a header of their own beside it (EXTRA_HEADERS:
-vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h, vibo_hip_tile_rows.h) are bound the same way; EXPORTED_SYMBOLS
-stays the list of vibo_hip.h itself, EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS, PERSON_TABLE_SYMBOLS and TILE_ROWS_SYMBOLS are theirs.
+vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h, vibo_hip_tile_rows.h, vibo_hip_given_tiles.h) are bound the same
+way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself, EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS, PERSON_TABLE_SYMBOLS, TILE_ROWS_SYMBOLS and
+GIVEN_TILES_SYMBOLS are theirs.
 
 The product path has no CPU or eager-PyTorch fallback: if the HIP library is
 missing or a call fails, this module raises.
@@ -106,7 +107,8 @@ def parse_prototypes(header):
     return protos
 
 
-EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h', 'vibo_hip_person_tables.h', 'vibo_hip_tile_rows.h')
+EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h', 'vibo_hip_person_tables.h', 'vibo_hip_tile_rows.h',
+                 'vibo_hip_given_tiles.h')
 
 with open(HEADER_PATH) as _header:
     PROTOTYPES = parse_prototypes(_header.read())
@@ -123,6 +125,7 @@ EXTRA_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_decoder_multi.h']
 SIGN_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sign_rows.h']
 PERSON_TABLE_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_person_tables.h']      # the VI / MLE train step (trainer.FusedVITrainer / FusedMLETrainer)
 TILE_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_tile_rows.h']
+GIVEN_TILES_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_given_tiles.h']          # the tile image under a caller-supplied posterior (ops._tile_rows)
 PTRAIN_VI, PTRAIN_MLE = 0, 1                                            # VIBO_PTRAIN_*
 PTRAIN_MAX_BLOCKS = 2048                                                # VIBO_PTRAIN_MAX_BLOCKS: the table update's grid cap
 

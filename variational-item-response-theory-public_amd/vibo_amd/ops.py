@@ -12,7 +12,7 @@ import contextlib
 import ctypes
 import math
 import weakref
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 from typing import Callable, NamedTuple, Optional
 
 import torch
@@ -543,9 +543,15 @@ TILE_ROWS_MIN_PERSONS = 16384
 # timer's test holds them within 25 % of each other; under capture a plain launch must read the caller's rows in any case, see
 # _tile_rows).  On: an eager plain launch counts as a sighting and uses the image like the trainers' step.
 TILE_ROWS_PLAIN_LAUNCHES = False
+# The image under a caller-supplied posterior (spec.given: the mean-merge, VI and MLE trainers' ELBO launch;
+# include/vibo_hip_given_tiles.h).  Those launches are no folded step: the trainers mark theirs `resident_step`.
+TILE_ROWS_GIVEN = True             # (tests / A-B runs switch it off; TILE_ROWS off turns this off too)
+# ... and a minimum of its own on top of TILE_ROWS_MIN_PERSONS (0: none) for shapes that measure slower on the image
+TILE_ROWS_GIVEN_MIN_PERSONS = 0
 
 
-def _tile_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode, want_grad, train_step, *, capturing):
+def _tile_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode, want_grad, train_step, *, capturing,
+               resident_step=False):
     """The one decision about a resident matrix' tile image (include/vibo_hip_tile_rows.h) -> the image this ELBO launch goes out on
     (a uint8 tensor: the launch is (image, None, MASK_TILES)), False (the launch keeps the caller's rows as they are: the matrix is
     on its way to an image, or a plain launch is being captured), or None (no image for this call: _sign_rows decides as ever).
@@ -563,8 +569,17 @@ def _tile_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode,
     matrix is _sign_rows' from then on.  A matrix with an image is never sign-verified: the fact would save nothing.
     While capturing, the two regimes of _lookup_counts / _sign_rows: a plain launch whose input is the whole matrix keeps the
     caller's rows (a replay after `response.copy_(new)` has to read what is there then); the trainers' folded step (train_step
-    given) uses the image -- the resident-matrix contract "counted once".  capturing(): asked only where the answer matters."""
-    if (not TILE_ROWS or (train_step is None and not TILE_ROWS_PLAIN_LAUNCHES)
+    given) uses the image -- the resident-matrix contract "counted once".  capturing(): asked only where the answer matters.
+    A caller-supplied posterior (spec.given; TILE_ROWS_GIVEN): the same rules with `resident_step` -- the mean-merge, VI and MLE
+    trainers' whole-matrix launch -- in the folded step's place, vibo_given_tile_rows_supported as the shape's query and
+    TILE_ROWS_GIVEN_MIN_PERSONS on top of the threshold.  The image is the same one on the same record (a plain trainer and a
+    mean-merge trainer on one matrix share it); it is built as the plain twin of the spec would build it, with the matrix kernel
+    pinned in the builder's descriptor, so that the builder's answer does not depend on the plain model's engine thresholds."""
+    given = bool(getattr(spec, 'given', False))
+    resident = resident_step if given else train_step is not None
+    if given and (not TILE_ROWS_GIVEN or num_person < TILE_ROWS_GIVEN_MIN_PERSONS):
+        return None
+    if (not TILE_ROWS or (not resident and not TILE_ROWS_PLAIN_LAUNCHES)
             or response is None or row_index is not None or num_person != response.shape[0]
             or num_person < TILE_ROWS_MIN_PERSONS or mask_code not in (_lib.MASK_U8, _lib.MASK_NONE, _lib.MASK_CODES)):
         return None
@@ -573,7 +588,7 @@ def _tile_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode,
     if not _matrix_kernel_rows(response, mask, mask_code):
         return None
     d = _tile_desc(spec, num_person, response.shape[1], reg_mode, want_grad)
-    if not _BACKEND['tile_supported'](d):
+    if not _BACKEND['tile_given_supported' if given else 'tile_supported'](d):
         return None
     known_mask = None if mask_code == _lib.MASK_CODES else mask        # (CellCodes rows are known by the codes alone)
     rec = getattr(response, '_vibo_row_counts', None)
@@ -584,16 +599,19 @@ def _tile_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode,
         if capturing():
             return False
         rec.tiles = False                                              # (a "no" until the image stands)
-        need = _BACKEND['tile_bytes'](d)
-        if 0 < need <= _BACKEND['tile_free'](response.device) // 2:
-            try:
-                rec.tiles = _BACKEND['tile_build'](spec, response, mask, mask_code, num_person, reg_mode, want_grad, need)
-            except torch.cuda.OutOfMemoryError:
-                pass
+        # (a given spec: the builder reads its plain twin under the matrix-kernel pin; it may still refuse the shape -- 0 bytes)
+        with desc_flags(DESC_FLAGS | _lib.FLAG_KERNEL_MATRIX) if given else contextlib.nullcontext():
+            build_spec = replace(spec, given=False) if given else spec
+            need = _BACKEND['tile_bytes'](_tile_desc(build_spec, num_person, response.shape[1], reg_mode, want_grad))
+            if 0 < need <= _BACKEND['tile_free'](response.device) // 2:
+                try:
+                    rec.tiles = _BACKEND['tile_build'](build_spec, response, mask, mask_code, num_person, reg_mode, want_grad, need)
+                except torch.cuda.OutOfMemoryError:
+                    pass
         return False if rec.tiles is not False else None               # (the building launch itself still reads the caller's rows)
     if rec.tiles is False:
         return None
-    if train_step is None and capturing():
+    if not resident and capturing():
         return False
     return rec.tiles
 
@@ -617,6 +635,10 @@ def _tile_desc(spec, num_person, num_item, reg_mode, want_grad):
 
 def _hip_tile_rows_supported(d):
     return _lib.load().vibo_tile_rows_supported(ctypes.byref(d)) == 1
+
+
+def _hip_given_tile_rows_supported(d):
+    return _lib.load().vibo_given_tile_rows_supported(ctypes.byref(d)) == 1
 
 
 def _hip_tile_rows_bytes(d):
@@ -649,8 +671,10 @@ class TrainStepCall(NamedTuple):
 
 
 def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, eps, flow, reg_mode,
-                     want_grad, num_person, train_step=None):
-    """Single call into vibo_elbo_fwd_bwd on the current stream, or (train_step: a TrainStepCall) into vibo_elbo_fwd_bwd_step."""
+                     want_grad, num_person, train_step=None, *, resident_step=False):
+    """Single call into vibo_elbo_fwd_bwd on the current stream, or (train_step: a TrainStepCall) into vibo_elbo_fwd_bwd_step.
+    resident_step: a trainer's whole-matrix launch under a caller-supplied posterior (spec.given) -- with the matrix' tile image
+    (_tile_rows) it goes into vibo_elbo_fwd_bwd_given_tiles."""
     lib = _lib.load()
     _require_device(response, mask, table, item, eps)
     dev = response.device
@@ -668,7 +692,8 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     ability_k = torch.empty(B, A, dtype=torch.float32, device=dev) if spec.n_flows else None
     ladj = torch.empty(B, dtype=torch.float32, device=dev) if spec.n_flows else None
     image = _tile_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step,
-                       capturing=torch.cuda.is_current_stream_capturing)
+                       capturing=torch.cuda.is_current_stream_capturing, resident_step=resident_step)
+    given_tiles = image is not None and image is not False and bool(getattr(spec, 'given', False))
     if image is None:
         mask, mask_code = _sign_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step,
                                      capturing=torch.cuda.is_current_stream_capturing)
@@ -677,9 +702,10 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     else:
         response, mask, mask_code = image, None, _lib.MASK_TILES
         d = _tile_desc(spec, B, I, reg_mode, want_grad)
-    ws_bytes = lib.vibo_workspace_bytes(ctypes.byref(d))
+    ws_query = 'vibo_given_tiles_workspace_bytes' if given_tiles else 'vibo_workspace_bytes'
+    ws_bytes = getattr(lib, ws_query)(ctypes.byref(d))
     if ws_bytes == 0:
-        _lib.check(-1, 'vibo_workspace_bytes')
+        _lib.check(-1, ws_query)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     vp, fbase, o_item = ctypes.c_void_p, flat.data_ptr(), _lib.NUM_SCALARS + 2 * n_table
     # the argument runs the four exports share (include/vibo_hip.h): the rows, the gradients, workspace and stream
@@ -698,7 +724,7 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
                 _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), *grads, *tail)
     else:
         counts = None if mask_code == _lib.MASK_TILES else _resident_row_counts(spec, response, mask, mask_code, row_index, B, stream)
-        name = 'vibo_elbo_fwd_bwd' if counts is None else 'vibo_elbo_fwd_bwd_counts'
+        name = 'vibo_elbo_fwd_bwd_given_tiles' if given_tiles else 'vibo_elbo_fwd_bwd' if counts is None else 'vibo_elbo_fwd_bwd_counts'
         args = (*rows, *(() if counts is None else (_ptr(counts),)), _ptr(table), _ptr(item), _ptr(eps), _ptr(flow), vp(fbase),
                 _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), _ptr(ability_k), _ptr(ladj), *grads,
                 vp(fbase + 4 * (o_item + n_item)) if n_flow else vp(0), *tail)
@@ -978,7 +1004,7 @@ _BACKEND = {'elbo': _hip_launch_elbo, 'encode': _hip_encode, 'decode': _hip_deco
             'mean_bwd': _hip_mean_encoder_bwd, 'flow_stack': _hip_flow_stack, 'cond_mean_sum': _hip_cond_mean_sum,
             'sign_supported': _hip_sign_rows_supported, 'sign_verify': _hip_sign_is_mask,
             'tile_supported': _hip_tile_rows_supported, 'tile_bytes': _hip_tile_rows_bytes, 'tile_free': _hip_free_bytes,
-            'tile_build': _hip_tile_rows_build}
+            'tile_build': _hip_tile_rows_build, 'tile_given_supported': _hip_given_tile_rows_supported}
 
 
 class FusedELBO(torch.autograd.Function):

@@ -188,6 +188,13 @@ class _FusedStep:
         ab_stream = 1 + getattr(self.model, '_shard_rank', 0)      # item noise: the same on every rank; ability noise: per rank
         return response, mask, code, B, I, stream, d, ab_stream
 
+    @staticmethod
+    def _resident_step():
+        """Keywords of an ELBO launch under a caller-supplied posterior (mean merge, VI, MLE): the HIP launcher is told that this is
+        a trainer's step on its resident matrix -- a whole-matrix step may then go out on the matrix' tile image (ops._tile_rows
+        decides).  Any other backend (the CPU stand-in, a test's fake) keeps its signature."""
+        return {'resident_step': True} if ops._BACKEND['elbo'] is ops._hip_launch_elbo else {}
+
     def _ab_buffer(self, B, dev):
         # one buffer per batch size, never freed or replaced: a captured hipGraph keeps the pointer it was recorded
         # with, and the epoch's last, shorter minibatch runs eagerly in between the replays
@@ -557,7 +564,8 @@ class FusedMeanTrainer(_FusedStep):
         dm = ops._mean_desc(counts, A)
         ops._call('vibo_mean_encoder_forward', ctypes.byref(dm), H, p(counts), p(self.uv[:H]), p(self.uv[H:]), p(self._w22), p(self._b22),
                   p(post), stream)
-        raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, post, self.item_feat, eps_ab, None, _lib.REG_KL, True, B)
+        raw = ops._BACKEND['elbo'](spec, response, mask, code, row_index, post, self.item_feat, eps_ab, None, _lib.REG_KL, True, B,
+                                   **self._resident_step())
         n_part = lib.vibo_mean_encoder_partials(ctypes.byref(dm))
         parts = self._parts.get(n_part)
         if parts is None:
@@ -855,7 +863,7 @@ class _PersonTableStep(_FusedStep):
         if eps_ab is None:                    # rng='torch': the reference's order, item noise then ability noise
             eps_ab = torch.randn(B, A, dtype=torch.float32, device=dev)
         raw = ops._BACKEND['elbo'](self.model.spec, response, mask, code, row_index, post, self.item_feat, eps_ab, None, _lib.REG_KL,
-                                   True, B)
+                                   True, B, **self._resident_step())
         self._pending = (d, eps_item, raw, index)
         self.last = raw
         return raw
