@@ -178,6 +178,9 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     constexpr bool kMayGather = ms_may_gather(RM);        // (the instantiation can meet p.row_index)
     // One barrier per batch (tile rows, 8 waves): see the batch loop.  Every other instantiation keeps the two-barrier loop.
     constexpr bool OB = ms_one_barrier(RM, XM, FLOWS, NW8);
+    // Paired code words (tile rows): see pair_words and the conversion in the tile.
+    constexpr bool WP = ms_word_pairs(RM);
+    static_assert(!WP || TILES, "paired code words: the words come from the image, one batch ahead");
     static_assert(!SIGN || (XM == 0 && !FLOWS), "sign-as-mask rows: the plain model's instantiations only");
     // (tile rows under a caller-supplied posterior, XM 2: the posterior comes from memory a batch ahead -- prs0..2, or between the
     //  barriers at fewer than 4 waves -- and the image's counts still go to wl.cnt for backward_slot's n0 / n1; two-barrier loop)
@@ -358,6 +361,21 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         const uint4 w1 = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs.r, tvo, tso + 2048 * h + 1024, 0));
         cw0[4 * h] = w0.x; cw0[4 * h + 1] = w0.y; cw0[4 * h + 2] = w0.z; cw0[4 * h + 3] = w0.w;
         cw1[4 * h] = w1.x; cw1[4 * h + 1] = w1.y; cw1[4 * h + 2] = w1.z; cw1[4 * h + 3] = w1.w;
+    };
+    // Paired words (WP).  The image's word k of a lane holds person k's cell of the u-step's four tiles, a byte per tile, and
+    // cvt_pk_f32_fp8 turns two ADJACENT bytes of one word into two adjacent registers: on the image's words that is one person's cells of
+    // tiles t and t + 1, while the tile's arithmetic runs packed on persons (k, k + 1) of ONE tile.  So the words are interleaved by bytes
+    // once per batch, where they become the current batch's: words a = [a0 a1 a2 a3] and b = [b0 b1 b2 b3] (persons k, k + 1, k even;
+    // byte 0 first) turn into X = [a0 b0 a1 b1] and Y = [a2 b2 a3 b3], and tile t converts bytes 2 (t & 1), 2 (t & 1) + 1 of (t < 2 ? X : Y).
+    // v_perm_b32 D = perm(S0, S1, sel): selector byte i picks D's byte i out of {S0, S1}, 0-3 = bytes of S1, 4-7 = bytes of S0.
+    // (dst may be src: both results are formed before either is written)
+    auto pair_words = [&](uint32_t (&dst)[8], const uint32_t (&src)[8]) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < 8; k += 2) {
+            const uint32_t a = src[k], b = src[k + 1];
+            dst[k] = __builtin_amdgcn_perm(b, a, 0x05010400u);
+            dst[k + 1] = __builtin_amdgcn_perm(b, a, 0x07030602u);
+        }
     };
     auto load_tile_counts = [&](const RowSrc& rs) __attribute__((always_inline)) {
         return (uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rs.r, tvc, tso + kTileWordBytes, 0);
@@ -1321,8 +1339,20 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         const float lg[8] = {d0[0], d0[1], d0[2], d0[3], d1[0], d1[1], d1[2], d1[3]};
         float gl[8];
         float pr0 = 1.0f, pr1 = 1.0f;
-        // the codes of tiles t and t + 1 are converted together at the even tile (one instruction per person and pair)
-        if constexpr ((t & 1) == 0) {
+        // The tile's code values wc[k] = -w, 0 for a missing cell (fp8 -> fp32, two cells per instruction).
+        // Paired words (WP, see pair_words): every tile converts its OWN four pairs -- (wc[k], wc[k + 1]) land in adjacent registers, the
+        // operands of the packed fp32 instructions below, and nothing is copied or kept for the next tile.
+        // Words as packed or loaded: the codes of tiles t and t + 1 are converted together at the even tile (one instruction per person:
+        // its cell of either tile), the odd tile's values live across the even one, and hipcc re-forms the pairs with register copies.
+        float wpr[8];
+        if constexpr (WP) {
+#pragma unroll
+            for (int k = 0; k < 8; k += 2) {
+                const float2v w2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)cw[k + (t >> 1)], (t & 1) != 0);
+                wpr[k] = w2[0];
+                wpr[k + 1] = w2[1];
+            }
+        } else if constexpr ((t & 1) == 0) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const float2v w2 = __builtin_amdgcn_cvt_pk_f32_fp8((int)cw[k], t == 2);
@@ -1330,7 +1360,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 wod[k] = w2[1];
             }
         }
-        const float (&wc)[8] = (t & 1) ? wod : wev;
+        const float (&wc)[8] = WP ? wpr : (t & 1) ? wod : wev;
         if constexpr (IRT != 3) {
             // wc = -w.  exponent e = -w l; ll = -log2(1 + 2^e); d ll/d l = w 2^e / (1 + 2^e) = wc / (1 + 2^e) - wc.
             // The reference's probability clamp (utils.py:46-49 -> torch) only matters for |logit| > 15.94: value capped at
@@ -1368,7 +1398,9 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(lmax) : "v"(lmax), "v"(uu[3]), "v"(uu[4]));
             asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(lmax) : "v"(lmax), "v"(uu[5]), "v"(uu[6]));
             asm("v_max_f32_e64 %0, %1, |%2|" : "=v"(lmax) : "v"(lmax), "v"(uu[7]));
-            if (__any(!(lmax <= kLoS))) {                              // (wave-uniform, rare)
+            // (WP: marked unlikely -- hipcc otherwise lays the clamp path out as the fall-through and the plain tile takes a branch)
+            const bool clamp2 = __any(!(lmax <= kLoS));              // (wave-uniform, rare)
+            if (WP ? __builtin_expect(clamp2, false) : clamp2) {
                 pr0 = pr1 = 1.0f;
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
@@ -1449,9 +1481,10 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 // eps32 says nothing -- four answers of probability 2 % in one lane's quad get there, which simulated or badly
                 // fitted responses do all the time: config 5's benchmark matrix sent every tile down the second path that way.)
                 // min3 / max3 drop a NaN operand (an exponential that overflowed: inf / inf), the products keep it.
-                if (__any(!(vlo >= kEps32 && vhi <= 1.0f - kEps32 && pr0 * pr1 > 0.f))) redo = sat3 = true;      // (wave-uniform)
+                const bool clamp3 = __any(!(vlo >= kEps32 && vhi <= 1.0f - kEps32 && pr0 * pr1 > 0.f));          // (wave-uniform)
+                if (WP ? __builtin_expect(clamp3, false) : clamp3) redo = sat3 = true;
             }
-            if (redo) {
+            if (WP ? __builtin_expect(redo, false) : redo) {      // (WP: out of line, as in 2PL)
                 // The same quantities with the clamp applied cell by cell: v clamped IS the reference's clamp of p (right: v = p;
                 // wrong: v = 1 - p, and 1 - clamp(p) = clamp(1 - p)), gradient zero where it bit; the exponent is held inside
                 // +-60 first (n t <= 2^121; beyond it v is 0, 1, guess or 1 - guess to the last bit anyway).  Unclamped cells
@@ -1542,10 +1575,18 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     using IC1 = std::integral_constant<int, 1>;
     using IC2 = std::integral_constant<int, 2>;
     using IC3 = std::integral_constant<int, 3>;
+    // The d LL/d theta shares: a_hi column + a_lo column, lanes l and l + 8 of a row (row_ror 8).  hipcc sinks the eight sums into the
+    // branch of the lanes that store them, and the DPP move is folded into its add only within one block: v_mov 0 (the move's `old`),
+    // v_mov_dpp and v_add per value.  Paired words (WP): the sums are held in front of the branch -- one v_add_f32_dpp per value (every
+    // lane of a row rotation is written, `old` is never read; same operands, same bits).
     auto put_gtheta = [&](const int par) {
         float v[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = acc_gt[k >> 2][k & 3] + dpp_f<0x128>(acc_gt[k >> 2][k & 3]);   // row_ror 8: a_hi col + a_lo col
+        for (int k = 0; k < 8; ++k) {                   // row_ror 8: a_hi col + a_lo col
+            const float s = acc_gt[k >> 2][k & 3];
+            v[k] = s + dpp_f<0x128>(s);
+            if constexpr (WP) asm volatile("" : "+v"(v[k]));
+        }
         if (i16 < 8) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) wl.gth[par][16 * (k >> 2) + 4 * g + (k & 3)][i16] = v[k];
@@ -1585,6 +1626,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         MS_P(23, t_entry)
         if constexpr (TILES) put_tile_counts(tcnt, true);      // (the words are where the tiles read them)
         else put_counts(pk, true);
+        if constexpr (WP) { pair_words(cwA0, cwA0); pair_words(cwA1, cwA1); }      // (the first batch's, loaded as the image has them: paired in place)
         put_stats();
         if constexpr (OB) {
             // one-barrier loop: the second batch's counts too, and theta of the first batch -- iteration 0's barrier publishes it
@@ -1691,6 +1733,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             put_tile_counts(tcnt, nxt + G < n_batches, par);      // (waits for the five loads: none crosses the back edge)
             MS_T(10)
             if constexpr (GRAD) put_gtheta(par);
+            if constexpr (WP) { pair_words(cwA0, cwB0); pair_words(cwA1, cwB1); }      // (the words become the next batch's, paired)
+            else
 #pragma unroll
             for (int k = 0; k < 8; ++k) { cwA0[k] = cwB0[k]; cwA1[k] = cwB1[k]; }
         }
@@ -1839,6 +1883,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         put_stats();
         MS_T(11)
         if constexpr (GRAD) put_gtheta(par);
+        if constexpr (WP) { pair_words(cwA0, cwB0); pair_words(cwA1, cwB1); }
+        else
 #pragma unroll
         for (int k = 0; k < 8; ++k) { cwA0[k] = cwB0[k]; cwA1[k] = cwB1[k]; }
     }

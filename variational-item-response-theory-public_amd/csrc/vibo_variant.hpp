@@ -46,6 +46,10 @@ constexpr bool ms_sample_optional(int xm, bool flows, bool grad, int rm, bool nw
 // SIMD partner's tiles): tile rows at exactly 8 waves -- their counts are data of the image, requested two batches ahead.  (Tile rows
 // under a caller-supplied posterior, kHooksGiven, keep the two-barrier loop at every width.)
 constexpr bool ms_one_barrier(int rm, int xm, bool flows, bool nw8) { return rm == kRowsTiles && xm == kHooksNone && !flows && nw8; }
+// the matrix kernel keeps a batch's code words PAIRED in registers (words k and k + 1 of a lane byte-interleaved where they become the
+// current batch's, so that a tile converts cells k and k + 1 of ITSELF into adjacent registers), sums the d LL/d theta shares with one
+// DPP add per value and lays the tile's clamp path out of line: every tile-rows instantiation.  The image in memory is not affected.
+constexpr bool ms_word_pairs(int rm) { return rm == kRowsTiles; }
 constexpr bool ms_draws_noise(const SplitVariant& v) { return v.engine == Engine::Matrix && ms_draws_noise(v.xm, v.flows, v.grad); }
 constexpr bool ms_sample_optional(const SplitVariant& v) {
     return v.engine == Engine::Matrix && ms_sample_optional(v.xm, v.flows, v.grad, v.rm, v.nw8);
