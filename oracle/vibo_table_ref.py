@@ -225,3 +225,43 @@ def fused_elbo_ref(table, item, response, mask, eps, *, irt_model, ability_dim,
         g_table.append(gt)
     out.update(g_table=g_table, g_item=g_item, g_flow=g_flow)
     return out
+
+
+PER_PERSON = ('ability_mu', 'ability_logvar', 'ability', 'ability_k', 'ladj')
+SUMMED = ('ll', 'reg', 'kl_ability', 'logq0', 'logp', 'ladj_sum')
+
+
+def flat_flow_grads(g_flow):
+    """g_flow of fused_elbo_ref -> [2, n_flows, 2A+1] (uhat | w | b per flow: the kernel's layout); [2, 0, 0] without flows."""
+    return torch.stack([torch.stack([torch.cat(gf) for gf in g_set]) if g_set else torch.zeros(0, 0) for g_set in g_flow])
+
+
+def fused_elbo_ref_sliced(table, item, response, mask, eps, rows_per_slice, *, keep_logit=False, **kw):
+    """fused_elbo_ref on consecutive slices of `rows_per_slice` persons (the last one shorter), put together into the dictionary of
+    the unsliced call: every reduction it returns is a sum over persons, so the [B, I, A] temporaries shrink to [rows_per_slice, I, A].
+    Per-person outputs are concatenated (the [B, I] logit only with keep_logit); the scalars, g_item, g_table and g_flow are summed
+    over the slices in float64 and cast to the inputs' dtype; with given_posterior the table is sliced with the persons and its
+    per-person g_table is concatenated.  Also 'g_flow_slices' [n_slices, 2, n_flows, 2A+1] (float64): each slice's own contribution
+    to g_flow, in the kernel's layout (flat_flow_grads)."""
+    B = response.shape[0]
+    given, want_grad = bool(kw.get('given_posterior')), kw.get('want_grad', True)
+    parts = []
+    for r0 in range(0, B, rows_per_slice):
+        sl = slice(r0, min(B, r0 + rows_per_slice))
+        parts.append(fused_elbo_ref(table[sl] if given else table, item, response[sl], mask[sl], eps[sl], **kw))
+    dt = table.dtype
+    out = {k: torch.cat([p[k] for p in parts]) for k in PER_PERSON + (('logit',) if keep_logit else ())}
+    for k in SUMMED:
+        out[k] = torch.stack([p[k].double() for p in parts]).sum(0).to(dt)
+    if not want_grad:
+        return out
+    out['g_item'] = torch.stack([p['g_item'].double() for p in parts]).sum(0).to(dt)
+    if given:
+        out['g_table'] = [torch.cat([p['g_table'][s] for p in parts]) for s in range(2)]
+    else:
+        out['g_table'] = [torch.stack([p['g_table'][s].double() for p in parts]).sum(0).to(dt) for s in range(2)]
+    out['g_flow_slices'] = torch.stack([flat_flow_grads(p['g_flow']).double() for p in parts])
+    total = out['g_flow_slices'].sum(0).to(dt)
+    A = kw['ability_dim']
+    out['g_flow'] = [[(f[:A], f[A:2 * A], f[2 * A:]) for f in total[s]] for s in range(2)]
+    return out

@@ -8,6 +8,9 @@
 
     VIBO_TOL_RECORD=record.jsonl python -m pytest tests/test_gpu_fallback_cells.py -q -m gpu
     python tools/split_record_table.py record.jsonl fallback_cells > profiles/fallback_cells_record.txt
+
+    VIBO_TOL_RECORD=record.jsonl python -m pytest tests/test_gpu_flow_batches.py -q -m gpu
+    python tools/split_record_table.py record.jsonl flow_batches >> profiles/flow_batches_record.txt
 """
 import collections
 import json
@@ -88,7 +91,28 @@ def fallback_cells(recs):
         print(f'  {cid:70s} {tuple(trips[cid])}')
 
 
-KINDS = {'split_worst_case': split_worst_case, 'narrow_cells': narrow_cells, 'fallback_cells': fallback_cells}
+def flow_batches(recs):
+    fam = lambda r: ('matrix' if r['kernel'] == 'matrix' else 'valu') + (' forward-only' if 'forward-only' in r['case'] else '')
+    worst, where = collections.defaultdict(float), {}
+    for r in recs:
+        k = (fam(r), r['observable'])
+        if r['ratio'] >= worst[k]:
+            worst[k], where[k] = r['ratio'], (r['err'], r['tol'], r['case'])
+    fams = sorted({k[0] for k in worst})
+    print(f'Worst observed error per case family and observable ({len(recs)} records of tests/test_gpu_flow_batches.py on one MI355X):')
+    print('the error in the units of its bound, the bound, the share of the bound, the case.  Scalars: relative (of max(1, |ref|) but for')
+    print('S_LL); ability_mu / logvar / ability: of max(1, max|ref|); ability_k / ability_ladj: absolute; g_flow block: of the block\'s')
+    print('max_e sum_batches |batch contribution| (oracle/vibo_table_ref.py fused_elbo_ref_sliced).')
+    print()
+    for f in fams:
+        print(f)
+        for o in sorted({k[1] for k in worst if k[0] == f}):
+            e, t, cid = where[(f, o)]
+            print(f'  {o:18s} {e:10.2e} {t:8.0e} {worst[(f, o)]:7.3f}  {cid}')
+        print()
+
+
+KINDS = {'flow_batches': flow_batches, 'split_worst_case': split_worst_case, 'narrow_cells': narrow_cells, 'fallback_cells': fallback_cells}
 
 
 def main(path, kind='split_worst_case'):
