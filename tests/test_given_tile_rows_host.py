@@ -11,7 +11,7 @@ import torch
 
 import tile_rows_common as T
 from conftest import ROOT
-from test_sign_rows_host import desc as sign_desc
+from row_format_common import desc as sign_desc, matrix
 from vibo_amd import _lib, ops
 
 GIVEN, MATRIX = _lib.POSTERIOR_GIVEN, _lib.FLAG_KERNEL_MATRIX
@@ -180,12 +180,6 @@ def fake(monkeypatch):
     monkeypatch.setattr(ops, 'TILE_ROWS_MIN_PERSONS', 8)
     monkeypatch.setattr(ops, 'TILE_ROWS_PLAIN_LAUNCHES', False)
     return log
-
-
-def matrix(P=12, I=8, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    mask = torch.rand(P, I, generator=g) > 0.2
-    return torch.where(mask, (torch.rand(P, I, generator=g) < 0.5).float(), torch.tensor(-1.0)), mask
 
 
 def decide(log, resp, mask, spec=GIVEN_SPEC, row_index=None, B=None, capturing=False, train_step=None, **kw):

@@ -16,7 +16,7 @@ import pytest
 import torch
 
 from gpu_common import assert_same_parameters, dev
-from test_gpu_tile_rows import build, device_rows, grid_of, host_rows
+from tile_rows_gpu_common import build, device_rows, grid_of, host_rows
 from vibo_amd import _lib, ops
 from vibo_amd.torch_core import models as M
 from vibo_amd.trainer import FusedMeanTrainer, FusedMLETrainer, FusedTrainer, FusedVITrainer

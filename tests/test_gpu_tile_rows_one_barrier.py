@@ -11,7 +11,7 @@ import pytest
 import torch
 
 from gpu_common import dev
-from test_gpu_tile_rows import assert_same_outputs, both, build, grid_of, host_rows, problem, strided
+from tile_rows_gpu_common import assert_same_outputs, both, build, grid_of, host_rows, problem, strided
 from vibo_amd import _lib
 
 pytestmark = pytest.mark.gpu

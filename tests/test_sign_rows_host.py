@@ -9,22 +9,11 @@ import pytest
 import torch
 
 from conftest import ROOT
+from row_format_common import _null_call, desc, matrix
 from vibo_amd import _lib, ops
 
 SIGN_ENTRY_POINTS = {'vibo_elbo_fwd_bwd', 'vibo_elbo_fwd_bwd_step', 'vibo_elbo_fwd_bwd_step_noise', 'vibo_workspace_bytes',
                      'vibo_plan_kernel', 'vibo_train_step_supported', 'vibo_train_step_draws_noise', 'vibo_train_step_sample_optional'}
-
-
-def desc(B=1_000_000, I=1000, A=8, irt=2, mask=_lib.MASK_SIGN, posterior=_lib.POSTERIOR_UNCONDITIONAL, n_flows=0, flags=0, grad=1,
-         stride=None):
-    d = _lib.ViboDesc()
-    d.abi_version = _lib.ABI_VERSION
-    d.num_person, d.num_item, d.ability_dim, d.irt_model = B, I, A, irt
-    d.posterior, d.n_flows, d.flags, d.want_grad = posterior, n_flows, flags, grad
-    d.reg_mode = _lib.REG_SAMPLED if n_flows else _lib.REG_KL
-    d.mask_dtype = mask
-    d.response_row_stride = d.mask_row_stride = ((I + 3) & ~3) if stride is None else stride
-    return d
 
 
 GRID = {'headline': {}, 'ability_dim 1': dict(A=1), '3PL forward only': dict(irt=3, grad=0), '132 items pinned': dict(B=500, I=132, flags=_lib.FLAG_KERNEL_MATRIX),
@@ -57,13 +46,6 @@ def test_supported_query_wants_the_format_itself():
     lib = _lib.load()
     assert lib.vibo_sign_rows_supported(ctypes.byref(desc(mask=_lib.MASK_U8))) == 0 and lib.vibo_sign_rows_supported(None) == 0
     assert lib.vibo_plan_kernel(ctypes.byref(desc(mask=5))) == -3
-
-
-def _null_call(fn, d):
-    args = []
-    for t in fn.argtypes[1:]:
-        args.append(None if t is ctypes.c_void_p or isinstance(t, type(ctypes.POINTER(_lib.ViboDesc))) else (64 if t is ctypes.c_int else 0))
-    return fn(ctypes.byref(d), *args)
 
 
 def test_every_other_export_refuses_the_format_before_any_launch():
@@ -140,15 +122,6 @@ def fake(monkeypatch):
     monkeypatch.setitem(ops._BACKEND, 'sign_verify', verify)
     monkeypatch.setattr(ops, 'SIGN_ROWS', True)
     return log
-
-
-def matrix(P=12, I=8, seed=0, consistent=True):
-    g = torch.Generator().manual_seed(seed)
-    mask = torch.rand(P, I, generator=g) > 0.2
-    resp = torch.where(mask, (torch.rand(P, I, generator=g) < 0.5).float(), torch.tensor(-1.0))
-    if not consistent:
-        resp[3, 4], mask[3, 4] = 1.0, False
-    return resp, mask
 
 
 def decide(log, resp, mask, row_index=None, B=None, capturing=False, train_step=None, keep_int64=False):

@@ -10,7 +10,7 @@ import torch
 
 import tile_rows_common as T
 from conftest import ROOT
-from test_sign_rows_host import _null_call, desc as sign_desc
+from row_format_common import _null_call, desc as sign_desc, matrix
 from vibo_amd import _lib, ops
 
 TILE_ENTRY_POINTS = {'vibo_elbo_fwd_bwd', 'vibo_elbo_fwd_bwd_step', 'vibo_elbo_fwd_bwd_step_noise', 'vibo_workspace_bytes',
@@ -178,12 +178,6 @@ def fake(monkeypatch):
     return log
 
 
-def matrix(P=12, I=8, seed=0):
-    g = torch.Generator().manual_seed(seed)
-    mask = torch.rand(P, I, generator=g) > 0.2
-    return torch.where(mask, (torch.rand(P, I, generator=g) < 0.5).float(), torch.tensor(-1.0)), mask
-
-
 def decide(log, resp, mask, row_index=None, B=None, capturing=False, train_step=None):
     """'tiles' / 'rows' (the caller's rows, _sign_rows not asked) / 'sign rows decide' (None: the call is _sign_rows')."""
     r, m, code = ops.prepare_rows(resp, mask)
@@ -283,15 +277,12 @@ def test_the_size_threshold(fake, monkeypatch):
 
 
 def test_below_the_threshold_sign_rows_is_reached_unchanged(fake, monkeypatch):
-    """_hip_launch_elbo's order of the two decisions, with both faked: a small matrix goes U8, U8, SIGN as before this format."""
+    """The launch's order of the two decisions (ops._launch_rows), with both faked: a small matrix goes U8, U8, SIGN as before this format."""
     resp, mask = matrix(P=7)
     r, m, code = ops.prepare_rows(resp, mask)
-    sent = []
-    for _ in range(4):
-        image = ops._tile_rows(SPEC, r, m, code, None, 7, _lib.REG_KL, True, None, capturing=lambda: False)
-        assert image is None
-        sent.append(ops._sign_rows(SPEC, r, m, code, None, 7, _lib.REG_KL, True, None, capturing=lambda: False)[1])
+    sent = [ops._launch_rows(SPEC, r, m, code, None, 7, _lib.REG_KL, True, None, capturing=lambda: False, stream=None).mask_code for _ in range(4)]
     assert sent == [_lib.MASK_U8, _lib.MASK_U8, _lib.MASK_SIGN, _lib.MASK_SIGN] and fake['build'] == 0
+    assert fake['supported'] == 0 and r._vibo_row_counts.tiles is None         # (no image for these calls: never asked for, never decided)
 
 
 @pytest.mark.parametrize('why', ['half of the free memory', 'the allocator'])

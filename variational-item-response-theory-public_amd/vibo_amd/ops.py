@@ -12,6 +12,7 @@ import contextlib
 import ctypes
 import math
 import weakref
+from collections import namedtuple
 from dataclasses import dataclass, field, replace
 from typing import Callable, NamedTuple, Optional
 
@@ -291,8 +292,6 @@ def chunkable_rows(response, mask, row_index=_NOT_GIVEN):
     return (response, mask) if row_index is _NOT_GIVEN else (response, mask, row_index)
 
 
-
-
 # vibo_desc.flags of every descriptor this module builds (_lib.FLAG_*): 0 = the planner chooses.  Tests and A/B tools
 # pin one row-split kernel here; the library itself reads no environment variable.
 DESC_FLAGS = 0
@@ -415,9 +414,16 @@ class ResidentMatrix:
     counts (vibo_row_counts; None until the matrix has come back), the stream they were produced on and an event behind them.
     ONE record per response tensor: a response that alternates between two masks is counted again at every switch.
     The record lives ON the response tensor (`_vibo_row_counts`): the counts are freed with the data they describe and never
-    before -- a captured hipGraph that holds the data's address holds the counts' too."""
+    before -- a captured hipGraph that holds the data's address holds the counts' too.
+    THE PROTOCOL of every fact kept here (the counts: _lookup_counts; `sign_is_mask`: _sign_rows; `tiles`: _tile_rows), once:
+    - Eligibility comes first: a call its decider does not cover is never looked up and leaves no record.
+    - The first sighting of a pair records it (lookup()), a later one produces the fact -- one pass over the matrix; that launch
+      still goes out as the caller sent it --, the ones after it are served.  A "no" is remembered like a "yes".
+    - An in-place write to response or mask (is_() reads the version counters), or another mask, starts over with a fresh record.
+    - While the stream is capturing there are two regimes, and nothing is produced: _capture_bars."""
     __slots__ = ('response', 'has_mask', 'mask', 'counts', 'stream', 'event', 'in_graph', 'sign_is_mask', 'tiles')
     __reduce__ = _not_saved
+    KNOWN, REPLACED, NEVER_SEEN = 'known', 'replaced', 'never seen'          # what lookup() found
 
     def __init__(self, response, mask):
         self.response, self.has_mask = _Seen(response), mask is not None
@@ -434,52 +440,61 @@ class ResidentMatrix:
             return False
         return not self.has_mask or self.mask.is_(_caller_mask(mask))
 
+    @classmethod
+    def lookup(cls, response, mask):
+        """-> (the response's record for exactly this pair, what was found): KNOWN -- the record that was there --, or a fresh one
+        planted in its place: REPLACED a stale record (an in-place write, another mask), NEVER_SEEN none."""
+        rec = getattr(response, '_vibo_row_counts', None)
+        if rec is not None and rec.is_(response, mask):
+            return rec, cls.KNOWN
+        response._vibo_row_counts = fresh = cls(response, mask)
+        return fresh, cls.NEVER_SEEN if rec is None else cls.REPLACED
+
+
+def _capture_bars(capturing, *, resident=False, gathered=False):
+    """THE capture rule of the ELBO launch -> True: the stream is capturing and that keeps the launch from the ResidentMatrix record.
+    A fact serves a captured launch only when that is a trainer's resident step (the contract "counted once") or reads gathered rows: a
+    plain launch's captured input IS the matrix, and a replay after `response.copy_(new)` has to read what is there then.  Nothing is
+    produced under capture (ask without the keywords).  capturing(): asked only where the answer matters."""
+    return not (resident or gathered) and capturing()
+
 
 def _lookup_counts(response, mask, rows, row_index, num_person, *, for_elbo, capturing, stream):
-    """The one decision about a resident matrix -> its whole-row counts, or None: the caller counts its own rows.
+    """The one decision about a resident matrix' whole-row counts -> the counts, or None: the caller counts its own rows.
     response / mask: the tensors it is known by (CellCodes rows: the codes and None); rows: (response, mask, code) as
-    _BACKEND['counts'] reads them, or a callable that prepares them; capturing(): is the stream capturing -- asked only where the
-    answer matters; stream: the consumer's torch stream (None off the GPU).  Touches neither the GPU nor torch.cuda itself: the
-    count goes through _BACKEND['counts'], the ordering through `stream`'s own methods.
-    The ELBO launch (for_elbo): the first sighting records only (the kernel counts in its own pass), the second counts the whole
-    matrix once, from then on the whole matrix and minibatches gathered through row_index are served.  While the stream is
-    capturing it counts nothing and serves gathered minibatches only: with row_index=None the captured input IS the matrix, and a
-    replay after `response.copy_(new)` has to count what is there then.
-    row_counts(): a whole-matrix request counts and keeps at once; the first gathered minibatch of a tensor never seen gets
-    None, the matrix coming back is counted whole.  Capture changes nothing here (the trainers' contract: counted once), but
-    counts recorded into a graph are not handed to the ELBO launch: they exist once that graph has replayed."""
+    _BACKEND['counts'] reads them, or a callable that prepares them; stream: the consumer's torch stream (None off the GPU), whose own
+    methods do the ordering.  The ELBO launch (for_elbo): ResidentMatrix' protocol; gathered minibatches of the matrix are served too.
+    row_counts(): a whole-matrix request counts and keeps at once, the first gathered minibatch of a tensor never seen gets None, and
+    capture changes nothing -- but counts recorded into a graph are not handed to the ELBO launch: they exist once it has replayed."""
     whole = row_index is None
     if for_elbo and whole and num_person != response.shape[0]:
         return None
-    rec = known = getattr(response, '_vibo_row_counts', None)
-    if rec is None or not rec.is_(response, mask):
-        rec = response._vibo_row_counts = ResidentMatrix(response, mask)
-        if for_elbo or (known is None and not whole):
-            return None
+    rec, found = ResidentMatrix.lookup(response, mask)
+    if found is not ResidentMatrix.KNOWN and (for_elbo or (found is ResidentMatrix.NEVER_SEEN and not whole)):
+        return None
     if rec.counts is None:
-        in_graph = stream is not None and capturing()
+        in_graph = stream is not None and _capture_bars(capturing)
         if for_elbo and in_graph:
             return None              # (a count recorded into a hipGraph would not have run when the next eager call reads it)
         rec.counts, rec.in_graph = _BACKEND['counts'](*(rows() if callable(rows) else rows), None), in_graph
         if stream is not None and not in_graph:
             rec.stream, rec.event = stream, stream.record_event()
-    elif for_elbo and (rec.in_graph or (whole and capturing())):
+    elif for_elbo and (rec.in_graph or _capture_bars(capturing, gathered=not whole)):
         return None
     elif rec.stream is not None and stream is not None and stream != rec.stream and not capturing():
         stream.wait_event(rec.event)     # (a capturing stream cannot wait on an eager event: its capture began behind the count)
     return rec.counts
 
 
-def _resident_row_counts(spec, response, mask, mask_code, row_index, num_person, stream):
-    """Whole-row counts for vibo_elbo_fwd_bwd_counts, or None.  Rows of more than 1024 items under the unconditional posterior are
-    counted in a pass of their own in front of the panels (half of the call: 5 B/cell); the counts depend on the data alone, so
-    a matrix that comes back (the resident training / evaluation split) is counted once: _lookup_counts."""
+def _resident_row_counts(spec, response, mask, mask_code, row_index, num_person, stream, *, capturing=torch.cuda.is_current_stream_capturing):
+    """Whole-row counts for vibo_elbo_fwd_bwd_counts, or None.  Rows of more than 1024 items under the unconditional posterior are counted
+    in a pass of their own in front of the panels (half of the call: 5 B/cell); a matrix that comes back is counted once: _lookup_counts."""
     I = response.shape[1]
-    if (not ROW_COUNT_CACHE or spec.conditional or getattr(spec, 'given', False) or I <= 1024 or I > 32767
+    if (not ROW_COUNT_CACHE or spec.conditional or spec.given or I <= 1024 or I > 32767
             or mask_code not in (_lib.MASK_NONE, _lib.MASK_U8, _lib.MASK_CODES)):
         return None
     return _lookup_counts(response, None if mask_code == _lib.MASK_CODES else mask, (response, mask, mask_code), row_index,
-                          num_person, for_elbo=True, capturing=torch.cuda.is_current_stream_capturing, stream=stream)
+                          num_person, for_elbo=True, capturing=capturing, stream=stream)
 
 
 SIGN_ROWS = True           # (tests / A-B runs switch it off)
@@ -489,17 +504,11 @@ def _sign_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode,
     """The one decision about the row format of an ELBO launch -> (mask, mask_code) it goes out with: the caller's, or
     (None, MASK_SIGN) -- the matrix kernel then reads no mask bytes (4 instead of 5 B per cell) and takes a cell as missing where its
     response's sign bit is set, which is how the reference stores its data (-1 at missing cells, every mask built from that).
-    Whether that holds for THESE tensors is verified, never assumed: the fact hangs on the matrix' ResidentMatrix record, so an
-    in-place edit of either tensor throws it away with the rest.
-    Eligibility first (nothing is looked up or verified without it): fp32 responses with a u8 mask, the whole matrix in order,
-    rows the matrix kernel's 16-byte loads can take (base 16-byte aligned, stride a multiple of 4: a MASK_U8 call on other rows
-    falls back to the tiled kernel, a MASK_SIGN call is refused), and a shape the library takes the format for
-    (vibo_sign_rows_supported).  Then: the first sighting of a pair records it, the second
-    verifies (one streaming pass and one .item(); never while the stream is capturing) and still carries the mask, from the third on
-    MASK_SIGN goes out; a "no" is kept as well.
-    While capturing, the two regimes of _lookup_counts: a plain launch whose input is the whole matrix keeps the mask
-    (a replay after `response.copy_(new)` has to read what is there then); the trainers' folded step (train_step given) uses the
-    verified fact -- the resident-matrix contract row_counts() has there.  capturing(): asked only where the answer matters."""
+    Whether that holds for THESE tensors is verified, never assumed: the fact (`sign_is_mask`) follows the protocol of ResidentMatrix.
+    Eligible: fp32 responses with a u8 mask, the whole matrix in order, rows the matrix kernel's 16-byte loads can take (base 16-byte
+    aligned, stride a multiple of 4: a MASK_U8 call on other rows falls back to the tiled kernel, a MASK_SIGN call is refused), and
+    a shape the library takes the format for (vibo_sign_rows_supported).  Producing the fact is one streaming pass and one .item();
+    the resident step of the capture rule is the trainers' folded step here (train_step given)."""
     keep = (mask, mask_code)
     if (not SIGN_ROWS or mask is None or mask_code != _lib.MASK_U8 or response is None or response.dtype != torch.float32
             or row_index is not None or num_person != response.shape[0]
@@ -507,16 +516,14 @@ def _sign_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode,
         return keep
     if not _BACKEND['sign_supported'](_rows_desc(spec, num_person, response, None, _lib.MASK_SIGN, reg_mode, want_grad)):
         return keep
-    rec = getattr(response, '_vibo_row_counts', None)
-    if rec is None or not rec.is_(response, mask):
-        response._vibo_row_counts = ResidentMatrix(response, mask)
+    rec, found = ResidentMatrix.lookup(response, mask)
+    if found is not ResidentMatrix.KNOWN:
         return keep
     if rec.sign_is_mask is None:
-        if capturing():
-            return keep
-        rec.sign_is_mask = bool(_BACKEND['sign_verify'](response, mask))
+        if not _capture_bars(capturing):
+            rec.sign_is_mask = bool(_BACKEND['sign_verify'](response, mask))
         return keep                  # (the verifying launch itself still carries the mask)
-    if not rec.sign_is_mask or (train_step is None and capturing()):
+    if not rec.sign_is_mask or _capture_bars(capturing, resident=train_step is not None):
         return keep
     return None, _lib.MASK_SIGN
 
@@ -538,10 +545,9 @@ TILE_ROWS = True                   # (tests / A-B runs switch it off)
 # From this many persons on, every workgroup of an 8-wave launch on 256 compute units runs the matrix kernel's batch loop at least once
 # (2 x 32 x 256 rows): below it the launch is that kernel's one-shot prologue and end code, and the loop the image shortens does not run.
 TILE_ROWS_MIN_PERSONS = 16384
-# Plain launches (fused_elbo, evaluation: no train_step) too?  Off: they keep the caller's rows, captured or not, and run as they ran
-# before the format existed -- an eager plain launch and the same launch replayed from a hipGraph stay one kernel (the in-situ
-# timer's test holds them within 25 % of each other; under capture a plain launch must read the caller's rows in any case, see
-# _tile_rows).  On: an eager plain launch counts as a sighting and uses the image like the trainers' step.
+# Plain launches (fused_elbo, evaluation: no train_step) too?  Off: they run as they ran before the format existed -- an eager plain
+# launch and the same launch replayed from a hipGraph, which must read the caller's rows in any case (_capture_bars), stay one kernel
+# (the in-situ timer's test holds them within 25 % of each other).  On: an eager plain launch is a sighting and uses the image.
 TILE_ROWS_PLAIN_LAUNCHES = False
 # The image under a caller-supplied posterior (spec.given: the mean-merge, VI and MLE trainers' ELBO launch;
 # include/vibo_hip_given_tiles.h).  Those launches are no folded step: the trainers mark theirs `resident_step`.
@@ -556,64 +562,41 @@ def _tile_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode,
     (a uint8 tensor: the launch is (image, None, MASK_TILES)), False (the launch keeps the caller's rows as they are: the matrix is
     on its way to an image, or a plain launch is being captured), or None (no image for this call: _sign_rows decides as ever).
     The matrix kernel then loads a batch's code words and counts instead of forming them from 4-5 bytes per cell: about 1.06 bytes
-    per cell, no pack.  What the words are depends on the data alone, so the image hangs on the matrix' ResidentMatrix record: freed
-    with the response, thrown away with the record by an in-place edit of response or mask.  It costs one more byte per cell of
-    device memory while the matrix lives.
-    Eligibility first (nothing is looked up or built without it): the trainers' folded step (train_step given; any launch with
-    TILE_ROWS_PLAIN_LAUNCHES on), the whole matrix in order -- fp32 responses with a u8 mask or without one, or CellCodes --, in
-    rows the matrix kernel itself can load (_matrix_kernel_rows: the launch on the image then has the bits of the launch on the
-    rows), at least TILE_ROWS_MIN_PERSONS persons, a shape the library takes the format for
-    (vibo_tile_rows_supported).  Then: the first sighting records, the second builds (one streaming pass, waited for; never while
-    the stream is capturing; only if the image takes at most half of the free device memory -- an allocation that fails all the
-    same counts as a "no") and still goes out on the caller's rows, from the third on the image goes out.  A "no" is kept: such a
-    matrix is _sign_rows' from then on.  A matrix with an image is never sign-verified: the fact would save nothing.
-    While capturing, the two regimes of _lookup_counts / _sign_rows: a plain launch whose input is the whole matrix keeps the
-    caller's rows (a replay after `response.copy_(new)` has to read what is there then); the trainers' folded step (train_step
-    given) uses the image -- the resident-matrix contract "counted once".  capturing(): asked only where the answer matters.
-    A caller-supplied posterior (spec.given; TILE_ROWS_GIVEN): the same rules with `resident_step` -- the mean-merge, VI and MLE
-    trainers' whole-matrix launch -- in the folded step's place, vibo_given_tile_rows_supported as the shape's query and
-    TILE_ROWS_GIVEN_MIN_PERSONS on top of the threshold.  The image is the same one on the same record (a plain trainer and a
-    mean-merge trainer on one matrix share it); it is built as the plain twin of the spec would build it, with the matrix kernel
-    pinned in the builder's descriptor, so that the builder's answer does not depend on the plain model's engine thresholds."""
-    given = bool(getattr(spec, 'given', False))
-    resident = resident_step if given else train_step is not None
-    if given and (not TILE_ROWS_GIVEN or num_person < TILE_ROWS_GIVEN_MIN_PERSONS):
+    per cell, no pack.  The image (`tiles`) follows the protocol of ResidentMatrix; it costs a byte per cell of device memory.
+    Eligible: a trainer's resident step -- the folded step (train_step given), under a caller-supplied posterior (spec.given) the
+    mean-merge, VI and MLE trainers' launch marked `resident_step` --, or any launch with TILE_ROWS_PLAIN_LAUNCHES on; the whole matrix
+    in order -- fp32 responses with or without a u8 mask, or CellCodes -- in rows the matrix kernel itself can load
+    (_matrix_kernel_rows); the thresholds above; a shape the library takes the format for.  Producing the image is one streaming pass,
+    waited for, and only if it takes at most half of the free device memory -- an allocation that fails all the same is a "no".
+    A matrix with a "no" is _sign_rows' from then on, and so is every launch not eligible here: with TILE_ROWS_PLAIN_LAUNCHES off, a
+    plain launch on a matrix that has an image is _sign_rows', which verifies the pair as ever.  One image serves the plain and the
+    given spec: it is built as the spec's plain twin would build it, under the matrix-kernel pin (no engine threshold in its answer)."""
+    resident = resident_step if spec.given else train_step is not None       # (the two marks of a trainer's step on its resident matrix)
+    if (not TILE_ROWS or (spec.given and (not TILE_ROWS_GIVEN or num_person < TILE_ROWS_GIVEN_MIN_PERSONS))
+            or not (resident or TILE_ROWS_PLAIN_LAUNCHES) or response is None or row_index is not None or num_person != response.shape[0]
+            or num_person < TILE_ROWS_MIN_PERSONS or mask_code not in (_lib.MASK_U8, _lib.MASK_NONE, _lib.MASK_CODES)
+            or (mask_code != _lib.MASK_CODES and (response.dtype != torch.float32 or (mask is None) != (mask_code == _lib.MASK_NONE)))
+            or not _matrix_kernel_rows(response, mask, mask_code)):
         return None
-    if (not TILE_ROWS or (not resident and not TILE_ROWS_PLAIN_LAUNCHES)
-            or response is None or row_index is not None or num_person != response.shape[0]
-            or num_person < TILE_ROWS_MIN_PERSONS or mask_code not in (_lib.MASK_U8, _lib.MASK_NONE, _lib.MASK_CODES)):
+    if not _BACKEND['tile_given_supported' if spec.given else 'tile_supported'](_tile_desc(spec, num_person, response.shape[1], reg_mode, want_grad)):
         return None
-    if mask_code != _lib.MASK_CODES and (response.dtype != torch.float32 or (mask is None) != (mask_code == _lib.MASK_NONE)):
-        return None
-    if not _matrix_kernel_rows(response, mask, mask_code):
-        return None
-    d = _tile_desc(spec, num_person, response.shape[1], reg_mode, want_grad)
-    if not _BACKEND['tile_given_supported' if given else 'tile_supported'](d):
-        return None
-    known_mask = None if mask_code == _lib.MASK_CODES else mask        # (CellCodes rows are known by the codes alone)
-    rec = getattr(response, '_vibo_row_counts', None)
-    if rec is None or not rec.is_(response, known_mask):
-        response._vibo_row_counts = ResidentMatrix(response, known_mask)
+    rec, found = ResidentMatrix.lookup(response, None if mask_code == _lib.MASK_CODES else mask)      # (CellCodes: known by the codes alone)
+    if found is not ResidentMatrix.KNOWN:
         return False
     if rec.tiles is None:
-        if capturing():
+        if _capture_bars(capturing):
             return False
         rec.tiles = False                                              # (a "no" until the image stands)
-        # (a given spec: the builder reads its plain twin under the matrix-kernel pin; it may still refuse the shape -- 0 bytes)
-        with desc_flags(DESC_FLAGS | _lib.FLAG_KERNEL_MATRIX) if given else contextlib.nullcontext():
-            build_spec = replace(spec, given=False) if given else spec
+        with desc_flags(DESC_FLAGS | _lib.FLAG_KERNEL_MATRIX) if spec.given else contextlib.nullcontext():
+            build_spec = replace(spec, given=False) if spec.given else spec
             need = _BACKEND['tile_bytes'](_tile_desc(build_spec, num_person, response.shape[1], reg_mode, want_grad))
-            if 0 < need <= _BACKEND['tile_free'](response.device) // 2:
-                try:
+            if 0 < need <= _BACKEND['tile_free'](response.device) // 2:        # (0 bytes: the builder may still refuse the shape)
+                with contextlib.suppress(torch.cuda.OutOfMemoryError):
                     rec.tiles = _BACKEND['tile_build'](build_spec, response, mask, mask_code, num_person, reg_mode, want_grad, need)
-                except torch.cuda.OutOfMemoryError:
-                    pass
         return False if rec.tiles is not False else None               # (the building launch itself still reads the caller's rows)
     if rec.tiles is False:
         return None
-    if not resident and capturing():
-        return False
-    return rec.tiles
+    return False if _capture_bars(capturing, resident=resident) else rec.tiles
 
 
 def _matrix_kernel_rows(response, mask, mask_code):
@@ -670,12 +653,42 @@ class TrainStepCall(NamedTuple):
     no_sample: bool = False           # ... which rebuilds `ability` when read (trainer._StepSample)
 
 
+# What one ELBO launch knows about its rows (_launch_rows): the tensors the library reads -- the caller's rows, or the matrix' tile image
+# and no mask -- with their VIBO_MASK_* code, the launch's vibo_desc, by name the export that sizes the workspace for it and the one the
+# launch goes into, the caller's row counts (vibo_elbo_fwd_bwd_counts) or None, and: is it on the image under a caller-supplied posterior?
+LaunchRows = namedtuple('LaunchRows', 'response mask mask_code desc workspace_query entry counts given_tiles')
+
+
+def _launch_rows(spec, response, mask, mask_code, row_index, num_person, reg_mode, want_grad, train_step, *, resident_step=False, capturing, stream):
+    """THE decision about the rows of an ELBO launch -> LaunchRows, from the three deciders of the ResidentMatrix record in their one
+    order: the tile image first (_tile_rows); the sign rows (_sign_rows) only where that answered "no image for this call" (None -- on
+    False the caller's rows go out as they are); the resident counts (_resident_row_counts) only for a launch without train_step that
+    is not on an image.  (With the library's shapes the three never meet on one matrix: the formats end at 1024 items, the counts
+    begin above.)  train_step: None, a TrainStepCall or a plain tuple of its fields; capturing / stream: as the deciders take them."""
+    launch = (spec, response, mask, mask_code, row_index, num_person, reg_mode, want_grad, train_step)
+    image = _tile_rows(*launch, capturing=capturing, resident_step=resident_step)
+    if image is None:
+        mask, mask_code = _sign_rows(*launch, capturing=capturing)
+    if image is None or image is False:
+        d, given_tiles = _rows_desc(spec, num_person, response, mask, mask_code, reg_mode, want_grad), False
+    else:
+        d, given_tiles = _tile_desc(spec, num_person, response.shape[1], reg_mode, want_grad), spec.given
+        response, mask, mask_code = image, None, _lib.MASK_TILES
+    counts = None
+    if train_step is not None:
+        entry = 'vibo_elbo_fwd_bwd_step_noise' if len(train_step) > 2 and train_step[2] is not None else 'vibo_elbo_fwd_bwd_step'
+    else:
+        if mask_code != _lib.MASK_TILES:
+            counts = _resident_row_counts(spec, response, mask, mask_code, row_index, num_person, stream, capturing=capturing)
+        entry = 'vibo_elbo_fwd_bwd_given_tiles' if given_tiles else 'vibo_elbo_fwd_bwd' if counts is None else 'vibo_elbo_fwd_bwd_counts'
+    return LaunchRows(response, mask, mask_code, d, 'vibo_given_tiles_workspace_bytes' if given_tiles else 'vibo_workspace_bytes',
+                      entry, counts, given_tiles)
+
+
 def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, eps, flow, reg_mode,
                      want_grad, num_person, train_step=None, *, resident_step=False):
-    """Single call into vibo_elbo_fwd_bwd on the current stream, or (train_step: a TrainStepCall) into vibo_elbo_fwd_bwd_step.
-    resident_step: a trainer's whole-matrix launch under a caller-supplied posterior (spec.given) -- with the matrix' tile image
-    (_tile_rows) it goes into vibo_elbo_fwd_bwd_given_tiles."""
-    lib = _lib.load()
+    """Single call into the ELBO export _launch_rows names, on the current stream.  train_step: a TrainStepCall -- the folded step;
+    resident_step: a trainer's whole-matrix launch under a caller-supplied posterior (spec.given), see _tile_rows."""
     _require_device(response, mask, table, item, eps)
     dev = response.device
     I = response.shape[1]
@@ -691,44 +704,30 @@ def _hip_launch_elbo(spec, response, mask, mask_code, row_index, table, item, ep
     post = None if no_sample else torch.empty(1 if own_noise else 3, B, A, dtype=torch.float32, device=dev)
     ability_k = torch.empty(B, A, dtype=torch.float32, device=dev) if spec.n_flows else None
     ladj = torch.empty(B, dtype=torch.float32, device=dev) if spec.n_flows else None
-    image = _tile_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step,
-                       capturing=torch.cuda.is_current_stream_capturing, resident_step=resident_step)
-    given_tiles = image is not None and image is not False and bool(getattr(spec, 'given', False))
-    if image is None:
-        mask, mask_code = _sign_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step,
-                                     capturing=torch.cuda.is_current_stream_capturing)
-    if image is None or image is False:
-        d = _rows_desc(spec, B, response, mask, mask_code, reg_mode, want_grad)
-    else:
-        response, mask, mask_code = image, None, _lib.MASK_TILES
-        d = _tile_desc(spec, B, I, reg_mode, want_grad)
-    ws_query = 'vibo_given_tiles_workspace_bytes' if given_tiles else 'vibo_workspace_bytes'
-    ws_bytes = getattr(lib, ws_query)(ctypes.byref(d))
+    stream = torch.cuda.current_stream(dev)
+    sent = _launch_rows(spec, response, mask, mask_code, row_index, B, reg_mode, want_grad, train_step, resident_step=resident_step,
+                        capturing=torch.cuda.is_current_stream_capturing, stream=stream)
+    ws_bytes = getattr(_lib.load(), sent.workspace_query)(ctypes.byref(sent.desc))
     if ws_bytes == 0:
-        _lib.check(-1, ws_query)
+        _lib.check(-1, sent.workspace_query)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     vp, fbase, o_item = ctypes.c_void_p, flat.data_ptr(), _lib.NUM_SCALARS + 2 * n_table
-    # the argument runs the four exports share (include/vibo_hip.h): the rows, the gradients, workspace and stream
-    stream = torch.cuda.current_stream(dev)
-    rows = (_ptr(response), _ptr(mask), _ptr(row_index))
+    # the argument runs the exports share (include/vibo_hip.h): the rows, the gradients, workspace and stream
+    rows = (_ptr(sent.response), _ptr(sent.mask), _ptr(row_index))
     grads = (vp(fbase + 4 * _lib.NUM_SCALARS), vp(fbase + 4 * o_item))
     tail = (_ptr(ws), ctypes.c_size_t(ws_bytes), vp(stream.cuda_stream))
     if own_noise:
-        name = 'vibo_elbo_fwd_bwd_step_noise'
         args = (_ptr(train_step.step_count), 1 if train_step.skip_finalize else 0, *rows, _ptr(table), _ptr(item), None,
                 ctypes.c_uint64(train_step.noise[0]), ctypes.c_uint32(train_step.noise[1]), vp(fbase), None, None,
                 None if no_sample else _ptr(post[0]), *grads, *tail)
     elif train_step is not None:
-        name = 'vibo_elbo_fwd_bwd_step'
         args = (_ptr(train_step.step_count), 1 if train_step.skip_finalize else 0, *rows, _ptr(table), _ptr(item), _ptr(eps), vp(fbase),
                 _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), *grads, *tail)
     else:
-        counts = None if mask_code == _lib.MASK_TILES else _resident_row_counts(spec, response, mask, mask_code, row_index, B, stream)
-        name = 'vibo_elbo_fwd_bwd_given_tiles' if given_tiles else 'vibo_elbo_fwd_bwd' if counts is None else 'vibo_elbo_fwd_bwd_counts'
-        args = (*rows, *(() if counts is None else (_ptr(counts),)), _ptr(table), _ptr(item), _ptr(eps), _ptr(flow), vp(fbase),
+        args = (*rows, *(() if sent.counts is None else (_ptr(sent.counts),)), _ptr(table), _ptr(item), _ptr(eps), _ptr(flow), vp(fbase),
                 _ptr(post[0]), _ptr(post[1]), _ptr(post[2]), _ptr(ability_k), _ptr(ladj), *grads,
                 vp(fbase + 4 * (o_item + n_item)) if n_flow else vp(0), *tail)
-    _call(name, ctypes.byref(d), *args)
+    _call(sent.entry, ctypes.byref(sent.desc), *args)
     raw = RawElbo(flat=flat, n_table=n_table, n_item=n_item, n_flow=n_flow, table_shape=table_shape,
                   ability_mu=None if own_noise else post[0], ability_logvar=None if own_noise else post[1],
                   ability=None if no_sample else post[-1],
@@ -764,7 +763,7 @@ _MULTI_CALLS = {
 
 
 def _multi_mode(spec):
-    return 'given' if getattr(spec, 'given', False) else 'cond' if spec.conditional else 'plain'
+    return 'given' if spec.given else 'cond' if spec.conditional else 'plain'
 
 
 def _hip_multi_forward(spec, response, mask, mask_code, row_index, table, items, eps, flow, reg_mode, num_person):
