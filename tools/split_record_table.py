@@ -11,6 +11,9 @@
 
     VIBO_TOL_RECORD=record.jsonl python -m pytest tests/test_gpu_flow_batches.py -q -m gpu
     python tools/split_record_table.py record.jsonl flow_batches >> profiles/flow_batches_record.txt
+
+    VIBO_TOL_RECORD=record.jsonl python -m pytest tests/test_gpu_decoder_cells.py -q -m gpu
+    python tools/split_record_table.py record.jsonl decoder_cells > profiles/decoder_cells_record.txt
 """
 import collections
 import json
@@ -112,7 +115,62 @@ def flow_batches(recs):
         print()
 
 
-KINDS = {'flow_batches': flow_batches, 'split_worst_case': split_worst_case, 'narrow_cells': narrow_cells, 'fallback_cells': fallback_cells}
+def decoder_cells(recs):
+    order = ('unit', 'hostile', 'cancel', 'small_w', 'small_g', 'large', 'elu0', 'zero', 'guess3')      # oracle/decoder_model.py CLASSES
+    parts = ('term', 'single', 'dense')
+    worst, grade = collections.defaultdict(float), {}
+    probes, seconds, other = [], None, collections.defaultdict(float)
+    for r in recs:
+        if r['part'] == 'time':
+            seconds = r['err']
+        elif r['part'] == 'split8-probe':
+            probes.append(r)
+        elif r['observable'].startswith('bound/fp32 '):
+            k = (r['class'], r['observable'][11:])
+            g = grade.get(k, (0.0, 0.0))
+            grade[k] = (max(g[0], r['median']), max(g[1], r['p95']))
+        elif r['part'] in parts:
+            worst[(r['part'], r['class'], r['observable'])] = max(worst[(r['part'], r['class'], r['observable'])], r['ratio'])
+        else:
+            other[(r['part'], r['observable'])] = max(other[(r['part'], r['observable'])], r['ratio'])
+    classes = [c for c in order if any(k[1] == c for k in worst)]
+    print(f'Worst error / a-priori bound per mask layout, input class and observable ({len(recs)} records of tests/test_gpu_decoder_cells.py on one')
+    print('MI355X; bounds: oracle/decoder_model.py).  term: one observed item per (person, 16-item wave group); single: one observed term per')
+    print('(person chunk, wave), "x|dz2": the backward half on the kernel\'s own dz2 (dvec_part row 0), split residual evaluated; dense: 30 %')
+    print('missing, summed bounds with the counted chains.  Shapes I in {1, 15, 16, 17, 63, 64, 65, 130}, B in {1, 2, 3, 7, 8, 9, 10}, person')
+    print('chunks 1, 2, ceil(B / 2), 4.  0 = bit for bit / exactly zero where the line says so; inf would be an entry outside a zero bound.')
+    print()
+    for part in parts:
+        print(f'{part:34s} ' + ' '.join(f'{c:>9s}' for c in classes))
+        for o in sorted({k[2] for k in worst if k[0] == part}):
+            print(f'  {o:32s} ' + ' '.join(f'{worst[(part, c, o)]:9.3f}' if (part, c, o) in worst else f'{"-":>9s}' for c in classes))
+        print()
+    print('Other parts (class unit): worst error / bound per observable')
+    for p in sorted({k[0] for k in other}):
+        print(f'  {p:14s} ' + '  '.join(f'{o} {other[(p, o)]:.3f}' for (q, o) in sorted(other) if q == p))
+    print()
+    print('The three contractions\' own bounds (representation of the pieces, the dropped lo x lo, accumulation; nothing propagated) over the')
+    print('bound of a plain fp32 evaluation of the same sum (decoder_model.fp32_grade), on observed terms with a live gradient: median and')
+    print('95th percentile over the entries, the largest over the cases.  About 1: "fp32-grade".  z2 = W2 . h1 (64 products), dH1 = W2^T . dz2')
+    print('(64 products), dW2: ONE outer product dz2[n] h1[k] against one fp32 multiplication.')
+    print(f'{"class":10s} ' + ' '.join(f'{n + " median":>14s} {n + " p95":>12s}' for n in ('z2', 'dH1', 'dW2')))
+    for c in classes:
+        print(f'{c:10s} ' + ' '.join((f'{grade[(c, n)][0]:14.3g} {grade[(c, n)][1]:12.3g}' if (c, n) in grade else f'{"-":>14s} {"-":>12s}') for n in ('z2', 'dH1', 'dW2')))
+    print()
+    print('split8 on the device (h1 = (1, 0) | (1, 2^-11) in pieces exactly: dW2_part[n][even k] = hi + lo and dW2_part[n][odd k] - dW2_part[n][even k] =')
+    print('2^-11 hi of dz2[n] = dvec_part[0][n]): dz2 values whose two pieces both equal the model that keeps f16 subnormals / one whose conversion')
+    print('flushes a subnormal hi, the largest residual |hi + lo - dz2|, pieces on the subnormal grid.')
+    print(f'{"scale":30s} {"entries":>8s} {"= model":>8s} {"= flushing":>10s} {"device residual":>16s} {"model residual":>15s} {"subnormal lo":>13s} {"subnormal hi":>13s}')
+    for r in probes:
+        print(f'{r["class"]:30s} {r["entries"]:8d} {r["equal_to_model"]:8d} {r["equal_to_flushing_model"]:10d} {r["err"]:16.3e} {r["model_residual"]:15.3e} '
+              f'{r["subnormal_lo"]:13d} {r["subnormal_hi"]:13d}')
+    if seconds is not None:
+        print()
+        print(f'The whole file: {seconds:.0f} s.')
+
+
+KINDS = {'flow_batches': flow_batches, 'split_worst_case': split_worst_case, 'narrow_cells': narrow_cells, 'fallback_cells': fallback_cells,
+         'decoder_cells': decoder_cells}
 
 
 def main(path, kind='split_worst_case'):

@@ -13,7 +13,9 @@
 // the outer product for d W2 -- 24.6 kFLOP per term, the only genuinely dense contraction of the model family.
 //
 // Matrix-pipe formulation (v_mfma_f32_16x16x32_f16, operands split x = hi + lo in f16, hi.hi + hi.lo + lo.hi with fp32
-// accumulation: fp32-grade products).  A wave owns 16 items and walks its persons two at a time (32 terms):
+// accumulation: fp32-grade products while both operands' lo pieces are normal f16 numbers, |W2|, |h1|, |dz2| >= 2^-3; below, an
+// operand is held to 2^-25 absolute -- DESIGN.md section 3.7 has the domain, profiles/decoder_cells_record.txt the figures per scale).
+// A wave owns 16 items and walks its persons two at a time (32 terms):
 //   forward   Z2^T[n, t] = W2[n, :] . h1[t, :]     A = W2 (LDS image), B = h1: lane (t = lane & 15, g = lane >> 4)
 //             holds h1[t, k] for k in K(g) = {16 kt + 4 g + j}: exactly what the lane computed element-wise
 //   backward  dH1^T[k, t] = W2[:, k] . dz2[t, :]   A = W2^T (LDS image), B = dz2: the D layout of the forward product

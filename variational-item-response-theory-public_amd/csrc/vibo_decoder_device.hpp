@@ -22,7 +22,10 @@ __device__ __forceinline__ dh4 dtr16(const _Float16* p) {
     return __builtin_bit_cast(dh4, __builtin_amdgcn_ds_read_tr16_b64_v4i16((ds4 __attribute__((address_space(3)))*)p));
 }
 __device__ __forceinline__ dh2 dpk(float a, float b) { return __builtin_bit_cast(dh2, __builtin_amdgcn_cvt_pkrtz(a, b)); }
-// 8 floats -> f16 hi and lo pieces (x = hi + lo to 2^-22)
+// 8 floats -> f16 hi and lo pieces: x = hi + lo to 2^-22 |x| while lo is a normal f16, i.e. for |x| >= 2^-3; below that lo sits on
+// the f16 subnormal grid and the pieces reassemble x to 2^-25 ABSOLUTE (3e-5 of an x near 1e-3); below 2^-14 hi is on that grid
+// too.  No operand is rescaled: oracle/decoder_model.py carries this floor in its bounds, tests/test_gpu_decoder_cells.py holds the
+// device's residual to it element by element (subnormal pieces are kept by the conversions and by the MFMA).
 // (hi = round-toward-zero pair; lo = f16(x - hi) by two mixed-precision fmas that write the two halves of one register)
 __device__ __forceinline__ void split8(const float* x, dh8& hi, dh8& lo) {
     uint32_t hw[4], lw[4];
