@@ -1,5 +1,6 @@
 // vibo_capi.hip -- C ABI of libvibo_hip.so (see include/vibo_hip.h): the extern "C" surface and the drivers that turn a plan
 // (vibo_planner.hpp) into launches.  The small kernels around the fused ELBO kernels are in vibo_helpers.hip.
+// vibo_host.hpp: what they share with the planner and the other units' entry points (panel split, workspace check, failed-launch path).
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -22,17 +23,6 @@ namespace vibo {
 
 // measurement hook (vibo_set_insitu_timer): the timer block the matrix row-split launches of THIS host thread stamp; null = none
 static thread_local unsigned long long* g_insitu = nullptr;
-
-static int hip_fail(hipError_t e, const char* what) {
-    return fail((int)e > 0 ? (int)e : 999, "%s: %s", what, hipGetErrorString(e));
-}
-
-// compute units of the current device (asked per call: the library keeps no state between calls)
-static int device_cus() {
-    int dev = 0, n = 0;
-    return (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-}
 
 // descriptor check + plan of the exports that launch nothing: 0, or the refusal's code (error string set)
 static int plan_for(const vibo_desc* d, Plan* pl, bool sign_rows = false) {
@@ -86,6 +76,13 @@ struct PanelBufs {
                               // of the minibatch's rows here (already gathered), every later pass reads those; null: not used
 };
 
+// the row description of a call, the same fields in every params struct (the item count is the struct's own: I, I_total or both)
+template <typename Params>
+static void fill_rows(Params& p, const vibo_desc* d, const float* response, const void* mask, const int64_t* row_index) {
+    p.response = response; p.mask = mask; p.row_index = row_index;
+    p.resp_stride = d->response_row_stride; p.mask_stride = d->mask_row_stride;
+    p.B = d->num_person; p.A = d->ability_dim; p.mask_dtype = d->mask_dtype;
+}
 // from here on the rows are the cell codes just written (in minibatch order)
 template <typename Params>
 static void read_emitted_codes(Params& p, const uint8_t* code_rows, long long codes_stride) {
@@ -107,71 +104,76 @@ static int run_general(const vibo_desc* d, const Plan& pl, const ElboArgs& a, in
     if (ge != hipSuccess) return hip_fail(ge, "memset");
     GeneralParams g;
     memset(&g, 0, sizeof(g));
-    g.response = a.response; g.mask = a.mask; g.row_index = a.row_index; g.table = a.table; g.item = a.item; g.eps = a.eps;
+    fill_rows(g, d, a.response, a.mask, a.row_index);
+    g.table = a.table; g.item = a.item; g.eps = a.eps;
     g.flow = a.flow; g.ability_mu = a.ability_mu; g.ability_logvar = a.ability_logvar; g.ability = a.ability;
     g.ability_k = a.ability_k; g.ability_ladj = a.ability_ladj;
     g.grad_table = a.grad_table; g.grad_item = a.grad_item; g.grad_flow = a.grad_flow;
     g.acc_scalars = static_cast<float*>(a.workspace); g.out_scalars = a.out_scalars;
-    g.resp_stride = d->response_row_stride; g.mask_stride = d->mask_row_stride;
-    g.B = d->num_person; g.I = I; g.A = A; g.D = pl.D; g.irt = d->irt_model;
+    g.I = I; g.D = pl.D; g.irt = d->irt_model;
     g.conditional = d->posterior == VIBO_POSTERIOR_CONDITIONAL; g.missing_mode = d->missing_mode;
-    g.mask_dtype = d->mask_dtype; g.reg_mode = d->reg_mode; g.n_flows = d->n_flows; g.want_grad = d->want_grad;
-    ge = launch_elbo_general(g, num_cu, s);
-    if (ge != hipSuccess) return hip_fail(ge, "general elbo kernel launch");
-    return 0;
+    g.reg_mode = d->reg_mode; g.n_flows = d->n_flows; g.want_grad = d->want_grad;
+    return hip_rc(launch_elbo_general(g, num_cu, s), "general elbo kernel launch");
+}
+
+// what every ELBO launch's params take from the descriptor and the plan: the rows, the model's shape, one whole-row panel
+static void elbo_shape(ElboParams& p, const vibo_desc* d, const Plan& pl, const float* response, const void* mask, const int64_t* row_index,
+                       const float* table, const float* flow) {
+    fill_rows(p, d, response, mask, row_index);
+    p.table = table; p.flow = flow;
+    p.I = p.I_total = d->num_item; p.D = pl.D; p.DP = pl.DP;
+    p.missing_mode = d->missing_mode; p.reg_mode = d->reg_mode; p.n_flows = d->n_flows;
+    p.lay = pl.lay; p.primary = 1;
 }
 
 static ElboParams elbo_params(const vibo_desc* d, const Plan& pl, const ElboArgs& a, bool vec) {
-    const int I = d->num_item;
     ElboParams p;
     memset(&p, 0, sizeof(p));
-    p.response = a.response; p.mask = a.mask; p.row_index = a.row_index;
-    p.table = a.table; p.item_prep = static_cast<float*>(a.workspace); p.item_raw = a.item; p.eps = a.eps;
+    elbo_shape(p, d, pl, a.response, a.mask, a.row_index, a.table, a.flow);
+    p.item_prep = static_cast<float*>(a.workspace); p.item_raw = a.item; p.eps = a.eps;
     p.ability_mu = a.ability_mu; p.ability_logvar = a.ability_logvar; p.ability = a.ability;
     p.partial = reinterpret_cast<float*>(static_cast<char*>(a.workspace) + pl.off_partial);
-    p.resp_stride = d->response_row_stride; p.mask_stride = d->mask_row_stride;
-    p.B = d->num_person; p.I = I; p.A = d->ability_dim; p.D = pl.D; p.DP = pl.DP;
     p.n_tiles = pl.n_tiles; p.lds_stride = pl.lds_stride; p.lds_main = pl.lds_main;
-    p.mask_dtype = d->mask_dtype; p.missing_mode = d->missing_mode; p.reg_mode = d->reg_mode;
-    p.flow = a.flow; p.ability_k = a.ability_k; p.ability_ladj = a.ability_ladj; p.n_flows = d->n_flows;
-    p.lay = pl.lay;
-    p.vec_ok = (vec && I % 4 == 0) ? 1 : 0;      // the tiled / wave-per-row kernels' vector loads assume whole chunks
-    p.row_cnt = nullptr; p.item0 = 0; p.I_total = I; p.primary = 1;
+    p.ability_k = a.ability_k; p.ability_ladj = a.ability_ladj;
+    p.vec_ok = (vec && p.I % 4 == 0) ? 1 : 0;      // the tiled / wave-per-row kernels' vector loads assume whole chunks
     p.step_tick = a.step_count;
     p.insitu = g_insitu;
     p.noise_seed_lo = (uint32_t)a.noise_seed; p.noise_seed_hi = (uint32_t)(a.noise_seed >> 32); p.noise_stream = a.noise_stream;
     return p;
 }
 
-// conditional posterior, VALU first pass: cond_pre_kernel per panel and per 4 ability dims
-static hipError_t cond_pre_valu(const vibo_desc* d, const Plan& pl, CondParams cp, const PanelBufs& b, hipStream_t s) {
-    const int I = d->num_item, A = d->ability_dim;
-    // more than one panel: ALL of them in one launch per 4 ability dims (CondParams::panel_count), the chip's workgroup
-    // slots shared out over the panels
-    const bool one_launch = pl.panels > 1;
-    const int pre_launches = one_launch ? 1 : pl.panels;
-    int pre_blocks = pl.cond_nblk;
-    if (one_launch) {
-        int per = pl.cond_nblk / pl.panels;
-        if (per < 1) per = 1;
-        pre_blocks = per * pl.panels;
-        cp.panel_count = pl.panels;
-    }
+// the row fields and the expert table of the conditional passes
+static CondParams cond_params(const vibo_desc* d, const float* response, const void* mask, const int64_t* row_index, const float* table) {
+    CondParams cp;
+    memset(&cp, 0, sizeof(cp));
+    fill_rows(cp, d, response, mask, row_index);
+    cp.table = table; cp.I_total = d->num_item;
+    return cp;
+}
+
+// cond_pre_kernel over the items [cp.item0, + cp.I) into cp.pre_out: 4 ability dims per launch.  code_rows: the first launch leaves the
+// rows' cell codes there, and dims 4..7 read those instead of the caller's rows
+static hipError_t cond_pre_span(CondParams cp, uint8_t* code_rows, long long codes_stride, int grid, hipStream_t s) {
+    const CondPassShape sh = cond_pass_shape(cp.A, cp.I);
     hipError_t e = hipSuccess;
-    for (int pn = 0; pn < pre_launches && e == hipSuccess; ++pn) {
-        cp.item0 = pn * 1024;
-        cp.I = one_launch ? 1024 : (I - cp.item0 < 1024 ? I - cp.item0 : 1024);
-        cp.pre_out = b.pre + (size_t)pn * d->num_person * (2 * A + 1);
-        for (cp.a0 = 0; cp.a0 < A && e == hipSuccess; cp.a0 += 4) {     // 4 ability dims per launch
-            cp.codes_out = cp.a0 == 0 ? b.code_rows : nullptr;
-            CondParams cq = cp;
-            // dims 4..7: the rows' cell codes are there already (written by the first launch)
-            if (b.code_rows && cp.a0 > 0) read_emitted_codes(cq, b.code_rows, pl.codes_stride);
-            e = launch_cond_pre(cq, A == 1 ? 1 : A <= 2 ? 2 : 4, (cp.I + 255) / 256, pre_blocks, s);   // own template width (3PL widens the split kernel's)
-        }
+    for (cp.a0 = 0; cp.a0 < cp.A && e == hipSuccess; cp.a0 += 4) {
+        cp.codes_out = cp.a0 == 0 ? code_rows : nullptr;
+        if (code_rows && cp.a0 > 0) read_emitted_codes(cp, code_rows, codes_stride);
+        e = launch_cond_pre(cp, sh.at, sh.waves, grid, s);
     }
-    if (pl.panels > 1 && e == hipSuccess) e = launch_panel_sum(b.pre, (long long)d->num_person * (2 * A + 1), pl.panels, s);
     return e;
+}
+
+// conditional posterior, VALU first pass
+static hipError_t cond_pre_valu(const vibo_desc* d, const Plan& pl, CondParams cp, const PanelBufs& b, hipStream_t s) {
+    cp.item0 = 0; cp.I = d->num_item; cp.pre_out = b.pre;
+    if (pl.panels == 1) return cond_pre_span(cp, b.code_rows, pl.codes_stride, pl.cond_nblk, s);
+    // more than one panel: ALL of them in one launch per 4 ability dims (CondParams::panel_count), the chip's workgroup
+    // slots shared out over the panels; their statistics summed into panel 0's block
+    const int per = pl.cond_nblk / pl.panels;
+    cp.I = kPanelItems; cp.panel_count = pl.panels;
+    const hipError_t e = cond_pre_span(cp, b.code_rows, pl.codes_stride, (per < 1 ? 1 : per) * pl.panels, s);
+    return e != hipSuccess ? e : launch_panel_sum(b.pre, (long long)d->num_person * (2 * d->ability_dim + 1), pl.panels, s);
 }
 
 // unconditional posterior over more than 1024 items: the whole-row counts
@@ -237,14 +239,14 @@ static hipError_t launch_panels(const vibo_desc* d, const Plan& pl, ElboParams& 
     if (pl.tail == Tail::None) coef = nullptr;      // (no pass reads the per-person backward coefficients)
     if (pl.engine == Engine::Matrix && pl.panels > 1) {
         // the matrix kernel takes all panels in one launch: workgroup = (panel, slot), see ElboParams::panel_count
-        p.item0 = 0; p.I = 1024; p.primary = 1; p.panel_count = pl.panels;
+        p.item0 = 0; p.I = kPanelItems; p.primary = 1; p.panel_count = pl.panels;
         p.post_coef = coef;
         return launch_split(d, pl, p, pl.panels * pl.split_nblk, s);
     }
     hipError_t e = hipSuccess;
     for (int pn = 0; pn < pl.panels && e == hipSuccess; ++pn) {
-        p.item0 = pn * 1024;
-        p.I = I - p.item0 < 1024 ? I - p.item0 : 1024;
+        const PanelSpan sp = panel_span(I, pn);
+        p.item0 = sp.item0; p.I = sp.items;
         p.primary = pn == 0 ? 1 : 0;
         p.partial = partial + (size_t)pn * pl.split_nblk * pl.lay.stride;
         p.post_coef = coef ? coef + (size_t)pn * d->num_person * 4 * A : nullptr;
@@ -272,11 +274,11 @@ static hipError_t gradient_tail(const vibo_desc* d, const Plan& pl, const ElboAr
         return e;
     }
     for (int pn = 0; pn < pl.panels && e == hipSuccess; ++pn) {
-        cp.item0 = pn * 1024;
-        cp.I = I - cp.item0 < 1024 ? I - cp.item0 : 1024;
+        const PanelSpan sp = panel_span(I, pn);
+        const CondPassShape sh = cond_pass_shape(A, sp.items);
+        cp.item0 = sp.item0; cp.I = sp.items;
         cp.partial = b.crec + (size_t)pn * pl.cond_post_nblk * pl.cond_rec;
-        for (cp.a0 = 0; cp.a0 < A && e == hipSuccess; cp.a0 += 4)
-            e = launch_cond_post(cp, A == 1 ? 1 : A <= 2 ? 2 : 4, (cp.I + 255) / 256, pl.cond_post_nblk, s);
+        for (cp.a0 = 0; cp.a0 < A && e == hipSuccess; cp.a0 += 4) e = launch_cond_post(cp, sh.at, sh.waves, pl.cond_post_nblk, s);
     }
     if (e == hipSuccess) e = launch_cond_finalize(b.crec, a.grad_table, I, A, pl.panels, pl.cond_post_nblk, pl.cond_rec, s, tail);
     return e;
@@ -290,12 +292,8 @@ static hipError_t run_panels(const vibo_desc* d, const Plan& pl, const ElboArgs&
     b.mscratch = wsb + pl.off_cpart;
     b.crec = reinterpret_cast<float*>(wsb + pl.off_crec);
     b.code_rows = pl.off_codes ? reinterpret_cast<uint8_t*>(wsb + pl.off_codes) : nullptr;
-    CondParams cp;
-    memset(&cp, 0, sizeof(cp));
+    CondParams cp = cond_params(d, a.response, a.mask, a.row_index, a.table);
     cp.codes_stride = pl.codes_stride;
-    cp.response = a.response; cp.mask = a.mask; cp.row_index = a.row_index; cp.table = a.table;
-    cp.resp_stride = d->response_row_stride; cp.mask_stride = d->mask_row_stride;
-    cp.B = d->num_person; cp.I_total = d->num_item; cp.A = d->ability_dim; cp.mask_dtype = d->mask_dtype;
     cp.coef_panels = pl.panels; cp.rec_stride = pl.cond_rec; cp.coef_in = b.coef;
 
     hipError_t e = first_pass(d, pl, a, num_cu, cp, b, p);
@@ -332,12 +330,10 @@ static int run_finalize(const vibo_desc* d, const Plan& pl, Path path, const Elb
     f.nblk = path == Path::Panels ? pl.panels * pl.split_nblk : path == Path::Split ? pl.split_nblk : path == Path::Row ? pl.row_nblk : pl.nblk;
     f.I = d->num_item; f.A = d->ability_dim; f.D = pl.D; f.n_flows = d->n_flows; f.reg_mode = d->reg_mode;
     f.irt = d->irt_model; f.want_grad = d->want_grad ? 1 : 0; f.lay = pl.lay;
-    f.panel_items = path == Path::Panels ? 1024 : 1 << 30;
+    f.panel_items = path == Path::Panels ? kPanelItems : 1 << 30;
     f.bpp = path == Path::Panels ? pl.split_nblk : f.nblk;
     f.tail = tail;
-    const hipError_t e = launch_finalize(f, a.stream);
-    if (e != hipSuccess) return hip_fail(e, "finalize launch");
-    return 0;
+    return hip_rc(launch_finalize(f, a.stream), "finalize launch");
 }
 
 static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
@@ -360,9 +356,7 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     if (d->n_flows > 0 && d->want_grad && !a.grad_flow) return fail(-5, "want_grad with flows needs grad_flow");
     Plan pl;
     if ((rc = make_plan(d, num_cu, &pl)) < 0) return rc;
-    if (!a.workspace || a.workspace_bytes < pl.total_bytes)
-        return fail(-7, "workspace too small: %zu < %zu", a.workspace_bytes, pl.total_bytes);
-    if ((uintptr_t)a.workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
+    if ((rc = check_workspace(a.workspace, a.workspace_bytes, pl.total_bytes)) != 0) return rc;
     // 16-byte row loads need aligned rows
     const bool vec = rows_vec_ok(d, a.response, a.mask);
     const Path path = resolve_path(pl, d, vec);
@@ -386,14 +380,12 @@ static int elbo_fwd_bwd_impl(const vibo_desc* d, const ElboArgs& a) {
     if (path == Path::General) return run_general(d, pl, a, num_cu);
 
     ElboParams p = elbo_params(d, pl, a, vec);
-    hipError_t e = hipSuccess;
-    if (!row_split) {            // (the row-split kernels read the item sample themselves)
-        e = launch_item_prep(a.item, static_cast<float*>(a.workspace), d->num_item, d->ability_dim, pl.AT, pl.D, pl.DP, d->irt_model, a.stream);
-        if (e != hipSuccess) return hip_fail(e, "item_prep launch");
-    }
+    if (!row_split &&            // (the row-split kernels read the item sample themselves)
+        (rc = hip_rc(launch_item_prep(a.item, static_cast<float*>(a.workspace), d->num_item, d->ability_dim, pl.AT, pl.D, pl.DP, d->irt_model,
+                                      a.stream), "item_prep launch")) != 0) return rc;
     CondFinTail tail;                  // the conditional posterior's last stage, launched with the ELBO finalize
     memset(&tail, 0, sizeof(tail));
-    e = path == Path::Panels ? run_panels(d, pl, a, num_cu, p, &tail) : run_single(d, pl, path, p, a.stream);
+    const hipError_t e = path == Path::Panels ? run_panels(d, pl, a, num_cu, p, &tail) : run_single(d, pl, path, p, a.stream);
     if (e != hipSuccess) return hip_fail(e, "elbo kernel launch");
     if (a.skip_finalize) return 0;      // the partial records stay in the workspace for vibo_train_epilogue_fused
     return run_finalize(d, pl, path, a, p.partial, tail);
@@ -426,9 +418,7 @@ int vibo_plan_kernel(const vibo_desc* d) {
 
 int vibo_selftest_lane_swaps(const float* in, float* out, void* stream) {
     if (!in || !out) return fail(-5, "null required pointer");
-    const hipError_t e = launch_lane_swap_selftest(in, out, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "lane swap selftest launch");
-    return 0;
+    return hip_rc(launch_lane_swap_selftest(in, out, (hipStream_t)stream), "lane swap selftest launch");
 }
 
 int vibo_set_insitu_timer(uint64_t* block) {
@@ -442,8 +432,7 @@ int vibo_insitu_timer_reset(uint64_t* block, void* stream) {
     hipError_t e = hipMemsetAsync(block, 0, 8 * sizeof(uint64_t), (hipStream_t)stream);
     if (e == hipSuccess) e = hipMemsetAsync(block, 0xff, sizeof(uint64_t), (hipStream_t)stream);
     if (e == hipSuccess) e = hipMemsetAsync(block + 5, 0xff, sizeof(uint64_t), (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "insitu timer reset");
-    return 0;
+    return hip_rc(e, "insitu timer reset");
 }
 
 size_t vibo_workspace_bytes(const vibo_desc* d) {
@@ -486,9 +475,7 @@ int vibo_rows_sign_is_mask(const vibo_desc* d, const float* response, const void
     if (rc) return rc;
     if (d->mask_dtype != VIBO_MASK_U8) return fail(-8, "vibo_rows_sign_is_mask: fp32 rows with a VIBO_MASK_U8 mask");
     if (!response || !mask || !differs) return fail(-5, "null required pointer");
-    const hipError_t e = launch_sign_is_mask(d, response, mask, rows_vec_ok(d, response, mask), differs, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "rows_sign_is_mask launch");
-    return 0;
+    return hip_rc(launch_sign_is_mask(d, response, mask, rows_vec_ok(d, response, mask), differs, (hipStream_t)stream), "rows_sign_is_mask launch");
 }
 
 int vibo_tile_rows_supported(const vibo_desc* d) {
@@ -514,20 +501,23 @@ int vibo_tile_rows_build(const vibo_desc* src, const void* response, const void*
     if (image_bytes < vibo_tile_rows_bytes(&t)) return fail(-7, "tile image too small: %zu < %zu", image_bytes, vibo_tile_rows_bytes(&t));
     if ((uintptr_t)image & 15) return fail(-7, "the tile image must be 16-byte aligned");
     const float* resp = fmt == VIBO_MASK_CODES ? nullptr : static_cast<const float*>(response);
-    const hipError_t e = launch_tile_rows_build(src, resp, mask, rows_vec_ok(src, resp, mask), image, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "tile_rows_build launch");
-    return 0;
+    return hip_rc(launch_tile_rows_build(src, resp, mask, rows_vec_ok(src, resp, mask), image, (hipStream_t)stream), "tile_rows_build launch");
 }
 
 int vibo_given_tile_rows_supported(const vibo_desc* d) {
     return (d && d->mask_dtype == VIBO_MASK_TILES && check_desc(d, false, true) == 0) ? 1 : 0;
 }
 
-size_t vibo_given_tiles_workspace_bytes(const vibo_desc* d) {
-    if (!vibo_given_tile_rows_supported(d)) return 0;
-    vibo_desc u = *d;                        // (a tile image: the same matrix as padded rows under a u8 mask)
+// a tile image plans like the same matrix as padded rows under a u8 mask
+static vibo_desc tiles_as_padded_rows(vibo_desc u) {
     u.mask_dtype = VIBO_MASK_U8;
     u.response_row_stride = u.mask_row_stride = (u.num_item + 3) & ~3;
+    return u;
+}
+
+size_t vibo_given_tiles_workspace_bytes(const vibo_desc* d) {
+    if (!vibo_given_tile_rows_supported(d)) return 0;
+    const vibo_desc u = tiles_as_padded_rows(*d);
     return vibo_workspace_bytes(&u);
 }
 
@@ -554,10 +544,7 @@ int vibo_elbo_fwd_bwd_given_tiles(const vibo_desc* d, const float* response, con
 static StepContract step_query(const vibo_desc* d, bool rows_gathered) {
     vibo_desc u = d ? *d : vibo_desc{};      // (null: refused by the descriptor check like any zeroed descriptor)
     if (u.mask_dtype == VIBO_MASK_SIGN) u.mask_dtype = VIBO_MASK_U8;
-    if (u.mask_dtype == VIBO_MASK_TILES) {      // (a tile image: the same matrix as padded rows under a u8 mask)
-        u.mask_dtype = VIBO_MASK_U8;
-        u.response_row_stride = u.mask_row_stride = (u.num_item + 3) & ~3;
-    }
+    if (u.mask_dtype == VIBO_MASK_TILES) u = tiles_as_padded_rows(u);
     Plan pl;
     return plan_for(&u, &pl) == 0 ? step_contract(&u, pl, rows_gathered) : StepContract{};
 }
@@ -616,7 +603,7 @@ int vibo_train_epilogue_fused(const vibo_desc* d, int hidden_dim, const void* wo
         Plan pl;
         if (make_plan(d, device_cus(), &pl) < 0) return fail(-8, "no plan for this descriptor");
         if (!step_contract(d, pl, false).ok) return fail(-8, "vibo_train_epilogue_fused: the descriptor is not a vibo_elbo_fwd_bwd_step call");
-        if ((uintptr_t)workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
+        if ((rc = check_workspace(workspace, 0, 0)) != 0) return rc;      // (its size is not an argument of this call)
         e.partial = reinterpret_cast<const float*>(static_cast<const char*>(workspace) + pl.off_partial);
         e.nblk = pl.split_nblk;
         e.lay = pl.lay;
@@ -627,9 +614,7 @@ int vibo_train_epilogue_fused(const vibo_desc* d, int hidden_dim, const void* wo
     e.seed_lo = (uint32_t)seed; e.seed_hi = (uint32_t)(seed >> 32);
     e.eps_ab = eps_ability; e.n_ab = (long long)n_eps_ability; e.ab_stream = ability_stream_id;
     e.n_item_blocks = train_epilogue_item_blocks(e.n_item_entries);
-    const hipError_t he = launch_train_epilogue_fused(e, (hipStream_t)stream);
-    if (he != hipSuccess) return hip_fail(he, "train_epilogue_fused launch");
-    return 0;
+    return hip_rc(launch_train_epilogue_fused(e, (hipStream_t)stream), "train_epilogue_fused launch");
 }
 
 static size_t multi_workspace_bytes(const vibo_desc* d, int num_samples, bool given) {
@@ -654,8 +639,7 @@ static int multi_check_args(const vibo_desc* d, bool have_pointers, const float*
     if ((rc = require_rows(d, response, mask)) != 0) return rc;
     if (d->n_flows > 0 && !flow) return fail(-5, "flows need flow");
     if (plan_rc) return plan_rc;
-    if (!workspace || workspace_bytes < need) return fail(-7, "workspace too small: %zu < %zu", workspace_bytes, need);
-    if ((uintptr_t)workspace & 255) return fail(-7, "workspace must be 256-byte aligned");
+    if ((rc = check_workspace(workspace, workspace_bytes, need)) != 0) return rc;
     if (!rows_vec_ok(d, response, mask)) return fail(-8, "multi-sample forward: rows are not 16-byte chunkable");
     return 0;
 }
@@ -688,11 +672,8 @@ static int multi_forward_impl(const vibo_desc* d, bool given, int num_samples, c
     MultiParams mp;
     memset(&mp, 0, sizeof(mp));
     ElboParams& p = mp.e;
-    p.response = response; p.mask = mask; p.row_index = row_index; p.table = table; p.item_prep = item_prep;
-    p.resp_stride = d->response_row_stride; p.mask_stride = d->mask_row_stride;
-    p.B = d->num_person; p.I = I; p.A = A; p.D = pl.D; p.DP = pl.DP;
-    p.mask_dtype = d->mask_dtype; p.missing_mode = d->missing_mode; p.reg_mode = d->reg_mode;
-    p.flow = flow; p.n_flows = d->n_flows; p.lay = pl.lay; p.I_total = I; p.primary = 1;
+    elbo_shape(p, d, pl, response, mask, row_index, table, flow);
+    p.item_prep = item_prep;
     mp.item_sstride = (long long)(prep / 4);
     mp.eps_sstride = (long long)d->num_person * A;
     mp.post_sstride = given ? post_sstride : 0;
@@ -713,15 +694,15 @@ static int multi_forward_impl(const vibo_desc* d, bool given, int num_samples, c
         p.eps = eps + (size_t)s0 * d->num_person * A;
         if (given) p.given_post = table + (size_t)s0 * post_sstride;
         for (int pn = 0; pn < panels && e == hipSuccess; ++pn) {
-            p.item0 = pn * 1024;
-            p.I = pl.panels > 0 ? (I - p.item0 < 1024 ? I - p.item0 : 1024) : I;
+            const PanelSpan sp = pl.panels > 0 ? panel_span(I, pn) : PanelSpan{0, I};
+            p.item0 = sp.item0; p.I = sp.items;
             p.primary = pn == 0 ? 1 : 0;
             p.partial = partial + (size_t)pn * nblk * pl.lay.stride;
             e = (given ? launch_elbo_multi_given : launch_elbo_multi)(mp, pl.AT, d->irt_model, sc, (p.I + 255) / 256, nblk, s);
         }
         if (e != hipSuccess) return hip_fail(e, "multi-sample forward launch");
-        e = launch_multi_finalize(partial, out_scalars + (size_t)s0 * VIBO_NUM_SCALARS, panels * nblk, pl.lay.stride, sc, d->reg_mode, s);
-        if (e != hipSuccess) return hip_fail(e, "multi-sample finalize launch");
+        if ((rc = hip_rc(launch_multi_finalize(partial, out_scalars + (size_t)s0 * VIBO_NUM_SCALARS, panels * nblk, pl.lay.stride, sc, d->reg_mode, s),
+                         "multi-sample finalize launch")) != 0) return rc;
         s0 += sc;
     }
     return 0;
@@ -750,7 +731,6 @@ struct MultiCondPlan {
     long long codes_stride;    // 0: the caller's rows are cell codes already
     int group, ldc;            // samples per contraction pass; floats per row of the sums (group * 2A + the count)
 };
-static size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 static int multi_cond_plan(const vibo_desc* d, int num_samples, int num_cu, MultiCondPlan* m) {
     if (d->posterior != VIBO_POSTERIOR_CONDITIONAL)
         return fail(-3, "vibo_elbo_multi_forward_cond: the descriptor's posterior must be VIBO_POSTERIOR_CONDITIONAL");
@@ -820,8 +800,7 @@ int vibo_elbo_multi_forward_cond(const vibo_desc* d, int num_samples, const floa
     const int64_t* ridx = row_index;
     if (m.codes_stride) {
         uint8_t* packed = reinterpret_cast<uint8_t*>(wsb + m.off_codes);
-        const hipError_t e = launch_pack_codes(d, response, mask, packed, m.codes_stride, true, s, row_index);
-        if (e != hipSuccess) return hip_fail(e, "multi-sample forward: pack_codes launch");
+        if ((rc = hip_rc(launch_pack_codes(d, response, mask, packed, m.codes_stride, true, s, row_index), "multi-sample forward: pack_codes launch")) != 0) return rc;
         codes = packed; stride = m.codes_stride; ridx = nullptr;
     }
     // 2.-4. per group of samples: stacked table image, one contraction pass over the codes, the per-person finish.  The first
@@ -830,11 +809,10 @@ int vibo_elbo_multi_forward_cond(const vibo_desc* d, int num_samples, const floa
     const int cnt_col = (num_samples < m.group ? num_samples : m.group) * 2 * A;
     for (int s0 = 0; s0 < num_samples; s0 += m.group) {
         const int G = num_samples - s0 < m.group ? num_samples - s0 : m.group;
-        hipError_t e = launch_cond_stack_sums(codes, stride, ridx, B, I, A, tables + (size_t)s0 * n_table, (long long)n_table, G, s0 == 0, sums,
-                                              m.ldc, wsb + m.off_image, s);
-        if (e != hipSuccess) return hip_fail(e, "multi-sample forward: experts' sums launch");
-        e = launch_cond_stack_finish(sums, m.ldc, cnt_col, post + (size_t)s0 * B * 2 * A, B, I, A, G, d->missing_mode, s);
-        if (e != hipSuccess) return hip_fail(e, "multi-sample forward: posterior finish launch");
+        if ((rc = hip_rc(launch_cond_stack_sums(codes, stride, ridx, B, I, A, tables + (size_t)s0 * n_table, (long long)n_table, G, s0 == 0, sums,
+                                                m.ldc, wsb + m.off_image, s), "multi-sample forward: experts' sums launch")) != 0) return rc;
+        if ((rc = hip_rc(launch_cond_stack_finish(sums, m.ldc, cnt_col, post + (size_t)s0 * B * 2 * A, B, I, A, G, d->missing_mode, s),
+                         "multi-sample forward: posterior finish launch")) != 0) return rc;
     }
     // 5. the GIVEN multi-sample pass on the codes
     return multi_forward_impl(&m.dg, true, num_samples, nullptr, codes, ridx, post, B * 2 * A, item, eps, flow, out_scalars, workspace,
@@ -849,10 +827,8 @@ int vibo_decode_mean(const vibo_desc* d, int num_samples, const float* ability, 
     if (!ability || !item || !response_mu_mean) return fail(-5, "null required pointer");
     const int A = d->ability_dim;
     if (((long long)d->num_person + 7) / 8 > 65535LL * 32768) return fail(-3, "num_person too large");
-    const hipError_t e = launch_decode_mean(num_samples, ability, item, response_mu_mean, d->num_person, d->num_item, A,
-                                            item_feat_dim(d->irt_model, A), d->irt_model, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "decode_mean launch");
-    return 0;
+    return hip_rc(launch_decode_mean(num_samples, ability, item, response_mu_mean, d->num_person, d->num_item, A,
+                                     item_feat_dim(d->irt_model, A), d->irt_model, (hipStream_t)stream), "decode_mean launch");
 }
 
 // vibo_encode's fast path: the row statistics of the row-split pipeline (16-byte row chunks at HBM speed) + a per-person finish
@@ -866,26 +842,20 @@ static hipError_t encode_fast(const vibo_desc* d, int num_cu, const float* respo
         return launch_encode_finish(cnt, nullptr, 0, table, ability_mu, ability_logvar, B, I, A, d->missing_mode, s);
     }
     float* pre = static_cast<float*>(workspace);
-    const int panels = (I + 1023) / 1024;
+    const int panels = panel_count(I);
     const bool mfma = encode_on_matrix_pipe(d);
     hipError_t e = hipSuccess;
     if (mfma) {
-        const size_t pre_bytes = ((size_t)panels * d->num_person * (2 * A + 1) * 4 + 255) & ~(size_t)255;
         e = launch_cond_pre_mfma(static_cast<const uint8_t*>(mask), d->mask_row_stride, row_index, d->num_person, I, A, table, pre,
-                                 static_cast<char*>(workspace) + pre_bytes, s);
+                                 static_cast<char*>(workspace) + pre_block_bytes(panels, B, A), s);
     } else {
-        CondParams cp;
-        memset(&cp, 0, sizeof(cp));
-        cp.response = response; cp.mask = mask; cp.row_index = row_index; cp.table = table;
-        cp.resp_stride = d->response_row_stride; cp.mask_stride = d->mask_row_stride;
-        cp.B = d->num_person; cp.I_total = I; cp.A = A; cp.mask_dtype = d->mask_dtype;
+        CondParams cp = cond_params(d, response, mask, row_index, table);
         const int grid = clamp_grid(num_cu, 3, d->num_person, 8);
         for (int pn = 0; pn < panels && e == hipSuccess; ++pn) {
-            cp.item0 = pn * 1024;
-            cp.I = I - cp.item0 < 1024 ? I - cp.item0 : 1024;
+            const PanelSpan sp = panel_span(I, pn);
+            cp.item0 = sp.item0; cp.I = sp.items;
             cp.pre_out = pre + (size_t)pn * d->num_person * (2 * A + 1);
-            for (cp.a0 = 0; cp.a0 < A && e == hipSuccess; cp.a0 += 4)
-                e = launch_cond_pre(cp, A == 1 ? 1 : A <= 2 ? 2 : 4, (cp.I + 255) / 256, grid, s);
+            e = cond_pre_span(cp, nullptr, 0, grid, s);
         }
     }
     if (e != hipSuccess) return e;
@@ -903,22 +873,17 @@ int vibo_encode(const vibo_desc* d, const float* response, const void* mask, con
     if ((rc = require_rows(d, response, mask)) != 0) return rc;
     const size_t need = encode_scratch_bytes(d);
     if (need > 0 && rows_vec_ok(d, response, mask) && workspace && workspace_bytes >= need && (((uintptr_t)workspace & 255) == 0)) {
-        const hipError_t e = encode_fast(d, num_cu, response, mask, row_index, table, ability_mu, ability_logvar, workspace, (hipStream_t)stream);
-        if (e != hipSuccess) return hip_fail(e, "encode (fast path) launch");
-        return 0;
+        return hip_rc(encode_fast(d, num_cu, response, mask, row_index, table, ability_mu, ability_logvar, workspace, (hipStream_t)stream),
+                      "encode (fast path) launch");
     }
     if (d->mask_dtype == VIBO_MASK_CODES) return codes_unsupported();      // (or the workspace is missing / too small)
     EncodeParams p;
     memset(&p, 0, sizeof(p));
-    p.response = response; p.mask = mask; p.row_index = row_index; p.table = table;
-    p.ability_mu = ability_mu; p.ability_logvar = ability_logvar;
-    p.resp_stride = d->response_row_stride; p.mask_stride = d->mask_row_stride;
-    p.B = d->num_person; p.I = d->num_item; p.A = d->ability_dim;
-    p.mask_dtype = d->mask_dtype; p.missing_mode = d->missing_mode;
+    fill_rows(p, d, response, mask, row_index);
+    p.table = table; p.ability_mu = ability_mu; p.ability_logvar = ability_logvar;
+    p.I = d->num_item; p.missing_mode = d->missing_mode;
     p.conditional = d->posterior == VIBO_POSTERIOR_CONDITIONAL;
-    const hipError_t e = launch_encode(p, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "encode launch");
-    return 0;
+    return hip_rc(launch_encode(p, (hipStream_t)stream), "encode launch");
 }
 
 int vibo_row_counts(const vibo_desc* d, const float* response, const void* mask, const int64_t* row_index, int32_t* counts,
@@ -933,8 +898,7 @@ int vibo_row_counts(const vibo_desc* d, const float* response, const void* mask,
     const bool chunks = d->num_item >= 4 && d->mask_dtype != VIBO_MASK_I64 && rows_vec_ok(d, response, mask);
     const hipError_t e = chunks ? launch_row_counts(d, num_cu, response, mask, row_index, counts, nullptr, 0, s)
                                 : launch_row_counts_scalar(d, response, mask, row_index, counts, s);
-    if (e != hipSuccess) return hip_fail(e, "row_counts launch");
-    return 0;
+    return hip_rc(e, "row_counts launch");
 }
 
 int vibo_pack_codes(const vibo_desc* d, const float* response, const void* mask, uint8_t* codes, int64_t codes_row_stride,
@@ -951,9 +915,7 @@ int vibo_pack_codes(const vibo_desc* d, const float* response, const void* mask,
         if ((d->mask_dtype == VIBO_MASK_NONE) != (mask == nullptr)) return fail(-5, "mask pointer / mask_dtype mismatch");
         if (codes_row_stride < d->num_item) return fail(-3, "codes_row_stride %lld < num_item", (long long)codes_row_stride);
     }
-    const hipError_t e = launch_pack_codes(d, response, mask, codes, (long long)codes_row_stride, chunks, (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "pack_codes launch");
-    return 0;
+    return hip_rc(launch_pack_codes(d, response, mask, codes, (long long)codes_row_stride, chunks, (hipStream_t)stream), "pack_codes launch");
 }
 
 int vibo_decode(const vibo_desc* d, const float* ability, const float* item, float* response_mu, void* stream) {
@@ -962,10 +924,8 @@ int vibo_decode(const vibo_desc* d, const float* ability, const float* item, flo
     if (!ability || !item || !response_mu) return fail(-5, "null required pointer");
     if (d->num_person > 65535 * 1024) return fail(-3, "num_person too large for decode grid");
     const int A = d->ability_dim;
-    const hipError_t e = launch_decode(ability, item, response_mu, d->num_person, d->num_item, A, item_feat_dim(d->irt_model, A), d->irt_model,
-                                       (hipStream_t)stream);
-    if (e != hipSuccess) return hip_fail(e, "decode launch");
-    return 0;
+    return hip_rc(launch_decode(ability, item, response_mu, d->num_person, d->num_item, A, item_feat_dim(d->irt_model, A), d->irt_model,
+                                (hipStream_t)stream), "decode launch");
 }
 
 }  // extern "C"

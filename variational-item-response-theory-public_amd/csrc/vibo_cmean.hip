@@ -37,6 +37,7 @@
 #include "vibo_device.hpp"
 #include "vibo_cond.hpp"
 #include "vibo_cond_finalize.hpp"
+#include "vibo_host.hpp"
 #include <string.h>
 
 namespace vibo {
@@ -826,13 +827,12 @@ static int cm_ranges(long long B, int nS, long long* per_r) {
     *per_r = per;
     return (int)((B + per - 1) / per);
 }
-static size_t cm_up(size_t b) { return (b + 255) & ~(size_t)255; }
-static size_t cm_timg_bytes(int nS, int NT) { return cm_up((size_t)nS * 4 * NT * kCmNP * 64 * 16); }
-static size_t cm_gimg_bytes(long long B, int NT) { return cm_up((size_t)((B + 63) / 64 * 2) * NT * kCmNP * 64 * 16); }
+static size_t cm_timg_bytes(int nS, int NT) { return up256((size_t)nS * 4 * NT * kCmNP * 64 * 16); }
+static size_t cm_gimg_bytes(long long B, int NT) { return up256((size_t)((B + 63) / 64 * 2) * NT * kCmNP * 64 * 16); }
 static size_t cm_rec_bytes(long long B, int nS, int NT) {
     long long per_r;
     const int nR = cm_ranges(B, nS, &per_r);
-    return cm_up((size_t)nS * nR * 128 * 16 * NT * 4);
+    return up256((size_t)nS * nR * 128 * 16 * NT * 4);
 }
 
 template <int NT, bool COUNT>
@@ -1008,10 +1008,9 @@ int vibo_code_table_sum_forward(int64_t num_person, int num_item, int hidden_dim
     hipStream_t s = (hipStream_t)stream;
     uint4* img = static_cast<uint4*>(scratch);
     hipLaunchKernelGGL((cm_table_image_kernel<false>), dim3((nS * 4 * 4 * 64 + 255) / 256), dim3(256), 0, s, feature, img, num_item, nS, 4, kCmH);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
-    return (int)cm_launch_forward<false>(4, codes, (long long)codes_row_stride, nullptr, (long long)num_person, num_item, nS, img, out_sum, kCmH,
-                                         kCmH, s);
+    if (const int rc = launch_rc("vibo_code_table_sum_forward: table image launch")) return rc;
+    return hip_rc(cm_launch_forward<false>(4, codes, (long long)codes_row_stride, nullptr, (long long)num_person, num_item, nS, img, out_sum, kCmH,
+                                           kCmH, s), "vibo_code_table_sum_forward launch");
 }
 
 /* d feature [2][I][64] = sum over the persons of [code == c] grad_sum[p][:] */
@@ -1030,14 +1029,13 @@ int vibo_code_table_sum_backward(int64_t num_person, int num_item, int hidden_di
     const long long n32 = (num_person + 63) / 64 * 2;
     hipLaunchKernelGGL(cm_grad_image_kernel, dim3((unsigned)((n32 * 4 * 64 + 255) / 256)), dim3(256), 0, s, grad_sum, gimg, (long long)num_person, n32,
                        4, kCmH);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (const int rc = launch_rc("vibo_code_table_sum_backward: gradient image launch")) return rc;
     int nR = 0;
-    e = cm_launch_backward(4, codes, (long long)codes_row_stride, nullptr, (long long)num_person, num_item, nS, gimg, rec, s, &nR);
-    if (e != hipSuccess) return (int)e;
+    if (const int rc = hip_rc(cm_launch_backward(4, codes, (long long)codes_row_stride, nullptr, (long long)num_person, num_item, nS, gimg, rec, s, &nR),
+                              "vibo_code_table_sum_backward launch")) return rc;
     hipLaunchKernelGGL(cm_backward_reduce_kernel, dim3((2 * num_item * kCmH + 255) / 256), dim3(256), 0, s, (const float*)rec, grad_feature, num_item,
                        nR, kCmH);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_code_table_sum_backward: reduce launch");
 }
 
 }  // extern "C"

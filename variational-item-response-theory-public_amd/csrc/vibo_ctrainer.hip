@@ -16,6 +16,7 @@
 #include "../../include/vibo_hip.h"
 #include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
+#include "vibo_host.hpp"
 #include "vibo_philox.hpp"
 #include "vibo_train_hook.hpp"
 
@@ -729,7 +730,7 @@ int vibo_ctrain_prologue(const vibo_desc* d, int hidden_dim, const float* params
     hipStream_t s = (hipStream_t)stream;
     q.table = table; q.ab_blocks = (int)ab_blocks; q.tpb = ct_tiles_per_block(L.rows);
     hipLaunchKernelGGL(ct_prologue_kernel, dim3((unsigned)(1 + L.n_ib + ab_blocks + L.n_rb)), dim3(kCtItems), 0, s, q);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_ctrain_prologue launch");
 }
 
 int vibo_ctrain_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, const float* eps_item, const float* item_feat,
@@ -752,10 +753,9 @@ int vibo_ctrain_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, 
     CtEpiParams qe;
     qe.it = qi; qe.fin = qf; qe.item_feat = item_feat; qe.tpb = ct_tiles_per_block(L.rows);
     hipLaunchKernelGGL(ct_backward_kernel, dim3(L.n_rb + (L.F > 0 ? L.n_ib : 0)), dim3(kCtItems), 0, s, qe);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (const int rc = launch_rc("vibo_ctrain_epilogue: backward launch")) return rc;
     hipLaunchKernelGGL(ct_update_kernel, dim3(L.n_ib + (L.n_mlp + 63) / 64 + 1), dim3(kCtItems), 0, s, qe);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_ctrain_epilogue: update launch");
 }
 
 }  // extern "C"

@@ -30,6 +30,7 @@
 #include <string.h>
 #include "../../include/vibo_hip.h"
 #include "vibo_decoder_device.hpp"
+#include "vibo_host.hpp"
 
 namespace vibo {
 
@@ -370,11 +371,8 @@ static int decoder_check(const vibo_decoder_desc* d) {
 
 extern "C" int vibo_decoder_person_chunks(int num_person, int num_item) {
     if (num_person < 1 || num_item < 1) return 0;
-    int dev = 0, n = 0;
-    const int cus = (hipGetDevice(&dev) == hipSuccess &&
-                     hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
     const int n_ib = (num_item + 63) / 64;
-    long long chunks = ((long long)cus * 2 + n_ib - 1) / n_ib;         // about two workgroups per CU in flight
+    long long chunks = ((long long)device_cus() * 2 + n_ib - 1) / n_ib;         // about two workgroups per CU in flight
     const long long most = ((long long)num_person + 1) / 2;            // at least one person pair per chunk
     if (chunks > most) chunks = most;
     if (chunks < 1) chunks = 1;
@@ -410,5 +408,5 @@ extern "C" int vibo_decoder_fwd_bwd(const vibo_decoder_desc* d, const float* res
         if (hasl) hipLaunchKernelGGL((decoder_kernel<false, true>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((decoder_kernel<false, false>), grid, block, 0, s, p);
     }
-    return (int)hipGetLastError();
+    return launch_rc("vibo_decoder_fwd_bwd launch");
 }

@@ -203,12 +203,6 @@ __global__ __launch_bounds__(256, 2) void decoder_multi_forward_kernel(const Dec
     }
 }
 
-static int device_cus() {
-    int dev = 0, n = 0;
-    return (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-}
-
 }  // namespace vibo
 
 using namespace vibo;
@@ -266,6 +260,5 @@ extern "C" int vibo_decoder_multi_forward(const vibo_decoder_desc* d, int num_sa
     hipStream_t s = (hipStream_t)stream;
     if (hasl) hipLaunchKernelGGL((decoder_multi_forward_kernel<true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((decoder_multi_forward_kernel<false>), grid, block, 0, s, p);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : fail((int)e, "%s: launch failed: %s", fn, hipGetErrorString(e));
+    return launch_rc("vibo_decoder_multi_forward launch");
 }

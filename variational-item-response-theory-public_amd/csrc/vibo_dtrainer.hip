@@ -45,6 +45,7 @@
 #include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
 #include "vibo_finalize.hpp"
+#include "vibo_host.hpp"
 #include "vibo_philox.hpp"
 #include "vibo_train_hook.hpp"
 
@@ -946,23 +947,21 @@ static int dt_prologue(const int post, const vibo_desc* d, int decoder, int hidd
     const long long ab_blocks = ((a.n_ab + 3) / 4 + kDThreads - 1) / kDThreads;
     hipLaunchKernelGGL(y.cond ? dt_prologue_cond_kernel : dt_prologue_kernel, dim3((unsigned)(1 + a.n_item_blocks + ab_blocks)),
                        dim3(kDThreads), 0, s, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (const int rc = launch_rc("vibo_dtrain_prologue launch")) return rc;
     if (y.mlp) {
         DItem it;
         memset(&it, 0, sizeof(it));
         it.p = a.p; it.I = y.I; it.nwg = y.gi; it.P = params; it.item_feat = item_feat;
         it.h1 = scratch + y.ih1; it.h2 = scratch + y.ih2; it.hid = scratch + y.ihid; it.U = scratch + y.U;
         hipLaunchKernelGGL(dt_item_fwd_kernel, dim3((unsigned)y.gi), dim3(kDThreads), 0, s, it);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
+        if (const int rc = launch_rc("vibo_dtrain_prologue: item forward launch")) return rc;
     }
     if (y.cond) {
         const DCond c = dcond(y, a.p, params, item_feat, scratch);
         hipLaunchKernelGGL(dt_table_fwd_kernel, dim3((unsigned)y.gt), dim3(kDThreads), 0, s, c);
-        e = hipGetLastError();
+        return launch_rc("vibo_dtrain_prologue: table forward launch");
     }
-    return (int)e;
+    return 0;
 }
 extern "C" int vibo_dtrain_prologue(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, const float* params,
                                     const float* item_mu, const float* item_logvar, float* eps_item, uint64_t seed, int draw_noise,
@@ -1026,8 +1025,8 @@ static int dt_forward_backward(const int post, const vibo_desc* d, int decoder, 
         if (y.cond) {
             cd.sums = scratch + y.sums + sp * kDW; cd.dsum = scratch + y.dsum + sp * kDW;
         }
-        hipError_t e = launch_for_posterior(dt_person_fwd_kernel, dt_person_fwd_cond_kernel, y.gp, kDThreads, s, a, y.cond ? &cd : nullptr);
-        if (e != hipSuccess) return (int)e;
+        if (const int rc = hip_rc(launch_for_posterior(dt_person_fwd_kernel, dt_person_fwd_cond_kernel, y.gp, kDThreads, s, a, y.cond ? &cd : nullptr),
+                                  "vibo_dtrain_forward_backward: person forward launch")) return rc;
         vibo_decoder_desc dd;
         memset(&dd, 0, sizeof(dd));
         dd.num_person = nb; dd.num_item = y.I; dd.hidden_dim = kDW; dd.want_grad = 1; dd.person_chunks = y.dc;
@@ -1041,14 +1040,13 @@ static int dt_forward_backward(const int post, const vibo_desc* d, int decoder, 
             scratch + y.dV, y.has_l ? scratch + y.dL + sp * y.I : nullptr, y.has_g ? scratch + y.dguess + (size_t)c * y.dc * y.I : nullptr,
             scratch + y.dW2 + cw * kDW * kDW, scratch + y.dvec + cw * 4 * kDW, nullptr, stream);
         if (drc) return drc;
-        e = launch_for_posterior(dt_person_bwd_kernel, dt_person_bwd_cond_kernel, y.gp, kDThreads, s, a, y.cond ? &cd : nullptr);
-        if (e != hipSuccess) return (int)e;
+        if (const int rc = hip_rc(launch_for_posterior(dt_person_bwd_kernel, dt_person_bwd_cond_kernel, y.gp, kDThreads, s, a, y.cond ? &cd : nullptr),
+                                  "vibo_dtrain_forward_backward: person backward launch")) return rc;
         if (y.has_l) {
             const int per = (nb + y.ns - 1) / y.ns;
             hipLaunchKernelGGL(dt_ditem_kernel, dim3((unsigned)((y.I * y.D + 255) / 256), (unsigned)y.ns), dim3(256), 0, s, y.I, y.A, y.D, y.irt,
                                nb, per, (const float*)a.dL, (const float*)a.ability, scratch + y.drec_item + (size_t)c * y.ns * y.I * y.D);
-            e = hipGetLastError();
-            if (e != hipSuccess) return (int)e;
+            if (const int rc = launch_rc("vibo_dtrain_forward_backward: item gradient launch")) return rc;
         }
     }
     if (y.cond)                                       // d [lambda | s] of every person is complete: its transpose onto the table rows
@@ -1088,8 +1086,7 @@ static int dt_epilogue(const int post, const vibo_desc* d, int decoder, int hidd
         cd = dcond(y, p, params, item_feat, scratch);
         cd.beta = beta;
         hipLaunchKernelGGL(dt_table_bwd_kernel, dim3((unsigned)y.gt), dim3(kDThreads), 0, s, cd);
-        const hipError_t te = hipGetLastError();
-        if (te != hipSuccess) return (int)te;
+        if (const int rc = launch_rc("vibo_dtrain_epilogue: table backward launch")) return rc;
     }
     DReduce q;
     memset(&q, 0, sizeof(q));
@@ -1110,8 +1107,7 @@ static int dt_epilogue(const int post, const vibo_desc* d, int decoder, int hidd
     if (y.has_l) seg(y.drec_item, y.s_ditem, y.n_chunk * y.ns, (size_t)y.I * y.D, y.I * y.D);
     if (y.cond) seg(y.trec, y.s_enc, y.gt, p.enc, p.enc);
     hipLaunchKernelGGL(dt_reduce_kernel, dim3((unsigned)blk), dim3(1024), 0, s, q);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (const int rc = launch_rc("vibo_dtrain_epilogue: reduce launch")) return rc;
     if (y.mlp) {
         DItem it;
         memset(&it, 0, sizeof(it));
@@ -1120,8 +1116,7 @@ static int dt_epilogue(const int post, const vibo_desc* d, int decoder, int hidd
         it.s_dU = scratch + y.s_dU; it.da = scratch + y.ida; it.db = scratch + y.idb; it.gx = scratch + y.gx;
         it.rec = scratch + y.irec; it.rec_stride = r.itotal; it.r_fi = r.fi; it.r_wci = r.wci;
         hipLaunchKernelGGL(dt_item_bwd_kernel, dim3((unsigned)y.gi), dim3(kDThreads), 0, s, it);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
+        if (const int rc = launch_rc("vibo_dtrain_epilogue: item backward launch")) return rc;
     }
     DEpilogue a;
     memset(&a, 0, sizeof(a));
@@ -1135,8 +1130,8 @@ static int dt_epilogue(const int post, const vibo_desc* d, int decoder, int hidd
     a.step_count = step_count; a.P = params; a.M = adam_m; a.V = adam_v; a.mu = item_mu; a.lv = item_logvar; a.im = item_m; a.iv = item_v;
     a.loss = loss_out;
     const int item_blocks = (a.n_item_entries + kEpiThreads - 1) / kEpiThreads;
-    return (int)launch_for_posterior(dt_epilogue_kernel, dt_epilogue_cond_kernel, 1 + a.n_dec_blocks + item_blocks, kEpiThreads, s, a,
-                                     y.cond ? &cd : nullptr);
+    return hip_rc(launch_for_posterior(dt_epilogue_kernel, dt_epilogue_cond_kernel, 1 + a.n_dec_blocks + item_blocks, kEpiThreads, s, a,
+                                       y.cond ? &cd : nullptr), "vibo_dtrain_epilogue launch");
 }
 extern "C" int vibo_dtrain_epilogue(const vibo_desc* d, int decoder, int hidden_dim, int person_chunk, float* scratch,
                                     const float* eps_item, const float* item_feat, const float* beta, const float* lr,

@@ -12,6 +12,7 @@
 #include <stdint.h>
 #include "../../include/vibo_hip.h"
 #include "vibo_device.hpp"
+#include "vibo_host.hpp"
 
 namespace vibo {
 
@@ -149,7 +150,7 @@ extern "C" int vibo_flow_stack_forward(int n_rows, int dim, int n_flows, const f
     if (!z || !packed || !z_out || !ladj || !tanh_out) return -5;
     hipLaunchKernelGGL(flow_stack_fwd_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, z, packed, z_out, ladj,
                        tanh_out, n_rows, dim, n_flows);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_flow_stack_forward launch");
 }
 
 extern "C" int vibo_flow_stack_backward(int n_rows, int dim, int n_flows, const float* z_out, const float* packed,
@@ -160,5 +161,5 @@ extern "C" int vibo_flow_stack_backward(int n_rows, int dim, int n_flows, const 
     if (!z_out || !packed || !tanh_saved || !g_zout || !g_ladj || !g_z || !partials) return -5;
     hipLaunchKernelGGL(flow_stack_bwd_kernel, dim3((n_rows + 255) / 256), dim3(256), 0, (hipStream_t)stream, z_out, packed,
                        tanh_saved, g_zout, g_ladj, g_z, partials, n_rows, dim, n_flows);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_flow_stack_backward launch");
 }

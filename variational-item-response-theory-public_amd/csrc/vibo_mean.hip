@@ -18,6 +18,7 @@
 #include "../../include/vibo_hip.h"
 #include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
+#include "vibo_host.hpp"
 
 namespace vibo {
 
@@ -172,10 +173,7 @@ using namespace vibo;
 
 extern "C" int vibo_mean_encoder_partials(const vibo_desc* d) {
     if (!d || d->num_person < 1 || VIBO_MASK_IS_ELBO_ONLY(d->mask_dtype)) return 0;
-    int dev = 0, n = 0;
-    const int cus = (hipGetDevice(&dev) == hipSuccess &&
-                     hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0) ? n : 256;
-    long long waves = (long long)cus * 4 * 4;             // 4 workgroups of 4 waves per CU
+    long long waves = (long long)device_cus() * 4 * 4;             // 4 workgroups of 4 waves per CU
     const long long need = ((long long)d->num_person + 63) / 64;      // at least 64 persons per wave
     if (waves > need) waves = need;
     if (waves < 4) waves = 4;
@@ -198,11 +196,11 @@ extern "C" int vibo_mean_encoder_forward(const vibo_desc* d, int hidden, const i
             case 3: hipLaunchKernelGGL(mean_encoder_fwd_wave_kernel<3>, grid, block, 0, s, counts, u, v, w2, b2, posterior, B, hidden, A2); break;
             default: hipLaunchKernelGGL(mean_encoder_fwd_wave_kernel<4>, grid, block, 0, s, counts, u, v, w2, b2, posterior, B, hidden, A2); break;
         }
-        return (int)hipGetLastError();
+        return launch_rc("vibo_mean_encoder_forward launch");
     }
     hipLaunchKernelGGL(mean_encoder_fwd_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, counts, u, v, w2, b2, posterior, B,
                        hidden, A2);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_mean_encoder_forward launch");
 }
 
 static int mean_backward_launch(const vibo_desc* d, int hidden, const int32_t* counts, const float* u, const float* v, const float* w2,
@@ -223,7 +221,7 @@ static int mean_backward_launch(const vibo_desc* d, int hidden, const int32_t* c
         case 3: hipLaunchKernelGGL(mean_encoder_bwd_kernel<3>, grid, block, 0, s, counts, u, v, w2, grad_posterior, partials, B, hidden, A2, sets, beta); break;
         default: hipLaunchKernelGGL(mean_encoder_bwd_kernel<4>, grid, block, 0, s, counts, u, v, w2, grad_posterior, partials, B, hidden, A2, sets, beta); break;
     }
-    return (int)hipGetLastError();
+    return launch_rc("vibo_mean_encoder_backward launch");
 }
 
 extern "C" int vibo_mean_encoder_backward(const vibo_desc* d, int hidden, const int32_t* counts, const float* u, const float* v,

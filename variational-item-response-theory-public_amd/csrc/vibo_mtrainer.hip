@@ -19,6 +19,7 @@
 #include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
 #include "vibo_finalize.hpp"
+#include "vibo_host.hpp"
 #include "vibo_philox.hpp"
 #include "vibo_train_hook.hpp"
 
@@ -214,7 +215,7 @@ extern "C" int vibo_mtrain_prologue(const vibo_desc* d, int hidden_dim, const fl
                        2 * d->ability_dim, d->num_item, D, params, item_mu, item_logvar, (const float*)eps_item, item_feat, uv, saved,
                        kl_parts, step_count, draw_noise ? 1 : 0, (uint32_t)seed, (uint32_t)(seed >> 32), eps_item, eps_ability, n_ab,
                        ability_stream_id, item_blocks);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_mtrain_prologue launch");
 }
 
 extern "C" int vibo_mtrain_epilogue(const vibo_desc* d, int hidden_dim, const float* flat, const float* partials, int n_partials,
@@ -231,12 +232,11 @@ extern "C" int vibo_mtrain_epilogue(const vibo_desc* d, int hidden_dim, const fl
     const int n_out = 2 * H + A2 * H + A2;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(mt_reduce_kernel, dim3((n_out + 63) / 64), dim3(1024), 0, s, partials, grad_sums, n_partials, n_out);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return (int)e;
+    if (const int rc = launch_rc("vibo_mtrain_epilogue: reduce launch")) return rc;
     const int n = d->num_item * item_feat_dim(d->irt_model, d->ability_dim);
     const long long n_table = (long long)d->num_person * A2;       // floats per table-gradient set of the VIBO_POSTERIOR_GIVEN call
     hipLaunchKernelGGL(mt_epilogue_kernel, dim3(1 + (n + kMtThreads - 1) / kMtThreads), dim3(kMtThreads), 0, s, H, A2, n, flat, grad_sums,
                        saved, kl_parts, eps_item, beta, lr, step_count, n_table, params, adam_m, adam_v, item_mu, item_logvar, item_m, item_v,
                        loss_out);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_mtrain_epilogue launch");
 }

@@ -76,7 +76,7 @@ bool sign_rows_ok(const vibo_desc* d) {
 }
 
 bool given_tile_rows_ok(const vibo_desc* d) {
-    if (d->mask_dtype != VIBO_MASK_TILES || d->posterior != VIBO_POSTERIOR_GIVEN || d->n_flows != 0 || d->num_item < 4 || d->num_item > 1024)
+    if (d->mask_dtype != VIBO_MASK_TILES || d->posterior != VIBO_POSTERIOR_GIVEN || d->n_flows != 0 || d->num_item < 4 || d->num_item > kPanelItems)
         return false;
     Plan pl;
     return make_plan(d, 256, &pl) == 0 && pl.path == Path::Panels && pl.first == FirstPass::GivenDirect && pl.engine == Engine::Matrix;
@@ -137,19 +137,19 @@ static int choose_path(const vibo_desc* d, Path* path) {
     if (is_given && !row_split_shape(d, 32767))
         return fail(-8, "VIBO_POSTERIOR_GIVEN needs the row-split path: 4..32767 items, rows chunkable in 4 cells, no int64 mask");
     // panel mode (item counts up to 32767: the whole-row counts are packed as n_correct << 16 | n_observed in an
-    // int): one row-split launch per 1024 items (the backward is linear in d LL/d theta, so the panels
+    // int): one row-split launch per kPanelItems items (the backward is linear in d LL/d theta, so the panels
     // backpropagate their partial sums independently).  Unconditional posterior: a row-count pass supplies the
     // whole-row counts.  Conditional posterior (any item count): cond_pre_kernel supplies the product-of-experts
     // sums, cond_post_kernel scatters the table gradient (vibo_cond.hip).  The wave-per-person kernel remains
     // the fallback for unaligned rows (decided at launch).
-    if (row_split_shape(d, 32767) && (is_cond || is_given || I > 1024)) { *path = Path::Panels; return 0; }
+    if (row_split_shape(d, 32767) && (is_cond || is_given || I > kPanelItems)) { *path = Path::Panels; return 0; }
     // wave-per-person kernel: conditional posterior, > 1024 items; planar flows only when the row-split kernel
     // cannot take the launch (ragged / unaligned rows, int64 mask, < 192 items)
-    if (is_cond || I > 1024 || (d->n_flows > 0 && !row_split_shape(d, 1024))) { *path = Path::General; return 0; }
+    if (is_cond || I > kPanelItems || (d->n_flows > 0 && !row_split_shape(d, kPanelItems))) { *path = Path::General; return 0; }
     // row-split kernel (192 <= I <= 1024, u8 / no mask): nq waves share a row, 8 waves per CU.
     // Preferred over the wave-per-row kernel (1.03 vs 1.10 ms at A = 1, 1.03 vs 1.49 ms at A = 2 on 1M x 1k),
     // which stays for int64 masks.
-    if (row_split_shape(d, 1024)) { *path = Path::Split; return 0; }
+    if (row_split_shape(d, kPanelItems)) { *path = Path::Split; return 0; }
     *path = row_kernel_shape(d) ? Path::Row : Path::Tiled;
     return 0;
 }
@@ -259,11 +259,11 @@ static bool want_msplit(const vibo_desc* d) {
     // Conditional posterior at ability_dim 1 on fp32 rows: the matrix kernel also replaces the first pass there (its XM == 3), which
     // moves the break-even down (tools/calibrate_planner.py-style hipGraph replays, round 6: 8 192 x 1 000 49 vs 57 us, 16 384 x 1 000
     // 59 vs 72, 65 536 x 512 111 vs 165, 65 536 x 256 102 vs 148; 4 096 persons: 42 vs 45 at 1 000 items, 41 vs 40 at 768, 35 vs 31 at 256)
-    if (d->posterior == VIBO_POSTERIOR_CONDITIONAL && d->ability_dim == 1 && d->n_flows == 0 && d->num_item <= 1024 && d->num_item >= 256 &&
+    if (d->posterior == VIBO_POSTERIOR_CONDITIONAL && d->ability_dim == 1 && d->n_flows == 0 && d->num_item <= kPanelItems && d->num_item >= 256 &&
         d->mask_dtype != VIBO_MASK_CODES && d->mask_dtype != VIBO_MASK_I64 && !(d->flags & (VIBO_FLAG_COND_THREE_PASS | VIBO_FLAG_COND_VALU)) &&
         (!d->want_grad || emit_codes_wanted(d)))
         return d->num_person >= (d->num_item >= 896 ? 4096 : 8192);
-    const int width = d->num_item < 1024 ? d->num_item : 1024;
+    const int width = panel_span(d->num_item, 0).items;
     // (round 6, profiles/r06_planner_calibration.txt: the kernel's launch got ~9 us shorter -- 2 048 x 1 000 at ability_dim 8 19.4 vs 22.6 us,
     //  and the 385..512-item exclusion of round 3 -- "2 workgroups per CU with one batch each at 16 384 persons: 48 vs 42 us" -- now
     //  measures 18.2 vs 21.9 us at 4 096 persons, 36.4 vs 38.8 at 16 384: dropped)
@@ -375,7 +375,7 @@ static void plan_tiled(const vibo_desc* d, int num_cu, Plan* pl) {
                  + 2 * (size_t)(pl->AT + 1) * 65 * 4                   // [theta|valid] share, double-buffered
                  + (size_t)waves * 16 * 20 * 4                         // per-wave G-tile transpose slab
                  + 2 * kTilePersons * 4 + 4 * 2 * pl->AT * 4;          // counts, encoder-table constants
-    lds = (lds + 255) & ~(size_t)255;
+    lds = up256(lds);
     const size_t lds_cu = 160 * 1024;
     int per_cu = (int)(lds_cu / lds);
     const int wave_cap = 16 / waves;             // 4 waves per SIMD (launch bound) = 16 per CU
@@ -391,7 +391,7 @@ static void plan_tiled(const vibo_desc* d, int num_cu, Plan* pl) {
 
 static void plan_panel_grids(const vibo_desc* d, int num_cu, bool allow_msplit, Plan* pl) {
     const int I = d->num_item;
-    plan_row_split(d, num_cu, I < 1024 ? I : 1024, 4, allow_msplit, pl);
+    plan_row_split(d, num_cu, panel_span(I, 0).items, 4, allow_msplit, pl);
     if (pl->engine == Engine::Matrix && pl->panels > 1) {
         // all panels in ONE launch (ElboParams::panel_count): the chip's workgroup slots are shared out over the panels
         int per = num_cu / pl->panels;
@@ -400,7 +400,7 @@ static void plan_panel_grids(const vibo_desc* d, int num_cu, bool allow_msplit, 
     }
     pl->cond_nblk = clamp_grid(num_cu, 2, d->num_person, 8);      // (4 per CU for one ability dim was tried: the fp32-row variants spill 35-46 registers, 2x slower)
     pl->cond_post_nblk = pl->cond_nblk;
-    pl->cond_rec = 8 * d->ability_dim * 1024;
+    pl->cond_rec = 8 * d->ability_dim * kPanelItems;
 }
 // cond_post on cell codes (the caller's, or the ones cond_pre leaves behind) has no fp32 row registers: 3 waves per SIMD
 static void raise_cond_post_grid(const vibo_desc* d, int num_cu, Plan* pl) {
@@ -411,14 +411,16 @@ static void raise_cond_post_grid(const vibo_desc* d, int num_cu, Plan* pl) {
 // ---------------------------------------------------------------------------
 // stage 4: workspace layout
 // ---------------------------------------------------------------------------
+// the prepped item rows (the head of every workspace; the multi-sample forward keeps up to 4 of them)
+static size_t prepped_item_bytes(int I, int DP) { return up256((size_t)((I + 15) & ~15) * DP * 4); }
+
 static void layout_workspace(const vibo_desc* d, Plan* pl) {
-    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
     const int I = d->num_item, A = d->ability_dim;
     if (pl->path == Path::General) {
         pl->total_bytes = 256;            // 8 scalar accumulators
         return;
     }
-    size_t off = up((size_t)((I + 15) & ~15) * pl->DP * 4);      // the prepped item rows
+    size_t off = prepped_item_bytes(I, pl->DP);
     if (pl->path != Path::Panels) {
         // one launch: the records of whichever kernel the launch resolves to
         int max_blk = pl->nblk;
@@ -429,24 +431,24 @@ static void layout_workspace(const vibo_desc* d, Plan* pl) {
         return;
     }
     pl->off_cnt = off;
-    off += up((size_t)d->num_person * 4);
+    off += up256((size_t)d->num_person * 4);
     pl->off_partial = off;
-    off += up((size_t)pl->panels * pl->split_nblk * pl->lay.stride * 4);
+    off += up256((size_t)pl->panels * pl->split_nblk * pl->lay.stride * 4);
     pl->off_pre = pl->off_coef = pl->off_cpart = pl->off_crec = off;
     if (pl->conditional()) {
         pl->off_pre = off;
-        off += up((size_t)pl->panels * d->num_person * (2 * A + 1) * 4);
+        off += pre_block_bytes(pl->panels, d->num_person, A);
         pl->off_coef = off;
-        off += up((size_t)pl->panels * d->num_person * 4 * A * 4);
+        off += up256((size_t)pl->panels * d->num_person * 4 * A * 4);
         pl->off_cpart = off;
-        if (pl->first == FirstPass::CondMatrix || pl->tail == Tail::CondMatrix) off += up(cond_mfma_scratch_bytes(d->num_person, I, A));
+        if (pl->first == FirstPass::CondMatrix || pl->tail == Tail::CondMatrix) off += up256(cond_mfma_scratch_bytes(d->num_person, I, A));
         pl->off_crec = off;
-        if (pl->tail != Tail::CondMatrix) off += up((size_t)pl->panels * pl->cond_post_nblk * pl->cond_rec * 4);
+        if (pl->tail != Tail::CondMatrix) off += up256((size_t)pl->panels * pl->cond_post_nblk * pl->cond_rec * 4);
     } else if (pl->given()) {
         pl->off_pre = off;
-        off += up((size_t)d->num_person * (2 * A + 1) * 4);
+        off += pre_block_bytes(1, d->num_person, A);
         pl->off_coef = off;
-        off += up((size_t)pl->panels * d->num_person * 4 * A * 4);
+        off += up256((size_t)pl->panels * d->num_person * 4 * A * 4);
     }
     // fp32 rows of the conditional posterior (three passes, five at ability_dim > 4): cond_pre also writes the rows' 1-byte
     // cell codes, the later passes read those: 8 instead of 15 B/term of HBM traffic.  (For the two passes of the
@@ -455,7 +457,7 @@ static void layout_workspace(const vibo_desc* d, Plan* pl) {
     pl->codes_stride = ((long long)I + 255) / 256 * 256;      // whole 128-byte lines per wave store (4 B per lane x 64 lanes)
     if (pl->conditional() && rows_become_codes(d)) {
         pl->off_codes = off;
-        off += up((size_t)d->num_person * pl->codes_stride);
+        off += up256((size_t)d->num_person * pl->codes_stride);
     }
     pl->total_bytes = off + 256;
 }
@@ -471,9 +473,9 @@ int make_plan(const vibo_desc* d, int num_cu, Plan* pl, bool allow_msplit) {
     pl->DP = prepped_item_width(d->irt_model, pl->AT);
     pl->n_tiles = (d->num_person + kTilePersons - 1) / kTilePersons;
     pl->lds_stride = 16;
-    pl->lay = partial_layout(A, pl->D, pl->path == Path::Panels ? 1024 : I, d->n_flows);
+    pl->lay = partial_layout(A, pl->D, pl->path == Path::Panels ? kPanelItems : I, d->n_flows);
     if (pl->path == Path::Panels) {
-        pl->panels = (I + 1023) / 1024;
+        pl->panels = panel_count(I);
         plan_panel_grids(d, num_cu, allow_msplit, pl);
         if (d->posterior == VIBO_POSTERIOR_CONDITIONAL) {
             choose_cond_passes(d, pl);
@@ -510,7 +512,7 @@ int multi_plan(const vibo_desc* d, int num_cu, vibo_desc* d0, Plan* pl, size_t* 
     if (d->posterior == VIBO_POSTERIOR_GIVEN && !given_call)
         return fail(-8, "multi-sample forward: caller-supplied posterior (use vibo_elbo_multi_forward_given)");
     if (!pl->row_split()) return fail(-8, "multi-sample forward: shape is not on the row-split path");
-    *prep_bytes = ((size_t)((d->num_item + 15) & ~15) * pl->DP * 4 + 255) & ~(size_t)255;
+    *prep_bytes = prepped_item_bytes(d->num_item, pl->DP);
     return 0;
 }
 
@@ -525,7 +527,7 @@ size_t encode_scratch_bytes(const vibo_desc* d) {
     if (A > VIBO_MAX_ABILITY_DIM) return 0;      // (wave-per-person encode kernel)
     if (!row_split_shape(d, 32767)) return 0;
     if (d->posterior == VIBO_POSTERIOR_CONDITIONAL) {
-        size_t pre = ((size_t)((I + 1023) / 1024) * d->num_person * (2 * A + 1) * 4 + 255) & ~(size_t)255;
+        size_t pre = pre_block_bytes(panel_count(I), d->num_person, A);
         if (encode_on_matrix_pipe(d)) pre += cond_mfma_scratch_bytes(d->num_person, I, A);      // (only its table image is used)
         return pre + 256;
     }

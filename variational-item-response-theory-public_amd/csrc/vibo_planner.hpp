@@ -1,18 +1,16 @@
 // vibo_planner.hpp -- descriptor checks and the launch plan of an ELBO call (vibo_planner.hip).  Host-only code: it reads the
 // descriptor and the number of compute units, launches nothing and keeps no state but the calling thread's last error string.
+// The facts it shares with the dispatch -- the panel split, 256-byte rounding, the error string -- are in vibo_host.hpp.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
 
 #include "../../include/vibo_hip.h"
+#include "vibo_host.hpp"
 #include "vibo_launch.hpp"
 #include "vibo_params.hpp"
 
 namespace vibo {
-
-// the calling thread's last error (vibo_last_error_string); fail() formats it and returns `code`
-int fail(int code, const char* fmt, ...);
-const char* last_error();
 
 // sign_rows: the entry point takes VIBO_MASK_SIGN rows (include/vibo_hip_sign_rows.h) and VIBO_MASK_TILES images
 // (include/vibo_hip_tile_rows.h) where sign_rows_ok says so; every other one
@@ -42,7 +40,7 @@ bool rows_vec_ok(const vibo_desc* d, const float* response, const void* mask);
 // plan, the refusals and the dispatch of vibo_elbo_fwd_bwd -- reads these.
 enum class Path {
     General,      // wave-per-person kernel (ability_dim 9..16; conditional posterior / flows / > 1024 items on rows no row-split kernel takes)
-    Panels,       // a first pass, one row-split launch per panel of 1024 items, a gradient tail
+    Panels,       // a first pass, one row-split launch per panel of kPanelItems items, a gradient tail
     Split,        // one row-split launch (4..1024 items, unconditional posterior)
     Row,          // wave-per-row register kernel (int64 masks)
     Tiled         // tiled kernel
@@ -73,7 +71,7 @@ struct Plan {
     int split_nq, split_nblk; // Panels / Split: waves per workgroup (VALU kernel), grid (per panel)
     int cond_nblk;            // workgroups of the conditional posterior's cond_pre launches (2 per CU)
     int cond_post_nblk;       // ... of cond_post: 3 per CU when it reads cell codes at template width <= 2 (its launch bound there)
-    int panels;               // Panels: ceil(num_item / 1024)
+    int panels;               // Panels: panel_count(num_item)
     int cond_rec;             // floats per cond_post workgroup record
     int AT, D, DP, n_tiles, nblk, lds_stride, lds_main;
     LaunchGeom geom;          // Tiled (and the fallback of Split / Row for unaligned rows)
@@ -112,6 +110,9 @@ StepContract step_contract(const vibo_desc* d, const Plan& pl, bool rows_gathere
 // given_call: vibo_elbo_multi_forward_given (VIBO_POSTERIOR_GIVEN descriptors only; the plain call refuses those)
 int multi_plan(const vibo_desc* d, int num_cu, vibo_desc* d0, Plan* pl, size_t* prep_bytes, bool given_call = false);
 
+// bytes of `panels` blocks of per-person row statistics (2A sums + the observed count): the conditional posterior's `pre` block of an
+// ELBO plan, and the head of the encode path's scratch (the matrix-pipe pass's own scratch lies right behind it)
+inline size_t pre_block_bytes(int panels, long long persons, int A) { return up256((size_t)panels * persons * (2 * A + 1) * 4); }
 bool encode_on_matrix_pipe(const vibo_desc* d);
 // scratch the fast encode path needs (0: not applicable -> wave-per-person encode_kernel)
 size_t encode_scratch_bytes(const vibo_desc* d);

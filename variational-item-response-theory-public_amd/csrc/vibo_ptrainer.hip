@@ -21,6 +21,7 @@
 #include "../../include/vibo_hip_tile_rows.h"
 #include "../../include/vibo_hip_person_tables.h"
 #include "vibo_device.hpp"
+#include "vibo_host.hpp"
 #include "vibo_params.hpp"
 #include "vibo_philox.hpp"
 #include "vibo_train_hook.hpp"
@@ -304,7 +305,7 @@ extern "C" int vibo_ptrain_prologue(const vibo_desc* d, int mode, int64_t table_
     const long long ab_blocks = ((q.n_ab + 3) / 4 + kPtThreads - 1) / kPtThreads;
     hipLaunchKernelGGL(pt_prologue_kernel, dim3((unsigned)(1 + q.n_item_blocks + q.n_gather_blocks + ab_blocks)), dim3(kPtThreads), 0,
                        (hipStream_t)stream, q);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_ptrain_prologue launch");
 }
 
 extern "C" int vibo_ptrain_epilogue(const vibo_desc* d, int mode, int64_t table_rows, const float* flat, const int64_t* index,
@@ -329,11 +330,10 @@ extern "C" int vibo_ptrain_epilogue(const vibo_desc* d, int mode, int64_t table_
     e.flat = flat; e.kl_parts = kl_parts; e.eps_item = eps_item; e.beta = beta; e.lr = lr;
     e.step_count = step_count;
     e.item_mu = item_mu; e.item_lv = item_logvar; e.im = item_m; e.iv = item_v; e.loss_out = loss_out;
-    hipError_t err = launch_epilogue(e, d->ability_dim, s);
-    if (err != hipSuccess) return (int)err;
+    if (const int rc = hip_rc(launch_epilogue(e, d->ability_dim, s), "vibo_ptrain_epilogue launch")) return rc;
     hipLaunchKernelGGL(pt_reset_kernel, dim3((d->num_person + kPtThreads - 1) / kPtThreads), dim3(kPtThreads), 0, s, index, d->num_person,
                        (long long)table_rows, slot);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_ptrain_epilogue: slot reset launch");
 }
 
 extern "C" int vibo_person_table_adam(const vibo_desc* d, int mode, int64_t table_rows, const int64_t* index, const float* grad_rows,
@@ -348,15 +348,13 @@ extern "C" int vibo_person_table_adam(const vibo_desc* d, int mode, int64_t tabl
     hipStream_t s = (hipStream_t)stream;
     const dim3 pos_blocks((d->num_person + kPtThreads - 1) / kPtThreads);
     hipLaunchKernelGGL(pt_claim_kernel, pos_blocks, dim3(kPtThreads), 0, s, index, d->num_person, (long long)table_rows, slot, bad_count);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) return (int)err;
+    if (const int rc = launch_rc("vibo_person_table_adam: slot claim launch")) return rc;
     PtEpilogue e = {};
     e.u = make_update(d, mode, table_rows, index, grad_rows, table_a, table_b, person_m, person_v, moment_stride, slot);
     e.head = 0;
     e.beta = beta; e.lr = lr;
     e.step_count = const_cast<int32_t*>(step_count);      // (head == 0: only read)
-    err = launch_epilogue(e, d->ability_dim, s);
-    if (err != hipSuccess) return (int)err;
+    if (const int rc = hip_rc(launch_epilogue(e, d->ability_dim, s), "vibo_person_table_adam launch")) return rc;
     hipLaunchKernelGGL(pt_reset_kernel, pos_blocks, dim3(kPtThreads), 0, s, index, d->num_person, (long long)table_rows, slot);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_person_table_adam: slot reset launch");
 }

@@ -7,6 +7,7 @@
 #include "../../include/vibo_hip_tile_rows.h"
 #include "vibo_device.hpp"
 #include "vibo_finalize.hpp"
+#include "vibo_host.hpp"
 #include "vibo_philox.hpp"
 #include "vibo_train_hook.hpp"
 
@@ -266,7 +267,7 @@ extern "C" int vibo_fill_normal(float* out, int64_t n, uint64_t seed, const int3
     const long long groups = (n + 3) / 4;
     hipLaunchKernelGGL(fill_normal_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, (hipStream_t)stream, out,
                        (long long)n, (uint32_t)seed, (uint32_t)(seed >> 32), step_count, stream_id);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_fill_normal launch");
 }
 
 // what the train-step entry points of this file take (they return -6 otherwise): the plain model, encoder width <= kMaxHidden
@@ -289,7 +290,7 @@ static int launch_prologue(const vibo_desc* d, int hidden_dim, const float* mlp_
     hipLaunchKernelGGL(train_prologue_kernel, dim3((unsigned)(1 + item_blocks + ab_blocks)), dim3(256), 0, (hipStream_t)stream, hidden_dim,
                        2 * d->ability_dim, d->num_item, D, mlp_params, item_mu, item_logvar, eps_item, item_feat, table, saved_h, kl_parts,
                        step_count, tick, gen, (uint32_t)seed, (uint32_t)(seed >> 32), eps_w, eps_ability, n_ab, ab_stream, item_blocks);
-    return (int)hipGetLastError();
+    return launch_rc("train prologue launch");
 }
 
 extern "C" int vibo_train_prologue(const vibo_desc* d, int hidden_dim, const float* mlp_params, const float* item_mu,
@@ -330,5 +331,5 @@ extern "C" int vibo_train_epilogue(const vibo_desc* d, int hidden_dim, const flo
     hipLaunchKernelGGL(train_epilogue_kernel, dim3(1 + (n + kEpiThreads - 1) / kEpiThreads), dim3(kEpiThreads), 0, (hipStream_t)stream,
                        hidden_dim, 2 * d->ability_dim, n, parts, flat, saved_h, kl_parts, eps_item, beta, lr, step_count, mlp_params, mlp_m, mlp_v, item_mu,
                        item_logvar, item_m, item_v, loss_out);
-    return (int)hipGetLastError();
+    return launch_rc("vibo_train_epilogue launch");
 }
