@@ -101,11 +101,15 @@ constexpr int kMsNoiseBytes = kMsRows * 8 * (int)sizeof(float);
 // writes, twice -- by batch parity -- in one block where the noise block otherwise sits (with or without the caller's noise).  The
 // single-buffered members of the records above (thA, thT, cnt) are not used by these instantiations.
 struct alignas(16) MsPipeLds {
-    _Float16 thA[2][2][kMsRows][8];   // [batch parity] as MsCommonLds::thA
+    _Float16 thA[2][3][kMsRows][8];   // [batch parity] as MsCommonLds::thA; plane 2 = the constant `ones` rows of the logit MFMA's A
+                                      // operand (lanes g == 3), written once in the prologue: read_theta_ops selects nothing
     _Float16 thT[2][16][kMsRows];     // [batch parity] as MsCommonLds::thT
     int cnt[2][8][kMsRows];           // [batch parity][wave] as MsWaveLds::cnt, written two batches ahead
     float nz[2][kMsRows * 8];         // [batch parity] the drawn noise, two batches ahead
 };
+// the registers that take the place of MsCommonLds::tacc and ::st of the wave's slot on the one-barrier loop
+template <bool ON> struct MsChainRegs { float sum[12] = {}, st[5] = {}; };
+template <> struct MsChainRegs<false> {};
 inline size_t msplit_lds_bytes(int nw, bool flows = false, bool guess = false, bool fuse = false) {
     return sizeof(MsCommonLds) + (size_t)nw * sizeof(MsWaveLds) + (flows ? sizeof(MsFlowLds) : 0) +
            (guess ? (size_t)nw * kMsGuessFloats * sizeof(float) : 0) + (fuse ? (size_t)nw * kMsFuseFloats * sizeof(float) : 0);
@@ -135,6 +139,13 @@ __device__ __forceinline__ f32x4 mfma16(const half8 a, const half8 b, const f32x
 }
 __device__ __forceinline__ half4v lds_tr16(const _Float16* p) {
     return __builtin_bit_cast(half4v, __builtin_amdgcn_ds_read_tr16_b64_v4i16((short4v __attribute__((address_space(3)))*)p));
+}
+// an LDS word by its 32-bit address (held in a register across the batch loop), and the address of one
+template <typename T> __device__ __forceinline__ uint32_t lds_addr(const T* p) {
+    return (uint32_t)(uintptr_t)(const T __attribute__((address_space(3)))*)p;
+}
+template <typename T> __device__ __forceinline__ T* lds_at(const uint32_t a) {
+    return (T*)(T __attribute__((address_space(3)))*)(uintptr_t)a;
 }
 __device__ __forceinline__ half8 cat8(const half4v a, const half4v b) {
     return half8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
@@ -398,7 +409,28 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     constexpr bool kDraw = ms_draws_noise(XM, FLOWS, GRAD);
     const bool draw = kDraw && p.eps == nullptr;      // (wave-uniform) the kernel draws the noise: see draw_eps
     float epn = 0.f;                                  // eps of this wave's slot of the next batch (4 or more waves), loaded a batch ahead
+    // One-barrier loop: a wave's slot never changes -- wave q owns slot q & 3 of the batches of parity q >> 2 -- so the (person, dim)
+    // chains take both as launch constants (every LDS address of theirs is then a per-lane constant, formed once in front of the
+    // loop), and the wave-uniform launch constants they test sit in ONE scalar mask instead of a register (or a spill lane) each.
+    const int own = q >> 2, osl = q & 3;
+    constexpr uint32_t kCmDraw = 1u, kCmMu = 2u, kCmSample = 4u, kCmRegSampled = 8u;
+    uint32_t cm = 0u;
+    if constexpr (OB) {
+        cm = (draw ? kCmDraw : 0u) | ((!kDraw || p.ability_mu) ? kCmMu : 0u) |
+             ((!ms_sample_optional(XM, FLOWS, GRAD, RM, NW8) || p.ability) ? kCmSample : 0u) | (p.reg_mode != 0 ? kCmRegSampled : 0u);
+        cm = (uint32_t)__builtin_amdgcn_readfirstlane((int)cm);
+        asm volatile("" : "+s"(cm));                  // (opaque: not taken apart into its conditions again)
+    }
+    // the running sums of the wave's slot (cl.tacc's twelve terms) and the forward state its backward reads two iterations later
+    // (cl.st's five values) stay in registers on the one-barrier loop: one owner lane per address, the adds in the same order; the
+    // sums go to cl.tacc once, in front of the end code
+    MsChainRegs<OB> cr;                              // (an empty record in every other instantiation)
     auto fetch_eps = [&](const int bt, const int par) __attribute__((always_inline)) {
+        if constexpr (OB) {
+            asm volatile("" : "+s"(cm));              // (as in forward_slot)
+            if (cm & kCmDraw) return;                 // (drawn: nothing to ask for)
+            asm volatile("");                         // (a test of its own: not merged with the batch bound's)
+        }
         if ((!NW8 && nw < 4) || bt >= n_batches) return;
         int s0, s1, step;
         my_slots(par, s0, s1, step);
@@ -442,6 +474,25 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     int nz_wave = 0;
     // (one-barrier loop: the parity-indexed block takes the noise block's place; `par` = parity of batch bt, unused otherwise)
     MsPipeLds& pl = *reinterpret_cast<MsPipeLds*>(nz);
+    // One-barrier loop: what the (person, dim) chains address in LDS, once per launch -- the LDS addresses of the lane's
+    // words of the wave's own slot, each behind an empty asm (MachineSink, see the Makefile, otherwise re-forms them from the lane
+    // number in every batch); everything else is an immediate offset from these.
+    int c_pp = 0;
+    uint32_t a_cnt = 0, a_nz = 0, a_thA = 0, a_thT = 0, a_gth = 0, a_ctab = 0;
+    if constexpr (OB) {
+        c_pp = (64 * osl + lane) >> 3;                                      // the lane's person of the batch
+        const int slot = 8 * ((c_pp & 15) >> 2) + 4 * (c_pp >> 4) + (c_pp & 3);
+        a_cnt = lds_addr(&pl.cnt[own][0][c_pp]);
+        a_nz = lds_addr(&pl.nz[own][0] + (c_pp * A + ed));
+        a_thA = lds_addr(&pl.thA[own][0][c_pp][ed]);
+        a_thT = lds_addr(&pl.thT[own][ed][slot]);
+        a_gth = lds_addr(&wls[0].gth[own][c_pp][ed]);
+        a_ctab = lds_addr(&cl.ctab[ed]);
+        asm volatile("" : "+v"(c_pp), "+v"(a_cnt), "+v"(a_nz), "+v"(a_thA), "+v"(a_thT), "+v"(a_gth), "+v"(a_ctab));
+    }
+    // entry k of the expert-table constants of the lane's dim
+    // (macros, here and MS_PAIR_ADD below, not lambdas: the other instantiations keep their statements -- and their code -- as they were)
+#define MS_CTAB(k) (OB ? lds_at<const float>(a_ctab)[(k) * 8] : cl.ctab[(k) * 8 + ed])
     auto draw_eps = [&](const int bt, const int par = 0) __attribute__((always_inline)) {
         if constexpr (kDraw) {
             if (draw) {
@@ -457,12 +508,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // eps of slot s of batch bt: drawn (LDS) or loaded (e0)
     auto slot_eps = [&](const int bt, const int par, const int s, const float e0) __attribute__((always_inline)) {
         if constexpr (kDraw) {
-            if (draw) {
+            if (OB ? (cm & kCmDraw) != 0 : draw) {
                 const int r = (64 * s + lane) >> 3;
                 float v;
-                if constexpr (OB) v = pl.nz[par][r * A + ed];
+                if constexpr (OB) v = *lds_at<const float>(a_nz);
                 else v = nz[r * A + ed];
-                return (ed < A && bt * R + r < p.B) ? v : 0.f;
+                return (ed < A && bt * R + (OB ? c_pp : r) < p.B) ? v : 0.f;
             }
         }
         return e0;
@@ -747,10 +798,16 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         }
     f32x4 acc_gt[2];                    // d LL/d theta of the batch: [16 persons of M-tile][a_hi cols | a_lo cols]
     acc_gt[0] = acc_gt[1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int k = tid; k < 2 * 12 * 256; k += (int)blockDim.x) (&cl.tacc[0][0][0])[k] = 0.f;
+    if constexpr (!OB)       // (one-barrier loop: the sums live in registers and are stored once, behind the loop)
+        for (int k = tid; k < 2 * 12 * 256; k += (int)blockDim.x) (&cl.tacc[0][0][0])[k] = 0.f;
     float s_log = 0.f;
     int unobs = 0;
     bool sat3 = false;                  // 3PL: this wave met a probability past the clamp in this batch (wave-uniform: see the tile)
+    if constexpr (OB) {          // the `ones` rows of both parities (see read_theta_ops)
+        if (tid < 2 * R)
+            *reinterpret_cast<half8*>(&pl.thA[tid >> 5][2][tid & 31][0]) =
+                half8{one_b, one_b, one_b, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
+    }
     MS_P(20, t_entry)                                 // operand image written
     __syncthreads();
     MS_P(21, t_entry)
@@ -758,6 +815,14 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // LDS image offsets (halfs): producer row 16 t + i16, piece g; consumer rows 32 kt + 4 g + (i16 >> 2) (+ 16), piece i16 & 3
     const int wofs = 16 * i16 + 4 * (g ^ (i16 >> 2));
     const int rofs = 64 * g + 16 * (i16 >> 2) + 4 * ((i16 & 3) ^ g);
+
+    // (tile rows: the K-tile reads' two bases as LDS addresses behind an empty asm -- not re-formed from the lane number in every batch)
+    uint32_t a_ktr = 0, a_kim = 0;
+    if constexpr (TILES) {
+        a_ktr = lds_addr(&wl.tr[0][0][0] + rofs);
+        a_kim = lds_addr(&wl.img[0][0] + b3ofs);
+        asm volatile("" : "+v"(a_ktr), "+v"(a_kim));
+    }
 
     // pack a quarter: the code words of person 4 h + j for both u-steps and its counts
     const uint32_t tm_tail = (I & 3) ? ((1u << (8 * (I & 3))) - 1u) : 0xFFFFFFFFu;
@@ -937,11 +1002,20 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     //  eps -- prs -- and the plain variant serves them: the conditional posterior's matrix pass runs on emitted codes)
     // prior experts of the missing cells (models.py:613-620): weight 1 / (1 + eps) each, or dropped
     const float prior_w = p.missing_mode == 0 ? 1.0f / (1.0f + kPoeEps) : 0.f;
-    auto forward_slot = [&](auto extc, const int bt, const int par, const int s, const float eps_c) {
+    // running sum k of pair e: the owner lane's register on the one-barrier loop, else its LDS word
+#define MS_PAIR_ADD(k, v) do { if constexpr (OB) cr.sum[k] += (v); else lds_add(&cl.tacc[par][k][e], (v)); } while (0)
+    // c + a b, c - a b, a b - c.  The two launches of a matrix -- on its rows and on its image -- agree bit for bit, so the one-barrier
+    // loop states the fused forms hipcc picks for these sums everywhere else (one v_fma each); with the running sums in registers its
+    // vectoriser pairs the products differently and would leave some of them unfused.  The other instantiations keep the plain text.
+#define MS_ADDMUL(c, a, b) (OB ? fmaf((a), (b), (c)) : (c) + (a) * (b))
+#define MS_SUBMUL(c, a, b) (OB ? fmaf(-(a), (b), (c)) : (c) - (a) * (b))
+#define MS_MULSUB(a, b, c) (OB ? fmaf((a), (b), -(c)) : (a) * (b) - (c))
+    auto forward_slot =[&](auto extc, const int bt, const int par, const int s, const float eps_c) {
         constexpr bool EXT = decltype(extc)::value;
+        if constexpr (OB) asm volatile("" : "+s"(cm));      // (tested here, bit by bit: not hoisted into a condition register each)
         static_assert(EXTRA || !EXT, "the global-memory variant belongs to the EXTRA instantiations");
         const int row0 = bt * R;
-        const int e = 64 * s + lane, pp = e >> 3;
+        const int e = 64 * s + lane, pp = OB ? c_pp : e >> 3;
         const bool live = ed < A && (row0 + pp) < p.B;
         int cnt = 0;
         bool have_cnt = false;
@@ -960,7 +1034,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         if (!have_cnt) {
             if constexpr (OB) {
 #pragma unroll
-                for (int w = 0; w < 8; ++w) cnt += pl.cnt[par][w][pp];
+                for (int w = 0; w < 8; ++w) cnt += lds_at<const int>(a_cnt)[w * R];
             } else if constexpr (NW8) {
                 int ppo = pp;
                 if constexpr (kPinFlowAddr) asm volatile("" : "+v"(ppo));     // (see backward_slot)
@@ -974,8 +1048,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         const float n1 = (float)(cnt >> 16);
         float nobs = (float)(cnt & 0xffff);
         const float n0 = nobs - n1;
-        const float tau0 = cl.ctab[(0 * 2 + 0) * 8 + ed], tau1 = cl.ctab[(0 * 2 + 1) * 8 + ed];
-        const float mt0 = cl.ctab[(1 * 2 + 0) * 8 + ed], mt1 = cl.ctab[(1 * 2 + 1) * 8 + ed];
+        const float tau0 = MS_CTAB(0 * 2 + 0), tau1 = MS_CTAB(0 * 2 + 1);
+        const float mt0 = MS_CTAB(1 * 2 + 0), mt1 = MS_CTAB(1 * 2 + 1);
         // (written as one fma each: the contraction hipcc picks for a sum of two products depends on the surrounding code,
         //  and the variants of this kernel have to agree bit for bit)
         float lam = fmaf(n0, tau0, n1 * tau1), smu = fmaf(n0, mt0, n1 * mt1);
@@ -1025,7 +1099,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         const float inv_lam = 1.0f / lam;
         const float amu = smu * inv_lam;
         const float sig = fast_rsq(lam);
-        const float th0 = live ? amu + sig * eps_c : 0.f;
+        const float th0 = live ? MS_ADDMUL(amu, sig, eps_c) : 0.f;
         float thv = th0;
         float ladj = 0.f;
         if constexpr (FLOWS) {              // z <- z + uhat tanh(w.z + b)
@@ -1051,18 +1125,28 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         const float ths = thv * sc_t;                   // operands carry theta 2^-jsh (see the operand image)
         if (live && primary) {
             const long long o = (long long)(row0 + pp) * A + ed;
+            // (one-barrier loop: the stores' row goes through an empty asm inside the branch that stores -- the 64-bit addresses are
+            //  formed there, not speculated in front of a branch the folded step never takes)
+            auto out_at = [&]() __attribute__((always_inline)) {
+                if constexpr (OB) {
+                    int orow = row0 + pp;
+                    asm volatile("" : "+v"(orow));
+                    return (long long)orow * A + ed;
+                } else return o;
+            };
             const float alv = -kLn2 * fast_log2(lam);
             // (non-temporal: 96 MB of per-person outputs per 1M x 8 launch that nothing on the device reads back soon -- kept out
             //  of the L2 the row loads share their segment-edge lines through: -0.9 % on the headline call)
-            if (!kDraw || p.ability_mu) {           // (the folded train step passes none: nothing reads them)
-                __builtin_nontemporal_store(amu, p.ability_mu + o);
-                __builtin_nontemporal_store(alv, p.ability_logvar + o);
+            if (OB ? (cm & kCmMu) != 0 : (!kDraw || p.ability_mu)) {           // (the folded train step passes none: nothing reads them)
+                const long long oa = out_at();
+                __builtin_nontemporal_store(amu, p.ability_mu + oa);
+                __builtin_nontemporal_store(alv, p.ability_logvar + oa);
             }
             // (... nor a sample where it draws its own noise: 32 MB per 1M x 8 launch, rebuilt on demand from the same table and
             //  draws.  Gathered fp32 rows at fewer than 8 waves always store: with the branch that instantiation ran 1.5-4 % slower,
             //  profiles/r12_lazy_sample.txt; the host refuses the NULL there)
             constexpr bool kSampleOptional = ms_sample_optional(XM, FLOWS, GRAD, RM, NW8);
-            if (!kSampleOptional || p.ability) __builtin_nontemporal_store(th0, p.ability + o);
+            if (OB ? (cm & kCmSample) != 0 : (!kSampleOptional || p.ability)) __builtin_nontemporal_store(th0, p.ability + out_at());
             if constexpr (FLOWS) {
                 p.ability_k[o] = thv;
                 if (ed == 0) {
@@ -1072,13 +1156,17 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             }
             // a sample beyond the f16 range (or NaN): the regulariser sum -- and with it the loss -- becomes NaN.  (A NaN logit
             // alone would not do: the clamp's v_med3 returns a finite bound for it.)
-            const float kl_term = -0.5f * (1.0f + alv - amu * amu - inv_lam);
-            lds_add(&cl.tacc[par][8][e], fabsf(ths) <= 65504.f ? kl_term : __builtin_nanf(""));
-            lds_add(&cl.tacc[par][9][e], -0.5f * kLog2Pi - 0.5f * alv - 0.5f * eps_c * eps_c);
-            lds_add(&cl.tacc[par][10][e], -0.5f * kLog2Pi - 0.5f * thv * thv);
-            if (ed == 0) lds_add(&cl.tacc[par][11][e], nobs);
+            const float kl_term = -0.5f * (MS_SUBMUL(1.0f + alv, amu, amu) - inv_lam);
+            MS_PAIR_ADD(8, fabsf(ths) <= 65504.f ? kl_term : __builtin_nanf(""));
+            MS_PAIR_ADD(9, MS_SUBMUL(MS_SUBMUL(-0.5f * kLog2Pi, 0.5f, alv), 0.5f * eps_c, eps_c));
+            MS_PAIR_ADD(10, MS_SUBMUL(-0.5f * kLog2Pi, 0.5f * thv, thv));
+            // (in a register every lane keeps the sum: the flush stores the lanes of dim 0 and zeros)
+            if (OB || ed == 0) MS_PAIR_ADD(11, nobs);
         }
-        if constexpr (GRAD) {
+        if constexpr (GRAD && OB) {
+            cr.st[0] = amu; cr.st[1] = sig; cr.st[2] = inv_lam; cr.st[3] = eps_c;
+            cr.st[4] = __builtin_bit_cast(float, cnt);
+        } else if constexpr (GRAD) {
             cl.st[par][0][e] = amu; cl.st[par][1][e] = sig; cl.st[par][2][e] = inv_lam; cl.st[par][3][e] = eps_c;
             cl.st[par][4][e] = __builtin_bit_cast(float, cnt);
         }
@@ -1086,10 +1174,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         split16(ths, hi, lo);
         const int slot = 8 * ((pp & 15) >> 2) + 4 * (pp >> 4) + (pp & 3);
         if constexpr (OB) {
-            pl.thA[par][0][pp][ed] = hi;
-            pl.thA[par][1][pp][ed] = lo;
-            pl.thT[par][ed][slot] = hi;
-            pl.thT[par][8 + ed][slot] = lo;
+            _Float16* const ta = lds_at<_Float16>(a_thA);
+            _Float16* const tt = lds_at<_Float16>(a_thT);
+            ta[0] = hi;
+            ta[R * 8] = lo;
+            tt[0] = hi;
+            tt[8 * R] = lo;
         } else {
             cl.thA[0][pp][ed] = hi;
             cl.thA[1][pp][ed] = lo;
@@ -1101,10 +1191,14 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // go to the wave's LDS record (fixed order: bitwise reproducible)
     auto backward_slot = [&](const int bt, const int par, const int s) {
         const int row0 = bt * R;
-        const int e = 64 * s + lane, pp = e >> 3;
+        const int e = 64 * s + lane, pp = OB ? c_pp : e >> 3;
         const bool live = ed < A && (row0 + pp) < p.B;
         float g0 = 0.f;
-        if constexpr (NW8) {
+        if constexpr (OB) {
+            const float* const g8 = lds_at<const float>(a_gth);
+#pragma unroll
+            for (int w = 0; w < 8; ++w) g0 += g8[w * (int)(sizeof(MsWaveLds) / sizeof(float))];
+        } else if constexpr (NW8) {
             // (flows: the element index behind an opaque copy -- the eight record addresses are then formed here from one base
             //  and immediate offsets; left to itself the compiler keeps eight loop-invariant addresses in registers for the
             //  whole batch loop, which the flow instantiations, already at the 256-register budget, pay for in spills)
@@ -1118,14 +1212,20 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             for (int w = 0; w < nw; ++w) g0 += wls[w].gth[par][pp][ed];
         }
         float gz0 = live ? g0 * (kLn2 * sc_t) : 0.f;          // (log2 units -> nats; sum g a' = 2^jsh sum g a)
-        const float amu = cl.st[par][0][e], sig = cl.st[par][1][e], inv_lam = cl.st[par][2][e], eps_c = cl.st[par][3][e];
-        const int cnt = __builtin_bit_cast(int, cl.st[par][4][e]);
+        // (the forward's kept state: its registers on the one-barrier loop)
+        auto kept = [&](const int i) __attribute__((always_inline)) {
+            if constexpr (OB) return cr.st[i];
+            else return cl.st[par][i][e];
+        };
+        const float amu = kept(0), sig = kept(1), inv_lam = kept(2), eps_c = kept(3);
+        const int cnt = __builtin_bit_cast(int, kept(4));
         const float n1 = (float)(cnt >> 16), n0 = (float)(cnt & 0xffff) - n1;
-        float thv = live ? amu + sig * eps_c : 0.f;
+        float thv = live ? MS_ADDMUL(amu, sig, eps_c) : 0.f;
         const bool reg_on = live && primary;
+        if constexpr (OB) asm volatile("" : "+s"(cm));      // (as in forward_slot)
         float gz1 = 0.f;
         if constexpr (!FLOWS) {
-            gz1 = (reg_on && p.reg_mode != 0) ? thv : 0.f;        // d REG / d theta_K (-log p)
+            gz1 = (reg_on && (OB ? (cm & kCmRegSampled) != 0 : p.reg_mode != 0)) ? thv : 0.f;        // d REG / d theta_K (-log p)
         } else {
             // the sample after the flows again (the forward's arithmetic on the kept tanh values: same bits).  (ppf, edf: the row
             // and dim indices behind opaque copies, so that the record and parameter addresses are formed here -- one base,
@@ -1136,7 +1236,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
 #pragma unroll
             for (int f = 0; f < kMsMF; ++f)
                 if (f < p.n_flows) thv = fmaf(fl.fpar[f][0][edf], fl.tps[par][f][0][ppf], thv);
-            gz1 = (reg_on && p.reg_mode != 0) ? thv : 0.f;
+            gz1 = (reg_on && (OB ? (cm & kCmRegSampled) != 0 : p.reg_mode != 0)) ? thv : 0.f;
             float znext = thv;                  // output of the flow being backpropagated
             const float lv = live ? 1.0f : 0.f, lv1 = reg_on ? 1.0f : 0.f;
             const int sl = (e >> 6) & 3;
@@ -1182,12 +1282,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         float gmu[2], glv[2];
         gmu[0] = gz0;
         glv[0] = gz0 * h;
-        if (p.reg_mode == 0) {
+        if (OB ? (cm & kCmRegSampled) == 0 : p.reg_mode == 0) {      // (wave-uniform: a bit of the mask on the one-barrier loop)
             gmu[1] = amu;
             glv[1] = -0.5f * (1.0f - inv_lam);
         } else {
             gmu[1] = gz1;
-            glv[1] = gz1 * h - 0.5f;
+            glv[1] = MS_MULSUB(gz1, h, 0.5f);
         }
         if (!reg_on) { gmu[1] = 0.f; glv[1] = 0.f; }
         if (XGIVEN && p.given_grad) {
@@ -1214,20 +1314,31 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         float dt[8];
 #pragma unroll
         for (int c = 0; c < 2; ++c) {
-            const float tau = cl.ctab[(0 * 2 + c) * 8 + ed];
-            const float te = cl.ctab[(2 * 2 + c) * 8 + ed], mm = cl.ctab[(3 * 2 + c) * 8 + ed];
+            const float tau = MS_CTAB(0 * 2 + c);
+            const float te = MS_CTAB(2 * 2 + c), mm = MS_CTAB(3 * 2 + c);
             const float nl = live ? nn[c] * inv_lam : 0.f;
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                dt[st * 4 + c * 2 + 0] = gmu[st] * nl * tau;
-                const float g_tau = nl * (gmu[st] * (mm - amu) - glv[st]);
-                dt[st * 4 + c * 2 + 1] = -g_tau * te;
+                if constexpr (!OB) dt[st * 4 + c * 2 + 0] = gmu[st] * nl * tau;
+                const float g_tau = nl * MS_MULSUB(gmu[st], mm - amu, glv[st]);
+                if constexpr (!OB) dt[st * 4 + c * 2 + 1] = -g_tau * te;
+                if constexpr (OB) {      // (the sums' own adds fused as well: acc + (gmu nl) tau, acc - g_tau te)
+                    cr.sum[st * 4 + c * 2 + 0] = fmaf(gmu[st] * nl, tau, cr.sum[st * 4 + c * 2 + 0]);
+                    cr.sum[st * 4 + c * 2 + 1] = fmaf(-g_tau, te, cr.sum[st * 4 + c * 2 + 1]);
+                }
             }
         }
 #pragma unroll
-        for (int k = 0; k < 8; ++k) lds_add(&cl.tacc[par][k][e], dt[k]);      // (one lane per address: order is program order)
+        for (int k = 0; k < 8; ++k) {                   // (one lane per address: order is program order)
+            if constexpr (!OB) lds_add(&cl.tacc[par][k][e], dt[k]);
+        }
     };
     auto person_forward = [&](const int bt, const int par) {
+        if constexpr (OB) {      // (the callers are the owners of parity `par`: the slot and the parity as launch constants)
+            asm volatile("" : "+s"(cm));
+            forward_slot(std::false_type{}, bt, own, osl, slot_eps(bt, own, osl, epn));
+            return;
+        }
         int s0, s1, step;
         my_slots(par, s0, s1, step);
         if constexpr (EXTRA || !NW8) {
@@ -1250,6 +1361,10 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         if (s0 < s1) forward_slot(std::false_type{}, bt, par, s0, slot_eps(bt, par, s0, epn));
     };
     auto person_backward = [&](const int bt, const int par) {
+        if constexpr (OB) {      // (as person_forward: one call)
+            backward_slot(bt, own, osl);
+            return;
+        }
         int s0, s1, step;
         my_slots(par, s0, s1, step);
 #pragma unroll 1
@@ -1276,8 +1391,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     struct KTileOps { half8 a3[2][2], b3; };
     auto ktile_read = [&](auto uc, auto ktc, KTileOps& ko) {
         constexpr int u = decltype(uc)::value, kt = decltype(ktc)::value;
-        const _Float16* rp = &wl.tr[0][0][0] + rofs;
-        const _Float16* ip = &wl.img[u][0] + b3ofs + 2 * kt * kMsItemRow;
+        const _Float16* rp = TILES ? lds_at<const _Float16>(a_ktr) : &wl.tr[0][0][0] + rofs;
+        const _Float16* ip = (TILES ? lds_at<const _Float16>(a_kim) + u * 16 * kMsItemLane : &wl.img[u][0] + b3ofs) + 2 * kt * kMsItemRow;
         ko.b3 = cat8(lds_tr16(ip), lds_tr16(ip + kMsItemRow));
 #pragma unroll
         for (int hl = 0; hl < 2; ++hl)
@@ -1323,6 +1438,9 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             constexpr int n = u * 4 + t;
             constexpr int pa = 3 - ((n + 1) >> 1) < 0 ? 0 : 3 - ((n + 1) >> 1);      // waves 0-3 (the older ones: they win ties)
             constexpr int pb = 3 - (n >> 1);                                            // waves 4-7
+            // (tile rows: in every second tile the two groups' levels are equal -- one s_setprio, no test)
+            if constexpr (TILES && pa == pb) asm volatile("s_setprio %0" :: "n"(pa));
+            else
             asm volatile("s_bitcmp1_b32 %0, 2\n\ts_setprio %1\n\ts_cbranch_scc0 .Lmsprio%=\n\ts_setprio %2\n.Lmsprio%=:" :: "s"(q), "n"(pa), "n"(pb) : "scc");
         } else if constexpr (((u * 4 + t) & 1) != 0)
             asm volatile("s_bitcmp1_b32 %0, 2\n\ts_setprio 0\n\ts_cbranch_scc0 .Lmsprio%=\n\ts_setprio 1\n.Lmsprio%=:" :: "s"(q) : "scc");
@@ -1394,10 +1512,16 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 }
             }
             float lmax;
+            // (tile rows: the four as ONE statement -- hipcc puts an s_nop behind every asm statement that follows an MFMA's issue)
+            if constexpr (TILES) {
+                asm("v_max3_f32 %0, |%1|, |%2|, |%3|\n\tv_max3_f32 %0, %0, |%4|, |%5|\n\tv_max3_f32 %0, %0, |%6|, |%7|\n\tv_max_f32_e64 %0, %0, |%8|"
+                    : "=&v"(lmax) : "v"(uu[0]), "v"(uu[1]), "v"(uu[2]), "v"(uu[3]), "v"(uu[4]), "v"(uu[5]), "v"(uu[6]), "v"(uu[7]));
+            } else {
             asm("v_max3_f32 %0, |%1|, |%2|, |%3|" : "=v"(lmax) : "v"(uu[0]), "v"(uu[1]), "v"(uu[2]));
             asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(lmax) : "v"(lmax), "v"(uu[3]), "v"(uu[4]));
             asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(lmax) : "v"(lmax), "v"(uu[5]), "v"(uu[6]));
             asm("v_max_f32_e64 %0, %1, |%2|" : "=v"(lmax) : "v"(lmax), "v"(uu[7]));
+            }
             // (WP: marked unlikely -- hipcc otherwise lays the clamp path out as the fall-through and the plain tile takes a branch)
             const bool clamp2 = __any(!(lmax <= kLoS));              // (wave-uniform, rare)
             if (WP ? __builtin_expect(clamp2, false) : clamp2) {
@@ -1597,10 +1721,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         const half8 ones = half8{one_b, one_b, one_b, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
-            half8 v;
-            if constexpr (OB) v = *reinterpret_cast<const half8*>(&pl.thA[par][g >> 1][16 * mt + i16][0]);
-            else v = *reinterpret_cast<const half8*>(&cl.thA[g >> 1][16 * mt + i16][0]);
-            A1[mt] = (g == 3) ? ones : v;
+            if constexpr (OB) {      // (lanes g == 3 read the `ones` plane: nothing to select)
+                A1[mt] = *reinterpret_cast<const half8*>(&pl.thA[par][g == 3 ? 2 : g >> 1][16 * mt + i16][0]);
+            } else {
+                const half8 v = *reinterpret_cast<const half8*>(&cl.thA[g >> 1][16 * mt + i16][0]);
+                A1[mt] = (g == 3) ? ones : v;
+            }
         }
         if constexpr (OB) B2 = *reinterpret_cast<const half8*>(&pl.thT[par][i16][8 * g]);
         else B2 = *reinterpret_cast<const half8*>(&cl.thT[i16][8 * g]);
@@ -1632,7 +1758,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             // one-barrier loop: the second batch's counts too, and theta of the first batch -- iteration 0's barrier publishes it
             put_tile_counts(tcnt2, bt + G < n_batches, 1);
             __syncthreads();                          // (workgroup-uniform branch) counts and noise of both batches are out
-            person_forward(bt, 0);
+            if (!OB || own == 0) person_forward(bt, 0);
             fetch_eps(bt + 2 * G, 0);                 // (a forward's owners ask for the noise of their next batch right behind it)
         }
         asm volatile("" : "+v"(epn));                 // (in before the loop: no wait on it behind the loop's own loads)
@@ -1895,7 +2021,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     if constexpr (GRAD) {
         // backward of the workgroup's last batch
         __syncthreads();
-        if (bt >= G + wg) person_backward(bt - G, par ^ 1);
+        if (bt >= G + wg && (!OB || own != par)) person_backward(bt - G, par ^ 1);
+    }
+    if constexpr (OB) {
+        // the wave's running sums, once: every address of cl.tacc has its owner lane (also in a workgroup without a batch: zeros)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) cl.tacc[own][k][64 * osl + lane] = (k == 11 && ed != 0) ? 0.f : cr.sum[k];
     }
 
     // ================= workgroup reduction -> partial record =================
@@ -2026,6 +2157,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     }
 #endif
 }
+
+#undef MS_CTAB
+#undef MS_PAIR_ADD
+#undef MS_ADDMUL
+#undef MS_SUBMUL
+#undef MS_MULSUB
 
 template <int IRT, bool GRAD, int RM, bool FLOWS, bool NW8, int XM>
 static hipError_t launch_msplit_inst(const ElboParams& p, int nw, int grid, hipStream_t s) {
