@@ -39,7 +39,8 @@
 #ifdef VIBO_MS_TIMING
 // development build (make TIMING=1): shader-clock time per phase of the batch loop, summed per wave
 constexpr int kMsTSlots = 32;
-__device__ long long g_ms_timing[1024 * 8 * kMsTSlots];
+constexpr int kMsTWaves = 12;       // wave columns per workgroup (8 tile waves; the chain-wave instantiations fill 8-11 as well)
+__device__ long long g_ms_timing[1024 * kMsTWaves * kMsTSlots];
 #define MS_T(i) { __builtin_amdgcn_sched_barrier(0); long long now_; asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_) :: "memory"); \
                   __builtin_amdgcn_sched_barrier(0); tacc[i] += now_ - tlast; tlast = now_; }
 #define MS_WAITV() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
@@ -110,6 +111,17 @@ struct alignas(16) MsPipeLds {
 // the registers that take the place of MsCommonLds::tacc and ::st of the wave's slot on the one-barrier loop
 template <bool ON> struct MsChainRegs { float sum[12] = {}, st[5] = {}; };
 template <> struct MsChainRegs<false> {};
+// Chain waves (ms_chain_waves): a chain wave owns its slot of BOTH batch parities -- two sets of those registers, and the parity a
+// compile-time constant of each call (std::integral_constant) that selects the set and, as an immediate offset from the lane's
+// parity-0 address, the parity's block of MsPipeLds / MsWaveLds::gth.  Every other instantiation passes the parity as an int: set 0.
+template <bool CW, typename P> struct MsParSet { static constexpr int v = 0; };
+template <int V> struct MsParSet<true, std::integral_constant<int, V>> { static constexpr int v = V; };
+template <int S, typename T0, typename T1> __device__ __forceinline__ auto& ms_par_pick(T0& a, T1& b) {
+    if constexpr (S == 0) return a;
+    else return b;
+}
+constexpr uint32_t kMsParThA = sizeof(MsPipeLds::thA) / 2, kMsParThT = sizeof(MsPipeLds::thT) / 2, kMsParCnt = sizeof(MsPipeLds::cnt) / 2,
+                   kMsParNz = sizeof(MsPipeLds::nz) / 2, kMsParGth = sizeof(MsWaveLds::gth) / 2;
 inline size_t msplit_lds_bytes(int nw, bool flows = false, bool guess = false, bool fuse = false) {
     return sizeof(MsCommonLds) + (size_t)nw * sizeof(MsWaveLds) + (flows ? sizeof(MsFlowLds) : 0) +
            (guess ? (size_t)nw * kMsGuessFloats * sizeof(float) : 0) + (fuse ? (size_t)nw * kMsFuseFloats * sizeof(float) : 0);
@@ -160,12 +172,15 @@ __device__ __forceinline__ half8 cat8(const half2v a, const half2v b, const half
 // NW8: the workgroup has exactly 8 waves (897..1024 items, the benchmark's width): slot ownership and the sums over the
 // waves' LDS records are compile-time.  XM: HookMode (vibo_variant.hpp), which hooks the launch uses (0: those branches do not exist
 // in the code; 3: the experts' sums of the conditional posterior are formed HERE: one panel, ability_dim 1, fp32 rows).
-// blockDim.x = 64 nw, dynamic LDS = msplit_lds_bytes(nw, FLOWS).
+// blockDim.x = 64 nw (64 (nw + 4) with chain waves: ms_block_threads), dynamic LDS = msplit_lds_bytes(nw, FLOWS).
 // The kernel runs at 2 waves per SIMD, where a wave issues at most one instruction per ~5 cycles whatever its type: every
 // scalar instruction, branch and spill reload in the batch loop costs as much as a vector instruction (round 3: the loop
 // lost ~500 of its ~2 300 executed instructions per wave and batch this way).
+// (the chain-wave instantiations -- ms_chain_waves, vibo_variant.hpp -- are twelve waves, three per SIMD: see the batch loop)
 template <int IRT, bool GRAD, int RM, bool FLOWS, bool NW8, int XM>
-__global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
+__global__ __launch_bounds__(ms_chain_waves(IRT, GRAD, RM, XM, FLOWS, NW8) ? ms_block_threads(8, true) : 512,
+                             ms_waves_per_simd(ms_chain_waves(IRT, GRAD, RM, XM, FLOWS, NW8)))
+void msplit_kernel(const ElboParams p) {
     // Hook modes 1 and 2 instead of one EXTRA flag (round 4): each carries the other's pointers, branches and -- the given mode's
     // expf / logvar loads -- spilled registers no longer.
     // 3 (round 6) = the conditional posterior q(theta | responses, items) (models.py:664-710) of ONE panel at ability_dim 1 with its
@@ -189,6 +204,11 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     constexpr bool kMayGather = ms_may_gather(RM);        // (the instantiation can meet p.row_index)
     // One barrier per batch (tile rows, 8 waves): see the batch loop.  Every other instantiation keeps the two-barrier loop.
     constexpr bool OB = ms_one_barrier(RM, XM, FLOWS, NW8);
+    // ... with the (person, dim) chains on waves 8-11 (blockDim.x = 768): see the batch loop.  `nw` stays 8, the TILE waves: it fixes the
+    // item spans, the image blocks, the records and the end code's folds; every statement that touches a wave's own LDS record, its rows
+    // or its items is a tile wave's (q < 8) there.
+    constexpr bool CW = ms_chain_waves(IRT, GRAD, RM, XM, FLOWS, NW8);
+    static_assert(!CW || (OB && GRAD), "chain waves: a form of the one-barrier loop with gradients");
     // Paired code words (tile rows): see pair_words and the conversion in the tile.
     constexpr bool WP = ms_word_pairs(RM);
     static_assert(!WP || TILES, "paired code words: the words come from the image, one batch ahead");
@@ -218,7 +238,10 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     const int lane = tid & 63;
     const int q = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nw = NW8 ? 8 : (int)(blockDim.x >> 6);
-    MsWaveLds& wl = wls[q];
+    // (wave-uniform.  A chain wave has no record of its own: `wl` names a tile wave's, which it never writes -- every store through
+    //  `wl` below is a tile wave's -- and what it reads there, the prologue's item staging, it does not use)
+    const bool tile_wave = !CW || q < 8;
+    MsWaveLds& wl = wls[CW ? (q & 7) : q];
     MsFlowLds& fl = *reinterpret_cast<MsFlowLds*>(ms_smem + sizeof(MsCommonLds) + (size_t)nw * sizeof(MsWaveLds));   // (FLOWS only)
     // Panel mode in ONE launch (rows of more than 1024 items, EXTRA only): p.panel_count 1024-item panels x G workgroups each,
     // workgroup blockIdx.x = G-slot * panel_count + panel -- the panels of a row batch start side by side (one DRAM page run),
@@ -412,7 +435,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // One-barrier loop: a wave's slot never changes -- wave q owns slot q & 3 of the batches of parity q >> 2 -- so the (person, dim)
     // chains take both as launch constants (every LDS address of theirs is then a per-lane constant, formed once in front of the
     // loop), and the wave-uniform launch constants they test sit in ONE scalar mask instead of a register (or a spill lane) each.
-    const int own = q >> 2, osl = q & 3;
+    // (chain waves: wave 8 + c owns slot c of both parities; `own` = 0 is the parity its held addresses point at)
+    const int own = CW ? 0 : q >> 2, osl = q & 3;
     constexpr uint32_t kCmDraw = 1u, kCmMu = 2u, kCmSample = 4u, kCmRegSampled = 8u;
     uint32_t cm = 0u;
     if constexpr (OB) {
@@ -425,6 +449,11 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // (cl.st's five values) stay in registers on the one-barrier loop: one owner lane per address, the adds in the same order; the
     // sums go to cl.tacc once, in front of the end code
     MsChainRegs<OB> cr;                              // (an empty record in every other instantiation)
+    MsChainRegs<CW> cr1;                             // (chain waves: the set of the odd batches; `cr` is that of the even ones)
+#define MS_SET(par) (MsParSet<CW, std::decay_t<decltype(par)>>::v)
+#define MS_CR(par) (ms_par_pick<MS_SET(par)>(cr, cr1))
+    // the caller's noise of a chain wave's slot: that of its next forward and of the one after (either parity's, two batches apart)
+    float epc0 = 0.f, epc1 = 0.f;
     auto fetch_eps = [&](const int bt, const int par) __attribute__((always_inline)) {
         if constexpr (OB) {
             asm volatile("" : "+s"(cm));              // (as in forward_slot)
@@ -493,6 +522,20 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // entry k of the expert-table constants of the lane's dim
     // (macros, here and MS_PAIR_ADD below, not lambdas: the other instantiations keep their statements -- and their code -- as they were)
 #define MS_CTAB(k) (OB ? lds_at<const float>(a_ctab)[(k) * 8] : cl.ctab[(k) * 8 + ed])
+    // chain waves: the caller's noise of the wave's slot of batch bt (fetch_eps' load; nothing where the kernel draws or past the end)
+    auto chain_eps = [&](const int bt) __attribute__((always_inline)) {
+        float v = 0.f;
+        if constexpr (CW) {
+            asm volatile("" : "+s"(cm));
+            if ((cm & kCmDraw) == 0 && bt < n_batches) {
+                const int row = bt * R + c_pp;
+                int ed = lane & 7;
+                asm volatile("" : "+v"(ed));          // (as in fetch_eps)
+                v = (ed < A && row < p.B) ? p.eps[(long long)row * A + ed] : 0.f;
+            }
+        }
+        return v;
+    };
     auto draw_eps = [&](const int bt, const int par = 0) __attribute__((always_inline)) {
         if constexpr (kDraw) {
             if (draw) {
@@ -506,12 +549,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         }
     };
     // eps of slot s of batch bt: drawn (LDS) or loaded (e0)
-    auto slot_eps = [&](const int bt, const int par, const int s, const float e0) __attribute__((always_inline)) {
+    auto slot_eps = [&](const int bt, const auto par, const int s, const float e0) __attribute__((always_inline)) {
         if constexpr (kDraw) {
             if (OB ? (cm & kCmDraw) != 0 : draw) {
                 const int r = (64 * s + lane) >> 3;
                 float v;
-                if constexpr (OB) v = *lds_at<const float>(a_nz);
+                if constexpr (OB) v = *lds_at<const float>(a_nz + MS_SET(par) * kMsParNz);
                 else v = nz[r * A + ed];
                 return (ed < A && bt * R + (OB ? c_pp : r) < p.B) ? v : 0.f;
             }
@@ -534,14 +577,21 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     auto first_rows = [&]() __attribute__((always_inline)) {      // the first batch's rows (both M-tiles) and noise; (two call sites)
         if constexpr (TILES) {
             if (bt < n_batches) {
+                if constexpr (CW) {       // chain waves: no rows -- the caller's noise of their slot of the first two batches
+                    if (!tile_wave) {
+                        epc0 = chain_eps(bt);
+                        epc1 = chain_eps(bt + G);
+                        return;
+                    }
+                }
                 load_tiles(src_first, 0, cwA0, cwA1);
                 load_tiles(src_first, 1, cwA0, cwA1);
                 tcnt = load_tile_counts(src_first);
-                fetch_eps(bt, 0);
+                if constexpr (!CW) fetch_eps(bt, 0);
                 draw_eps(bt);
                 if constexpr (OB) {       // counts and noise run two batches ahead there: the second batch's as well
                     tcnt2 = load_tile_counts(row_src(bt + G));
-                    fetch_eps(bt + G, 1);
+                    if constexpr (!CW) fetch_eps(bt + G, 1);
                     draw_eps(bt + G, 1);
                 }
             }
@@ -578,7 +628,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
 #pragma unroll
         for (int k = 0; k < kItemReq; ++k) {
             it_req[k] = 0.f;
-            if (64 * k < it_floats) {                                       // (scalar branch; clamped index: always a valid address)
+            if (64 * k < it_floats && tile_wave) {                          // (scalar branch; clamped index: always a valid address)
                 const long long f = it_base + min(64 * k + lane, it_floats - 1);
                 it_req[k] = p.item_raw[f < it_last ? f : it_last];
             }
@@ -688,7 +738,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     static_assert(sizeof(wl.tr) + sizeof(wl.img) >= (size_t)kMsSpan * (VIBO_MAX_ABILITY_DIM + 2) * sizeof(float), "item staging area");
 #pragma unroll
     for (int k = 0; k < kItemReq; ++k)
-        if (64 * k < it_floats) it_stage[64 * k + lane] = it_req[k];
+        if (64 * k < it_floats && tile_wave) it_stage[64 * k + lane] = it_req[k];
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the wave's own LDS writes, in order: visible to its reads)
     float a_req[2][8], b_req[2];
     float g_raw[2][4];                                      // 3PL: guess logits of the lane's items of tile (u, t)
@@ -735,7 +785,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         mb = fmaxf(mb, dpp_f<0xb1>(mb)); mb = fmaxf(mb, dpp_f<0x4e>(mb));
         mb = fmaxf(mb, dpp_f<0x124>(mb)); mb = fmaxf(mb, dpp_f<0x128>(mb));
         mb = fmaxf(mb, __shfl_xor(mb, 16)); mb = fmaxf(mb, __shfl_xor(mb, 32));
-        if (lane == 0) { wl.red[1] = ma; wl.red[2] = mb; }
+        if (lane == 0 && tile_wave) { wl.red[1] = ma; wl.red[2] = mb; }
     }
     MS_P(18, t_entry)                                 // item sample in, wave maxima
     __syncthreads();
@@ -769,6 +819,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         _Float16 b0, b1, b2, b3;
         split16(nb, b0, b1);
         split16(nb - (float)b0 - (float)b1, b2, b3);
+        if (!tile_wave) continue;                   // (chain waves build no image)
         *reinterpret_cast<half8*>(dst) = hi8;
         *reinterpret_cast<half8*>(dst + 8) = lo8;
         *reinterpret_cast<half8*>(dst + 16) = half8{b0, b1, b2, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f, (_Float16)0.f};
@@ -1003,14 +1054,14 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     // prior experts of the missing cells (models.py:613-620): weight 1 / (1 + eps) each, or dropped
     const float prior_w = p.missing_mode == 0 ? 1.0f / (1.0f + kPoeEps) : 0.f;
     // running sum k of pair e: the owner lane's register on the one-barrier loop, else its LDS word
-#define MS_PAIR_ADD(k, v) do { if constexpr (OB) cr.sum[k] += (v); else lds_add(&cl.tacc[par][k][e], (v)); } while (0)
+#define MS_PAIR_ADD(k, v) do { if constexpr (OB) MS_CR(par).sum[k] += (v); else lds_add(&cl.tacc[par][k][e], (v)); } while (0)
     // c + a b, c - a b, a b - c.  The two launches of a matrix -- on its rows and on its image -- agree bit for bit, so the one-barrier
     // loop states the fused forms hipcc picks for these sums everywhere else (one v_fma each); with the running sums in registers its
     // vectoriser pairs the products differently and would leave some of them unfused.  The other instantiations keep the plain text.
 #define MS_ADDMUL(c, a, b) (OB ? fmaf((a), (b), (c)) : (c) + (a) * (b))
 #define MS_SUBMUL(c, a, b) (OB ? fmaf(-(a), (b), (c)) : (c) - (a) * (b))
 #define MS_MULSUB(a, b, c) (OB ? fmaf((a), (b), -(c)) : (a) * (b) - (c))
-    auto forward_slot =[&](auto extc, const int bt, const int par, const int s, const float eps_c) {
+    auto forward_slot =[&](auto extc, const int bt, const auto par, const int s, const float eps_c) {
         constexpr bool EXT = decltype(extc)::value;
         if constexpr (OB) asm volatile("" : "+s"(cm));      // (tested here, bit by bit: not hoisted into a condition register each)
         static_assert(EXTRA || !EXT, "the global-memory variant belongs to the EXTRA instantiations");
@@ -1034,7 +1085,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         if (!have_cnt) {
             if constexpr (OB) {
 #pragma unroll
-                for (int w = 0; w < 8; ++w) cnt += lds_at<const int>(a_cnt)[w * R];
+                for (int w = 0; w < 8; ++w) cnt += lds_at<const int>(a_cnt + MS_SET(par) * kMsParCnt)[w * R];
             } else if constexpr (NW8) {
                 int ppo = pp;
                 if constexpr (kPinFlowAddr) asm volatile("" : "+v"(ppo));     // (see backward_slot)
@@ -1164,8 +1215,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             if (OB || ed == 0) MS_PAIR_ADD(11, nobs);
         }
         if constexpr (GRAD && OB) {
-            cr.st[0] = amu; cr.st[1] = sig; cr.st[2] = inv_lam; cr.st[3] = eps_c;
-            cr.st[4] = __builtin_bit_cast(float, cnt);
+            MS_CR(par).st[0] = amu; MS_CR(par).st[1] = sig; MS_CR(par).st[2] = inv_lam; MS_CR(par).st[3] = eps_c;
+            MS_CR(par).st[4] = __builtin_bit_cast(float, cnt);
         } else if constexpr (GRAD) {
             cl.st[par][0][e] = amu; cl.st[par][1][e] = sig; cl.st[par][2][e] = inv_lam; cl.st[par][3][e] = eps_c;
             cl.st[par][4][e] = __builtin_bit_cast(float, cnt);
@@ -1174,8 +1225,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         split16(ths, hi, lo);
         const int slot = 8 * ((pp & 15) >> 2) + 4 * (pp >> 4) + (pp & 3);
         if constexpr (OB) {
-            _Float16* const ta = lds_at<_Float16>(a_thA);
-            _Float16* const tt = lds_at<_Float16>(a_thT);
+            _Float16* const ta = lds_at<_Float16>(a_thA + MS_SET(par) * kMsParThA);
+            _Float16* const tt = lds_at<_Float16>(a_thT + MS_SET(par) * kMsParThT);
             ta[0] = hi;
             ta[R * 8] = lo;
             tt[0] = hi;
@@ -1189,13 +1240,13 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     };
     // backward of one slot through the sample and the product of experts; the 8 table-gradient sums of the wave's lanes
     // go to the wave's LDS record (fixed order: bitwise reproducible)
-    auto backward_slot = [&](const int bt, const int par, const int s) {
+    auto backward_slot = [&](const int bt, const auto par, const int s) {
         const int row0 = bt * R;
         const int e = 64 * s + lane, pp = OB ? c_pp : e >> 3;
         const bool live = ed < A && (row0 + pp) < p.B;
         float g0 = 0.f;
         if constexpr (OB) {
-            const float* const g8 = lds_at<const float>(a_gth);
+            const float* const g8 = lds_at<const float>(a_gth + MS_SET(par) * kMsParGth);
 #pragma unroll
             for (int w = 0; w < 8; ++w) g0 += g8[w * (int)(sizeof(MsWaveLds) / sizeof(float))];
         } else if constexpr (NW8) {
@@ -1214,7 +1265,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         float gz0 = live ? g0 * (kLn2 * sc_t) : 0.f;          // (log2 units -> nats; sum g a' = 2^jsh sum g a)
         // (the forward's kept state: its registers on the one-barrier loop)
         auto kept = [&](const int i) __attribute__((always_inline)) {
-            if constexpr (OB) return cr.st[i];
+            if constexpr (OB) return MS_CR(par).st[i];
             else return cl.st[par][i][e];
         };
         const float amu = kept(0), sig = kept(1), inv_lam = kept(2), eps_c = kept(3);
@@ -1323,8 +1374,8 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 const float g_tau = nl * MS_MULSUB(gmu[st], mm - amu, glv[st]);
                 if constexpr (!OB) dt[st * 4 + c * 2 + 1] = -g_tau * te;
                 if constexpr (OB) {      // (the sums' own adds fused as well: acc + (gmu nl) tau, acc - g_tau te)
-                    cr.sum[st * 4 + c * 2 + 0] = fmaf(gmu[st] * nl, tau, cr.sum[st * 4 + c * 2 + 0]);
-                    cr.sum[st * 4 + c * 2 + 1] = fmaf(-g_tau, te, cr.sum[st * 4 + c * 2 + 1]);
+                    MS_CR(par).sum[st * 4 + c * 2 + 0] = fmaf(gmu[st] * nl, tau, MS_CR(par).sum[st * 4 + c * 2 + 0]);
+                    MS_CR(par).sum[st * 4 + c * 2 + 1] = fmaf(-g_tau, te, MS_CR(par).sum[st * 4 + c * 2 + 1]);
                 }
             }
         }
@@ -1439,6 +1490,10 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             constexpr int pa = 3 - ((n + 1) >> 1) < 0 ? 0 : 3 - ((n + 1) >> 1);      // waves 0-3 (the older ones: they win ties)
             constexpr int pb = 3 - (n >> 1);                                            // waves 4-7
             // (tile rows: in every second tile the two groups' levels are equal -- one s_setprio, no test)
+            // (chain waves: all eight tile waves on ONE staircase, that of waves 4-7 -- measured together with the noise drawn by the
+            //  chain waves, see the batch loop; no test)
+            if constexpr (CW) asm volatile("s_setprio %0" :: "n"(pb));
+            else
             if constexpr (TILES && pa == pb) asm volatile("s_setprio %0" :: "n"(pa));
             else
             asm volatile("s_bitcmp1_b32 %0, 2\n\ts_setprio %1\n\ts_cbranch_scc0 .Lmsprio%=\n\ts_setprio %2\n.Lmsprio%=:" :: "s"(q), "n"(pa), "n"(pb) : "scc");
@@ -1750,6 +1805,16 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         MS_P(22, t_entry)
         if constexpr (!TILES) pack_half(bt, 1, cwA0, cwA1, pk, x2, m2, src_first);
         MS_P(23, t_entry)
+        if constexpr (CW) {
+            // chain waves: the tile waves put the counts of the first two batches out and pair the first batch's words; the chain waves
+            // meet them at the barrier and run forward(first) at the head of their own loop
+            if (tile_wave) {
+                put_tile_counts(tcnt, true);
+                pair_words(cwA0, cwA0); pair_words(cwA1, cwA1);
+                put_tile_counts(tcnt2, bt + G < n_batches, 1);
+            }
+            __syncthreads();                          // (workgroup-uniform branch, all twelve waves) counts and noise of both batches are out
+        } else {
         if constexpr (TILES) put_tile_counts(tcnt, true);      // (the words are where the tiles read them)
         else put_counts(pk, true);
         if constexpr (WP) { pair_words(cwA0, cwA0); pair_words(cwA1, cwA1); }      // (the first batch's, loaded as the image has them: paired in place)
@@ -1760,6 +1825,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
             __syncthreads();                          // (workgroup-uniform branch) counts and noise of both batches are out
             if (!OB || own == 0) person_forward(bt, 0);
             fetch_eps(bt + 2 * G, 0);                 // (a forward's owners ask for the noise of their next batch right behind it)
+        }
         }
         asm volatile("" : "+v"(epn));                 // (in before the loop: no wait on it behind the loop's own loads)
         if constexpr (EXTRA && kPrs) asm volatile("" : "+v"(prs0), "+v"(prs1), "+v"(prs2));
@@ -1811,6 +1877,125 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     //   epn                  the caller's noise: a register of the slot's owner, asked for right behind the forward that used it,
     //                        two batches ahead, and waited for at the end of the iteration
     // A batch past the end has no buffer records (its loads return zeros) and no forward.
+    //
+    // Chain waves (CW: the one-barrier loop with gradients, 1PL / 2PL; twelve waves, three per SIMD).  The chains above sit on the path
+    // of the tile wave that runs them -- its tile stream stands still for ~2 k cycles every second batch, and its partner's tiles take
+    // as long beside it as beside tiles (profiles/one_barrier_record.txt) -- so they get an instruction stream of their own: wave 8 + c
+    // (one per SIMD) owns slot c of EVERY batch, waves 0-7 run tiles only.  Behind X(bt) a chain wave runs backward(bt - G), then
+    // forward(bt + G), asks for the caller's noise two batches ahead, draws the kernel's own in its turn and waits at X(bt + G).  It
+    // keeps two sets of the running sums and of the kept state, one per batch parity (the loop is unrolled by two: the set, and the
+    // parity's block of every LDS address, are compile-time), so each owner lane still meets its parity's batches in their old order:
+    // same bits.
+    // Placement and priority (whole step at 1M x 1k, ability_dim 8, libraries alternated on one box, ms per step, min-max over three to
+    // five runs; profiles/chain_waves_record.txt, section 4).  The chain waves need ~2.6 k of a batch's ~8.6 k cycles and wait for the
+    // rest: at priority 3 (where the chains ran inside a tile wave) they take issue slots from two tile waves each -- the tiles grew
+    // from 6.9-7.4 k to 7.2-7.8 k cycles -- 0.5154-0.5213 against the parent's 0.5368-0.5438; at priority 2 0.5074-0.5106; at 1
+    // 0.5287-0.5335 against 0.5237-0.5314 at 0 (another box); at 0, below or level with every tile, 0.5014-0.5022: this form.  On
+    // top of that, the noise drawn by the chain waves (one per batch in turn, behind its chains; it was ~100 VALU instructions on one
+    // tile wave per batch, for which the other seven waited) with all tile waves on the staircase of waves 4-7 (no offset between the
+    // groups: neither is "busy" any more): 0.4971-0.5105 against 0.5084-0.5184, 0.5054-0.5125 against 0.5126-0.5256 and
+    // 0.5013-0.5234 against 0.5099-0.5159, five runs each -- the medians 2.1 % apart every time, the ranges clear in the second -- kept;
+    // either alone 0.5021-0.5172 / 0.5128-0.5194 against 0.5084-0.5184: nothing beyond the spread.  The offset turned into a whole level
+    // for waves 4-7 0.5197-0.5359, all waves on the staircase of waves 0-3 0.5181-0.5221 against 0.5154-0.5213 (priority 3): not kept.
+    // Backward behind forward was not built: the kept state of a parity is read by the backward and overwritten by the forward of the
+    // same iteration, and both chains end ~6 k cycles before the barrier that publishes them.
+    // Hazards (par = parity of bt; T = tile waves, C = chain waves; every row as above, the owner now a chain wave):
+    //   thA / thT [par ^ 1]  C writes theta(bt + G) behind X(bt); T read theta(bt - G) into registers behind X(bt - G), before they
+    //                        reach X(bt); T read the new contents behind X(bt + G), which C reaches after its forward
+    //   gth [par]            T write at the end of iteration bt; C read in backward(bt) behind X(bt + G); T write again at the end of
+    //                        iteration bt + 2 G, behind X(bt + 2 G), which C reaches after that backward
+    //   cnt [par]            T write those of bt + 2 G at the end of iteration bt, behind X(bt); C read in forward(bt + 2 G) behind
+    //                        X(bt + G); the last reader of the old contents, forward(bt), ran before C reached X(bt)
+    //   nz [par]             ONE chain wave writes the noise of bt + 2 G behind X(bt); all four read it in forward(bt + 2 G) behind
+    //                        X(bt + G); the last readers of the old contents, the four forward(bt), ran before their waves reached X(bt)
+    //   st, sums [par ^ 1]   registers of the chain wave: backward(bt - G) reads, forward(bt + G) writes -- program order
+    //   epc0 / epc1          the caller's noise: registers of the chain wave, asked for two batches ahead
+    //   prologue             T put cnt [0], cnt [1], nz [0], nz [1] out in front of the prologue's barrier; C run forward(first) behind
+    //                        it and in front of X(first); cnt [0] / nz [0] are overwritten behind X(first)
+    // Barriers: every one is reached by all twelve waves under workgroup-uniform conditions -- the two of the prologue (always), the
+    // prologue's third (bt < n_batches), X(bt) (the same trip count bt, n_batches, G in either role's loop), the one behind the loop
+    // (always), the end code's (always) and insitu_exit's (a kernel argument).
+    if constexpr (CW) {
+        if (!tile_wave) {
+            __builtin_amdgcn_s_setprio(0);            // (below or level with every tile: see Placement and priority above)
+            if (bt < n_batches) {
+                forward_slot(std::false_type{}, bt, IC0{}, osl, slot_eps(bt, IC0{}, osl, epc0));
+                epc0 = epc1;
+                epc1 = chain_eps(bt + 2 * G);
+            }
+            // iteration bt of parity `parc`: both chains work on the set of the OTHER parity
+            auto chain_step = [&](auto parc) {
+                using PO = std::integral_constant<int, decltype(parc)::value ^ 1>;
+                const int nxt = bt + G;
+                MS_T(4)
+                __syncthreads();                      // X(bt)
+                MS_T(5)
+                if (bt >= G + wg) backward_slot(bt - G, PO{}, osl);
+                MS_T(9)
+                if (nxt < n_batches) forward_slot(std::false_type{}, nxt, PO{}, osl, slot_eps(nxt, PO{}, osl, epc0));
+                epc0 = epc1;
+                epc1 = chain_eps(nxt + 2 * G);
+                if (draw) {       // draw_eps' block for batch bt + 2 G, into nz [parity of bt]: one chain wave per batch, in turn
+                    if ((nz_wave & 3) == osl && nxt + G < n_batches && lane < 8 * A)
+                        reinterpret_cast<float4*>(pl.nz[decltype(parc)::value])[lane] =
+                            philox_normal4((long long)(nxt + G) * (8 * A) + lane, nz_step, p.noise_stream, p.noise_seed_lo, p.noise_seed_hi);
+                    nz_wave = nz_wave + 1;
+                }
+                MS_T(6)
+            };
+            for (;;) {
+                if (bt >= n_batches) break;
+                chain_step(IC0{});
+                bt += G; par ^= 1;
+                if (bt >= n_batches) break;
+                chain_step(IC1{});
+                bt += G; par ^= 1;
+            }
+            // backward of the workgroup's last batch, and the running sums, once: every address of cl.tacc has its owner lane (also in
+            // a workgroup without a batch: zeros)
+            __syncthreads();
+            if (bt >= G + wg) {
+                if (par) backward_slot(bt - G, IC0{}, osl);
+                else backward_slot(bt - G, IC1{}, osl);
+            }
+#pragma unroll
+            for (int st = 0; st < 2; ++st)
+#pragma unroll
+                for (int k = 0; k < 12; ++k) cl.tacc[st][k][64 * osl + lane] = (k == 11 && ed != 0) ? 0.f : (st ? cr1.sum[k] : cr.sum[k]);
+        } else {
+            for (; bt < n_batches; bt += G, par ^= 1) {
+                const int nxt = bt + G;
+                const RowSrc sn = row_src(nxt), sc = row_src(nxt + G);
+                __builtin_amdgcn_sched_barrier(0);
+                load_tiles(sn, 0, cwB0, cwB1);
+                load_tiles(sn, 1, cwB0, cwB1);
+                tcnt = load_tile_counts(sc);
+                __builtin_amdgcn_sched_barrier(0);
+                MS_T(4)
+                __syncthreads();                      // X(bt): theta(bt) and the d LL/d theta shares of bt - G are out
+                MS_T(5)
+                read_theta_ops(par);
+                MS_T(8)
+                f32x4 da0, da1, db0, db1;
+                logits(bopA, da0, da1);
+                tile(IC0{}, IC0{}, da0, da1, db0, db1, cwA0, bopB, bopA);
+                tile(IC0{}, IC1{}, db0, db1, da0, da1, cwA0, bopA, bopB);
+                tile(IC0{}, IC2{}, da0, da1, db0, db1, cwA0, bopB, bopA);
+                tile(IC0{}, IC3{}, db0, db1, da0, da1, cwA0, bopA, bopB);
+                MS_T(0)
+                tile(IC1{}, IC0{}, da0, da1, db0, db1, cwA1, bopB, bopA);
+                tile(IC1{}, IC1{}, db0, db1, da0, da1, cwA1, bopA, bopB);
+                tile(IC1{}, IC2{}, da0, da1, db0, db1, cwA1, bopB, bopA);
+                tile(IC1{}, IC3{}, db0, db1, da0, da1, cwA1, bopA, bopB);
+                MS_T(2)
+                put_tile_counts(tcnt, nxt + G < n_batches, par);      // (waits for the five loads: none crosses the back edge)
+                MS_T(10)
+                put_gtheta(par);
+                pair_words(cwA0, cwB0); pair_words(cwA1, cwB1);       // (the words become the next batch's, paired)
+            }
+            __syncthreads();                          // (the chain waves run backward(last) behind it)
+        }
+    } else
     if constexpr (OB) {
         for (; bt < n_batches; bt += G, par ^= 1) {
             const int nxt = bt + G;
@@ -2018,12 +2203,12 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     long long t_loop_end;
     asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t_loop_end) :: "memory");
 #endif
-    if constexpr (GRAD) {
+    if constexpr (GRAD && !CW) {       // (chain waves: both inside the roles' branches above)
         // backward of the workgroup's last batch
         __syncthreads();
         if (bt >= G + wg && (!OB || own != par)) person_backward(bt - G, par ^ 1);
     }
-    if constexpr (OB) {
+    if constexpr (OB && !CW) {
         // the wave's running sums, once: every address of cl.tacc has its owner lane (also in a workgroup without a batch: zeros)
 #pragma unroll
         for (int k = 0; k < 12; ++k) cl.tacc[own][k][64 * osl + lane] = (k == 11 && ed != 0) ? 0.f : cr.sum[k];
@@ -2041,7 +2226,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
     {
         // every cell without an observation contributed exactly log2(1 + 2^0) = 1 to s_log
         const float ll = -kLn2 * wave_total(s_log - (float)unobs);
-        if (lane_e == 0) wl.red[0] = range_fault ? __builtin_nanf("") : ll;      // (operands beyond the rescaling range: loud)
+        if (lane_e == 0 && tile_wave) wl.red[0] = range_fault ? __builtin_nanf("") : ll;      // (operands beyond the rescaling range: loud)
     }
     __syncthreads();
     MS_P(25, t_loop_end)
@@ -2108,6 +2293,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         float* stage = reinterpret_cast<float*>(&wl.tr[0][0][0]);
         static_assert(sizeof(wl.tr) + sizeof(wl.img) >= (size_t)(VIBO_MAX_ABILITY_DIM + 2) * kStage * sizeof(float), "staging area");
         const int brow = IRT == 1 ? 0 : A;
+        if (tile_wave) {                             // (chain waves hold no items)
 #pragma unroll
         for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -2143,6 +2329,7 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
                 if (il < I) out[p.lay.off_item + (size_t)row * p.lay.i_pad + il] = stage[row * kStage + 64 * h + lane_e];
             }
         }
+        }
     }
     insitu_exit(p.insitu, gridDim.x);
 #ifdef VIBO_MS_TIMING
@@ -2152,13 +2339,15 @@ __global__ __launch_bounds__(512, 2) void msplit_kernel(const ElboParams p) {
         tacc[13] = t_exit - t_loop_end;              // kernel epilogue (records)
         tacc[15] = t_real_exit;
         if (lane == 0 && blockIdx.x < 1024) {
-            for (int k = 0; k < kMsTSlots; ++k) g_ms_timing[((size_t)blockIdx.x * 8 + q) * kMsTSlots + k] = tacc[k];
+            for (int k = 0; k < kMsTSlots; ++k) g_ms_timing[((size_t)blockIdx.x * kMsTWaves + q) * kMsTSlots + k] = tacc[k];
         }
     }
 #endif
 }
 
 #undef MS_CTAB
+#undef MS_SET
+#undef MS_CR
 #undef MS_PAIR_ADD
 #undef MS_ADDMUL
 #undef MS_SUBMUL
@@ -2179,7 +2368,9 @@ static hipError_t launch_msplit_inst(const ElboParams& p, int nw, int grid, hipS
     // (p.eps null -- split_variant: only where the instantiation draws the noise -- takes 1 KB more LDS)
     // (... and the one-barrier loop's parity block takes the noise block's place, whoever supplies the noise)
     const size_t lds = msplit_lds_bytes(nw, FLOWS, IRT == 3, kFuse) + (kOB ? sizeof(MsPipeLds) : p.eps ? 0 : kMsNoiseBytes);
-    hipLaunchKernelGGL((msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>), dim3(grid), dim3(64 * nw), lds, s, p);
+    // (block size: the tile waves, plus the chain waves of the instantiations that run them)
+    hipLaunchKernelGGL((msplit_kernel<IRT, GRAD, RM, FLOWS, NW8, XM>), dim3(grid),
+                       dim3(ms_block_threads(nw, ms_chain_waves(IRT, GRAD, RM, XM, FLOWS, NW8))), lds, s, p);
     return hipGetLastError();
 }
 // the unit's instantiations of one hook mode: IRT x GRAD x NW8

@@ -46,6 +46,17 @@ constexpr bool ms_sample_optional(int xm, bool flows, bool grad, int rm, bool nw
 // SIMD partner's tiles): tile rows at exactly 8 waves -- their counts are data of the image, requested two batches ahead.  (Tile rows
 // under a caller-supplied posterior, kHooksGiven, keep the two-barrier loop at every width.)
 constexpr bool ms_one_barrier(int rm, int xm, bool flows, bool nw8) { return rm == kRowsTiles && xm == kHooksNone && !flows && nw8; }
+// ... and with the (person, dim) chains on four waves of their own, one per SIMD beside the eight tile waves (a third wave per SIMD:
+// at most 168 registers): the one-barrier instantiations with gradients, 1PL / 2PL.  (3PL holds 204 registers without the chains;
+// a forward-only launch has no backward chain to move.)  ONE definition for the kernel's constant, its launch bounds and the
+// launch's block size.
+constexpr bool ms_chain_waves(int irt, bool grad, int rm, int xm, bool flows, bool nw8) {
+    return ms_one_barrier(rm, xm, flows, nw8) && grad && irt != 3;
+}
+constexpr int kMsChainWaves = 4;
+// threads of a matrix-kernel workgroup of nw (tile) waves, and the waves per SIMD the instantiation is compiled for
+constexpr int ms_block_threads(int nw, bool chain_waves) { return 64 * (nw + (chain_waves ? kMsChainWaves : 0)); }
+constexpr int ms_waves_per_simd(bool chain_waves) { return chain_waves ? 3 : 2; }
 // the matrix kernel keeps a batch's code words PAIRED in registers (words k and k + 1 of a lane byte-interleaved where they become the
 // current batch's, so that a tile converts cells k and k + 1 of ITSELF into adjacent registers), sums the d LL/d theta shares with one
 // DPP add per value and lays the tile's clamp path out of line: every tile-rows instantiation.  The image in memory is not affected.
