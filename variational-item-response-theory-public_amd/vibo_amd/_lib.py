@@ -1,9 +1,9 @@
 """ctypes binding of libvibo_hip.so.  The C ABI is declared in include/vibo_hip.h and read from there: every export's
 restype / argtypes come from its prototype (parse_prototypes); the constants and the two structs mirror the header by hand
 (tests/test_capi_symbols.py compares them).  Exports declared in a header of their own beside it (EXTRA_HEADERS:
-vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h, vibo_hip_tile_rows.h, vibo_hip_given_tiles.h) are bound the same
-way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself, EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS, PERSON_TABLE_SYMBOLS, TILE_ROWS_SYMBOLS and
-GIVEN_TILES_SYMBOLS are theirs.
+vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h, vibo_hip_tile_rows.h, vibo_hip_given_tiles.h,
+vibo_hip_sparse_rows.h) are bound the same way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself, EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS,
+PERSON_TABLE_SYMBOLS, TILE_ROWS_SYMBOLS, GIVEN_TILES_SYMBOLS and SPARSE_ROWS_SYMBOLS are theirs.
 
 The product path has no CPU or eager-PyTorch fallback: if the HIP library is
 missing or a call fails, this module raises.
@@ -23,6 +23,8 @@ MASK_U8, MASK_I64, MASK_NONE, MASK_CODES = 0, 1, 2, 3
 MASK_SIGN = 4                 # include/vibo_hip_sign_rows.h: no mask, the response's sign bit says "missing"
 MASK_TILES = 6                # include/vibo_hip_tile_rows.h: `response` is the matrix' prepacked tile image, no mask
 TILE_WAVE_BLOCK_BYTES = 4352  # ... one wave's 128 items x 32 rows: 16 code words and a counts dword per lane
+# include/vibo_hip_sparse_rows.h: the matrix as its observed cells (VIBO_SPARSE_*)
+SPARSE_CHUNK, SPARSE_ROWS_PER_BLOCK, SPARSE_MAX_BLOCKS, SPARSE_RECORD_FLOATS = 512, 32, 1024, 72
 REG_KL, REG_SAMPLED = 0, 1
 FLAG_KERNEL_VALU, FLAG_KERNEL_MATRIX, FLAG_NO_EMIT_CODES, FLAG_COND_VALU, FLAG_COND_MATRIX, FLAG_COND_THREE_PASS = 1, 2, 4, 8, 16, 32
 KERNEL_NAMES = {1: 'matrix row-split (msplit_kernel)', 2: 'VALU row-split (split_kernel)', 3: 'wave-per-row', 4: 'tiled',
@@ -74,10 +76,27 @@ class ViboDecoderDesc(ctypes.Structure):
     ]
 
 
+class ViboSparseImage(ctypes.Structure):
+    """struct vibo_sparse_image (include/vibo_hip_sparse_rows.h); the pointers are device pointers."""
+    _fields_ = [
+        ('num_person', ctypes.c_int64),
+        ('num_item', ctypes.c_int64),
+        ('nnz', ctypes.c_int64),
+        ('num_chunk', ctypes.c_int64),
+        ('row_ptr', ctypes.c_void_p),
+        ('row_cell', ctypes.c_void_p),
+        ('col_ptr', ctypes.c_void_p),
+        ('col_cell', ctypes.c_void_p),
+        ('col_chunk', ctypes.c_void_p),
+        ('chunk_item', ctypes.c_void_p),
+        ('chunk_first', ctypes.c_void_p),
+    ]
+
+
 HEADER_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..', 'include', 'vibo_hip.h')
 _SCALAR_TYPES = {'int': ctypes.c_int, 'int32_t': ctypes.c_int32, 'uint32_t': ctypes.c_uint32, 'int64_t': ctypes.c_int64,
                  'uint64_t': ctypes.c_uint64, 'size_t': ctypes.c_size_t}
-_DESC_TYPES = {'vibo_desc': ViboDesc, 'vibo_decoder_desc': ViboDecoderDesc}
+_DESC_TYPES = {'vibo_desc': ViboDesc, 'vibo_decoder_desc': ViboDecoderDesc, 'vibo_sparse_image': ViboSparseImage}
 
 
 class ViboLibraryError(RuntimeError):
@@ -108,7 +127,7 @@ def parse_prototypes(header):
 
 
 EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h', 'vibo_hip_person_tables.h', 'vibo_hip_tile_rows.h',
-                 'vibo_hip_given_tiles.h')
+                 'vibo_hip_given_tiles.h', 'vibo_hip_sparse_rows.h')
 
 with open(HEADER_PATH) as _header:
     PROTOTYPES = parse_prototypes(_header.read())
@@ -126,6 +145,7 @@ SIGN_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sign_rows.h']
 PERSON_TABLE_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_person_tables.h']      # the VI / MLE train step (trainer.FusedVITrainer / FusedMLETrainer)
 TILE_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_tile_rows.h']
 GIVEN_TILES_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_given_tiles.h']          # the tile image under a caller-supplied posterior (ops._tile_rows)
+SPARSE_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sparse_rows.h']          # the matrix as its observed cells (vibo_amd/sparse.py)
 PTRAIN_VI, PTRAIN_MLE = 0, 1                                            # VIBO_PTRAIN_*
 PTRAIN_MAX_BLOCKS = 2048                                                # VIBO_PTRAIN_MAX_BLOCKS: the table update's grid cap
 

@@ -19,6 +19,8 @@ from typing import Callable, NamedTuple, Optional
 import torch
 
 from . import _lib
+from . import sparse as _sparse
+from .sparse import SparseRows
 
 
 def item_feat_dim(irt_model, ability_dim):
@@ -1003,7 +1005,9 @@ _BACKEND = {'elbo': _hip_launch_elbo, 'encode': _hip_encode, 'decode': _hip_deco
             'mean_bwd': _hip_mean_encoder_bwd, 'flow_stack': _hip_flow_stack, 'cond_mean_sum': _hip_cond_mean_sum,
             'sign_supported': _hip_sign_rows_supported, 'sign_verify': _hip_sign_is_mask,
             'tile_supported': _hip_tile_rows_supported, 'tile_bytes': _hip_tile_rows_bytes, 'tile_free': _hip_free_bytes,
-            'tile_build': _hip_tile_rows_build, 'tile_given_supported': _hip_given_tile_rows_supported}
+            'tile_build': _hip_tile_rows_build, 'tile_given_supported': _hip_given_tile_rows_supported,
+            # sparse rows (vibo_amd/sparse.py): the launch, the encode and the validation pass
+            'sparse_elbo': _sparse._hip_sparse_elbo, 'sparse_encode': _sparse._hip_sparse_encode, 'sparse_check': _sparse._hip_sparse_check}
 
 
 class FusedELBO(torch.autograd.Function):
@@ -1065,7 +1069,10 @@ def fused_elbo(spec, table, item, flow, response, mask, eps, *, reg_mode=_lib.RE
     """Functional front end.  response [B,I(,1)] fp32, mask [B,I(,1)] bool/int64/None,
     table per ElboSpec.table_shape, item [I,D], eps [B,A], flow [n_flows,2A+1] or None.
     With row_index (int64 [B]) the rows response[row_index] / mask[row_index] are
-    gathered inside the kernel (device-resident dataset, shuffled minibatches)."""
+    gathered inside the kernel (device-resident dataset, shuffled minibatches).
+    response may be a SparseRows (mask None, row_index None or a range of consecutive persons): vibo_amd/sparse.py."""
+    if isinstance(response, SparseRows):
+        return _sparse.fused_elbo(spec, table, item, flow, response, mask, eps, reg_mode=reg_mode, row_index=row_index, reducer=reducer)
     response, mask, code = prepare_rows(response, mask)
     I = response.shape[1]
     spec.check_supported(I)
@@ -1081,6 +1088,8 @@ def fused_elbo(spec, table, item, flow, response, mask, eps, *, reg_mode=_lib.RE
 
 def encode_posterior(spec, table, response, mask, row_index=None):
     """Forward-only q(ability | responses): (mu, logvar) [B,A] (models.py:356-371 under no_grad)."""
+    if isinstance(response, SparseRows):
+        return _sparse.encode_posterior(spec, table, response, mask, row_index=row_index)
     response, mask, code = prepare_rows(response, mask)
     B = int(row_index.numel()) if row_index is not None else response.shape[0]
     return _BACKEND['encode'](spec, response, mask, code, row_index, table.detach().contiguous(), B)

@@ -1,0 +1,401 @@
+"""Sparse response rows: a matrix held as its observed cells only (include/vibo_hip_sparse_rows.h states the image; this module
+builds it with torch ops on the data's device and calls the three exports that read it).
+
+    rows = SparseRows.from_dense(response, mask)          # or from_cell_codes / from_coo / from_arrays
+    ops.fused_elbo(spec, table, item, None, rows, None, eps, row_index=range(a, b))
+    model.elbo_step(rows.rows(range(a, b)), None)         # a range view goes wherever a `response` goes, with mask=None
+
+Covered: the plain model (unconditional product-of-experts posterior, IRT decoder, no flows, ability_dim 1..8), contiguous person
+ranges.  Everything else raises NotImplementedError naming the format: gathered minibatches (a tensor row_index), person sharding
+(a reducer), the conditional and caller-supplied posteriors, flows, ability_dim 9..16.
+"""
+import ctypes
+import math
+
+import torch
+
+from . import _lib
+
+FORMAT = 'sparse rows'
+CHUNK = _lib.SPARSE_CHUNK
+
+
+class RowBlock:
+    """A block of consecutive persons, range(start, stop): what a resident split on sparse rows yields as a minibatch's `row_index`.
+    It answers numel() like the index tensors of the other formats, so the loops that weight a loss by the batch size need no change."""
+    __slots__ = ('start', 'stop')
+
+    def __init__(self, start, stop):
+        self.start, self.stop = int(start), int(stop)
+
+    def numel(self):
+        return self.stop - self.start
+
+    __len__ = numel
+
+    def as_range(self):
+        return range(self.start, self.stop)
+
+    def __repr__(self):
+        return f'RowBlock({self.start}, {self.stop})'
+
+
+def _as_range(rows, num_person):
+    """None / range (step 1) / RowBlock -> range inside [0, num_person); anything else is refused by name."""
+    if rows is None:
+        return range(0, num_person)
+    if isinstance(rows, RowBlock):
+        rows = rows.as_range()
+    if isinstance(rows, torch.Tensor):
+        raise NotImplementedError(f'{FORMAT}: a tensor row_index (a gathered minibatch) is not covered -- pass a range of consecutive '
+                                  f'persons; arbitrary gathers are a follow-up')
+    if not isinstance(rows, range) or rows.step != 1:
+        raise NotImplementedError(f'{FORMAT}: row_index must be None or a range with step 1, not {rows!r}')
+    if len(rows) < 1 or rows.start < 0 or rows.stop > num_person:
+        raise ValueError(f'{FORMAT}: persons {rows!r} are not a non-empty range inside [0, {num_person})')
+    return rows
+
+
+def check_spec(spec):
+    """The ElboSpecs the format does not cover raise here, by name, instead of surfacing as the library's -8."""
+    if spec.conditional:
+        raise NotImplementedError(f'{FORMAT}: the conditional posterior is not covered (unconditional product of experts only)')
+    if spec.given:
+        raise NotImplementedError(f'{FORMAT}: a caller-supplied posterior (--ability-merge mean, VI) is not covered')
+    if spec.n_flows > 0:
+        raise NotImplementedError(f'{FORMAT}: planar flows are not covered (n_flows must be 0)')
+    if not (1 <= spec.ability_dim <= _lib.MAX_ABILITY_DIM_FAST):
+        raise NotImplementedError(f'{FORMAT}: ability_dim={spec.ability_dim} is not covered (1..{_lib.MAX_ABILITY_DIM_FAST})')
+
+
+def _cells(index, right):
+    """index << 1 | right as the image stores it: the uint32's bits in an int32 tensor."""
+    return ((index.to(torch.int64) << 1) | right.to(torch.int64)).to(torch.int32)
+
+
+def _index_of(cells):
+    return (cells.to(torch.int64) & 0xffffffff) >> 1
+
+
+def _ptr_from_counts(index, n):
+    counts = torch.bincount(index, minlength=n)
+    return torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)])
+
+
+def chunk_list(col_ptr, chunk=CHUNK):
+    """(col_chunk int64 [I + 1], chunk_item int32 [n], chunk_first int64 [n]) of a column pointer array: every column's list cut into
+    pieces of at most `chunk` entries, columns in order, pieces in order."""
+    lens = col_ptr[1:] - col_ptr[:-1]
+    n = (lens + (chunk - 1)) // chunk
+    col_chunk = torch.cat([n.new_zeros(1), torch.cumsum(n, 0)])
+    items = torch.repeat_interleave(torch.arange(lens.numel(), device=col_ptr.device), n)
+    piece = torch.arange(items.numel(), device=col_ptr.device) - col_chunk[items]
+    return col_chunk, items.to(torch.int32), col_ptr[items] + chunk * piece
+
+
+class SparseRows:
+    """The device arrays of an image of P persons x I items, or a view of a range of its persons (rows()).  Passed wherever a
+    `response` goes, with mask=None."""
+
+    def __init__(self, row_ptr, row_cell, col_ptr, col_cell, num_person, num_item, *, _view=None):
+        self.row_ptr, self.row_cell, self.col_ptr, self.col_cell = row_ptr, row_cell, col_ptr, col_cell
+        self.image_persons, self.num_item = int(num_person), int(num_item)
+        if not (1 <= self.image_persons < 2 ** 31 and 1 <= self.num_item < 2 ** 31):
+            raise ValueError(f'{FORMAT}: 1 <= P, I < 2^31')
+        for name, t, dt in (('row_ptr', row_ptr, torch.int64), ('row_cell', row_cell, torch.int32), ('col_ptr', col_ptr, torch.int64),
+                            ('col_cell', col_cell, torch.int32)):
+            if t.dtype != dt or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError(f'{FORMAT}: {name} must be a contiguous 1-d {dt} tensor (cells: the uint32 bits)')
+        if row_ptr.numel() != self.image_persons + 1 or col_ptr.numel() != self.num_item + 1 or row_cell.numel() != col_cell.numel():
+            raise ValueError(f'{FORMAT}: row_ptr [P + 1], col_ptr [I + 1], row_cell and col_cell [nnz]')
+        self.nnz = int(row_cell.numel())
+        if _view is None:
+            self.col_chunk, self.chunk_item, self.chunk_first = chunk_list(col_ptr)
+            self.bad_cells = torch.zeros(1, dtype=torch.int64, device=row_ptr.device)      # the library's sticky counter
+            self.row0, self.num_person = 0, self.image_persons
+        else:
+            base, rng = _view
+            self.col_chunk, self.chunk_item, self.chunk_first, self.bad_cells = base.col_chunk, base.chunk_item, base.chunk_first, base.bad_cells
+            self.row0, self.num_person = base.row0 + rng.start, len(rng)
+        self.num_chunk = int(self.chunk_item.numel())
+
+    # ---- builders ----
+    @classmethod
+    def from_coo(cls, person, item, right, num_person, num_item, check=True):
+        """From the observed cells as three equally long vectors (any order; a cell listed twice fails check())."""
+        person, item = person.to(torch.int64).reshape(-1), item.to(torch.int64).reshape(-1)
+        right = (right.reshape(-1) != 0)
+        if person.numel() and (int(person.min()) < 0 or int(person.max()) >= num_person or int(item.min()) < 0 or int(item.max()) >= num_item):
+            raise ValueError(f'{FORMAT}: a cell outside {num_person} persons x {num_item} items')
+        by_row = torch.argsort(person * num_item + item)
+        by_col = torch.argsort(item * num_person + person)
+        self = cls(_ptr_from_counts(person, num_person), _cells(item[by_row], right[by_row]),
+                   _ptr_from_counts(item, num_item), _cells(person[by_col], right[by_col]), num_person, num_item)
+        if check:
+            self.check()
+        return self
+
+    @classmethod
+    def from_arrays(cls, row_ptr, row_cell, col_ptr, col_cell, num_person, num_item):
+        """From a caller's CSR + CSC arrays as the header lays them out (the chunk list is built here); runs check() once."""
+        self = cls(row_ptr, row_cell, col_ptr, col_cell, num_person, num_item)
+        self.check()
+        return self
+
+    @classmethod
+    def _from_observed(cls, observed, right):
+        """observed, right: bool [P, I].  Both sides come out of nonzero() in their order: valid by construction, no check()."""
+        P, I = observed.shape
+        rc = observed.nonzero()
+        row_ptr = _ptr_from_counts(rc[:, 0], P)
+        row_cell = _cells(rc[:, 1], right[rc[:, 0], rc[:, 1]])
+        del rc
+        cr = observed.t().nonzero()
+        col_ptr = _ptr_from_counts(cr[:, 0], I)
+        col_cell = _cells(cr[:, 1], right[cr[:, 1], cr[:, 0]])
+        return cls(row_ptr, row_cell, col_ptr, col_cell, P, I)
+
+    @classmethod
+    def from_dense(cls, response, mask):
+        """From [P, I(, 1)] responses (1.0 = right) and a mask (nonzero = observed; None: every cell)."""
+        response = response.reshape(response.shape[0], response.shape[1])
+        observed = torch.ones_like(response, dtype=torch.bool) if mask is None else (mask.reshape(response.shape) != 0)
+        return cls._from_observed(observed, response == 1)
+
+    @classmethod
+    def from_cell_codes(cls, codes):
+        """From 1-byte cell codes (ops.CellCodes, or its [P, I] uint8 tensor): 0 wrong, 1 right, 2 missing."""
+        c = codes.codes if hasattr(codes, 'codes') else codes
+        return cls._from_observed(c != 2, c == 1)
+
+    # ---- the image ----
+    shape = property(lambda self: (self.num_person, self.num_item))
+    device = property(lambda self: self.row_ptr.device)
+    density = property(lambda self: self.nnz / (self.image_persons * self.num_item))
+
+    def dim(self):
+        return 2
+
+    def __len__(self):
+        return self.num_person
+
+    def rows(self, rng):
+        """The persons `rng` (a range with step 1, or a RowBlock) of this image as a view: the same arrays, another range."""
+        return SparseRows(self.row_ptr, self.row_cell, self.col_ptr, self.col_cell, self.image_persons, self.num_item,
+                          _view=(self, _as_range(rng, self.num_person)))
+
+    def to(self, device):
+        if self.row0 != 0 or self.num_person != self.image_persons:
+            raise ValueError(f'{FORMAT}: move the whole image, not a range view')
+        return SparseRows(self.row_ptr.to(device), self.row_cell.to(device), self.col_ptr.to(device), self.col_cell.to(device),
+                          self.image_persons, self.num_item)
+
+    def image(self, columns=True):
+        """struct vibo_sparse_image of the arrays (device pointers); columns=False: the row side alone."""
+        im = _lib.ViboSparseImage()
+        im.num_person, im.num_item, im.nnz = self.image_persons, self.num_item, self.nnz
+        im.row_ptr, im.row_cell = self.row_ptr.data_ptr(), self.row_cell.data_ptr()
+        if columns:
+            im.num_chunk = self.num_chunk
+            im.col_ptr, im.col_cell, im.col_chunk = self.col_ptr.data_ptr(), self.col_cell.data_ptr(), self.col_chunk.data_ptr()
+            im.chunk_item, im.chunk_first = self.chunk_item.data_ptr(), self.chunk_first.data_ptr()
+        return im
+
+    def to_dense(self, rng=None):
+        """(response fp32 [n, I] with -1 at missing cells, mask bool [n, I]) of the persons `rng` of this view."""
+        rng = _as_range(rng, self.num_person)
+        a, b = self.row0 + rng.start, self.row0 + rng.stop
+        k0, k1 = int(self.row_ptr[a]), int(self.row_ptr[b])
+        counts = self.row_ptr[a + 1:b + 1] - self.row_ptr[a:b]
+        person = torch.repeat_interleave(torch.arange(b - a, device=self.device), counts)
+        cells = self.row_cell[k0:k1].to(torch.int64) & 0xffffffff
+        response = torch.full((b - a, self.num_item), -1.0, dtype=torch.float32, device=self.device)
+        mask = torch.zeros(b - a, self.num_item, dtype=torch.bool, device=self.device)
+        response[person, cells >> 1] = (cells & 1).float()
+        mask[person, cells >> 1] = True
+        return response, mask
+
+    @property
+    def bad_index_count(self):
+        """Cells the launches on this image skipped because their index was out of range (sticky; 0 on a valid image)."""
+        return int(self.bad_cells.item())
+
+    def check(self):
+        """Run the validation pass (vibo_sparse_rows_check; on host tensors its mirror check_host) and raise with the count."""
+        from . import ops
+        n = ops._BACKEND['sparse_check'](self)
+        if n:
+            raise ValueError(f'{FORMAT}: the image fails {n} of its invariants (pointers monotone, indices in range, lists sorted, '
+                             f'both sides the same cells, chunk list consistent with col_ptr)')
+
+    def violations(self):
+        """The validation pass's count, as a number."""
+        from . import ops
+        return ops._BACKEND['sparse_check'](self)
+
+
+def check_host(rows):
+    """vibo_sparse_rows_check restated on the host, check by check (csrc/vibo_sparse.hip): the count of failed checks.  Plain Python
+    loops: for tests and small images."""
+    P, I, nnz = rows.image_persons, rows.num_item, rows.nnz
+    row_ptr, col_ptr = rows.row_ptr.cpu().tolist(), rows.col_ptr.cpu().tolist()
+    row_cell = (rows.row_cell.cpu().to(torch.int64) & 0xffffffff).tolist()
+    col_cell = (rows.col_cell.cpu().to(torch.int64) & 0xffffffff).tolist()
+    col_chunk, chunk_item, chunk_first = rows.col_chunk.cpu().tolist(), rows.chunk_item.cpu().tolist(), rows.chunk_first.cpu().tolist()
+    num_chunk = len(chunk_item)
+
+    def sane(a, b):
+        return 0 <= a <= b <= nnz
+
+    def lower_bound(cell, lo, hi, key):
+        while lo < hi:
+            mid = lo + ((hi - lo) >> 1)
+            if (cell[mid] >> 1) < key:
+                lo = mid + 1
+            else:
+                hi = mid
+        return lo
+
+    def side(ptr, cell, n_lists, limit, other=None):
+        v = 0
+        for q in range(n_lists):
+            a, b = ptr[q], ptr[q + 1]
+            v += (q == 0 and a != 0) + (q == n_lists - 1 and b != nnz)
+            if not sane(a, b):
+                v += 1
+                continue
+            for k in range(a, b):
+                idx = cell[k] >> 1
+                v += idx >= limit
+                v += k > a and (cell[k - 1] >> 1) >= idx
+                if other is not None and idx < other[2]:
+                    ra, rb = other[0][idx], other[0][idx + 1]
+                    found = False
+                    if sane(ra, rb):
+                        pos = lower_bound(other[1], ra, rb, q)
+                        found = pos < rb and other[1][pos] == ((q << 1) | (cell[k] & 1))
+                    v += not found
+        return v
+
+    v = side(row_ptr, row_cell, P, I) + side(col_ptr, col_cell, I, P, (row_ptr, row_cell, P))
+    for i in range(I):
+        c0, c1 = col_chunk[i], col_chunk[i + 1]
+        v += (i == 0 and c0 != 0) + (i == I - 1 and c1 != num_chunk)
+        a, b = col_ptr[i], col_ptr[i + 1]
+        if sane(a, b):
+            expect = (b - a + CHUNK - 1) // CHUNK
+            if c0 < 0 or c1 > num_chunk or c1 - c0 != expect:
+                v += 1
+            else:
+                v += sum(chunk_item[c0 + t] != i or chunk_first[c0 + t] != a + t * CHUNK for t in range(expect))
+    return int(v)
+
+
+# ---- the native calls (ops._BACKEND['sparse_elbo' | 'sparse_encode' | 'sparse_check']) ----
+def _desc(spec, B, I, reg_mode, want_grad):
+    from . import ops
+    return ops._make_desc(spec, B, I, _lib.MASK_NONE, reg_mode, want_grad, 0, 0)      # (mask_dtype and the strides are not read)
+
+
+def _hip_sparse_check(rows):
+    if not rows.row_ptr.is_cuda:
+        return check_host(rows)
+    from . import ops
+    out = torch.zeros(1, dtype=torch.int64, device=rows.device)
+    im = rows.image()
+    ops._call('vibo_sparse_rows_check', ctypes.byref(im), ops._ptr(out), ops._stream(rows.device))
+    return int(out.item())
+
+
+def _hip_sparse_elbo(spec, rows, table, item, eps, reg_mode, want_grad):
+    """vibo_sparse_elbo_fwd_bwd on the view's persons, on the current stream -> ops.RawElbo."""
+    from . import ops
+    ops._require_device(rows.row_ptr, table, item, eps)
+    dev = rows.device
+    B, I, A, D = rows.num_person, rows.num_item, spec.ability_dim, spec.item_dim
+    table_shape = tuple(table.shape)
+    n_table, n_item = math.prod(table_shape), I * D
+    flat = torch.empty(_lib.NUM_SCALARS + 2 * n_table + n_item, dtype=torch.float32, device=dev)
+    post = torch.empty(3, B, A, dtype=torch.float32, device=dev)
+    d = _desc(spec, B, I, reg_mode, want_grad)
+    im = rows.image(columns=bool(want_grad))
+    ws_bytes = _lib.load().vibo_sparse_workspace_bytes(ctypes.byref(d), ctypes.c_int64(im.num_chunk))
+    if ws_bytes == 0:
+        _lib.check(-8, 'vibo_sparse_workspace_bytes')
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    vp, fbase = ctypes.c_void_p, flat.data_ptr()
+    ops._call('vibo_sparse_elbo_fwd_bwd', ctypes.byref(d), ctypes.byref(im), ctypes.c_int64(rows.row0), ops._ptr(table), ops._ptr(item),
+              ops._ptr(eps), vp(fbase), ops._ptr(post[0]), ops._ptr(post[1]), ops._ptr(post[2]), vp(fbase + 4 * _lib.NUM_SCALARS),
+              vp(fbase + 4 * (_lib.NUM_SCALARS + 2 * n_table)), ops._ptr(rows.bad_cells), ops._ptr(ws), ctypes.c_size_t(ws_bytes),
+              ops._stream(dev))
+    return ops.RawElbo(flat=flat, n_table=n_table, n_item=n_item, n_flow=0, table_shape=table_shape, ability_mu=post[0],
+                       ability_logvar=post[1], ability=post[2], ability_k=None, ability_ladj=None)
+
+
+def _hip_sparse_encode(spec, rows, table):
+    from . import ops
+    ops._require_device(rows.row_ptr, table)
+    dev = rows.device
+    out = torch.empty(2, rows.num_person, spec.ability_dim, dtype=torch.float32, device=dev)
+    d = _desc(spec, rows.num_person, rows.num_item, _lib.REG_KL, False)
+    im = rows.image(columns=False)
+    ops._call('vibo_sparse_encode', ctypes.byref(d), ctypes.byref(im), ctypes.c_int64(rows.row0), ops._ptr(table), ops._ptr(out[0]),
+              ops._ptr(out[1]), ops._ptr(rows.bad_cells), ops._stream(dev))
+    return out[0], out[1]
+
+
+class SparseFusedELBO(torch.autograd.Function):
+    """ops.FusedELBO on sparse rows: (table, item) -> the same eight outputs, the same composition g_ll grad[0] + g_reg grad[1]."""
+
+    @staticmethod
+    def forward(ctx, table, item, rows, eps, spec, reg_mode):
+        from . import ops
+        need_grad = any(ctx.needs_input_grad[:2])
+        raw = ops._BACKEND['sparse_elbo'](spec, rows, table.detach().contiguous(), item.detach().contiguous(), eps.contiguous(),
+                                          reg_mode, need_grad)
+        ctx.raw, ctx.item_shape, ctx.need_grad = raw, tuple(item.shape), need_grad
+        sc = raw.scalars
+        outs = (sc[_lib.S_LL].clone(), sc[_lib.S_REG].clone(), sc.clone(), raw.ability_mu, raw.ability_logvar, raw.ability,
+                raw.ability, sc.new_zeros(()))
+        ctx.mark_non_differentiable(*outs[2:])
+        return outs
+
+    @staticmethod
+    def backward(ctx, g_ll, g_reg, *_):
+        raw = ctx.raw
+        if not ctx.need_grad:
+            return (None,) * 6
+        g_table = g_ll * raw.grad_table(0) + g_reg * raw.grad_table(1) if ctx.needs_input_grad[0] else None
+        g_item = g_ll * raw.grad_item(ctx.item_shape) if ctx.needs_input_grad[1] else None
+        return (g_table, g_item) + (None,) * 4
+
+
+def _view(rows, mask, row_index, reducer=None):
+    if mask is not None:
+        raise ValueError(f'{FORMAT} carry their own missingness: pass mask=None')
+    if reducer is not None:
+        raise NotImplementedError(f'{FORMAT}: person sharding (a reducer) is not covered')
+    return rows if row_index is None else rows.rows(row_index)
+
+
+def fused_elbo(spec, table, item, flow, rows, mask, eps, *, reg_mode=_lib.REG_KL, row_index=None, reducer=None):
+    """ops.fused_elbo's branch for a SparseRows `response`."""
+    check_spec(spec)
+    rows = _view(rows, mask, row_index, reducer)
+    B, I = rows.shape
+    if flow is not None:
+        raise NotImplementedError(f'{FORMAT}: planar flows are not covered')
+    if tuple(table.shape) != spec.table_shape(I, B):
+        raise ValueError(f'table shape {tuple(table.shape)} != {spec.table_shape(I, B)}')
+    if tuple(item.shape) != (I, spec.item_dim):
+        raise ValueError(f'item shape {tuple(item.shape)} != {(I, spec.item_dim)}')
+    if tuple(eps.shape) != (B, spec.ability_dim):
+        raise ValueError(f'eps shape {tuple(eps.shape)} != {(B, spec.ability_dim)}')
+    return SparseFusedELBO.apply(table, item, rows, eps, spec, reg_mode)
+
+
+def encode_posterior(spec, table, rows, mask, row_index=None):
+    """ops.encode_posterior's branch for a SparseRows `response`."""
+    from . import ops
+    check_spec(spec)
+    return ops._BACKEND['sparse_encode'](spec, _view(rows, mask, row_index), table.detach().contiguous())

@@ -26,6 +26,7 @@ import torch
 
 from .. import config, ops
 from ..datasets import artificially_mask_dataset, load_dataset
+from ..sparse import RowBlock, SparseRows
 from ..utils import AverageMeter, save_checkpoint
 from .models import VIBO_1PL, VIBO_2PL, VIBO_3PL
 
@@ -70,11 +71,18 @@ def build_parser():
     # additive (not in the reference)
     p.add_argument('--torch-optimizer', action='store_true', default=False,
                    help='use autograd + torch.optim.Adam for the O(I) part instead of the fused HIP trainer kernels')
-    p.add_argument('--row-format', choices=['auto', 'f32', 'codes'], default='auto',
+    p.add_argument('--row-format', choices=['auto', 'f32', 'codes', 'sparse'], default='auto',
                    help="device-resident rows: 'f32' = the reference's fp32 responses + mask bytes (5 B/cell), 'codes' = "
                         "one byte per cell (same results, a fifth of the memory and HBM traffic); 'auto' = codes "
                         "whenever the fused kernels support them (--cuda, 4..32767 items, ability dim <= 4 with "
-                        "--conditional-posterior)")
+                        "--conditional-posterior); 'sparse' = the observed cells only (opt-in, never chosen by 'auto'; vibo_amd/sparse.py): "
+                        "the one format above 32767 items; below that the record (profiles/sparse_rows_record.txt) supports it only "
+                        "around 100000 persons x 10000 items at densities of 2 %% and below, at 1000 items 'codes' won at every measured "
+                        "density -- "
+                        "plain model only (product encoder, unconditional posterior, IRT decoder, no flows, ability dim <= 8, one "
+                        "GPU, module + torch.optim.Adam step); minibatches are blocks of --batch-size CONSECUTIVE persons of the split's "
+                        "stored order visited in a fresh random order every epoch (block-shuffled SGD, not a per-epoch permutation of "
+                        "persons; the real-world loaders store the persons in a seeded shuffle already)")
     p.add_argument('--rng', choices=['torch', 'native'], default='torch',
                    help="reparameterisation noise of the fused trainer: torch.randn (the stream torch.manual_seed(--seed) governs) or "
                         "the library's Philox generator drawn inside the prologue kernel (two launches fewer per step)")
@@ -138,8 +146,37 @@ def check_supported(args):
         why = native_decoder_step_problem(args)
         if why:
             problems.append(f"--native-decoder-step with {why} (that configuration trains through the module + torch.optim.Adam: drop the flag)")
+    if getattr(args, 'row_format', 'auto') == 'sparse':
+        why = sparse_rows_problems(args)
+        if why:
+            problems.append('--row-format sparse with ' + ', '.join(why) + ' (sparse rows cover the plain model on one GPU)')
     if problems:
         raise SystemExit('not supported by the MI355X engine: ' + '; '.join(problems))
+
+
+def sparse_rows_problems(args, num_item=None):
+    """What --row-format sparse cannot serve among these flags ([] : nothing), from the flags alone; with num_item (known once the data
+    is loaded, or from --num-item) also the item count past which the dense engine cannot densify blocks for log_marginal."""
+    from .. import ops
+    why = []
+    if args.conditional_posterior:
+        why.append('--conditional-posterior')
+    if args.n_norm_flows > 0:
+        why.append('--n-norm-flows')
+    if args.ability_merge != 'product':
+        why.append(f'--ability-merge {args.ability_merge}')
+    if args.generative_model != 'irt':
+        why.append(f'--generative-model {args.generative_model} (an MLP decoder)')
+    if args.ability_dim > 8:
+        why.append('--ability-dim above 8')
+    if int(os.environ.get('WORLD_SIZE', '1')) > 1:
+        why.append('WORLD_SIZE > 1 (person sharding)')
+    if not args.cuda and ops._BACKEND['sparse_elbo'] is ops._sparse._hip_sparse_elbo:
+        why.append('no --cuda')
+    num_item = num_item if num_item is not None else getattr(args, 'num_item', None)
+    if num_item is not None and num_item > 32767 and not args.no_marginal:
+        why.append(f'{num_item} items without --no-marginal (log_marginal densifies each block, and the dense engine stops at 32767 items)')
+    return why
 
 
 def native_decoder_step_problem(args):
@@ -169,14 +206,17 @@ def out_dir_name(args):
 
 class ResidentSplit:
     """One dataset split resident on the device: response f32 [P,I] + mask bool [P,I] (the reference's layout, 5 B per
-    cell), or with row_format='codes' one byte per cell (ops.CellCodes; mask is None then)."""
+    cell), with row_format='codes' one byte per cell (ops.CellCodes; mask is None then), or with row_format='sparse' the observed
+    cells only (sparse.SparseRows; mask is None, and batches() yields blocks of consecutive persons)."""
 
     def __init__(self, dataset, device, row_slice=None, row_format='f32'):
         r, m = dataset.matrix()
         if row_slice is not None:
             r, m = r[row_slice], m[row_slice]
         # rows padded to 16 bytes when the item count is not a multiple of 4 (vector loads of the row-split kernel)
-        if row_format == 'codes':
+        if row_format == 'sparse':
+            self.response, self.mask = SparseRows.from_dense(torch.from_numpy(r).to(device), torch.from_numpy(m).to(device)), None
+        elif row_format == 'codes':
             self.response, self.mask = ops.pack_cell_codes(torch.from_numpy(r).to(device), torch.from_numpy(m).to(device)), None
         else:
             self.response, self.mask = ops.pad_rows(torch.from_numpy(r).to(device), torch.from_numpy(m).to(device))
@@ -185,6 +225,8 @@ class ResidentSplit:
 
     def rows(self, index):
         """(response, mask) of the persons `index` as their own small matrices."""
+        if isinstance(self.response, SparseRows):          # (log_marginal: the block densified, on the dense path)
+            return self.response.to_dense(index.as_range())
         if isinstance(self.response, ops.CellCodes):
             return self.response.rows(index), None
         return self.response[index], self.mask[index]
@@ -198,7 +240,17 @@ class ResidentSplit:
     def batches(self, batch_size, shuffle, generator=None, n_steps=None):
         """Row-index vectors (int64, on device); the kernel gathers the rows itself.  With n_steps (person-sharded runs) the
         shard is cut into exactly that many nearly equal minibatches instead of ceil(rows / batch_size) of them: a rank
-        whose shard is one row shorter must not run one step (= one all-reduce) fewer than its peers."""
+        whose shard is one row shorter must not run one step (= one all-reduce) fewer than its peers.
+        Sparse rows: RowBlocks of batch_size consecutive persons instead -- in order, or with shuffle in a fresh random order of the
+        blocks (one torch.randperm over block ids per epoch): block-shuffled SGD over the split's stored row order."""
+        if isinstance(self.response, SparseRows):
+            if n_steps is not None:
+                raise NotImplementedError('sparse rows: person sharding is not covered')
+            n_blocks = (self.num_person + batch_size - 1) // batch_size
+            order = torch.randperm(n_blocks, device=self.device, generator=generator).tolist() if shuffle else range(n_blocks)
+            for b in order:
+                yield RowBlock(b * batch_size, min(self.num_person, (b + 1) * batch_size))
+            return
         if shuffle:
             order = torch.randperm(self.num_person, device=self.device, generator=generator)
         else:
@@ -481,7 +533,11 @@ def main(argv=None):
         return slice(rank * n // world, (rank + 1) * n // world) if world > 1 else None
     row_format = args.row_format
     codes_ok = bool(args.cuda) and 4 <= num_item <= 32767 and args.ability_dim <= 8      # (9..16 ability dims: the wave-per-person kernel reads fp32 rows)
-    if row_format == 'auto':
+    if row_format == 'sparse':          # (opt-in; the item count is known now: the log_marginal ceiling once more)
+        why = sparse_rows_problems(args, num_item)
+        if why:
+            raise SystemExit('not supported by the MI355X engine: --row-format sparse with ' + ', '.join(why))
+    elif row_format == 'auto':
         row_format = 'codes' if codes_ok else 'f32'
     elif row_format == 'codes' and not codes_ok:
         raise SystemExit('--row-format codes needs --cuda, 4..32767 items and --ability-dim <= 8')
@@ -514,7 +570,9 @@ def main(argv=None):
         model.enable_person_sharding(lambda flat: dist.all_reduce(flat), seed=args.seed, rank=rank)
     trainer = None
     from ..trainer import fused_trainer_covers
-    if args.cuda and not args.torch_optimizer and fused_trainer_covers(model, args.hidden_dim):      # (else: module + torch.optim.Adam)
+    if row_format == 'sparse':
+        pass          # module path: model.elbo_step + torch.optim.Adam on blocks of persons; no FusedTrainer, no graph replay
+    elif args.cuda and not args.torch_optimizer and fused_trainer_covers(model, args.hidden_dim):      # (else: module + torch.optim.Adam)
         # the whole step natively: FusedTrainer's kernels, (conditional posterior / planar flows) FusedCondFlowTrainer's, or
         # (--ability-merge mean, unconditional posterior) FusedMeanTrainer's -- same Adam arithmetic, 2-12 launches
         # per step, no PyTorch autograd inside the replayed graph
@@ -536,7 +594,7 @@ def main(argv=None):
     # `deep` decoder's item network at 1 500) -- DESIGN.md section 4.  Round 6 isolated it: pure PyTorch shows the same fault
     # (tools/repro_graph_replay_bias_grad.py: 8 192 rows wrong from replay 22 on, also with frozen parameters) -- a fault of the
     # PyTorch-ROCm hipGraph stack, not of this library's launches.  The default stays the eager step.
-    module_graph = trainer is None and args.cuda and world == 1 and not args.no_graph and args.graph_module_step
+    module_graph = trainer is None and args.cuda and world == 1 and not args.no_graph and args.graph_module_step and row_format != 'sparse'
     # (capturable: Adam's step counter and bias corrections stay on the device -- required inside a captured graph)
     # (fused: one multi-tensor launch for all parameters instead of ~40 small ones; same update rule)
     optimizer = torch.optim.Adam(model.parameters(), lr=args.lr, capturable=bool(module_graph), fused=bool(args.cuda))
