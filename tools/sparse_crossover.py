@@ -15,6 +15,17 @@ plus the gathered 4 (D + A) (the item's row in the person pass, theta in the ite
 
     python tools/sparse_crossover.py --out profiles/sparse_rows_record_table.txt
 
+--gathered times minibatches instead (include/vibo_hip_sparse_gather.h): at 100k x 10k and densities 2 % and 0.1 %, forward + backward
+for B = 1 024, 16 384 and P persons of the resident matrix, three legs per row:
+
+    gather   vibo_sparse_elbo_fwd_bwd_gather on rows.take(randperm(P)[:B])                 (the item pass streams the whole column side)
+    range    vibo_sparse_elbo_fwd_bwd on B consecutive persons of the same image           (the item pass bisects its chunks to the range)
+    codes    the cell-code format's in-kernel gather of the same B persons (row_index)     (B x I code bytes)
+
+timed the same way; the gather leg is compared with the codes leg on the same persons before a time is quoted.
+
+    python tools/sparse_crossover.py --gathered --out profiles/sparse_gather_record_table.txt
+
 A run without a GPU fails: there is no fallback and no number.
 """
 import argparse
@@ -102,6 +113,55 @@ def fmt_ms(ts):
     return f'{statistics.median(ts):9.3f} ({min(ts):.3f} - {max(ts):.3f})'
 
 
+GATHER_SHAPE = (100_000, 10_000)
+GATHER_DENSITIES = (0.02, 0.001)
+GATHER_BATCHES = (1_024, 16_384, None)          # None: every person
+
+
+def gathered_table(args, dev, gen, spec):
+    """The --gathered table's lines (see the docstring)."""
+    D = spec.item_dim
+    P, I = max(64, int(GATHER_SHAPE[0] * args.scale)), GATHER_SHAPE[1]
+    table, item, eps = problem(P, I, gen, dev)
+    lines = [f'{"shape":>16} {"density":>8} {"cells":>12} {"B":>7} {"batch cells":>12} | {"gather leg ms":>28} {"range leg ms":>28} '
+             f'{"codes leg (row_index) ms":>28} | {"column side MB":>14} | gather agrees with codes']
+    for density in GATHER_DENSITIES:
+        right, observed = draw_matrix(P, I, density, gen, dev)
+        codes_t = torch.where(observed, right.to(torch.uint8), torch.full((), 2, dtype=torch.uint8, device=dev))
+        padded = torch.full((P, (I + 15) // 16 * 16), 2, dtype=torch.uint8, device=dev)
+        padded[:, :I] = codes_t
+        codes = ops.CellCodes(padded[:, :I])
+        rows = SparseRows._from_observed(observed, right)
+        del right, observed, codes_t
+        for B in GATHER_BATCHES:
+            B = P if B is None else min(B, P)
+            idx = torch.randperm(P, device=dev, generator=gen)[:B].contiguous()
+            view, start, e = rows.take(idx), (P - B) // 2, eps[:B].contiguous()
+            block = rows.rows(range(start, start + B))
+
+            def gather_leg():
+                return sparse._hip_sparse_elbo(spec, view, table, item, e, _lib.REG_KL, True)
+
+            def range_leg():
+                return sparse._hip_sparse_elbo(spec, block, table, item, e, _lib.REG_KL, True)
+
+            def codes_leg():
+                return ops._hip_launch_elbo(spec, codes.codes, codes.codes, _lib.MASK_CODES, idx, table, item, e, None, _lib.REG_KL, True, B)
+
+            ok, why = worst_disagreement(gather_leg(), codes_leg(), (I, D))
+            torch.cuda.synchronize()
+            t = time_blocks({'gather': gather_leg, 'range': range_leg, 'codes': codes_leg}, args.blocks, args.block_seconds)
+            batch_cells = int((rows.row_ptr[idx + 1] - rows.row_ptr[idx]).sum())
+            lines.append(f'{f"{P} x {I}":>16} {density:8.3%} {rows.nnz:12d} {B:7d} {batch_cells:12d} | '
+                         f'{fmt_ms(t["gather"]) if ok else "outputs differ":>28} {fmt_ms(t["range"]):>28} {fmt_ms(t["codes"]):>28} | '
+                         f'{4 * rows.nnz / 1e6:14.1f} | {"yes" if ok else "NO"}: {why}')
+            print(lines[-1], flush=True)
+        assert rows.bad_index_count == 0 and bool((rows.slot_map() == _lib.SPARSE_NO_SLOT).all())
+        del codes, padded, rows
+        torch.cuda.empty_cache()
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('--out', default=None, help='also write the table to this file')
@@ -109,6 +169,7 @@ def main(argv=None):
     ap.add_argument('--block-seconds', type=float, default=0.15, help='launches per block are sized to about this long')
     ap.add_argument('--scale', type=float, default=1.0, help='scale every person count (rehearsals; the record is taken at 1.0)')
     ap.add_argument('--skip-wide', action='store_true', help='leave out the 1M x 100k sparse-only row')
+    ap.add_argument('--gathered', action='store_true', help='the gathered-minibatch table instead (gather / range / codes legs at 100k x 10k)')
     args = ap.parse_args(argv)
     if not torch.cuda.is_available():
         raise SystemExit('sparse_crossover: no GPU -- nothing is measured without one')
@@ -118,6 +179,17 @@ def main(argv=None):
     gen = torch.Generator(device=dev).manual_seed(0)
     spec = ops.ElboSpec(irt_model=IRT, ability_dim=A)
     D = spec.item_dim
+    if args.gathered:
+        lines = ['command: python tools/sparse_crossover.py ' + ' '.join(sys.argv[1:] if argv is None else argv),
+                 f'device: {torch.cuda.get_device_name(0)}; 2PL, ability_dim {A}, forward + backward, VIBO_SPARSE_CHUNK {_lib.SPARSE_CHUNK}',
+                 'ms per launch: median (min - max) over %d alternating blocks' % args.blocks, ''] + gathered_table(args, dev, gen, spec)
+        text = '\n'.join(lines) + '\n'
+        print(text)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, 'w') as f:
+                f.write(text)
+        return
     lines = ['command: python tools/sparse_crossover.py ' + ' '.join(sys.argv[1:] if argv is None else argv),
              f'device: {torch.cuda.get_device_name(0)}; 2PL, ability_dim {A}, forward + backward, VIBO_SPARSE_CHUNK {_lib.SPARSE_CHUNK}',
              'ms per launch: median (min - max) over %d alternating blocks' % args.blocks,

@@ -1,5 +1,7 @@
 // vibo_sparse.hip -- the ELBO, the encode and the validation pass on sparse response rows (include/vibo_hip_sparse_rows.h: THE IMAGE,
 // THE GRID RULE), with their extern "C" tails.  The plain model only: unconditional product-of-experts posterior, IRT decoder, no flows.
+// The person, encode and item kernels are stated once and instantiated twice: for a contiguous range of persons (GATHER = false, the
+// calls of that header) and for an index vector of persons (GATHER = true, include/vibo_hip_sparse_gather.h: THE INDEX AND THE MAP).
 //
 //   person pass   one wave per row of the call, lane l the row's cells l, l + 64, ...:
 //                 counts (answered wrong / right) -> product of experts from the counts -> sample, heads -> decode over the row's cells
@@ -7,11 +9,13 @@
 //                 gradient.  theta goes to `ability`; every wave leaves one partial record.
 //   item pass     one wave per chunk of a column's list: bisect the chunk to the call's persons, gather theta, the same logit
 //                 statements again, d LL / d item summed over the chunk (no g[nnz] store, no read-back through a permutation).
+//   gathered      the person pass takes a row's person from person_index; the item pass walks whole chunks and finds a person's row of
+//                 the call in person_slot, a map built before the person pass (an integer atomicMin) and cleared after the item finish.
 //   finish        fixed-order sums of the waves' records (heads, table gradient) and of the chunks' records (items of several chunks).
 // The statements of the math are those of the unconditional branch of vibo_general.hip; the table gradient's row-invariant factors
 // (tau; tau^2 exp(logvar)) are multiplied in once per wave instead of once per row.  No float atomics, no LDS, no index is trusted.
 #include <hip/hip_runtime.h>
-#include "../../include/vibo_hip_sparse_rows.h"
+#include "../../include/vibo_hip_sparse_gather.h"
 #include "vibo_device.hpp"
 #include "vibo_host.hpp"
 
@@ -30,6 +34,8 @@ struct SparseParams {
     const int32_t* chunk_item;
     const int64_t* chunk_first;
     long long P, nnz, num_chunk, row0;
+    const int64_t* person_index;   // gathered calls: [B], the person of the call's row r
+    int32_t* person_slot;          // gathered calls with gradients: [P], person -> the row of the call that owns it, or VIBO_SPARSE_NO_SLOT
     int I, B, A, D, irt, missing_mode, reg_mode, want_grad;
     const float* table;
     const float* item;
@@ -96,10 +102,27 @@ __device__ __forceinline__ void cell_terms(const int irt, const int A, const flo
     }
 }
 
-// The call's row r: its cell range (pointer entries clamped to [0, nnz]) and its counts; cells whose item is >= I are counted in `bad`.
-__device__ __forceinline__ void row_counts(const SparseParams& p, const long long r, const int lane, long long& k0, long long& k1,
+// The person q of the call's row r: row0 + r, or (GATHER) person_index[r].  -> whether the row is live: q inside the image and, where the
+// call has a map (`mapped`: gradients), row r the one that owns q.  Wave-uniform.
+template <bool GATHER>
+__device__ __forceinline__ bool row_person(const SparseParams& p, const long long r, const bool mapped, long long& q) {
+    if constexpr (!GATHER) {
+        q = p.row0 + r;
+        return true;
+    } else {
+        q = p.person_index[r];
+        if (q < 0 || q >= p.P) return false;
+        if (mapped && p.person_slot[q] != (int32_t)r) return false;
+        unsigned qv = (unsigned)q;                  // (q < P < 2^31)
+        asm volatile("" : "+v"(qv));                // (kept in a vector register: as scalars the person and its cell range spill scalar registers at MA = 3)
+        q = qv;
+        return true;
+    }
+}
+
+// Person q: its cell range (pointer entries clamped to [0, nnz]) and its counts; cells whose item is >= I are counted in `bad`.
+__device__ __forceinline__ void row_counts(const SparseParams& p, const long long q, const int lane, long long& k0, long long& k1,
                                            int& n0, int& n1, int& bad) {
-    const long long q = p.row0 + r;
     k0 = clamp_ll(p.row_ptr[q], 0, p.nnz);
     k1 = clamp_ll(p.row_ptr[q + 1], k0, p.nnz);
     int c0 = 0, c1 = 0;
@@ -124,7 +147,7 @@ __device__ __forceinline__ void poe_counts(const float n0, const float n1, const
     amu = smu * ilam;
 }
 
-template <int MA>
+template <int MA, bool GATHER>
 __global__ __launch_bounds__(256) void sparse_person_kernel(const SparseParams p) {
     const int lane = threadIdx.x & 63;
     constexpr int A = MA;      // (one instantiation per ability_dim: every `a < A` below is decided at compile time)
@@ -157,9 +180,18 @@ __global__ __launch_bounds__(256) void sparse_person_kernel(const SparseParams p
     int bad = 0;
 
     for (long long r = w; r < p.B; r += n_waves) {
-        long long k0, k1;
+        long long q, k0, k1;
+        if (!row_person<GATHER>(p, r, grad, q)) {      // an index outside the image, or a person an earlier row owns: zeros, one more in `bad`
+            if (lane == 0) {
+#pragma unroll
+                for (int a = 0; a < MA; ++a)
+                    if (a < A) p.ability_mu[r * A + a] = p.ability_logvar[r * A + a] = p.ability[r * A + a] = 0.f;
+                ++bad;
+            }
+            continue;
+        }
         int n0i, n1i;
-        row_counts(p, r, lane, k0, k1, n0i, n1i, bad);
+        row_counts(p, q, lane, k0, k1, n0i, n1i, bad);
         const float n0 = (float)n0i, n1 = (float)n1i;
         const float nmiss = p.missing_mode == VIBO_MISSING_PRIOR ? (float)(p.I - n0i - n1i) : 0.f;
         s_nobs += n0i + n1i;
@@ -274,7 +306,7 @@ __global__ __launch_bounds__(256) void sparse_person_kernel(const SparseParams p
 }
 
 // vibo_sparse_encode: the posterior of the call's rows from their counts
-template <int MA>
+template <int MA, bool GATHER>
 __global__ __launch_bounds__(256) void sparse_encode_kernel(const SparseParams p) {
     const int lane = threadIdx.x & 63;
     constexpr int A = MA;
@@ -282,9 +314,18 @@ __global__ __launch_bounds__(256) void sparse_encode_kernel(const SparseParams p
     const long long n_waves = (long long)gridDim.x * 4;
     int bad = 0;
     for (long long r = w; r < p.B; r += n_waves) {
-        long long k0, k1;
+        long long q, k0, k1;
+        if (!row_person<GATHER>(p, r, false, q)) {      // (no map: every row is independent, repeats are ordinary rows)
+            if (lane == 0) {
+#pragma unroll
+                for (int a = 0; a < MA; ++a)
+                    if (a < A) p.ability_mu[r * A + a] = p.ability_logvar[r * A + a] = 0.f;
+                ++bad;
+            }
+            continue;
+        }
         int n0i, n1i;
-        row_counts(p, r, lane, k0, k1, n0i, n1i, bad);
+        row_counts(p, q, lane, k0, k1, n0i, n1i, bad);
         const float nmiss = p.missing_mode == VIBO_MISSING_PRIOR ? (float)(p.I - n0i - n1i) : 0.f;
         if (lane == 0) {
 #pragma unroll
@@ -302,7 +343,7 @@ __global__ __launch_bounds__(256) void sparse_encode_kernel(const SparseParams p
     if (lane == 0 && tbad > 0 && p.bad) atomicAdd(p.bad, (unsigned long long)tbad);
 }
 
-template <int MA>
+template <int MA, bool GATHER>
 __global__ __launch_bounds__(256) void sparse_item_kernel(const SparseParams p) {
     const int lane = threadIdx.x & 63;
     constexpr int A = MA;      // (one instantiation per ability_dim: every `a < A` below is decided at compile time)
@@ -314,8 +355,12 @@ __global__ __launch_bounds__(256) void sparse_item_kernel(const SparseParams p) 
     const long long first = clamp_ll(p.chunk_first[c], 0, p.nnz);
     long long end = clamp_ll(p.col_ptr[i + 1], first, p.nnz);
     if (end > first + kChunk) end = first + kChunk;
-    const long long lo = lower_bound_cell(p.col_cell, first, end, p.row0);
-    const long long hi = lower_bound_cell(p.col_cell, lo, end, p.row0 + p.B);
+    // the call's entries: a range of persons is one window of the sorted chunk; an index vector may name any of them (the whole chunk)
+    long long lo = first, hi = end;
+    if constexpr (!GATHER) {
+        lo = lower_bound_cell(p.col_cell, first, end, p.row0);
+        hi = lower_bound_cell(p.col_cell, lo, end, p.row0 + p.B);
+    }
 
     const float* it = p.item + (size_t)i * D;
     float disc[MA], diff, glogit = 0.f;
@@ -339,8 +384,14 @@ __global__ __launch_bounds__(256) void sparse_item_kernel(const SparseParams p) 
         const uint32_t cell = p.col_cell[k];
         const long long q = cell >> 1;
         if (q >= p.P) { ++bad; continue; }
-        const long long r = q - p.row0;
-        if (r < 0 || r >= p.B) continue;                   // (a list out of order: the person is not this call's)
+        long long r;
+        if constexpr (GATHER) {
+            r = p.person_slot[q];
+            if (r == VIBO_SPARSE_NO_SLOT) continue;        // not a person of this call
+        } else {
+            r = q - p.row0;
+        }
+        if (r < 0 || r >= p.B) continue;                   // (a list out of order, a map entry that is no row: the person is not this call's)
         float th[MA];
 #pragma unroll
         for (int a = 0; a < MA; ++a) th[a] = (a < A) ? p.ability[r * A + a] : 0.f;
@@ -376,6 +427,17 @@ __global__ __launch_bounds__(256) void sparse_item_kernel(const SparseParams p) 
     if (lane < D) dst[lane] = out;
     const int tbad = wave_total_i(bad);
     if (lane == 0 && tbad > 0 && p.bad) atomicAdd(p.bad, (unsigned long long)tbad);
+}
+
+// The map of a gathered call with gradients, B threads.  BUILD: the smallest row r that names person q owns it (an integer minimum: the
+// same whatever the arrival order); else the clear: the call's entries back to VIBO_SPARSE_NO_SLOT.  An index outside [0, P) writes nothing.
+template <bool BUILD>
+__global__ __launch_bounds__(256) void sparse_map_kernel(const int64_t* person_index, const long long B, const long long P, int32_t* person_slot) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= B) return;
+    const long long q = person_index[r];
+    if (q < 0 || q >= P) return;
+    if (BUILD) atomicMin(&person_slot[q], (int32_t)r); else person_slot[q] = VIBO_SPARSE_NO_SLOT;
 }
 
 // finish, heads and table gradient: workgroup 0 the four head sums and the cell count, workgroup 1 + e entry e of the records' [2][2][16] table part
@@ -519,13 +581,13 @@ static int sparse_person_blocks(int B) {
 }
 static size_t sparse_record_bytes(const vibo_desc* d) { return up256((size_t)sparse_person_blocks(d->num_person) * 4 * kRec * sizeof(float)); }
 
-// the image against the descriptor and the call's range: 0, or the code (error string set)
-static int sparse_image_rc(const vibo_desc* d, const vibo_sparse_image* im, int64_t row0, bool need_cols) {
+// the image against the descriptor and (ranged) the call's range: 0, or the code (error string set)
+static int sparse_image_rc(const vibo_desc* d, const vibo_sparse_image* im, int64_t row0, bool need_cols, bool ranged = true) {
     if (!im) return fail(-5, "sparse rows: null image");
     if (im->num_person < 1 || im->num_person >= (1ll << 31) || im->num_item < 1 || im->num_item >= (1ll << 31) || im->nnz < 0 || im->num_chunk < 0)
         return fail(-3, "sparse rows: image sizes out of range (1 <= P, I < 2^31; nnz, num_chunk >= 0)");
     if (d && im->num_item != d->num_item) return fail(-3, "sparse rows: the image has %lld items, the descriptor %d", (long long)im->num_item, d->num_item);
-    if (d && (row0 < 0 || row0 + d->num_person > im->num_person))
+    if (d && ranged && (row0 < 0 || row0 + d->num_person > im->num_person))
         return fail(-3, "sparse rows: persons [%lld, %lld) are outside the image's %lld", (long long)row0, (long long)row0 + d->num_person, (long long)im->num_person);
     if (!im->row_ptr || (im->nnz > 0 && !im->row_cell)) return fail(-5, "sparse rows: null row side");
     if (need_cols) {
@@ -546,19 +608,71 @@ static SparseParams sparse_params(const vibo_desc* d, const vibo_sparse_image* i
     return p;
 }
 
-// one instantiation per ability_dim 1..VIBO_MAX_ABILITY_DIM
-#define VIBO_SPARSE_LAUNCH(kernel, W, grid, stream, p) hipLaunchKernelGGL(kernel<W>, dim3((unsigned)(grid)), dim3(256), 0, stream, p)
-#define VIBO_SPARSE_BY_WIDTH(kernel, A, grid, stream, p)                  \
-    switch (A) {                                                          \
-        case 1: VIBO_SPARSE_LAUNCH(kernel, 1, grid, stream, p); break;    \
-        case 2: VIBO_SPARSE_LAUNCH(kernel, 2, grid, stream, p); break;    \
-        case 3: VIBO_SPARSE_LAUNCH(kernel, 3, grid, stream, p); break;    \
-        case 4: VIBO_SPARSE_LAUNCH(kernel, 4, grid, stream, p); break;    \
-        case 5: VIBO_SPARSE_LAUNCH(kernel, 5, grid, stream, p); break;    \
-        case 6: VIBO_SPARSE_LAUNCH(kernel, 6, grid, stream, p); break;    \
-        case 7: VIBO_SPARSE_LAUNCH(kernel, 7, grid, stream, p); break;    \
-        default: VIBO_SPARSE_LAUNCH(kernel, 8, grid, stream, p); break;   \
+// one instantiation per ability_dim 1..VIBO_MAX_ABILITY_DIM, for a range (G = false) and for an index vector (G = true)
+#define VIBO_SPARSE_LAUNCH(kernel, W, G, grid, stream, p) hipLaunchKernelGGL((kernel<W, G>), dim3((unsigned)(grid)), dim3(256), 0, stream, p)
+#define VIBO_SPARSE_BY_WIDTH_G(kernel, A, G, grid, stream, p)                \
+    switch (A) {                                                             \
+        case 1: VIBO_SPARSE_LAUNCH(kernel, 1, G, grid, stream, p); break;    \
+        case 2: VIBO_SPARSE_LAUNCH(kernel, 2, G, grid, stream, p); break;    \
+        case 3: VIBO_SPARSE_LAUNCH(kernel, 3, G, grid, stream, p); break;    \
+        case 4: VIBO_SPARSE_LAUNCH(kernel, 4, G, grid, stream, p); break;    \
+        case 5: VIBO_SPARSE_LAUNCH(kernel, 5, G, grid, stream, p); break;    \
+        case 6: VIBO_SPARSE_LAUNCH(kernel, 6, G, grid, stream, p); break;    \
+        case 7: VIBO_SPARSE_LAUNCH(kernel, 7, G, grid, stream, p); break;    \
+        default: VIBO_SPARSE_LAUNCH(kernel, 8, G, grid, stream, p); break;   \
     }
+#define VIBO_SPARSE_BY_WIDTH(kernel, A, gather, grid, stream, p)             \
+    if (gather) { VIBO_SPARSE_BY_WIDTH_G(kernel, A, true, grid, stream, p) } else { VIBO_SPARSE_BY_WIDTH_G(kernel, A, false, grid, stream, p) }
+
+// The ELBO call on a range (gather == false: row0) or on an index vector (gather == true: person_index, person_slot), after the
+// descriptor and the image have passed their checks: the rest of the checks and the launches.
+static int sparse_elbo_call(const vibo_desc* d, const vibo_sparse_image* im, bool gather, int64_t row0, const int64_t* person_index,
+                            int32_t* person_slot, const float* table, const float* item, const float* eps, float* out_scalars,
+                            float* ability_mu, float* ability_logvar, float* ability, float* grad_table, float* grad_item,
+                            int64_t* bad_cells, void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = 0;
+    const bool grad = d->want_grad != 0;
+    if (!table || !item || !eps || !out_scalars || !ability_mu || !ability_logvar || !ability || (grad && (!grad_table || !grad_item)))
+        return fail(-5, "sparse rows: null required pointer");
+    const size_t need = vibo_sparse_workspace_bytes(d, grad ? im->num_chunk : 0);
+    if (!workspace || workspace_bytes < need) return fail(-7, "sparse rows: workspace too small: %zu < %zu", workspace_bytes, need);
+    if ((uintptr_t)workspace & 255) return fail(-7, "sparse rows: workspace must be 256-byte aligned");
+
+    hipStream_t s = (hipStream_t)stream;
+    SparseParams p = sparse_params(d, im, row0);
+    p.person_index = person_index; p.person_slot = person_slot;
+    p.table = table; p.item = item; p.eps = eps;
+    p.ability_mu = ability_mu; p.ability_logvar = ability_logvar; p.ability = ability; p.grad_item = grad_item;
+    p.records = static_cast<float*>(workspace);
+    p.chunk_rec = reinterpret_cast<float*>(static_cast<char*>(workspace) + sparse_record_bytes(d));
+    p.bad = reinterpret_cast<unsigned long long*>(bad_cells);
+    const int G = sparse_person_blocks(p.B);
+    const bool mapped = gather && grad;
+    const unsigned map_grid = (unsigned)(((long long)p.B + 255) / 256);
+    if (mapped) {
+        hipLaunchKernelGGL(sparse_map_kernel<true>, dim3(map_grid), dim3(256), 0, s, person_index, (long long)p.B, p.P, person_slot);
+        if ((rc = launch_rc("sparse rows map build launch")) != 0) return rc;
+    }
+    VIBO_SPARSE_BY_WIDTH(sparse_person_kernel, p.A, gather, G, s, p);
+    if ((rc = launch_rc("sparse rows person pass launch")) != 0) return rc;
+    hipLaunchKernelGGL(sparse_finish_kernel, dim3(grad ? 65u : 1u), dim3(64), 0, s, p.records, 4 * G, p.A, p.reg_mode, out_scalars, grad_table);
+    if ((rc = launch_rc("sparse rows finish launch")) != 0) return rc;
+    if (!grad) return 0;
+    if (p.num_chunk > 0) {
+        const long long blocks = (p.num_chunk + 3) / 4;
+        if (blocks > 0x7fffffffll) return fail(-8, "sparse rows: more chunks than one launch takes");
+        VIBO_SPARSE_BY_WIDTH(sparse_item_kernel, p.A, gather, blocks, s, p);
+        if ((rc = launch_rc("sparse rows item pass launch")) != 0) return rc;
+    }
+    hipLaunchKernelGGL(sparse_item_finish_kernel, dim3((unsigned)(((long long)p.I * p.D + 255) / 256)), dim3(256), 0, s, p.col_chunk, p.num_chunk,
+                       p.chunk_rec, p.I, p.D, grad_item);
+    if ((rc = launch_rc("sparse rows item finish launch")) != 0) return rc;
+    if (mapped) {
+        hipLaunchKernelGGL(sparse_map_kernel<false>, dim3(map_grid), dim3(256), 0, s, person_index, (long long)p.B, p.P, person_slot);
+        rc = launch_rc("sparse rows map clear launch");
+    }
+    return rc;
+}
 
 }  // namespace vibo
 
@@ -600,36 +714,9 @@ int vibo_sparse_elbo_fwd_bwd(const vibo_desc* d, const vibo_sparse_image* im, in
                              float* grad_table, float* grad_item, int64_t* bad_cells, void* workspace, size_t workspace_bytes, void* stream) {
     int rc = sparse_desc_rc(d);
     if (rc) return rc;
-    const bool grad = d->want_grad != 0;
-    if ((rc = sparse_image_rc(d, im, row0, grad)) != 0) return rc;
-    if (!table || !item || !eps || !out_scalars || !ability_mu || !ability_logvar || !ability || (grad && (!grad_table || !grad_item)))
-        return fail(-5, "sparse rows: null required pointer");
-    const size_t need = vibo_sparse_workspace_bytes(d, grad ? im->num_chunk : 0);
-    if (!workspace || workspace_bytes < need) return fail(-7, "sparse rows: workspace too small: %zu < %zu", workspace_bytes, need);
-    if ((uintptr_t)workspace & 255) return fail(-7, "sparse rows: workspace must be 256-byte aligned");
-
-    hipStream_t s = (hipStream_t)stream;
-    SparseParams p = sparse_params(d, im, row0);
-    p.table = table; p.item = item; p.eps = eps;
-    p.ability_mu = ability_mu; p.ability_logvar = ability_logvar; p.ability = ability; p.grad_item = grad_item;
-    p.records = static_cast<float*>(workspace);
-    p.chunk_rec = reinterpret_cast<float*>(static_cast<char*>(workspace) + sparse_record_bytes(d));
-    p.bad = reinterpret_cast<unsigned long long*>(bad_cells);
-    const int G = sparse_person_blocks(p.B);
-    VIBO_SPARSE_BY_WIDTH(sparse_person_kernel, p.A, G, s, p);
-    if ((rc = launch_rc("sparse rows person pass launch")) != 0) return rc;
-    hipLaunchKernelGGL(sparse_finish_kernel, dim3(grad ? 65u : 1u), dim3(64), 0, s, p.records, 4 * G, p.A, p.reg_mode, out_scalars, grad_table);
-    if ((rc = launch_rc("sparse rows finish launch")) != 0) return rc;
-    if (!grad) return 0;
-    if (p.num_chunk > 0) {
-        const long long blocks = (p.num_chunk + 3) / 4;
-        if (blocks > 0x7fffffffll) return fail(-8, "sparse rows: more chunks than one launch takes");
-        VIBO_SPARSE_BY_WIDTH(sparse_item_kernel, p.A, blocks, s, p);
-        if ((rc = launch_rc("sparse rows item pass launch")) != 0) return rc;
-    }
-    hipLaunchKernelGGL(sparse_item_finish_kernel, dim3((unsigned)(((long long)p.I * p.D + 255) / 256)), dim3(256), 0, s, p.col_chunk, p.num_chunk,
-                       p.chunk_rec, p.I, p.D, grad_item);
-    return launch_rc("sparse rows item finish launch");
+    if ((rc = sparse_image_rc(d, im, row0, d->want_grad != 0)) != 0) return rc;
+    return sparse_elbo_call(d, im, false, row0, nullptr, nullptr, table, item, eps, out_scalars, ability_mu, ability_logvar, ability, grad_table,
+                            grad_item, bad_cells, workspace, workspace_bytes, stream);
 }
 
 int vibo_sparse_encode(const vibo_desc* d, const vibo_sparse_image* im, int64_t row0, const float* table, float* ability_mu,
@@ -641,7 +728,35 @@ int vibo_sparse_encode(const vibo_desc* d, const vibo_sparse_image* im, int64_t 
     SparseParams p = sparse_params(d, im, row0);
     p.table = table; p.ability_mu = ability_mu; p.ability_logvar = ability_logvar;
     p.bad = reinterpret_cast<unsigned long long*>(bad_cells);
-    VIBO_SPARSE_BY_WIDTH(sparse_encode_kernel, p.A, sparse_person_blocks(p.B), (hipStream_t)stream, p);
+    VIBO_SPARSE_BY_WIDTH(sparse_encode_kernel, p.A, false, sparse_person_blocks(p.B), (hipStream_t)stream, p);
+    return launch_rc("sparse rows encode launch");
+}
+
+int vibo_sparse_elbo_fwd_bwd_gather(const vibo_desc* d, const vibo_sparse_image* im, const int64_t* person_index, int32_t* person_slot,
+                                    const float* table, const float* item, const float* eps, float* out_scalars, float* ability_mu,
+                                    float* ability_logvar, float* ability, float* grad_table, float* grad_item, int64_t* bad_cells,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    int rc = sparse_desc_rc(d);
+    if (rc) return rc;
+    if ((rc = sparse_image_rc(d, im, 0, d->want_grad != 0, false)) != 0) return rc;
+    if (!person_index) return fail(-5, "sparse rows: null person_index");
+    if (d->want_grad && !person_slot) return fail(-5, "sparse rows: gradients of a gathered call need the person_slot map");
+    return sparse_elbo_call(d, im, true, 0, person_index, person_slot, table, item, eps, out_scalars, ability_mu, ability_logvar, ability,
+                            grad_table, grad_item, bad_cells, workspace, workspace_bytes, stream);
+}
+
+int vibo_sparse_encode_gather(const vibo_desc* d, const vibo_sparse_image* im, const int64_t* person_index, const float* table,
+                              float* ability_mu, float* ability_logvar, int64_t* bad_cells, void* stream) {
+    int rc = sparse_desc_rc(d);
+    if (rc) return rc;
+    if ((rc = sparse_image_rc(d, im, 0, false, false)) != 0) return rc;
+    if (!person_index) return fail(-5, "sparse rows: null person_index");
+    if (!table || !ability_mu || !ability_logvar) return fail(-5, "sparse rows: null required pointer");
+    SparseParams p = sparse_params(d, im, 0);
+    p.person_index = person_index;
+    p.table = table; p.ability_mu = ability_mu; p.ability_logvar = ability_logvar;
+    p.bad = reinterpret_cast<unsigned long long*>(bad_cells);
+    VIBO_SPARSE_BY_WIDTH(sparse_encode_kernel, p.A, true, sparse_person_blocks(p.B), (hipStream_t)stream, p);
     return launch_rc("sparse rows encode launch");
 }
 

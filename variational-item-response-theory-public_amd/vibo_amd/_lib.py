@@ -2,8 +2,9 @@
 restype / argtypes come from its prototype (parse_prototypes); the constants and the two structs mirror the header by hand
 (tests/test_capi_symbols.py compares them).  Exports declared in a header of their own beside it (EXTRA_HEADERS:
 vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h, vibo_hip_tile_rows.h, vibo_hip_given_tiles.h,
-vibo_hip_sparse_rows.h) are bound the same way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself, EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS,
-PERSON_TABLE_SYMBOLS, TILE_ROWS_SYMBOLS, GIVEN_TILES_SYMBOLS and SPARSE_ROWS_SYMBOLS are theirs.
+vibo_hip_sparse_rows.h, vibo_hip_sparse_gather.h) are bound the same way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself,
+EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS, PERSON_TABLE_SYMBOLS, TILE_ROWS_SYMBOLS, GIVEN_TILES_SYMBOLS, SPARSE_ROWS_SYMBOLS and
+SPARSE_GATHER_SYMBOLS are theirs.
 
 The product path has no CPU or eager-PyTorch fallback: if the HIP library is
 missing or a call fails, this module raises.
@@ -25,6 +26,7 @@ MASK_TILES = 6                # include/vibo_hip_tile_rows.h: `response` is the 
 TILE_WAVE_BLOCK_BYTES = 4352  # ... one wave's 128 items x 32 rows: 16 code words and a counts dword per lane
 # include/vibo_hip_sparse_rows.h: the matrix as its observed cells (VIBO_SPARSE_*)
 SPARSE_CHUNK, SPARSE_ROWS_PER_BLOCK, SPARSE_MAX_BLOCKS, SPARSE_RECORD_FLOATS = 512, 32, 1024, 72
+SPARSE_NO_SLOT = 0x7fffffff   # include/vibo_hip_sparse_gather.h: a person_slot entry no row of a gathered call owns
 REG_KL, REG_SAMPLED = 0, 1
 FLAG_KERNEL_VALU, FLAG_KERNEL_MATRIX, FLAG_NO_EMIT_CODES, FLAG_COND_VALU, FLAG_COND_MATRIX, FLAG_COND_THREE_PASS = 1, 2, 4, 8, 16, 32
 KERNEL_NAMES = {1: 'matrix row-split (msplit_kernel)', 2: 'VALU row-split (split_kernel)', 3: 'wave-per-row', 4: 'tiled',
@@ -127,7 +129,7 @@ def parse_prototypes(header):
 
 
 EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h', 'vibo_hip_person_tables.h', 'vibo_hip_tile_rows.h',
-                 'vibo_hip_given_tiles.h', 'vibo_hip_sparse_rows.h')
+                 'vibo_hip_given_tiles.h', 'vibo_hip_sparse_rows.h', 'vibo_hip_sparse_gather.h')
 
 with open(HEADER_PATH) as _header:
     PROTOTYPES = parse_prototypes(_header.read())
@@ -146,6 +148,7 @@ PERSON_TABLE_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_person_tables.h']      # the VI
 TILE_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_tile_rows.h']
 GIVEN_TILES_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_given_tiles.h']          # the tile image under a caller-supplied posterior (ops._tile_rows)
 SPARSE_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sparse_rows.h']          # the matrix as its observed cells (vibo_amd/sparse.py)
+SPARSE_GATHER_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sparse_gather.h']      # ... for an index vector of persons (SparseRows.take)
 PTRAIN_VI, PTRAIN_MLE = 0, 1                                            # VIBO_PTRAIN_*
 PTRAIN_MAX_BLOCKS = 2048                                                # VIBO_PTRAIN_MAX_BLOCKS: the table update's grid cap
 

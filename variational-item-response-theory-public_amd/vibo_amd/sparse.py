@@ -1,12 +1,19 @@
 """Sparse response rows: a matrix held as its observed cells only (include/vibo_hip_sparse_rows.h states the image; this module
-builds it with torch ops on the data's device and calls the three exports that read it).
+builds it with torch ops on the data's device and calls the exports that read it: the range calls of that header and the gathered
+calls of include/vibo_hip_sparse_gather.h).
 
     rows = SparseRows.from_dense(response, mask)          # or from_cell_codes / from_coo / from_arrays
     ops.fused_elbo(spec, table, item, None, rows, None, eps, row_index=range(a, b))
     model.elbo_step(rows.rows(range(a, b)), None)         # a range view goes wherever a `response` goes, with mask=None
+    model.elbo_step(rows, None, row_index=RowGather(idx)) # a gathered minibatch: idx int64 [B] on the image's device
+    model.encode(rows.take(idx), None)                    # the same as a view
 
-Covered: the plain model (unconditional product-of-experts posterior, IRT decoder, no flows, ability_dim 1..8), contiguous person
-ranges.  Everything else raises NotImplementedError naming the format: gathered minibatches (a tensor row_index), person sharding
+Covered: the plain model (unconditional product-of-experts posterior, IRT decoder, no flows, ability_dim 1..8) on contiguous person
+ranges and on index vectors of persons.  A range call costs its persons' cells.  A gathered call's person pass costs the batch's
+cells, but its item pass streams the image's whole column side whatever the batch size (the header says why): small batches of a
+large image pay for it.  With gradients a person named twice in one index vector is owned by its first row; the later rows come
+back as zeros and are counted in bad_index_count, as is an index outside the image.
+Everything else raises NotImplementedError naming the format: a bare tensor row_index (wrap it in RowGather), person sharding
 (a reducer), the conditional and caller-supplied posteriors, flows, ability_dim 9..16.
 """
 import ctypes
@@ -40,6 +47,25 @@ class RowBlock:
         return f'RowBlock({self.start}, {self.stop})'
 
 
+class RowGather:
+    """An index vector of persons (int64 [B], on the image's device, relative to the view it is applied to): what a resident split on
+    sparse rows yields as a person-shuffled minibatch's `row_index`, beside RowBlock."""
+    __slots__ = ('index',)
+
+    def __init__(self, index):
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
+            raise ValueError(f'{FORMAT}: RowGather takes a non-empty 1-d int64 tensor of persons')
+        self.index = index
+
+    def numel(self):
+        return int(self.index.numel())
+
+    __len__ = numel
+
+    def __repr__(self):
+        return f'RowGather({self.numel()} persons)'
+
+
 def _as_range(rows, num_person):
     """None / range (step 1) / RowBlock -> range inside [0, num_person); anything else is refused by name."""
     if rows is None:
@@ -47,8 +73,8 @@ def _as_range(rows, num_person):
     if isinstance(rows, RowBlock):
         rows = rows.as_range()
     if isinstance(rows, torch.Tensor):
-        raise NotImplementedError(f'{FORMAT}: a tensor row_index (a gathered minibatch) is not covered -- pass a range of consecutive '
-                                  f'persons; arbitrary gathers are a follow-up')
+        raise NotImplementedError(f'{FORMAT}: a bare tensor row_index is not taken -- wrap it, row_index=sparse.RowGather(index), or pass '
+                                  f'the view rows.take(index) (a gathered call has its own cost and its own rule for repeats)')
     if not isinstance(rows, range) or rows.step != 1:
         raise NotImplementedError(f'{FORMAT}: row_index must be None or a range with step 1, not {rows!r}')
     if len(rows) < 1 or rows.start < 0 or rows.stop > num_person:
@@ -94,8 +120,8 @@ def chunk_list(col_ptr, chunk=CHUNK):
 
 
 class SparseRows:
-    """The device arrays of an image of P persons x I items, or a view of a range of its persons (rows()).  Passed wherever a
-    `response` goes, with mask=None."""
+    """The device arrays of an image of P persons x I items, or a view of its persons: a range (rows()) or an index vector (take(),
+    with an `index` attribute; None on every other object).  Passed wherever a `response` goes, with mask=None."""
 
     def __init__(self, row_ptr, row_cell, col_ptr, col_cell, num_person, num_item, *, _view=None):
         self.row_ptr, self.row_cell, self.col_ptr, self.col_cell = row_ptr, row_cell, col_ptr, col_cell
@@ -112,11 +138,23 @@ class SparseRows:
         if _view is None:
             self.col_chunk, self.chunk_item, self.chunk_first = chunk_list(col_ptr)
             self.bad_cells = torch.zeros(1, dtype=torch.int64, device=row_ptr.device)      # the library's sticky counter
-            self.row0, self.num_person = 0, self.image_persons
+            self._slot = [None]          # the gathered calls' person_slot map, made on first use; views share the holder
+            self.row0, self.num_person, self.index, self.image_index = 0, self.image_persons, None, None
         else:
-            base, rng = _view
+            base, rng, index = _view
             self.col_chunk, self.chunk_item, self.chunk_first, self.bad_cells = base.col_chunk, base.chunk_item, base.chunk_first, base.bad_cells
-            self.row0, self.num_person = base.row0 + rng.start, len(rng)
+            self._slot = base._slot
+            if index is None:
+                self.row0, self.num_person, self.index, self.image_index = base.row0 + rng.start, len(rng), None, None
+            else:
+                # image_index: the same persons counted from the image's first.  Of the whole image: the index as it is (the launches
+                # check it); of a range view: an entry outside the view becomes -1, which no launch follows
+                self.row0, self.num_person, self.index = base.row0, int(index.numel()), index
+                if base.row0 == 0 and base.num_person == base.image_persons:
+                    self.image_index = index
+                else:
+                    inside = (index >= 0) & (index < base.num_person)
+                    self.image_index = torch.where(inside, index + base.row0, torch.full_like(index, -1)).contiguous()
         self.num_chunk = int(self.chunk_item.numel())
 
     # ---- builders ----
@@ -179,14 +217,39 @@ class SparseRows:
     def __len__(self):
         return self.num_person
 
+    def _no_gathered(self, what):
+        if self.index is not None:
+            raise NotImplementedError(f'{FORMAT}: {what} of a gathered view is not covered -- index the vector instead: take(index[...]) '
+                                      f'of the view it was taken from')
+
     def rows(self, rng):
         """The persons `rng` (a range with step 1, or a RowBlock) of this image as a view: the same arrays, another range."""
+        self._no_gathered('rows()')
         return SparseRows(self.row_ptr, self.row_cell, self.col_ptr, self.col_cell, self.image_persons, self.num_item,
-                          _view=(self, _as_range(rng, self.num_person)))
+                          _view=(self, _as_range(rng, self.num_person), None))
+
+    def take(self, index):
+        """The persons index[0..B) of this image or range view (int64 [B] on its device, or a RowGather; persons relative to this view)
+        as a view of B rows: row r is person index[r].  Nothing is copied and nothing is read back: an entry outside the view is left
+        to the launches, which skip it, return zeros for its row and count it (bad_index_count)."""
+        self._no_gathered('take()')
+        index = index.index if isinstance(index, RowGather) else index
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
+            raise ValueError(f'{FORMAT}: take() needs a non-empty 1-d int64 tensor of persons')
+        if index.device != self.device:
+            raise ValueError(f'{FORMAT}: the index is on {index.device}, the image on {self.device}')
+        return SparseRows(self.row_ptr, self.row_cell, self.col_ptr, self.col_cell, self.image_persons, self.num_item,
+                          _view=(self, None, index.contiguous()))
+
+    def slot_map(self):
+        """The gathered calls' person_slot map of this image (int32 [P], all NO_SLOT between calls), made on first use."""
+        if self._slot[0] is None:
+            self._slot[0] = torch.full((self.image_persons,), _lib.SPARSE_NO_SLOT, dtype=torch.int32, device=self.device)
+        return self._slot[0]
 
     def to(self, device):
-        if self.row0 != 0 or self.num_person != self.image_persons:
-            raise ValueError(f'{FORMAT}: move the whole image, not a range view')
+        if self.index is not None or self.row0 != 0 or self.num_person != self.image_persons:
+            raise ValueError(f'{FORMAT}: move the whole image, not a view')
         return SparseRows(self.row_ptr.to(device), self.row_cell.to(device), self.col_ptr.to(device), self.col_cell.to(device),
                           self.image_persons, self.num_item)
 
@@ -202,15 +265,27 @@ class SparseRows:
         return im
 
     def to_dense(self, rng=None):
-        """(response fp32 [n, I] with -1 at missing cells, mask bool [n, I]) of the persons `rng` of this view."""
+        """(response fp32 [n, I] with -1 at missing cells, mask bool [n, I]) of the persons `rng` of this view; of a gathered view
+        its rows in the index's order (dense[index]; the index must lie inside the view it was taken from)."""
         rng = _as_range(rng, self.num_person)
-        a, b = self.row0 + rng.start, self.row0 + rng.stop
-        k0, k1 = int(self.row_ptr[a]), int(self.row_ptr[b])
-        counts = self.row_ptr[a + 1:b + 1] - self.row_ptr[a:b]
-        person = torch.repeat_interleave(torch.arange(b - a, device=self.device), counts)
-        cells = self.row_cell[k0:k1].to(torch.int64) & 0xffffffff
-        response = torch.full((b - a, self.num_item), -1.0, dtype=torch.float32, device=self.device)
-        mask = torch.zeros(b - a, self.num_item, dtype=torch.bool, device=self.device)
+        if self.index is not None:
+            q = self.image_index[rng.start:rng.stop]
+            if int(q.min()) < 0 or int(q.max()) >= self.image_persons:
+                raise ValueError(f'{FORMAT}: the index names a person outside the view it was taken from')
+            first, counts = self.row_ptr[q], self.row_ptr[q + 1] - self.row_ptr[q]
+            n = int(q.numel())
+            person = torch.repeat_interleave(torch.arange(n, device=self.device), counts)
+            within = torch.arange(person.numel(), device=self.device) - (torch.cumsum(counts, 0) - counts)[person]
+            cells = self.row_cell[first[person] + within].to(torch.int64) & 0xffffffff
+        else:
+            a, b = self.row0 + rng.start, self.row0 + rng.stop
+            n = b - a
+            k0, k1 = int(self.row_ptr[a]), int(self.row_ptr[b])
+            counts = self.row_ptr[a + 1:b + 1] - self.row_ptr[a:b]
+            person = torch.repeat_interleave(torch.arange(n, device=self.device), counts)
+            cells = self.row_cell[k0:k1].to(torch.int64) & 0xffffffff
+        response = torch.full((n, self.num_item), -1.0, dtype=torch.float32, device=self.device)
+        mask = torch.zeros(n, self.num_item, dtype=torch.bool, device=self.device)
         response[person, cells >> 1] = (cells & 1).float()
         mask[person, cells >> 1] = True
         return response, mask
@@ -308,7 +383,8 @@ def _hip_sparse_check(rows):
 
 
 def _hip_sparse_elbo(spec, rows, table, item, eps, reg_mode, want_grad):
-    """vibo_sparse_elbo_fwd_bwd on the view's persons, on the current stream -> ops.RawElbo."""
+    """vibo_sparse_elbo_fwd_bwd on the view's persons, or vibo_sparse_elbo_fwd_bwd_gather on a gathered view's, on the current stream
+    -> ops.RawElbo."""
     from . import ops
     ops._require_device(rows.row_ptr, table, item, eps)
     dev = rows.device
@@ -324,10 +400,20 @@ def _hip_sparse_elbo(spec, rows, table, item, eps, reg_mode, want_grad):
         _lib.check(-8, 'vibo_sparse_workspace_bytes')
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     vp, fbase = ctypes.c_void_p, flat.data_ptr()
-    ops._call('vibo_sparse_elbo_fwd_bwd', ctypes.byref(d), ctypes.byref(im), ctypes.c_int64(rows.row0), ops._ptr(table), ops._ptr(item),
-              ops._ptr(eps), vp(fbase), ops._ptr(post[0]), ops._ptr(post[1]), ops._ptr(post[2]), vp(fbase + 4 * _lib.NUM_SCALARS),
-              vp(fbase + 4 * (_lib.NUM_SCALARS + 2 * n_table)), ops._ptr(rows.bad_cells), ops._ptr(ws), ctypes.c_size_t(ws_bytes),
-              ops._stream(dev))
+    tail = (ops._ptr(table), ops._ptr(item), ops._ptr(eps), vp(fbase), ops._ptr(post[0]), ops._ptr(post[1]), ops._ptr(post[2]),
+            vp(fbase + 4 * _lib.NUM_SCALARS), vp(fbase + 4 * (_lib.NUM_SCALARS + 2 * n_table)), ops._ptr(rows.bad_cells), ops._ptr(ws),
+            ctypes.c_size_t(ws_bytes), ops._stream(dev))
+    if rows.index is None:
+        ops._call('vibo_sparse_elbo_fwd_bwd', ctypes.byref(d), ctypes.byref(im), ctypes.c_int64(rows.row0), *tail)
+    else:
+        slot = rows.slot_map() if want_grad else None
+        try:
+            ops._call('vibo_sparse_elbo_fwd_bwd_gather', ctypes.byref(d), ctypes.byref(im), ops._ptr(rows.image_index),
+                      ops._ptr(slot), *tail)
+        except BaseException:
+            if slot is not None:          # (a call that stopped between the map's build and its clear: the next one needs it empty)
+                slot.fill_(_lib.SPARSE_NO_SLOT)
+            raise
     return ops.RawElbo(flat=flat, n_table=n_table, n_item=n_item, n_flow=0, table_shape=table_shape, ability_mu=post[0],
                        ability_logvar=post[1], ability=post[2], ability_k=None, ability_ladj=None)
 
@@ -339,8 +425,11 @@ def _hip_sparse_encode(spec, rows, table):
     out = torch.empty(2, rows.num_person, spec.ability_dim, dtype=torch.float32, device=dev)
     d = _desc(spec, rows.num_person, rows.num_item, _lib.REG_KL, False)
     im = rows.image(columns=False)
-    ops._call('vibo_sparse_encode', ctypes.byref(d), ctypes.byref(im), ctypes.c_int64(rows.row0), ops._ptr(table), ops._ptr(out[0]),
-              ops._ptr(out[1]), ops._ptr(rows.bad_cells), ops._stream(dev))
+    tail = (ops._ptr(table), ops._ptr(out[0]), ops._ptr(out[1]), ops._ptr(rows.bad_cells), ops._stream(dev))
+    if rows.index is None:
+        ops._call('vibo_sparse_encode', ctypes.byref(d), ctypes.byref(im), ctypes.c_int64(rows.row0), *tail)
+    else:          # (no map: every row is independent)
+        ops._call('vibo_sparse_encode_gather', ctypes.byref(d), ctypes.byref(im), ops._ptr(rows.image_index), *tail)
     return out[0], out[1]
 
 
@@ -375,7 +464,9 @@ def _view(rows, mask, row_index, reducer=None):
         raise ValueError(f'{FORMAT} carry their own missingness: pass mask=None')
     if reducer is not None:
         raise NotImplementedError(f'{FORMAT}: person sharding (a reducer) is not covered')
-    return rows if row_index is None else rows.rows(row_index)
+    if row_index is None:
+        return rows
+    return rows.take(row_index) if isinstance(row_index, RowGather) else rows.rows(row_index)
 
 
 def fused_elbo(spec, table, item, flow, rows, mask, eps, *, reg_mode=_lib.REG_KL, row_index=None, reducer=None):

@@ -26,7 +26,7 @@ import torch
 
 from .. import config, ops
 from ..datasets import artificially_mask_dataset, load_dataset
-from ..sparse import RowBlock, SparseRows
+from ..sparse import RowBlock, RowGather, SparseRows
 from ..utils import AverageMeter, save_checkpoint
 from .models import VIBO_1PL, VIBO_2PL, VIBO_3PL
 
@@ -83,6 +83,15 @@ def build_parser():
                         "GPU, module + torch.optim.Adam step); minibatches are blocks of --batch-size CONSECUTIVE persons of the split's "
                         "stored order visited in a fresh random order every epoch (block-shuffled SGD, not a per-epoch permutation of "
                         "persons; the real-world loaders store the persons in a seeded shuffle already)")
+    p.add_argument('--sparse-shuffle', choices=['blocks', 'persons'], default='blocks',
+                   help="with --row-format sparse, the training minibatches: 'blocks' = the block-shuffled order above; 'persons' = "
+                        "one random permutation of the persons per epoch cut into --batch-size pieces, as the dense formats and the "
+                        "reference's DataLoader(shuffle=True) draw them (gathered calls, include/vibo_hip_sparse_gather.h).  The price: "
+                        "a gathered step's item pass streams the split's WHOLE column side, 4 bytes per observed cell of the matrix, "
+                        "whatever --batch-size is, where a block's step reads its own cells only -- it pays where the stored order "
+                        "carries structure and the batch is a fair share of the split, and costs most at small batches of a large "
+                        "split (profiles/sparse_gather_record.txt: at 100000 persons x 10000 items a gathered step took 7 to 43 %% "
+                        "longer than a block step, 0.154 against 0.108 ms for 1024 persons at a density of 2 %%)")
     p.add_argument('--rng', choices=['torch', 'native'], default='torch',
                    help="reparameterisation noise of the fused trainer: torch.randn (the stream torch.manual_seed(--seed) governs) or "
                         "the library's Philox generator drawn inside the prologue kernel (two launches fewer per step)")
@@ -150,6 +159,8 @@ def check_supported(args):
         why = sparse_rows_problems(args)
         if why:
             problems.append('--row-format sparse with ' + ', '.join(why) + ' (sparse rows cover the plain model on one GPU)')
+    elif getattr(args, 'sparse_shuffle', 'blocks') != 'blocks':
+        problems.append(f'--sparse-shuffle {args.sparse_shuffle} without --row-format sparse (the other formats shuffle persons already)')
     if problems:
         raise SystemExit('not supported by the MI355X engine: ' + '; '.join(problems))
 
@@ -207,9 +218,11 @@ def out_dir_name(args):
 class ResidentSplit:
     """One dataset split resident on the device: response f32 [P,I] + mask bool [P,I] (the reference's layout, 5 B per
     cell), with row_format='codes' one byte per cell (ops.CellCodes; mask is None then), or with row_format='sparse' the observed
-    cells only (sparse.SparseRows; mask is None, and batches() yields blocks of consecutive persons)."""
+    cells only (sparse.SparseRows; mask is None, and batches() yields blocks of consecutive persons or, shuffled under
+    sparse_shuffle='persons', gathered minibatches)."""
 
-    def __init__(self, dataset, device, row_slice=None, row_format='f32'):
+    def __init__(self, dataset, device, row_slice=None, row_format='f32', sparse_shuffle='blocks'):
+        self.sparse_shuffle = sparse_shuffle
         r, m = dataset.matrix()
         if row_slice is not None:
             r, m = r[row_slice], m[row_slice]
@@ -226,7 +239,7 @@ class ResidentSplit:
     def rows(self, index):
         """(response, mask) of the persons `index` as their own small matrices."""
         if isinstance(self.response, SparseRows):          # (log_marginal: the block densified, on the dense path)
-            return self.response.to_dense(index.as_range())
+            return self.response.take(index).to_dense() if isinstance(index, RowGather) else self.response.to_dense(index.as_range())
         if isinstance(self.response, ops.CellCodes):
             return self.response.rows(index), None
         return self.response[index], self.mask[index]
@@ -242,10 +255,17 @@ class ResidentSplit:
         shard is cut into exactly that many nearly equal minibatches instead of ceil(rows / batch_size) of them: a rank
         whose shard is one row shorter must not run one step (= one all-reduce) fewer than its peers.
         Sparse rows: RowBlocks of batch_size consecutive persons instead -- in order, or with shuffle in a fresh random order of the
-        blocks (one torch.randperm over block ids per epoch): block-shuffled SGD over the split's stored row order."""
+        blocks (one torch.randperm over block ids per epoch): block-shuffled SGD over the split's stored row order.  With
+        sparse_shuffle='persons' a shuffled pass yields RowGathers of batch_size persons of one torch.randperm over persons per
+        epoch, cut exactly as the dense branch below cuts `order`; unshuffled passes stay RowBlocks."""
         if isinstance(self.response, SparseRows):
             if n_steps is not None:
                 raise NotImplementedError('sparse rows: person sharding is not covered')
+            if shuffle and self.sparse_shuffle == 'persons':
+                order = torch.randperm(self.num_person, device=self.device, generator=generator)
+                for s in range(0, self.num_person, batch_size):
+                    yield RowGather(order[s:s + batch_size])
+                return
             n_blocks = (self.num_person + batch_size - 1) // batch_size
             order = torch.randperm(n_blocks, device=self.device, generator=generator).tolist() if shuffle else range(n_blocks)
             for b in order:
@@ -541,7 +561,7 @@ def main(argv=None):
         row_format = 'codes' if codes_ok else 'f32'
     elif row_format == 'codes' and not codes_ok:
         raise SystemExit('--row-format codes needs --cuda, 4..32767 items and --ability-dim <= 8')
-    train = ResidentSplit(train_dataset, device, shard(train_dataset.num_person), row_format)
+    train = ResidentSplit(train_dataset, device, shard(train_dataset.num_person), row_format, sparse_shuffle=args.sparse_shuffle)
     test = ResidentSplit(test_dataset, device, shard(test_dataset.num_person), row_format)
     local_bs = max(1, args.batch_size // world)
     # steps per epoch: identical on every rank (one all-reduce per step), derived from the largest shard
