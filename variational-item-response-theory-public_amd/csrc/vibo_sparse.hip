@@ -1,5 +1,6 @@
 // vibo_sparse.hip -- the ELBO, the encode and the validation pass on sparse response rows (include/vibo_hip_sparse_rows.h: THE IMAGE,
 // THE GRID RULE), with their extern "C" tails.  The plain model only: unconditional product-of-experts posterior, IRT decoder, no flows.
+// What this unit shares with the row-driven item pass (vibo_sparse_row_driven.hip) is in vibo_sparse_device.hpp.
 // The person, encode and item kernels are stated once and instantiated twice: for a contiguous range of persons (GATHER = false, the
 // calls of that header) and for an index vector of persons (GATHER = true, include/vibo_hip_sparse_gather.h: THE INDEX AND THE MAP).
 //
@@ -15,42 +16,13 @@
 // The statements of the math are those of the unconditional branch of vibo_general.hip; the table gradient's row-invariant factors
 // (tau; tau^2 exp(logvar)) are multiplied in once per wave instead of once per row.  No float atomics, no LDS, no index is trusted.
 #include <hip/hip_runtime.h>
-#include "../../include/vibo_hip_sparse_gather.h"
-#include "vibo_device.hpp"
-#include "vibo_host.hpp"
+#include "vibo_sparse_device.hpp"
 
 namespace vibo {
 
 constexpr int kChunk = VIBO_SPARSE_CHUNK;
 constexpr int kRec = VIBO_SPARSE_RECORD_FLOATS;
 constexpr int kRecTable = 8;            // the record's table gradient starts here: [2][2][16]
-
-struct SparseParams {
-    const int64_t* row_ptr;
-    const uint32_t* row_cell;
-    const int64_t* col_ptr;
-    const uint32_t* col_cell;
-    const int64_t* col_chunk;
-    const int32_t* chunk_item;
-    const int64_t* chunk_first;
-    long long P, nnz, num_chunk, row0;
-    const int64_t* person_index;   // gathered calls: [B], the person of the call's row r
-    int32_t* person_slot;          // gathered calls with gradients: [P], person -> the row of the call that owns it, or VIBO_SPARSE_NO_SLOT
-    int I, B, A, D, irt, missing_mode, reg_mode, want_grad;
-    const float* table;
-    const float* item;
-    const float* eps;
-    float* ability_mu;
-    float* ability_logvar;
-    float* ability;
-    float* grad_item;
-    float* records;          // [4 G][kRec]
-    float* chunk_rec;        // [num_chunk][D]
-    unsigned long long* bad; // sticky counter (may be null)
-};
-
-__device__ __forceinline__ int wave_total_i(int v) { return lane63(wave_sum63(v)); }
-__device__ __forceinline__ long long clamp_ll(long long v, long long lo, long long hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // first k in [lo, hi) with (cell[k] >> 1) >= key, or hi
 __device__ __forceinline__ long long lower_bound_cell(const uint32_t* cell, long long lo, long long hi, long long key) {
@@ -59,47 +31,6 @@ __device__ __forceinline__ long long lower_bound_cell(const uint32_t* cell, long
         if ((long long)(cell[mid] >> 1) < key) lo = mid + 1; else hi = mid;
     }
     return lo;
-}
-
-// One observed cell: logit, Bernoulli log-likelihood, d LL / d logit and d LL / d guess-logit (vibo_general.hip, pass 2).
-// disc: the item's discriminations (2PL / 3PL), diff: its difficulty column, glogit: its guess logit (3PL).
-template <int MA>
-__device__ __forceinline__ void cell_terms(const int irt, const int A, const float (&disc)[MA], const float diff, const float glogit,
-                                           const float (&th)[MA], const float x, float& ll, float& gl, float& gguess) {
-    float l = diff;
-    if (irt == 1) {
-#pragma unroll
-        for (int a = 0; a < MA; ++a)
-            if (a < A) l += th[a];
-    } else {
-#pragma unroll
-        for (int a = 0; a < MA; ++a)
-            if (a < A) l = fmaf(-disc[a], th[a], l);
-    }
-    gguess = 0.f;
-    if (irt != 3) {
-        const float lc = fminf(fmaxf(l, -kLogitLo), kLogitLo);
-        const bool live = (l >= -kLogitLo) && (l <= kLogitHi);
-        const float e = expf(-fabsf(lc));
-        ll = x * lc - fmaxf(lc, 0.f) - log1pf(e);
-        const float r = 1.0f / (1.0f + e);
-        const float sgm = (lc >= 0.f) ? r : e * r;
-        gl = live ? (x - sgm) : 0.f;
-    } else {
-        const float guess = 1.0f / (1.0f + expf(-glogit));
-        const float e = expf(-fabsf(l));
-        const float r = 1.0f / (1.0f + e);
-        const float sp = (l >= 0.f) ? r : e * r, sn = (l >= 0.f) ? e * r : r;
-        const float pr = fmaf(1.0f - guess, sp, guess);
-        const float qr = (1.0f - guess) * sn;
-        const float pc = fminf(fmaxf(pr, kEps32), 1.0f - kEps32);
-        const float qc = fminf(fmaxf(qr, kEps32), 1.0f - kEps32);
-        ll = (x > 0.5f) ? logf(pc) : logf(qc);
-        const float dll_dp = (pr == pc) ? ((x > 0.5f) ? 1.0f / pc : -1.0f / qc) : 0.f;
-        const float common = dll_dp * (1.0f - guess) * sn;
-        gl = common * sp;
-        gguess = common * guess;
-    }
 }
 
 // The person q of the call's row r: row0 + r, or (GATHER) person_index[r].  -> whether the row is live: q inside the image and, where the
@@ -429,17 +360,6 @@ __global__ __launch_bounds__(256) void sparse_item_kernel(const SparseParams p) 
     if (lane == 0 && tbad > 0 && p.bad) atomicAdd(p.bad, (unsigned long long)tbad);
 }
 
-// The map of a gathered call with gradients, B threads.  BUILD: the smallest row r that names person q owns it (an integer minimum: the
-// same whatever the arrival order); else the clear: the call's entries back to VIBO_SPARSE_NO_SLOT.  An index outside [0, P) writes nothing.
-template <bool BUILD>
-__global__ __launch_bounds__(256) void sparse_map_kernel(const int64_t* person_index, const long long B, const long long P, int32_t* person_slot) {
-    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (r >= B) return;
-    const long long q = person_index[r];
-    if (q < 0 || q >= P) return;
-    if (BUILD) atomicMin(&person_slot[q], (int32_t)r); else person_slot[q] = VIBO_SPARSE_NO_SLOT;
-}
-
 // finish, heads and table gradient: workgroup 0 the four head sums and the cell count, workgroup 1 + e entry e of the records' [2][2][16] table part
 __global__ __launch_bounds__(64) void sparse_finish_kernel(const float* records, const int n_rec, const int A, const int reg_mode,
                                                            float* out_scalars, float* grad_table) {
@@ -554,7 +474,7 @@ __global__ __launch_bounds__(256) void sparse_check_chunks_kernel(const int64_t*
 }
 
 // ---- host ----
-static int sparse_desc_rc(const vibo_desc* d) {
+int sparse_desc_rc(const vibo_desc* d) {
     if (!d) return fail(-1, "sparse rows: null descriptor");
     if (d->abi_version != VIBO_ABI_VERSION) return fail(-2, "sparse rows: abi_version %d != %d", d->abi_version, VIBO_ABI_VERSION);
     if (d->num_person < 1) return fail(-3, "sparse rows: num_person must be >= 1");
@@ -574,15 +494,15 @@ static int sparse_desc_rc(const vibo_desc* d) {
     return 0;
 }
 
-static int sparse_item_dim(const vibo_desc* d) { return d->irt_model == 1 ? 1 : d->ability_dim + (d->irt_model == 3 ? 2 : 1); }
-static int sparse_person_blocks(int B) {
+int sparse_item_dim(const vibo_desc* d) { return d->irt_model == 1 ? 1 : d->ability_dim + (d->irt_model == 3 ? 2 : 1); }
+int sparse_person_blocks(int B) {
     const int g = (B + VIBO_SPARSE_ROWS_PER_BLOCK - 1) / VIBO_SPARSE_ROWS_PER_BLOCK;
     return g > VIBO_SPARSE_MAX_BLOCKS ? VIBO_SPARSE_MAX_BLOCKS : g;
 }
-static size_t sparse_record_bytes(const vibo_desc* d) { return up256((size_t)sparse_person_blocks(d->num_person) * 4 * kRec * sizeof(float)); }
+size_t sparse_record_bytes(const vibo_desc* d) { return up256((size_t)sparse_person_blocks(d->num_person) * 4 * kRec * sizeof(float)); }
 
 // the image against the descriptor and (ranged) the call's range: 0, or the code (error string set)
-static int sparse_image_rc(const vibo_desc* d, const vibo_sparse_image* im, int64_t row0, bool need_cols, bool ranged = true) {
+int sparse_image_rc(const vibo_desc* d, const vibo_sparse_image* im, int64_t row0, bool need_cols, bool ranged) {
     if (!im) return fail(-5, "sparse rows: null image");
     if (im->num_person < 1 || im->num_person >= (1ll << 31) || im->num_item < 1 || im->num_item >= (1ll << 31) || im->nnz < 0 || im->num_chunk < 0)
         return fail(-3, "sparse rows: image sizes out of range (1 <= P, I < 2^31; nnz, num_chunk >= 0)");
@@ -625,16 +545,19 @@ static SparseParams sparse_params(const vibo_desc* d, const vibo_sparse_image* i
     if (gather) { VIBO_SPARSE_BY_WIDTH_G(kernel, A, true, grid, stream, p) } else { VIBO_SPARSE_BY_WIDTH_G(kernel, A, false, grid, stream, p) }
 
 // The ELBO call on a range (gather == false: row0) or on an index vector (gather == true: person_index, person_slot), after the
-// descriptor and the image have passed their checks: the rest of the checks and the launches.
-static int sparse_elbo_call(const vibo_desc* d, const vibo_sparse_image* im, bool gather, int64_t row0, const int64_t* person_index,
-                            int32_t* person_slot, const float* table, const float* item, const float* eps, float* out_scalars,
-                            float* ability_mu, float* ability_logvar, float* ability, float* grad_table, float* grad_item,
-                            int64_t* bad_cells, void* workspace, size_t workspace_bytes, void* stream) {
+// descriptor and the image have passed their checks: the rest of the checks and the launches.  max_row_cells > 0 (gathered, with
+// gradients): the row-driven item pass of vibo_sparse_row_driven.hip in place of the column-driven one; the column side is not read.
+int sparse_elbo_call(const vibo_desc* d, const vibo_sparse_image* im, bool gather, int64_t row0, const int64_t* person_index,
+                     int32_t* person_slot, const float* table, const float* item, const float* eps, float* out_scalars,
+                     float* ability_mu, float* ability_logvar, float* ability, float* grad_table, float* grad_item,
+                     int64_t* bad_cells, void* workspace, size_t workspace_bytes, void* stream, long long max_row_cells) {
     int rc = 0;
     const bool grad = d->want_grad != 0;
+    const bool row_driven = gather && grad && max_row_cells > 0;
     if (!table || !item || !eps || !out_scalars || !ability_mu || !ability_logvar || !ability || (grad && (!grad_table || !grad_item)))
         return fail(-5, "sparse rows: null required pointer");
-    const size_t need = vibo_sparse_workspace_bytes(d, grad ? im->num_chunk : 0);
+    const size_t need = row_driven ? vibo_sparse_row_driven_workspace_bytes(d, im->num_item, im->num_person, max_row_cells)
+                                   : vibo_sparse_workspace_bytes(d, grad ? im->num_chunk : 0);
     if (!workspace || workspace_bytes < need) return fail(-7, "sparse rows: workspace too small: %zu < %zu", workspace_bytes, need);
     if ((uintptr_t)workspace & 255) return fail(-7, "sparse rows: workspace must be 256-byte aligned");
 
@@ -658,15 +581,19 @@ static int sparse_elbo_call(const vibo_desc* d, const vibo_sparse_image* im, boo
     hipLaunchKernelGGL(sparse_finish_kernel, dim3(grad ? 65u : 1u), dim3(64), 0, s, p.records, 4 * G, p.A, p.reg_mode, out_scalars, grad_table);
     if ((rc = launch_rc("sparse rows finish launch")) != 0) return rc;
     if (!grad) return 0;
-    if (p.num_chunk > 0) {
-        const long long blocks = (p.num_chunk + 3) / 4;
-        if (blocks > 0x7fffffffll) return fail(-8, "sparse rows: more chunks than one launch takes");
-        VIBO_SPARSE_BY_WIDTH(sparse_item_kernel, p.A, gather, blocks, s, p);
-        if ((rc = launch_rc("sparse rows item pass launch")) != 0) return rc;
+    if (row_driven) {
+        if ((rc = sparse_row_driven_item_pass(p, max_row_cells, static_cast<char*>(workspace) + sparse_record_bytes(d), s)) != 0) return rc;
+    } else {
+        if (p.num_chunk > 0) {
+            const long long blocks = (p.num_chunk + 3) / 4;
+            if (blocks > 0x7fffffffll) return fail(-8, "sparse rows: more chunks than one launch takes");
+            VIBO_SPARSE_BY_WIDTH(sparse_item_kernel, p.A, gather, blocks, s, p);
+            if ((rc = launch_rc("sparse rows item pass launch")) != 0) return rc;
+        }
+        hipLaunchKernelGGL(sparse_item_finish_kernel, dim3((unsigned)(((long long)p.I * p.D + 255) / 256)), dim3(256), 0, s, p.col_chunk, p.num_chunk,
+                           p.chunk_rec, p.I, p.D, grad_item);
+        if ((rc = launch_rc("sparse rows item finish launch")) != 0) return rc;
     }
-    hipLaunchKernelGGL(sparse_item_finish_kernel, dim3((unsigned)(((long long)p.I * p.D + 255) / 256)), dim3(256), 0, s, p.col_chunk, p.num_chunk,
-                       p.chunk_rec, p.I, p.D, grad_item);
-    if ((rc = launch_rc("sparse rows item finish launch")) != 0) return rc;
     if (mapped) {
         hipLaunchKernelGGL(sparse_map_kernel<false>, dim3(map_grid), dim3(256), 0, s, person_index, (long long)p.B, p.P, person_slot);
         rc = launch_rc("sparse rows map clear launch");

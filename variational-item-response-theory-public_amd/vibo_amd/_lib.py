@@ -2,9 +2,9 @@
 restype / argtypes come from its prototype (parse_prototypes); the constants and the two structs mirror the header by hand
 (tests/test_capi_symbols.py compares them).  Exports declared in a header of their own beside it (EXTRA_HEADERS:
 vibo_hip_decoder_multi.h, vibo_hip_sign_rows.h, vibo_hip_person_tables.h, vibo_hip_tile_rows.h, vibo_hip_given_tiles.h,
-vibo_hip_sparse_rows.h, vibo_hip_sparse_gather.h) are bound the same way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself,
-EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS, PERSON_TABLE_SYMBOLS, TILE_ROWS_SYMBOLS, GIVEN_TILES_SYMBOLS, SPARSE_ROWS_SYMBOLS and
-SPARSE_GATHER_SYMBOLS are theirs.
+vibo_hip_sparse_rows.h, vibo_hip_sparse_gather.h, vibo_hip_sparse_row_driven.h) are bound the same way; EXPORTED_SYMBOLS stays the list of vibo_hip.h itself,
+EXTRA_SYMBOLS, SIGN_ROWS_SYMBOLS, PERSON_TABLE_SYMBOLS, TILE_ROWS_SYMBOLS, GIVEN_TILES_SYMBOLS, SPARSE_ROWS_SYMBOLS,
+SPARSE_GATHER_SYMBOLS and SPARSE_ROW_DRIVEN_SYMBOLS are theirs.
 
 The product path has no CPU or eager-PyTorch fallback: if the HIP library is
 missing or a call fails, this module raises.
@@ -129,7 +129,7 @@ def parse_prototypes(header):
 
 
 EXTRA_HEADERS = ('vibo_hip_decoder_multi.h', 'vibo_hip_sign_rows.h', 'vibo_hip_person_tables.h', 'vibo_hip_tile_rows.h',
-                 'vibo_hip_given_tiles.h', 'vibo_hip_sparse_rows.h', 'vibo_hip_sparse_gather.h')
+                 'vibo_hip_given_tiles.h', 'vibo_hip_sparse_rows.h', 'vibo_hip_sparse_gather.h', 'vibo_hip_sparse_row_driven.h')
 
 with open(HEADER_PATH) as _header:
     PROTOTYPES = parse_prototypes(_header.read())
@@ -149,6 +149,7 @@ TILE_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_tile_rows.h']
 GIVEN_TILES_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_given_tiles.h']          # the tile image under a caller-supplied posterior (ops._tile_rows)
 SPARSE_ROWS_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sparse_rows.h']          # the matrix as its observed cells (vibo_amd/sparse.py)
 SPARSE_GATHER_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sparse_gather.h']      # ... for an index vector of persons (SparseRows.take)
+SPARSE_ROW_DRIVEN_SYMBOLS = _HEADER_SYMBOLS['vibo_hip_sparse_row_driven.h']  # ... with the row-driven item pass (item_pass='rows')
 PTRAIN_VI, PTRAIN_MLE = 0, 1                                            # VIBO_PTRAIN_*
 PTRAIN_MAX_BLOCKS = 2048                                                # VIBO_PTRAIN_MAX_BLOCKS: the table update's grid cap
 

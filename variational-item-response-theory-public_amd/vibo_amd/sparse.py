@@ -1,17 +1,20 @@
 """Sparse response rows: a matrix held as its observed cells only (include/vibo_hip_sparse_rows.h states the image; this module
-builds it with torch ops on the data's device and calls the exports that read it: the range calls of that header and the gathered
-calls of include/vibo_hip_sparse_gather.h).
+builds it with torch ops on the data's device and calls the exports that read it: the range calls of that header, the gathered
+calls of include/vibo_hip_sparse_gather.h and the gathered call with a row-driven item pass of include/vibo_hip_sparse_row_driven.h).
 
     rows = SparseRows.from_dense(response, mask)          # or from_cell_codes / from_coo / from_arrays
     ops.fused_elbo(spec, table, item, None, rows, None, eps, row_index=range(a, b))
     model.elbo_step(rows.rows(range(a, b)), None)         # a range view goes wherever a `response` goes, with mask=None
     model.elbo_step(rows, None, row_index=RowGather(idx)) # a gathered minibatch: idx int64 [B] on the image's device
     model.encode(rows.take(idx), None)                    # the same as a view
+    model.elbo_step(rows, None, row_index=RowGather(idx, item_pass='rows'))      # ... with the row-driven item pass (opt-in)
 
 Covered: the plain model (unconditional product-of-experts posterior, IRT decoder, no flows, ability_dim 1..8) on contiguous person
 ranges and on index vectors of persons.  A range call costs its persons' cells.  A gathered call's person pass costs the batch's
 cells, but its item pass streams the image's whole column side whatever the batch size (the header says why): small batches of a
-large image pay for it.  With gradients a person named twice in one index vector is owned by its first row; the later rows come
+large image pay for it.  item_pass='rows' (RowGather, take) selects the row-driven item pass instead: the batch's own cells, ordered
+by item once per call; its cost follows B x the image's longest row, and it never reads the column side.  The default stays
+'columns'; which one wins where is measured, not guessed (profiles/sparse_row_driven_record.txt).  With gradients a person named twice in one index vector is owned by its first row; the later rows come
 back as zeros and are counted in bad_index_count, as is an index outside the image.
 Everything else raises NotImplementedError naming the format: a bare tensor row_index (wrap it in RowGather), person sharding
 (a reducer), the conditional and caller-supplied posteriors, flows, ability_dim 9..16.
@@ -25,6 +28,20 @@ from . import _lib
 
 FORMAT = 'sparse rows'
 CHUNK = _lib.SPARSE_CHUNK
+ITEM_PASSES = ('columns', 'rows')      # a gathered call's item pass: vibo_hip_sparse_gather.h | vibo_hip_sparse_row_driven.h
+
+
+def _check_item_pass(item_pass):
+    if item_pass not in ITEM_PASSES:
+        raise ValueError(f"{FORMAT}: item_pass must be 'columns' or 'rows', not {item_pass!r}")
+    return item_pass
+
+
+def key_layout(num_person, num_item):
+    """THE KEY of include/vibo_hip_sparse_row_driven.h for an image of P persons x I items -> (bP, end_bit, pad_key): a cell's key is
+    item << (bP + 1) | person << 1 | right, sorted over the bits [0, end_bit); the pad key is above every real key."""
+    bp = max(1, (int(num_person) - 1).bit_length())
+    return bp, bp + 1 + int(num_item).bit_length(), int(num_item) << (bp + 1)
 
 
 class RowBlock:
@@ -49,13 +66,14 @@ class RowBlock:
 
 class RowGather:
     """An index vector of persons (int64 [B], on the image's device, relative to the view it is applied to): what a resident split on
-    sparse rows yields as a person-shuffled minibatch's `row_index`, beside RowBlock."""
-    __slots__ = ('index',)
+    sparse rows yields as a person-shuffled minibatch's `row_index`, beside RowBlock.  item_pass: the item pass of the calls with
+    gradients on these persons, 'columns' (the image's column side) or 'rows' (the batch's own cells, ordered per call)."""
+    __slots__ = ('index', 'item_pass')
 
-    def __init__(self, index):
+    def __init__(self, index, item_pass='columns'):
         if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
             raise ValueError(f'{FORMAT}: RowGather takes a non-empty 1-d int64 tensor of persons')
-        self.index = index
+        self.index, self.item_pass = index, _check_item_pass(item_pass)
 
     def numel(self):
         return int(self.index.numel())
@@ -139,11 +157,13 @@ class SparseRows:
             self.col_chunk, self.chunk_item, self.chunk_first = chunk_list(col_ptr)
             self.bad_cells = torch.zeros(1, dtype=torch.int64, device=row_ptr.device)      # the library's sticky counter
             self._slot = [None]          # the gathered calls' person_slot map, made on first use; views share the holder
+            self._max_row = [None]       # the longest row's cells, read back on first use; views share the holder
             self.row0, self.num_person, self.index, self.image_index = 0, self.image_persons, None, None
+            self.item_pass = 'columns'
         else:
-            base, rng, index = _view
+            base, rng, index, self.item_pass = _view
             self.col_chunk, self.chunk_item, self.chunk_first, self.bad_cells = base.col_chunk, base.chunk_item, base.chunk_first, base.bad_cells
-            self._slot = base._slot
+            self._slot, self._max_row = base._slot, base._max_row
             if index is None:
                 self.row0, self.num_person, self.index, self.image_index = base.row0 + rng.start, len(rng), None, None
             else:
@@ -226,26 +246,37 @@ class SparseRows:
         """The persons `rng` (a range with step 1, or a RowBlock) of this image as a view: the same arrays, another range."""
         self._no_gathered('rows()')
         return SparseRows(self.row_ptr, self.row_cell, self.col_ptr, self.col_cell, self.image_persons, self.num_item,
-                          _view=(self, _as_range(rng, self.num_person), None))
+                          _view=(self, _as_range(rng, self.num_person), None, 'columns'))
 
-    def take(self, index):
+    def take(self, index, item_pass=None):
         """The persons index[0..B) of this image or range view (int64 [B] on its device, or a RowGather; persons relative to this view)
         as a view of B rows: row r is person index[r].  Nothing is copied and nothing is read back: an entry outside the view is left
-        to the launches, which skip it, return zeros for its row and count it (bad_index_count)."""
+        to the launches, which skip it, return zeros for its row and count it (bad_index_count).  item_pass ('columns' | 'rows';
+        default: a RowGather's own, else 'columns') is carried by the view as its `item_pass` attribute."""
         self._no_gathered('take()')
-        index = index.index if isinstance(index, RowGather) else index
+        if isinstance(index, RowGather):
+            index, item_pass = index.index, index.item_pass if item_pass is None else item_pass
+        item_pass = _check_item_pass('columns' if item_pass is None else item_pass)
         if not isinstance(index, torch.Tensor) or index.dtype != torch.int64 or index.dim() != 1 or index.numel() < 1:
             raise ValueError(f'{FORMAT}: take() needs a non-empty 1-d int64 tensor of persons')
         if index.device != self.device:
             raise ValueError(f'{FORMAT}: the index is on {index.device}, the image on {self.device}')
         return SparseRows(self.row_ptr, self.row_cell, self.col_ptr, self.col_cell, self.image_persons, self.num_item,
-                          _view=(self, None, index.contiguous()))
+                          _view=(self, None, index.contiguous(), item_pass))
 
     def slot_map(self):
         """The gathered calls' person_slot map of this image (int32 [P], all NO_SLOT between calls), made on first use."""
         if self._slot[0] is None:
             self._slot[0] = torch.full((self.image_persons,), _lib.SPARSE_NO_SLOT, dtype=torch.int32, device=self.device)
         return self._slot[0]
+
+    @property
+    def max_row_cells(self):
+        """The cells of the image's longest row (at least 1), computed from row_ptr on first use (one read-back) and shared by the views:
+        what the row-driven item pass sizes its key buffers by."""
+        if self._max_row[0] is None:
+            self._max_row[0] = max(1, int((self.row_ptr[1:] - self.row_ptr[:-1]).max()))
+        return self._max_row[0]
 
     def to(self, device):
         if self.index is not None or self.row0 != 0 or self.num_person != self.image_persons:
@@ -383,8 +414,8 @@ def _hip_sparse_check(rows):
 
 
 def _hip_sparse_elbo(spec, rows, table, item, eps, reg_mode, want_grad):
-    """vibo_sparse_elbo_fwd_bwd on the view's persons, or vibo_sparse_elbo_fwd_bwd_gather on a gathered view's, on the current stream
-    -> ops.RawElbo."""
+    """vibo_sparse_elbo_fwd_bwd on the view's persons, or on a gathered view's vibo_sparse_elbo_fwd_bwd_gather (item_pass 'columns') or
+    vibo_sparse_elbo_fwd_bwd_gather_rows (item_pass 'rows': the column side is not passed), on the current stream -> ops.RawElbo."""
     from . import ops
     ops._require_device(rows.row_ptr, table, item, eps)
     dev = rows.device
@@ -394,10 +425,19 @@ def _hip_sparse_elbo(spec, rows, table, item, eps, reg_mode, want_grad):
     flat = torch.empty(_lib.NUM_SCALARS + 2 * n_table + n_item, dtype=torch.float32, device=dev)
     post = torch.empty(3, B, A, dtype=torch.float32, device=dev)
     d = _desc(spec, B, I, reg_mode, want_grad)
-    im = rows.image(columns=bool(want_grad))
-    ws_bytes = _lib.load().vibo_sparse_workspace_bytes(ctypes.byref(d), ctypes.c_int64(im.num_chunk))
-    if ws_bytes == 0:
-        _lib.check(-8, 'vibo_sparse_workspace_bytes')
+    by_rows = rows.index is not None and getattr(rows, 'item_pass', 'columns') == 'rows'
+    im = rows.image(columns=bool(want_grad) and not by_rows)
+    if by_rows:
+        max_row = ctypes.c_int64(rows.max_row_cells)
+        ws_bytes = _lib.load().vibo_sparse_row_driven_workspace_bytes(ctypes.byref(d), ctypes.c_int64(I), ctypes.c_int64(rows.image_persons), max_row)
+        if ws_bytes == 0:
+            raise _lib.ViboLibraryError(f'{FORMAT}: the row-driven item pass does not take this call (item_pass=\'rows\' needs '
+                                        f'{B} persons x {rows.max_row_cells} cells of the longest row < 2^31 and a supported descriptor): '
+                                        f'use item_pass=\'columns\'')
+    else:
+        ws_bytes = _lib.load().vibo_sparse_workspace_bytes(ctypes.byref(d), ctypes.c_int64(im.num_chunk))
+        if ws_bytes == 0:
+            _lib.check(-8, 'vibo_sparse_workspace_bytes')
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     vp, fbase = ctypes.c_void_p, flat.data_ptr()
     tail = (ops._ptr(table), ops._ptr(item), ops._ptr(eps), vp(fbase), ops._ptr(post[0]), ops._ptr(post[1]), ops._ptr(post[2]),
@@ -408,8 +448,12 @@ def _hip_sparse_elbo(spec, rows, table, item, eps, reg_mode, want_grad):
     else:
         slot = rows.slot_map() if want_grad else None
         try:
-            ops._call('vibo_sparse_elbo_fwd_bwd_gather', ctypes.byref(d), ctypes.byref(im), ops._ptr(rows.image_index),
-                      ops._ptr(slot), *tail)
+            if by_rows:
+                ops._call('vibo_sparse_elbo_fwd_bwd_gather_rows', ctypes.byref(d), ctypes.byref(im), ops._ptr(rows.image_index),
+                          ops._ptr(slot), max_row, *tail)
+            else:
+                ops._call('vibo_sparse_elbo_fwd_bwd_gather', ctypes.byref(d), ctypes.byref(im), ops._ptr(rows.image_index),
+                          ops._ptr(slot), *tail)
         except BaseException:
             if slot is not None:          # (a call that stopped between the map's build and its clear: the next one needs it empty)
                 slot.fill_(_lib.SPARSE_NO_SLOT)

@@ -92,6 +92,12 @@ def build_parser():
                         "carries structure and the batch is a fair share of the split, and costs most at small batches of a large "
                         "split (profiles/sparse_gather_record.txt: at 100000 persons x 10000 items a gathered step took 7 to 43 %% "
                         "longer than a block step, 0.154 against 0.108 ms for 1024 persons at a density of 2 %%)")
+    p.add_argument('--sparse-item-pass', choices=['columns', 'rows'], default='columns',
+                   help="with --row-format sparse --sparse-shuffle persons, the gathered step's item pass: 'columns' = the walk over "
+                        "the split's whole column side described above; 'rows' = the row-driven pass of "
+                        "include/vibo_hip_sparse_row_driven.h: the batch's own cells, ordered by item once per step (a device radix "
+                        "sort) and summed in a fixed order -- its cost follows --batch-size times the split's longest row, not the "
+                        "split.  Opt-in; where each one wins is a measurement: profiles/sparse_row_driven_record.txt")
     p.add_argument('--rng', choices=['torch', 'native'], default='torch',
                    help="reparameterisation noise of the fused trainer: torch.randn (the stream torch.manual_seed(--seed) governs) or "
                         "the library's Philox generator drawn inside the prologue kernel (two launches fewer per step)")
@@ -161,6 +167,10 @@ def check_supported(args):
             problems.append('--row-format sparse with ' + ', '.join(why) + ' (sparse rows cover the plain model on one GPU)')
     elif getattr(args, 'sparse_shuffle', 'blocks') != 'blocks':
         problems.append(f'--sparse-shuffle {args.sparse_shuffle} without --row-format sparse (the other formats shuffle persons already)')
+    if getattr(args, 'sparse_item_pass', 'columns') != 'columns' and not (
+            getattr(args, 'row_format', 'auto') == 'sparse' and getattr(args, 'sparse_shuffle', 'blocks') == 'persons'):
+        problems.append(f'--sparse-item-pass {args.sparse_item_pass} without --row-format sparse --sparse-shuffle persons (it chooses the '
+                        f'item pass of sparse rows\' gathered minibatches: no other step has one)')
     if problems:
         raise SystemExit('not supported by the MI355X engine: ' + '; '.join(problems))
 
@@ -219,10 +229,10 @@ class ResidentSplit:
     """One dataset split resident on the device: response f32 [P,I] + mask bool [P,I] (the reference's layout, 5 B per
     cell), with row_format='codes' one byte per cell (ops.CellCodes; mask is None then), or with row_format='sparse' the observed
     cells only (sparse.SparseRows; mask is None, and batches() yields blocks of consecutive persons or, shuffled under
-    sparse_shuffle='persons', gathered minibatches)."""
+    sparse_shuffle='persons', gathered minibatches whose item pass is sparse_item_pass)."""
 
-    def __init__(self, dataset, device, row_slice=None, row_format='f32', sparse_shuffle='blocks'):
-        self.sparse_shuffle = sparse_shuffle
+    def __init__(self, dataset, device, row_slice=None, row_format='f32', sparse_shuffle='blocks', sparse_item_pass='columns'):
+        self.sparse_shuffle, self.sparse_item_pass = sparse_shuffle, sparse_item_pass
         r, m = dataset.matrix()
         if row_slice is not None:
             r, m = r[row_slice], m[row_slice]
@@ -264,7 +274,7 @@ class ResidentSplit:
             if shuffle and self.sparse_shuffle == 'persons':
                 order = torch.randperm(self.num_person, device=self.device, generator=generator)
                 for s in range(0, self.num_person, batch_size):
-                    yield RowGather(order[s:s + batch_size])
+                    yield RowGather(order[s:s + batch_size], item_pass=self.sparse_item_pass)
                 return
             n_blocks = (self.num_person + batch_size - 1) // batch_size
             order = torch.randperm(n_blocks, device=self.device, generator=generator).tolist() if shuffle else range(n_blocks)
@@ -561,7 +571,8 @@ def main(argv=None):
         row_format = 'codes' if codes_ok else 'f32'
     elif row_format == 'codes' and not codes_ok:
         raise SystemExit('--row-format codes needs --cuda, 4..32767 items and --ability-dim <= 8')
-    train = ResidentSplit(train_dataset, device, shard(train_dataset.num_person), row_format, sparse_shuffle=args.sparse_shuffle)
+    train = ResidentSplit(train_dataset, device, shard(train_dataset.num_person), row_format, sparse_shuffle=args.sparse_shuffle,
+                          sparse_item_pass=getattr(args, 'sparse_item_pass', 'columns'))
     test = ResidentSplit(test_dataset, device, shard(test_dataset.num_person), row_format)
     local_bs = max(1, args.batch_size // world)
     # steps per epoch: identical on every rank (one all-reduce per step), derived from the largest shard
